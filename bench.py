@@ -14,12 +14,21 @@ pixels of all ranks / max-over-ranks wall time of the K timed steps (every timed
 batch waited for).  The host threads the GPU path may use are stated (--threads,
 default 32 = an 8-GPU node's 256 cores / 8).
 
-pcie_inclusive: the same steps with the PNG files in HOST memory (page-locked, as a
-server reads request bodies with ik_host_alloc) through ik_transform_batch_submit,
+A plain run (python bench.py --gpus 1 --steps K --warmup W) does only that: it makes
+the inputs (one forked worker per frame), lets the path settle (--settle-steps
+untimed batches, reported as `settle_steps`), warms up, times the K steps and prints
+the result line (`value`, `ms_per_step`, and the stage and roofline figures read
+from the timed steps themselves).  --dump-outputs DIR then writes the encoded files the last timed step
+returned to DIR/encoded_sizes.npy and DIR/encoded_bytes.npy (dump_outputs); the
+inputs are seeded, so two builds can be compared output for output.  Every other
+leg below takes runs of its own and is measured with --full only.
+
+pcie_inclusive (--full): the same steps with the PNG files in HOST memory (page-locked,
+as a server reads request bodies with ik_host_alloc) through ik_transform_batch_submit,
 so the compressed bytes cross PCIe inside the timed region (upload of one batch
 under another's kernels).
 
-Beside it, in the same JSON line:
+Beside it with --full, in the same JSON line:
   cpu_baseline   the same PNG bytes through the reference CPU path restated
                  (oracle/: png decode + image 0.25.8 resize + libwebp), one image
                  per worker at a time, on 1 core and on every core the job can
@@ -36,7 +45,7 @@ Beside it, in the same JSON line:
   decode_inclusive_jpeg   the same frames as JPEG q90 4:2:0 with restart markers
                  (configs[2]'s container) through ik_transform_batch.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]; for N>1 under
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full]; for N>1 under
 torch.distributed.run (one rank per GPU; RCCL only for barrier / max).
 """
 from __future__ import annotations
@@ -109,7 +118,40 @@ def parse():
                     help="drive N logical devices from this one process (ik_init(-1), IK_DEVICES)")
     ap.add_argument("--inproc-map", default="",
                     help="physical device of each logical device, e.g. 0,0 (default 0..N-1)")
-    return ap.parse_args()
+    ap.add_argument("--settle-steps", type=int, default=24,
+                    help="untimed batches of the headline path before the warmup (setup: pools, in-flight slots "
+                         "and clocks at their steady state), as many as fit into --settle-seconds")
+    ap.add_argument("--settle-seconds", type=float, default=2.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg (cpu_baseline, pcie_inclusive, pageable_input, webp_coder_alt, "
+                         "hbm_resident, decode_inclusive_jpeg, roofline_resize); the --no-* switches and *-steps 0 "
+                         "take single legs out again.  Without it: setup, warmup, the timed steps, the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (the encoded files) to DIR/*.npy")
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run measures `value` only: no leg that takes runs of its own
+        args.no_cpu_baseline = args.no_extras = args.no_pcie_leg = True
+        args.alt_steps = args.pageable_steps = 0
+    return args
+
+
+DUMP_MAX_VALUES = 12 << 20  # float32 values per dumped array (48 MB: the whole dump stays under 64 MB)
+
+
+def dump_outputs(path: str, files, rank: int = 0):
+    """The encoded files the last timed step returned, for comparing two builds output
+    for output: encoded_sizes.npy (float64, bytes of each file, in request order) and
+    encoded_bytes.npy (float32, every file's bytes one after another).  Past
+    DUMP_MAX_VALUES bytes, a fixed seeded sample of the byte positions, in order."""
+    os.makedirs(path, exist_ok=True)
+    tag = "" if rank == 0 else f"_rank{rank}"
+    sizes = np.array([len(f) for f in files], dtype=np.float64)
+    flat = np.frombuffer(b"".join(files), dtype=np.uint8)
+    if flat.size > DUMP_MAX_VALUES:
+        flat = flat[np.sort(np.random.default_rng(0).choice(flat.size, DUMP_MAX_VALUES, replace=False))]
+    np.save(os.path.join(path, f"encoded_sizes{tag}.npy"), sizes)
+    np.save(os.path.join(path, f"encoded_bytes{tag}.npy"), flat.astype(np.float32))
 
 
 def shard_seeds(rank: int, n: int):
@@ -195,6 +237,30 @@ def make_jpegs(frames, rst):
                                                                      **kw)
         out.append(b.getvalue())
     return out
+
+
+def _make_input(job):
+    """One synthetic frame and its encoded file (a worker of make_inputs)."""
+    import ikutil
+    seed, S, source = job
+    frame = ikutil.synth(S, S, 4, seed=seed, pattern="S")
+    enc = make_pngs([frame])[0] if source == "png" else make_jpegs([frame], source == "jpeg-rst")[0]
+    return frame, enc
+
+
+def make_inputs(seeds, S, source):
+    """The frames of `seeds` and their encoded files, one forked worker per frame (at
+    most 8): the same bytes as made one after another, in a fraction of the time
+    (zlib level 6 over 64 MB takes seconds per frame).  Runs before anything
+    initialises the GPU (the pool forks)."""
+    import multiprocessing as mp
+    jobs = [(sd, S, source) for sd in seeds]
+    if len(jobs) < 2:
+        made = [_make_input(j) for j in jobs]
+    else:
+        with mp.get_context("fork").Pool(min(len(jobs), 8)) as pool:
+            made = pool.map(_make_input, jobs, chunksize=1)
+    return [m[0] for m in made], [m[1] for m in made]
 
 
 _CPU = {}  # the oracle and the inputs, inherited by the forked cpu_baseline workers
@@ -342,8 +408,7 @@ def main():
     # the codec libraries are explicit dependencies of libimagekit_hip.so
     # (IK_LIBWEBP / IK_LIBAVIF, else the system sonames): name the copies used here
     ikutil.use_pillow_codecs()
-    frames = [ikutil.synth(S, S, 4, seed=sd, pattern="S") for sd in shard_seeds(rank, args.distinct)]
-    pngs = make_pngs(frames) if args.source == "png" else make_jpegs(frames, args.source == "jpeg-rst")
+    frames, pngs = make_inputs(shard_seeds(rank, args.distinct), S, args.source)
     # the CPU leg first: its worker pools fork, and nothing may have touched the GPU yet
     cpu = cpu_baseline(args, pngs) if rank == 0 and world == 1 and not args.no_cpu_baseline else None
     dist = None
@@ -448,6 +513,15 @@ def main():
 
     # headline: inputs resident in HBM
     run = (lambda k: run_pipelined(k, rq=dreqs)) if args.pipeline else run_blocking
+    # settle (setup, untimed): `value` is a steady-state rate, and the library's pools,
+    # its in-flight slots and the device clocks reach that state over the first dozens
+    # of batches, more than a short --warmup gives (the first process on an idle
+    # device measured 39.4 ms per step straight after 5 warmup steps, 36.5 with this).
+    # Until now the pcie_inclusive leg ran first and did this; it is behind --full.
+    settled, ts = 0, time.perf_counter()
+    while settled < args.settle_steps and time.perf_counter() - ts < args.settle_seconds:
+        run(max(1, args.inflight))
+        settled += max(1, args.inflight)
     run(args.warmup)
     stage_ms.clear()
     batch_ms.clear()
@@ -467,6 +541,8 @@ def main():
     rank_cpu = gather_floats([cpu_s, elapsed], dist, dev, world)
     elapsed = reduce_max(elapsed, dist, dev)
     assert all(r is not None and magic(r) for r in res)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, rank)
     cnt1 = (ctypes.c_ulonglong * 2)()
     lib.ik_png_counters(cnt1)
     gpu_streams, host_streams = cnt1[0] - cnt0[0], cnt1[1] - cnt0[1]
@@ -709,7 +785,7 @@ def main():
                    "bytes_per_source_image": sum(len(p) for p in jp) // 2,
                    "value": round(aggregate_mpix(world, n, S, te), 2), "unit": "MPix/s"}
 
-    if roof_resize is None:
+    if roof_resize is None and args.full:
         # the resize kernel alone on the measured batch's geometry (C channels as the
         # decoded frames: 3 for JPEG sources): in the four-stage pipeline the batch's
         # own resize runs beside the next batch's decode kernels, so its event time
@@ -762,6 +838,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "settle_steps": settled,
             "ms_per_step": round(elapsed / args.steps * 1e3, 3),
             "higher_is_better": True,
             "scaling": "weak",

@@ -34,30 +34,30 @@ for s in $STEPS; do
         || { echo "SMOKE FAILED"; tail -20 ${O}_smoke.log; exit 1; }
       tail -2 ${O}_smoke.log ;;
     bench)
-      timeout -k 10 600 python -u bench.py > ${O}_bench.json 2> ${O}_bench.err \
+      timeout -k 10 600 python -u bench.py --full > ${O}_bench.json 2> ${O}_bench.err \
         || { echo "BENCH FAILED"; tail -20 ${O}_bench.err; exit 1; }
       python tools/bench_summary.py ${O}_bench.json ;;
     prof)
-      timeout -k 10 600 rocprofv3 --kernel-trace --stats -d ${O}_prof -o run -f csv -- python bench.py --no-cpu-baseline --no-extras --steps 8 > ${O}_prof.json 2> ${O}_prof.err \
+      timeout -k 10 600 rocprofv3 --kernel-trace --stats -d ${O}_prof -o run -f csv -- python bench.py --full --no-cpu-baseline --no-extras --steps 8 > ${O}_prof.json 2> ${O}_prof.err \
         || { echo "PROFILE FAILED"; tail -20 ${O}_prof.err; exit 1; }
       python tools/bench_summary.py ${O}_prof.json
       find ${O}_prof -name "*kernel_stats.csv" -exec cp {} ${O}_kernel_stats.csv \; ;;
     c2)
-      timeout -k 10 900 python -u bench.py --source jpeg-rst --format jpeg --quality 85 --filter lanczos3 --batch 256 --steps 6 --warmup 1 --no-extras --cpu-seconds 10 > ${O}_c2.json 2> ${O}_c2.err \
+      timeout -k 10 900 python -u bench.py --full --source jpeg-rst --format jpeg --quality 85 --filter lanczos3 --batch 256 --steps 6 --warmup 1 --no-extras --cpu-seconds 10 > ${O}_c2.json 2> ${O}_c2.err \
         || { echo "C2 FAILED"; tail -20 ${O}_c2.err; exit 1; }
       python tools/bench_summary.py ${O}_c2.json ;;
     c2prof)
-      timeout -k 10 900 rocprofv3 --kernel-trace --stats -d ${O}_c2prof -o run -f csv -- python bench.py --source jpeg-rst --format jpeg --quality 85 --filter lanczos3 --batch 256 --steps 4 --warmup 1 --no-extras --no-cpu-baseline > ${O}_c2prof.json 2> ${O}_c2prof.err \
+      timeout -k 10 900 rocprofv3 --kernel-trace --stats -d ${O}_c2prof -o run -f csv -- python bench.py --full --source jpeg-rst --format jpeg --quality 85 --filter lanczos3 --batch 256 --steps 4 --warmup 1 --no-extras --no-cpu-baseline > ${O}_c2prof.json 2> ${O}_c2prof.err \
         || { echo "C2PROF FAILED"; tail -20 ${O}_c2prof.err; exit 1; }
       python tools/bench_summary.py ${O}_c2prof.json
       find ${O}_c2prof -name "*kernel_stats.csv" -exec cp {} ${O}_c2_kernel_stats.csv \; ;;
     c2norst)
-      timeout -k 10 900 python -u bench.py --source jpeg --format jpeg --quality 85 --filter lanczos3 --batch 256 --steps 4 --warmup 1 --no-extras --no-cpu-baseline > ${O}_c2norst.json 2> ${O}_c2norst.err \
+      timeout -k 10 900 python -u bench.py --full --source jpeg --format jpeg --quality 85 --filter lanczos3 --batch 256 --steps 4 --warmup 1 --no-extras --no-cpu-baseline > ${O}_c2norst.json 2> ${O}_c2norst.err \
         || { echo "C2NORST FAILED"; tail -20 ${O}_c2norst.err; exit 1; }
       python tools/bench_summary.py ${O}_c2norst.json ;;
     c4)
       # configs[4]: 32 x 8192^2 RGBA PNG (HBM) -> 1024^2 Lanczos3 -> AVIF q60, under rocprofv3 (kernel stats)
-      timeout -k 10 900 rocprofv3 --kernel-trace --stats -d ${O}_c4prof -o run -f csv -- python bench.py --size 8192 --out 1024 --filter lanczos3 --format avif --quality 60 --batch 32 --steps 3 --warmup 1 --no-extras --no-pcie-leg --cpu-seconds 10 > ${O}_c4.json 2> ${O}_c4.err \
+      timeout -k 10 900 rocprofv3 --kernel-trace --stats -d ${O}_c4prof -o run -f csv -- python bench.py --full --size 8192 --out 1024 --filter lanczos3 --format avif --quality 60 --batch 32 --steps 3 --warmup 1 --no-extras --no-pcie-leg --cpu-seconds 10 > ${O}_c4.json 2> ${O}_c4.err \
         || { echo "C4 FAILED"; tail -20 ${O}_c4.err; exit 1; }
       python tools/bench_summary.py ${O}_c4.json
       find ${O}_c4prof -name "*kernel_stats.csv" -exec cp {} ${O}_c4_kernel_stats.csv \; ;;
@@ -74,7 +74,7 @@ for s in $STEPS; do
         || { echo "JPEG TESTS FAILED"; tail -40 ${O}_jtests.log; exit 1; }
       tail -2 ${O}_jtests.log ;;
     ptime)
-      IK_TIMING=1 timeout -k 10 600 python -u bench.py --no-cpu-baseline --no-extras --steps 6 > ${O}_ptime.json 2> ${O}_ptime.err \
+      IK_TIMING=1 timeout -k 10 600 python -u bench.py --full --no-cpu-baseline --no-extras --steps 6 > ${O}_ptime.json 2> ${O}_ptime.err \
         || { echo "PTIME FAILED"; tail -20 ${O}_ptime.err; exit 1; }
       python tools/bench_summary.py ${O}_ptime.json ;;
     pmc)
