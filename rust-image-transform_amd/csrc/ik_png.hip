@@ -770,10 +770,19 @@ __global__ __launch_bounds__(64) void k_png_wave(const PngImgDev* imgs, const Pn
     __shared__ __attribute__((aligned(16))) uint32_t s_win[kWaveWinWords];
     __shared__ uint32_t s_lit[1u << wave::kLB];
     __shared__ uint32_t s_dist[1u << wave::kDB];
-    __shared__ uint16_t s_lsym[288];
+    __shared__ uint16_t s_lsym[288];  // (read by the body too: sub_decode's slow codes)
     __shared__ uint16_t s_dsym[32];
-    __shared__ uint8_t s_lens[288 + 32];
     __shared__ wave::Code s_code[2];
+    // The code lengths live only inside wave_block_codes, which runs before the block's
+    // first window is staged and after the previous block's last one was read: they
+    // overlay the window.
+    uint8_t* const s_lens = reinterpret_cast<uint8_t*>(s_win);
+    static_assert(sizeof(s_win) >= 288 + 32, "the code lengths overlay the window");
+    // The LDS budget of a CU shared with the WebP coder (gfx950: 128 units of 1,280 B;
+    // ik_vp8x.hip asserts the coder's 24): 8 of these workgroups at 13 units each.
+    static_assert(sizeof(s_win) + sizeof(s_lit) + sizeof(s_dist) + sizeof(s_lsym) + sizeof(s_dsym) + sizeof(s_code) <=
+                      13 * 1280,
+                  "k_png_wave's LDS: 8 workgroups beside one k_vp8x_run workgroup on a CU");
     const int slot = blockIdx.x;
     if (slot >= nlanes) return;
     const int t = order ? (int)order[slot] : slot;
@@ -907,7 +916,7 @@ __global__ __launch_bounds__(64) void k_png_wave(const PngImgDev* imgs, const Pn
                     typedef uint32_t u4 __attribute__((ext_vector_type(4)));
                     const IK_GLOBAL u4* src = (const IK_GLOBAL u4*)(W + w0);
                     __syncthreads();  // the previous window's readers are done
-                    // 7 loads in flight per lane (a 12 KiB window is 13 per lane): two memory
+                    // 7 loads in flight per lane (a full window is 11 per lane): two memory
                     // latencies per window, not one per load
                     for (uint32_t k0 = (uint32_t)lane; k0 < nq; k0 += 7 * 64) {
                         u4 v[7];

@@ -54,10 +54,17 @@ constexpr uint32_t kLM = (1u << kLB) - 1u, kDM = (1u << kDB) - 1u;
 constexpr int kSub = 64;                // sub-lanes (one wave)
 constexpr int kWarmBits = 256;          // warm-up before a guessed sub-range start
 constexpr int kMinSubBits = 512;        // fewer sub-lanes for shorter ranges
-// stream bits of one window of a block's body (LDS staging): 12 KiB keeps the
-// wave's LDS at ~20 KB (8 waves per CU) at ~8 % more sub-lane steps than a
-// window holding a whole ~18 KB block
-constexpr uint64_t kWindowBits = 8ull * 12288;
+// stream bits of one window of a block's body (LDS staging), a multiple of 128 (the
+// staging moves 16-byte groups).  gfx950 allocates LDS in units of 1,280 B, 128 to a
+// CU: 10.25 KiB keeps the wave decoder's workgroup at 13 units, so that 8 of them
+// and one workgroup of the WebP coder (k_vp8x_run, 24 units) are resident on a CU
+// together (ik_png.hip asserts the budget).  A 12 KiB window took 15
+// units: beside the coder a CU then held 6 decoder waves, not 8.
+#ifndef IK_WAVE_WINDOW_BYTES
+#define IK_WAVE_WINDOW_BYTES 10496
+#endif
+constexpr uint64_t kWindowBits = 8ull * IK_WAVE_WINDOW_BYTES;
+static_assert(kWindowBits % 128 == 0, "windows are staged in 16-byte groups");
 
 // literal/length entry (u32):
 //   bits 0..4   bits consumed by the entry's symbols (0: slow / invalid)
@@ -415,7 +422,9 @@ IK_HD uint64_t window_end(uint64_t bp, uint64_t stop_eff, uint64_t est_end) {
 // (a quarter token per bit, plus each window's rounding; `big`: a token per bit,
 // the bound, for a lane whose region overflowed)
 IK_HD uint64_t region_capacity(uint64_t bits, bool big) {
-    const uint64_t slack = (bits / kWindowBits + 2) * 3072 + 64;
+    // (per window: 48 tokens of rounding per sub-lane -- the odd word count, split_range's
+    // + 32 and the group of 8 -- whatever the window's size; the window count follows it)
+    const uint64_t slack = (bits / kWindowBits + 2) * (48ull * kSub) + 64;
     const uint64_t c = big ? bits + 32ull * pieces_capacity(bits) + slack : bits / 8 * 3 + slack;
     return (c + 7) & ~7ull;  // (regions start 16-byte aligned: whole groups of 8 tokens)
 }

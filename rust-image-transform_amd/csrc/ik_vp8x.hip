@@ -1058,6 +1058,12 @@ __global__ __launch_bounds__(kNT) void k_vp8x_run(XArgs a, XRun r) {
     __shared__ XLds S;
     __shared__ uint64_t s_task;
     __shared__ int s_ok;
+#ifndef IK_VP8X_STAMPS
+    // gfx950 allocates LDS in units of 1,280 B, 128 to a CU: at 24 units this workgroup
+    // shares a CU with 8 workgroups of the PNG wave decoder (ik_png.hip: 13 each)
+    static_assert(sizeof(XLds) + sizeof(uint64_t) + sizeof(int) <= 24 * 1280,
+                  "k_vp8x_run's LDS: one workgroup beside 8 k_png_wave workgroups on a CU");
+#endif
     const int l = threadIdx.x;
     const int nmb = a.mb_w * a.mb_h;
     uint32_t* err = r.sync + 1;
