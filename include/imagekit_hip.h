@@ -149,9 +149,10 @@ int ik_decode_batch(const uint8_t *const *bytes, const size_t *lens, uint32_t n,
 /* PNG decoding on the GPU (ik_decode / ik_decode_batch / ik_transform*): streams
  * whose filtered image data is at least min_raw_bytes are inflated and unfiltered
  * on the GPU (parallel DEFLATE over block-start candidates, row-wavefront
- * unfilter), every non-interlaced colour type included (palette, low bit depths,
- * tRNS, 16-bit); smaller ones, interlaced (Adam7) streams and any the GPU finds
- * inconsistent use the host decoder.  -1 = host decoder only.  Default 256 KiB
+ * unfilter), every colour type included (palette, low bit depths, tRNS, 16-bit),
+ * interlaced (Adam7) streams too: their seven pass images are unfiltered side by
+ * side and gathered into the image by one more kernel; smaller ones and any the
+ * GPU finds inconsistent use the host decoder.  -1 = host decoder only.  Default 256 KiB
  * (IK_PNG_GPU_MIN; IK_PNG_GPU=0 = off). */
 int ik_set_png_gpu_min(long long min_raw_bytes);
 /* the last GPU PNG batch finished on the calling thread's device (n <= 17 values):
@@ -178,6 +179,13 @@ int ik_batch_last_timing(double *out, int n);
 /* process-wide counts of PNG streams decoded since load: out[0] by the GPU path,
  * out[1] by the host decoder (outside the GPU path, or rejected by it) */
 int ik_png_counters(unsigned long long *out);
+/* the Adam7 pass table of a w x h image of bits_pp bits per pixel, as the GPU
+ * decoder lays an interlaced stream out (no GPU needed): for each non-empty pass,
+ * in stream order, 8 values in out (room for 7 x 8; may be NULL): x0, y0, dx, dy,
+ * pass width, pass height, row bytes, offset of the pass's first filter byte in
+ * the inflated stream; *raw_total (may be NULL) = the inflated length.  Returns
+ * the number of non-empty passes. */
+int ik_png_adam7_plan(uint32_t w, uint32_t h, int bits_pp, uint64_t *out, uint64_t *raw_total);
 /* process-wide JPEG counters: out[0] = streams whose entropy decoding ran on the
  * GPU (restart intervals or self-synchronising scans), out[1] = on the host */
 int ik_jpeg_counters(unsigned long long *out);

@@ -39,6 +39,7 @@ struct PngImgDev {
     uint8_t* dst;            // the image (pitched); filtered rows, then pixels in place
     size_t pitch;
     const int* flags;        // the image's resolve flags: 1 bad filter type, 2 bad marker, 4 Average/Paeth rows
+    uint64_t raw0;           // first filter byte of its rows in the stream's inflated bytes (an Adam7 pass; else 0)
 };
 
 struct PngLaneDev {
@@ -157,6 +158,29 @@ hipError_t launch_png_wave(const PngImgDev* imgs, const PngLaneDev* lanes, const
 hipError_t launch_png_units(const PngImgDev* imgs, const PngLaneDev* lanes, int n, const uint2* units,
                             uint32_t* ulane, hipStream_t s);
 hipError_t launch_png_resolve(const PngImgDev* imgs, const int2* rows, int nrows, int* err, hipStream_t s);
+
+// Adam7 (k_png_adam7): an interlaced stream's unfiltered pass images (each an image
+// entry of its own for resolve and the unfilter, rows at pass[p].pitch) gathered
+// into the rows of the equivalent non-interlaced image: rowbytes bytes a row at the
+// file's bit depth (bits per pixel: 1, 2, 4, 8, 16, 24, 32, 48, 64).  A workgroup
+// takes one segment (kA7Threads units of 16 bytes; 48 for 3- and 6-byte pixels, a
+// whole number of pixels) of one output row; blk0 is the image's first workgroup
+// of the launch, nseg its segments per row.
+constexpr int kA7Threads = 256;
+IK_HD int png_adam7_unit_bytes(int bits_pp) { return bits_pp == 24 || bits_pp == 48 ? 48 : 16; }
+struct PngA7Dev {
+    uint8_t* dst;
+    size_t pitch;
+    uint32_t blk0, nseg;
+    int w, h, rowbytes, bits;
+    struct Pass {
+        const uint8_t* src;  // nullptr: the pass is empty
+        size_t pitch;
+        int rowbytes, ph;
+    } pass[7];
+};
+// one launch for the n images (nblocks workgroups in all)
+hipError_t launch_png_adam7(const PngA7Dev* imgs, int n, uint32_t nblocks, hipStream_t s);
 // groups[t] = (image, band group) of the workgroup holding ticket t; prog: one
 // zeroed counter per band (the image's at prog_base[image]); ticket: zeroed
 // The unfilter's scan path (k_png_unfilter_su): an RGBA8 image without Average /

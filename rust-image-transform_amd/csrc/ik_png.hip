@@ -30,6 +30,9 @@
 //                   first row reads the previous band's last row from memory once
 //                   it is published (global progress counters, agent-scope
 //                   release/acquire; workgroups ordered by a start ticket).
+//   k_png_adam7     interlaced streams: their seven pass images (each resolved and
+//                   unfiltered as an image of its own) -> the rows of the whole
+//                   image, a row segment per workgroup staged through LDS
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -1517,7 +1520,7 @@ __global__ __launch_bounds__(256) void k_png_resolve(const PngImgDev* imgs, cons
     const int2 ir = rows[rr];
     const PngImgDev I = imgs[ir.x];
     const int y = ir.y;
-    const int64_t rs = (int64_t)y * (I.rowbytes + 1);  // filter byte of row y
+    const int64_t rs = (int64_t)I.raw0 + (int64_t)y * (I.rowbytes + 1);  // filter byte of row y
     __shared__ int64_t s_hlo, s_hhi;  // the output range of the unit holding the row's first symbol
     if (threadIdx.x == 0) s_cnt = 0;
     __syncthreads();
@@ -2162,6 +2165,135 @@ hipError_t launch_png_walk(const uint64_t* files, const uint64_t* lens, int n, P
                            int* out_n, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_png_walk, dim3((unsigned)n), dim3(64), 0, s, files, lens, recs, side, out_n);
+    return hipGetLastError();
+}
+
+// ---- Adam7 --------------------------------------------------------------------------
+// The unfiltered pass images of an interlaced stream -> the rows of the equivalent
+// non-interlaced image.  A workgroup takes one segment of one output row: 256 units
+// of 16 bytes (48 for 3- and 6-byte pixels), i.e. a multiple of 8 pixels from a
+// multiple of 8, so the segment's share of pass p's row is one contiguous, 16-byte
+// aligned run of (segment bytes >> log2 dx) bytes.  Odd rows are pass 7's rows as
+// they are: copied chunk by chunk.  An even row interleaves two to four passes whose
+// runs add up to exactly the segment's size: they are staged into LDS by coalesced
+// 16-byte loads (0-based pass p: its run is SEG >> (3 - p / 2) bytes long and starts
+// at 0 for even p, at its own length for odd p -- rows 0 mod 8 hold passes 0 1 3 5
+// at 0, 1/8, 1/4, 1/2 of the segment, rows 4 mod 8 passes 2 3 5, rows 2 mod 4
+// passes 4 5), and each thread then assembles its unit from LDS (pixel x of the row: pass by the 8 x 8
+// pattern, source pixel x >> log2 dx) and stores whole 16-byte chunks.
+__device__ __forceinline__ int a7_pass(uint32_t xr, int yr) {  // 0-based pass of pixel (x & 7, y & 7)
+    if (yr & 1) return 6;
+    if (xr & 1) return 5;
+    if (yr & 2) return 4;
+    if (xr & 2) return 3;
+    if (yr & 4) return 2;
+    return (xr & 4) ? 1 : 0;
+}
+
+template <int BITS>
+__device__ __forceinline__ void a7_row(const PngA7Dev& I, int y, uint32_t seg, uint8_t* lds) {
+    constexpr int UB = BITS == 24 || BITS == 48 ? 48 : 16;  // png_adam7_unit_bytes
+    constexpr uint32_t SEG = kA7Threads * UB;
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    const uint32_t tid = threadIdx.x;
+    const size_t ub = (size_t)seg * SEG + (size_t)tid * UB;  // this thread's unit in the output row
+    IK_GLOBAL uint8_t* const drow = (IK_GLOBAL uint8_t*)(I.dst + (size_t)y * I.pitch);
+    if (y & 1) {
+        const IK_GLOBAL uint8_t* srow = (const IK_GLOBAL uint8_t*)(I.pass[6].src + (size_t)(y >> 1) * I.pass[6].pitch);
+#pragma unroll
+        for (int c = 0; c < UB / 16; ++c)
+            if (ub + 16 * c < (size_t)I.rowbytes) *(IK_GLOBAL u4*)(drow + ub + 16 * c) = *(const IK_GLOBAL u4*)(srow + ub + 16 * c);
+        return;
+    }
+    const int yr = y & 7;
+#pragma unroll
+    for (int p = 0; p < 6; ++p) {
+        const int ldx = 3 - (p >> 1), ldy = p < 3 ? 3 : p < 5 ? 2 : 1, y0 = p == 2 ? 4 : p == 4 ? 2 : 0;
+        if ((yr - y0) & ((1 << ldy) - 1)) continue;  // (uniform) the pass has no pixel in this row
+        const uint32_t len = SEG >> ldx, ro = (p & 1) ? len : 0u;
+        const size_t s0 = ((size_t)seg * SEG) >> ldx;  // the segment's first byte in the pass row
+        const IK_GLOBAL uint8_t* srow = (const IK_GLOBAL uint8_t*)(I.pass[p].src + (size_t)(y >> ldy) * I.pass[p].pitch);
+        for (uint32_t b = tid * 16; b < len; b += kA7Threads * 16) {
+            u4 v = {0, 0, 0, 0};
+            if (I.pass[p].src && s0 + b < (size_t)I.pass[p].rowbytes) v = *(const IK_GLOBAL u4*)(srow + s0 + b);
+            *reinterpret_cast<u4*>(lds + ro + b) = v;
+        }
+    }
+    __syncthreads();
+    uint32_t o[UB / 4];
+#pragma unroll
+    for (int k = 0; k < UB / 4; ++k) o[k] = 0;
+    if constexpr (BITS >= 8) {
+        constexpr int BPP = BITS / 8, NPX = UB / BPP;
+        constexpr int E = BPP % 4 == 0 ? 4 : BPP % 2 == 0 ? 2 : 1;  // bytes per LDS read
+#pragma unroll
+        for (int i = 0; i < NPX; ++i) {
+            const uint32_t xl = tid * NPX + i;  // pixel of the segment (which starts at a multiple of 8)
+            const int p = a7_pass(xl & 7u, yr), ldx = 3 - (p >> 1);
+            const uint32_t a = ((p & 1) ? SEG >> ldx : 0u) + (xl >> ldx) * BPP;
+#pragma unroll
+            for (int k = 0; k < BPP / E; ++k) {
+                const int pos = i * BPP + k * E;
+                uint32_t v;
+                if constexpr (E == 4) v = *reinterpret_cast<const uint32_t*>(lds + a + 4 * k);
+                else if constexpr (E == 2) v = *reinterpret_cast<const uint16_t*>(lds + a + 2 * k);
+                else v = lds[a + k];
+                o[pos >> 2] |= v << (8 * (pos & 3));
+            }
+        }
+    } else {
+        constexpr int F = 8 / BITS;  // MSB-first fields per byte
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            uint32_t byte = 0;
+#pragma unroll
+            for (int f = 0; f < F; ++f) {
+                const uint32_t xl = (tid * 16 + j) * F + f;
+                const int p = a7_pass(xl & 7u, yr), ldx = 3 - (p >> 1);
+                const uint32_t sb = (xl >> ldx) * BITS;  // bit offset of the source field in the pass's run
+                const uint32_t v = ((uint32_t)lds[((p & 1) ? SEG >> ldx : 0u) + (sb >> 3)] >> (8 - BITS - (sb & 7u))) & ((1u << BITS) - 1u);
+                byte |= v << (8 - BITS - f * BITS);
+            }
+            o[j >> 2] |= byte << (8 * (j & 3));
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < UB / 16; ++c)
+        if (ub + 16 * c < (size_t)I.rowbytes)
+            *(IK_GLOBAL u4*)(drow + ub + 16 * c) = u4{o[4 * c], o[4 * c + 1], o[4 * c + 2], o[4 * c + 3]};
+}
+
+__global__ __launch_bounds__(kA7Threads) void k_png_adam7(const PngA7Dev* imgs, int n) {
+    raise_priority();
+    __shared__ __attribute__((aligned(16))) uint8_t s_run[kA7Threads * 48];
+    int lo = 0, hi = n - 1;  // (uniform) the image holding this workgroup: the last with blk0 <= blockIdx.x
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (imgs[mid].blk0 <= blockIdx.x) lo = mid;
+        else hi = mid - 1;
+    }
+    const PngA7Dev& I = imgs[lo];
+    const uint32_t r = blockIdx.x - I.blk0;
+    const int y = (int)(r / I.nseg);
+    const uint32_t seg = r % I.nseg;
+    if (y >= I.h) return;
+    switch (I.bits) {
+    case 1: a7_row<1>(I, y, seg, s_run); break;
+    case 2: a7_row<2>(I, y, seg, s_run); break;
+    case 4: a7_row<4>(I, y, seg, s_run); break;
+    case 8: a7_row<8>(I, y, seg, s_run); break;
+    case 16: a7_row<16>(I, y, seg, s_run); break;
+    case 24: a7_row<24>(I, y, seg, s_run); break;
+    case 32: a7_row<32>(I, y, seg, s_run); break;
+    case 48: a7_row<48>(I, y, seg, s_run); break;
+    case 64: a7_row<64>(I, y, seg, s_run); break;
+    default: break;
+    }
+}
+
+hipError_t launch_png_adam7(const PngA7Dev* imgs, int n, uint32_t nblocks, hipStream_t s) {
+    if (n <= 0 || !nblocks) return hipSuccess;
+    hipLaunchKernelGGL(k_png_adam7, dim3(nblocks), dim3(kA7Threads), 0, s, imgs, n);
     return hipGetLastError();
 }
 

@@ -11,11 +11,15 @@
 //          predecessor decodes on)
 //   GPU    k_png_expand (tokens -> u16 symbols + window markers), k_png_resolve
 //          (filtered rows into the image, markers followed), k_png_unfilter
-// The GPU path covers non-interlaced 8-bit streams of every colour type, palette
-// and gray streams of 1/2/4 bits, and tRNS (png's EXPAND: k_png_px); 16-bit and
-// interlaced streams, and any stream the GPU finds inconsistent, go through the
-// host decoder, whose error messages are png's.  The zlib Adler-32 is not verified, as png 0.18 does
-// not by default (CRCs cover the data).
+//   GPU    interlaced (Adam7) streams: resolve and unfilter take each of the
+//          stream's pass images as an image of its own (ik_png_plan.h adam7_plan:
+//          its rows, filter types and place in the inflated bytes), and
+//          k_png_adam7 gathers them into the rows of the whole image
+// The GPU path covers 8- and 16-bit streams of every colour type, palette and gray
+// streams of 1/2/4 bits, and tRNS (png's EXPAND: k_png_px), interlaced or not; any
+// stream the GPU finds inconsistent (and an interlace method above 1) goes through
+// the host decoder, whose error messages are png's.  The zlib Adler-32 is not
+// verified, as png 0.18 does not by default (CRCs cover the data).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -70,6 +74,15 @@ struct PngJob {
     int out_c = 0;
     PngPxDev px{};
     ik_image* rows = nullptr;
+    // Adam7: the stream's bytes are npass pass images (ik_png_plan.h adam7_plan),
+    // each an image entry of its own from entry pass_e0 on, unfiltered in `stage`
+    // (one pooled block; pass_off[q]: pass q's rows in it) and gathered into
+    // rows / img by k_png_adam7
+    bool interlaced = false;
+    int bits_pp = 0, npass = 0, pass_e0 = 0;
+    pngplan::Adam7Pass pass[7];
+    size_t pass_off[7] = {};
+    ik_image* stage = nullptr;
 };
 
 // One chunk as parse_chunks sees it: its type, its data where the host can read
@@ -164,7 +177,8 @@ bool parse_chunks(const std::vector<ChunkRef>& C, PngJob& J) {
             break;
         }
     }
-    if (!ihdr || J.idat.empty() || !J.w || !J.h || interlace) return false;
+    // (interlace > 1: the host decoder reports png's error)
+    if (!ihdr || J.idat.empty() || !J.w || !J.h || interlace > 1) return false;
     // 8-bit L / LA / RGB / RGBA as they are; palette (1/2/4/8 bits), gray below 8
     // bits and tRNS through png's EXPAND on the GPU (k_png_px); 16-bit: host
     int spp;
@@ -223,6 +237,9 @@ bool parse_chunks(const std::vector<ChunkRef>& C, PngJob& J) {
     if ((uint64_t)J.w * J.h * J.out_c * (d16 ? 2 : 1) > (512ull << 20) || rb > 0x7FFFFFF0ull) return false;
     J.rowbytes = (int)rb;
     J.raw_total = (rb + 1) * J.h;
+    J.bits_pp = (int)bits_pp;
+    J.interlaced = interlace == 1;
+    if (J.interlaced) J.npass = pngplan::adam7_plan(J.w, J.h, J.bits_pp, J.pass, &J.raw_total);
     // zlib header: CM 8, window <= 32 KiB, FCHECK, no preset dictionary
     uint8_t cmf, flg;
     if (zl0 >= 2) { cmf = zh[0][0]; flg = zh[0][1]; }
@@ -536,9 +553,15 @@ struct PngBatchState {
 // their 164 M markers per 64 frames (3.8 % of the bytes, near every unit start) cost
 // expand 3.9 ms of list writes and byte stores and k_png_marks 3.1 ms, against the
 // resolve pass's 4.3 ms (profiles/r05_ab_notes.md).
+// The direct rows know one image per stream (k_png_expand8 and k_png_marks place a
+// byte by position / (rowbytes + 1), without PngImgDev::raw0), so with the switch
+// set interlaced (Adam7) streams go to the host decoder (png_takes below).
 static bool png_direct_rows() {
     static const bool v = getenv("IK_PNG_DIRECT") != nullptr;
     return v;
+}
+static bool png_takes(const PngJob& j) {
+    return png_gpu_enabled(j.raw_total) && !(j.interlaced && png_direct_rows());
 }
 
 bool png_find_beside_decode() {
@@ -620,14 +643,13 @@ int png_upload_begin(const uint8_t* const* bytes, const size_t* lens, int n, Png
             // (a file shorter than the signature, or without it, goes to the host decoder)
             S.gpu[i] = lens[i] >= 8 && up.heads && !std::memcmp(up.heads[i], "\x89PNG\r\n\x1a\n", 8) &&
                        walk_chunks(recs + (size_t)i * kPngWalkRecs, cnt[i], side + (size_t)i * kPngWalkSide, cr) &&
-                       parse_chunks(cr, S.jobs[i]) && png_gpu_enabled(S.jobs[i].raw_total);
+                       parse_chunks(cr, S.jobs[i]) && png_takes(S.jobs[i]);
         });
     } else {
         parallel_for(n, 0, [&](int i) {
             S.jobs[i].idx = i;
             thread_local std::vector<ChunkRef> cr;
-            S.gpu[i] = host_chunks(bytes[i], lens[i], cr) && parse_chunks(cr, S.jobs[i]) &&
-                       png_gpu_enabled(S.jobs[i].raw_total);
+            S.gpu[i] = host_chunks(bytes[i], lens[i], cr) && parse_chunks(cr, S.jobs[i]) && png_takes(S.jobs[i]);
         });
     }
     for (int i = 0; i < n; ++i)
@@ -856,16 +878,26 @@ int png_decode_finish(PngUpload& up, ik_image** outs, int* status, std::string* 
         // ---- the kernel stage's work area (this thread's) ----
         size_t total = 0;
         const int nchunks = S.nchunks;
+        // image entries: one per stream, then one per pass image of the interlaced
+        // streams (a batch without those: M == m, n_il == 0, and nothing below differs)
+        int M = m, n_il = 0;
         for (PngJob* j : J) {
+            size_t ftb = j->h;  // filter types: one per row of the image, or of its pass images
+            if (j->interlaced) {
+                ftb = 0;
+                for (int q = 0; q < j->npass; ++q) ftb += j->pass[q].ph;
+                M += j->npass;
+                ++n_il;
+            }
             j->o_u16 = total;
             total += up256(2 * (j->raw_total + 64));
             j->o_ft = total;
-            total += up256(j->h);
+            total += up256(ftb);
         }
         const size_t o_imgs = total;
-        total += up256(sizeof(PngImgDev) * m);
+        total += up256(sizeof(PngImgDev) * M);
         const size_t o_err = total;
-        total += up256(sizeof(int) * m);
+        total += up256(sizeof(int) * M);
         const size_t o_dyn = total;  // lane tables, results, obase, rows, subtables: sized per round below
         // the work area: lane tables (bounded by the chunk count), row / page
         // tables, unfilter class descriptors, and the token area: a quarter token
@@ -890,19 +922,24 @@ int png_decode_finish(PngUpload& up, ik_image** outs, int* status, std::string* 
         const size_t pieces_bytes = up256(sizeof(uint2) * pieces_total);  // (twice: pieces, unit records)
         size_t dyn = up256(sizeof(PngLaneDev) * max_lanes) + up256(sizeof(infl::LaneResult) * max_lanes) +
                      up256(sizeof(int64_t) * max_lanes) + up256(2 * sizeof(int) * max_lanes) +
-                     up256(sizeof(uint32_t) * max_lanes) + up256(sizeof(PngImgDev) * m);
+                     up256(sizeof(uint32_t) * max_lanes) + up256(sizeof(PngImgDev) * M);
         size_t nrows = 0, npages = 0, nbands = 0, ngroups = 0;
         for (PngJob* j : J) {
-            nrows += j->h;
             npages += (j->raw_total >> kPngPageShift) + 1;
-            nbands += ((size_t)j->h + 63) / 64;
-            ngroups += (size_t)png_unfilter_groups((int)j->h);
+            // (resolve and the unfilter take an interlaced stream pass image by pass image)
+            for (int q = 0; q < (j->interlaced ? j->npass : 1); ++q) {
+                const uint32_t hq = j->interlaced ? j->pass[q].ph : j->h;
+                nrows += hq;
+                nbands += ((size_t)hq + 63) / 64;
+                ngroups += (size_t)png_unfilter_groups((int)hq);
+            }
         }
         // unfilter: band-group table + per-image band offsets (staged), then one
         // progress counter per band and one ticket per class (zeroed)
-        const size_t unf_tab = up256(sizeof(int2) * ngroups) + up256(sizeof(int) * m);
+        const size_t unf_tab = up256(sizeof(int2) * ngroups) + up256(sizeof(int) * M);
         const size_t unf_zero = up256(sizeof(unsigned) * (nbands + 8));
-        dyn += up256(sizeof(int2) * nrows) + up256(sizeof(int) * npages) + unf_tab + unf_zero + 2 * pieces_bytes +
+        const size_t a7_tab = up256(sizeof(PngA7Dev) * n_il);  // k_png_adam7's image table
+        dyn += up256(sizeof(int2) * nrows) + up256(sizeof(int) * npages) + unf_tab + unf_zero + a7_tab + 2 * pieces_bytes +
                up256(2 * tok_total);
         uint8_t* dev = scratch_slot(2, o_dyn + dyn);
         if (!dev) rc = fail(IK_ERR_DEVICE, "cannot allocate the PNG batch work area (%zu bytes)", o_dyn + dyn);
@@ -915,6 +952,7 @@ int png_decode_finish(PngUpload& up, ik_image** outs, int* status, std::string* 
         int2* d_rows = nullptr;
         int* d_pages = nullptr;
         uint8_t* d_unf = nullptr;
+        PngA7Dev* d_a7 = nullptr;
         uint2* d_pieces = nullptr;
         uint2* d_units = nullptr;  // the wave decoder's expand-unit records (slots parallel to d_pieces)
         uint16_t* d_tok = nullptr;
@@ -931,13 +969,15 @@ int png_decode_finish(PngUpload& up, ik_image** outs, int* status, std::string* 
             d_order = reinterpret_cast<uint32_t*>(dev + o);
             o += up256(sizeof(uint32_t) * max_lanes);
             d_cls = reinterpret_cast<PngImgDev*>(dev + o);
-            o += up256(sizeof(PngImgDev) * m);
+            o += up256(sizeof(PngImgDev) * M);
             d_rows = reinterpret_cast<int2*>(dev + o);
             o += up256(sizeof(int2) * nrows);
             d_pages = reinterpret_cast<int*>(dev + o);
             o += up256(sizeof(int) * npages);
             d_unf = dev + o;
             o += unf_tab + unf_zero;
+            d_a7 = reinterpret_cast<PngA7Dev*>(dev + o);
+            o += a7_tab;
             d_pieces = pieces_bytes ? reinterpret_cast<uint2*>(dev + o) : nullptr;
             o += pieces_bytes;
             d_units = pieces_bytes ? reinterpret_cast<uint2*>(dev + o) : nullptr;
@@ -955,13 +995,15 @@ int png_decode_finish(PngUpload& up, ik_image** outs, int* status, std::string* 
         if (!rc && !X.init(2 * sizeof(PngLaneDev) * max_lanes + sizeof(infl::LaneResult) * max_lanes +
                                sizeof(int64_t) * (max_lanes + nchunks) + 3 * sizeof(int) * max_lanes +
                                2 * sizeof(int) * max_units +
-                               sizeof(int2) * (nrows + ngroups) + sizeof(int) * (npages + 4 * m) +
-                               3 * sizeof(PngImgDev) * m + 2 * sizeof(int) * nchunks + (64u << 10), s))
+                               sizeof(int2) * (nrows + ngroups) + sizeof(int) * (npages + 4 * M) +
+                               3 * sizeof(PngImgDev) * M + sizeof(PngA7Dev) * n_il + 512 * (n_il ? 1 : 0) +
+                               2 * sizeof(int) * nchunks + (64u << 10), s))
             rc = fail(IK_ERR_NOMEM, "cannot allocate pinned PNG transfer area");
         // the kernels run under the device's kernel gate (ik_runtime.h)
         gate_enter(kGateKernels);
         // ---- image descriptors ----
         std::vector<PngImgDev> hd(m);
+        hd.reserve(M);  // (the pass images' entries are appended once their streams are verified)
         // the large host tables are kept per thread between batches (clear() keeps
         // the capacity): fresh multi-MB vectors cost page faults every batch
         static thread_local HostTables ht;
@@ -1276,6 +1318,20 @@ int png_decode_finish(PngUpload& up, ik_image** outs, int* status, std::string* 
                 reject(j, "image allocation");
                 continue;
             }
+            if (j.interlaced) {
+                // the pass images' rows: one block from the image pool, each pass pitched
+                // and padded as alloc_image would (resolve stores whole 16-byte chunks,
+                // the unfilter reads its rows through a buffer descriptor)
+                size_t sb = 0;
+                for (int q = 0; q < j.npass; ++q) {
+                    j.pass_off[q] = sb;
+                    sb += pitch_for((uint32_t)j.pass[q].rowbytes, 1) * (size_t)j.pass[q].ph;
+                }
+                if (alloc_image(256, (uint32_t)(sb / 256), 1, &j.stage)) {
+                    reject(j, "image allocation");
+                    continue;
+                }
+            }
             hd[k].obase = d_obase + hob.size();  // (the wave decoder's: its unit table, set below)
             hd[k].page_lane = d_pages + npg;  // (the page table itself is built while expand runs)
             hd[k].nlanes = (int)ob.size();
@@ -1337,21 +1393,70 @@ int png_decode_finish(PngUpload& up, ik_image** outs, int* status, std::string* 
                 }
             }
         }
+        // the pass images of the verified interlaced streams: entries of their own
+        // behind the streams' (the stream's symbols, unit offsets and page table; their
+        // own rows, filter types, flags and place in the inflated bytes), and
+        // k_png_adam7's table of them
+        std::vector<PngA7Dev> ha7;
+        uint32_t a7_blocks = 0;
+        for (const auto& q : pj) {
+            PngJob& j = *J[q.first];
+            if (rc || !j.interlaced) continue;
+            j.pass_e0 = (int)hd.size();
+            PngA7Dev a{};
+            a.dst = hd[q.first].dst;
+            a.pitch = hd[q.first].pitch;
+            a.w = (int)j.w;
+            a.h = (int)j.h;
+            a.rowbytes = j.rowbytes;
+            a.bits = j.bits_pp;
+            a.nseg = (uint32_t)((j.rowbytes + kA7Threads * png_adam7_unit_bytes(j.bits_pp) - 1) /
+                                (kA7Threads * png_adam7_unit_bytes(j.bits_pp)));
+            a.blk0 = a7_blocks;
+            a7_blocks += a.nseg * j.h;
+            size_t fo = 0;
+            for (int t = 0; t < j.npass; ++t) {
+                const pngplan::Adam7Pass& P = j.pass[t];
+                PngImgDev d = hd[q.first];
+                d.raw0 = P.raw_off;
+                d.rowbytes = (int)P.rowbytes;
+                d.H = (int)P.ph;
+                d.ft = dev + j.o_ft + fo;
+                d.dst = j.stage->d + j.pass_off[t];
+                d.pitch = pitch_for((uint32_t)P.rowbytes, 1);
+                d.flags = reinterpret_cast<const int*>(dev + o_err) + hd.size();
+                fo += P.ph;
+                a.pass[P.pass].src = d.dst;
+                a.pass[P.pass].pitch = d.pitch;
+                a.pass[P.pass].rowbytes = d.rowbytes;
+                a.pass[P.pass].ph = d.H;
+                hd.push_back(d);
+            }
+            ha7.push_back(a);
+        }
+        const int ne = (int)hd.size();  // image entries in use
+        // entry -> the job whose rows the unfilter takes from it (-1: an interlaced stream's own entry)
+        std::vector<int> unf_job(ne, -1);
+        for (int k = 0; k < m; ++k)
+            if (!J[k]->interlaced) unf_job[k] = k;
+        for (const auto& q : pj)
+            if (!rc && J[q.first]->interlaced)
+                for (int t = 0; t < J[q.first]->npass; ++t) unf_job[J[q.first]->pass_e0 + t] = q.first;
         const size_t nexp = wavedec ? (size_t)nunits : hl.size();  // expand waves: units, or lanes
         mk[1] = now_ms();  // offsets, images, page tables, lane table built
         std::vector<int2>& hrows = ht.rows;
         std::vector<int>& hxst = ht.xst;
         hrows.clear();
         hxst.clear();
-        std::vector<int> herr(m, 0);
+        std::vector<int> herr(ne, 0);
         if (!rc && !hl.empty()) {
             // expand goes out first; the resolve pass's page and row tables are built
             // on the host while it runs (stream order puts their uploads after it)
             const size_t lb = sizeof(PngLaneDev) * hl.size();
             hipError_t ue = X.h2d(d_lanes, hl.data(), lb);
             if (ue == hipSuccess) ue = X.h2d(d_obase, hob.data(), sizeof(int64_t) * hob.size());
-            if (ue == hipSuccess) ue = X.h2d(dev + o_imgs, hd.data(), sizeof(PngImgDev) * m);
-            if (ue == hipSuccess) ue = hipMemsetAsync(dev + o_err, 0, sizeof(int) * m, s);
+            if (ue == hipSuccess) ue = X.h2d(dev + o_imgs, hd.data(), sizeof(PngImgDev) * ne);
+            if (ue == hipSuccess) ue = hipMemsetAsync(dev + o_err, 0, sizeof(int) * ne, s);
             if (ue == hipSuccess && marks.count) ue = hipMemsetAsync(marks.count, 0, sizeof(uint32_t) * kMarkLists, s);
             if (ue != hipSuccess) rc = hip_fail(ue, "PNG expand tables");
             hxst.resize(2 * nexp);
@@ -1388,6 +1493,11 @@ int png_decode_finish(PngUpload& up, ik_image** outs, int* status, std::string* 
                             hpages.push_back((int)ln);
                         }
                     }
+                    if (j.interlaced) {  // pass rows: (pass-image entry, row of the pass)
+                        for (int t = 0; t < j.npass; ++t)
+                            for (uint32_t y = 0; y < j.pass[t].ph; ++y) hrows.push_back(make_int2(j.pass_e0 + t, (int)y));
+                        continue;
+                    }
                     for (uint32_t y = 0; y < j.h; ++y) hrows.push_back(make_int2(q.first, (int)y));
                 }
                 if (e3 == hipSuccess && !wavedec) e3 = X.h2d(d_pages, hpages.data(), sizeof(int) * hpages.size());
@@ -1416,8 +1526,8 @@ int png_decode_finish(PngUpload& up, ik_image** outs, int* status, std::string* 
                         int band0 = 0;
                         for (int bpp : {1, 2, 3, 4, 6, 8}) {
                             const Range r{bpp, (int)cls.size(), (int)groups.size()};
-                            for (int k = 0; k < m; ++k)
-                                if (J[k]->state == 1 && hd[k].bpp == bpp) {
+                            for (int k = 0; k < ne; ++k)
+                                if (unf_job[k] >= 0 && J[unf_job[k]]->state == 1 && hd[k].bpp == bpp) {
                                     for (int g = 0; g < png_unfilter_groups(hd[k].H); ++g)
                                         groups.push_back(make_int2((int)cls.size() - r.img0, g));
                                     pbase.push_back(band0);
@@ -1467,6 +1577,11 @@ int png_decode_finish(PngUpload& up, ik_image** outs, int* status, std::string* 
                             }
                         }
                     }
+                    // the interlaced streams' pass images into their rows (one launch)
+                    if (e3 == hipSuccess && !ha7.empty()) {
+                        e3 = X.h2d(d_a7, ha7.data(), sizeof(PngA7Dev) * ha7.size());
+                        if (e3 == hipSuccess) e3 = launch_png_adam7(d_a7, (int)ha7.size(), a7_blocks, s);
+                    }
                     // png's EXPAND for the palette / low-bit / tRNS images
                     for (int k = 0; k < m && e3 == hipSuccess; ++k) {
                         PngJob& j = *J[k];
@@ -1515,14 +1630,15 @@ int png_decode_finish(PngUpload& up, ik_image** outs, int* status, std::string* 
                     // the marker list overflowed (runs of copies across units, e.g. a flat
                     // image): the rows from the u16 symbols after all, then the unfilter again
                     if (timing) fprintf(stderr, "[png] %u window markers > list %u: resolve pass\n", nmarks, marks.cap);
-                    e3 = hipMemsetAsync(dev + o_err, 0, sizeof(int) * m, s);
+                    e3 = hipMemsetAsync(dev + o_err, 0, sizeof(int) * ne, s);
                     if (e3 == hipSuccess)
                         e3 = launch_png_resolve(d_imgs, d_rows, (int)hrows.size(), reinterpret_cast<int*>(dev + o_err), s);
                     e3 = unfilter_all(e3);
                 }
                 if (timing && marks.count) fprintf(stderr, "[png] window markers %u (list %u)\n", nmarks, marks.cap);
                 if (e3 == hipSuccess) e3 = X.d2h(hxst.data(), wavedec ? d_uxst : d_xst, 2 * sizeof(int) * nexp);
-                if (e3 == hipSuccess) e3 = X.d2h(herr.data(), dev + o_err, sizeof(int) * m);
+                if (e3 == hipSuccess) e3 = X.d2h(herr.data(), dev + o_err, sizeof(int) * ne);
+                for (int k = m; k < ne; ++k) herr[unf_job[k]] |= herr[k];  // a pass image's flags are its stream's
                 mk[3] = now_ms();  // expand .. unfilter done
                 if (e3 != hipSuccess) rc = hip_fail(e3, "PNG inflate (expand) / unfilter");
                 if (!rc) {
@@ -1596,6 +1712,7 @@ int png_decode_finish(PngUpload& up, ik_image** outs, int* status, std::string* 
         for (int k = 0; k < m; ++k) {
             PngJob& j = *J[k];
             if (j.rows) { ik_image_free(j.rows); j.rows = nullptr; }
+            if (j.stage) { ik_image_free(j.stage); j.stage = nullptr; }
             if (!rc && j.state == 1) {
                 outs[j.idx] = j.img;
                 j.img = nullptr;
@@ -1669,6 +1786,16 @@ extern "C" int ik_png_counters(unsigned long long* out) {
     out[0] = ik::g_png_gpu_streams.load();
     out[1] = ik::g_png_host_streams.load();
     return IK_OK;
+}
+
+extern "C" int ik_png_adam7_plan(uint32_t w, uint32_t h, int bits_pp, uint64_t* out, uint64_t* raw_total) {
+    ik::pngplan::Adam7Pass P[7];
+    const int n = ik::pngplan::adam7_plan(w, h, bits_pp, P, raw_total);
+    for (int q = 0; q < n && out; ++q) {
+        const uint64_t v[8] = {P[q].x0, P[q].y0, P[q].dx, P[q].dy, P[q].pw, P[q].ph, P[q].rowbytes, P[q].raw_off};
+        std::memcpy(out + 8 * q, v, sizeof(v));
+    }
+    return n;
 }
 
 extern "C" int ik_png_last_timing(double* out, int n) {

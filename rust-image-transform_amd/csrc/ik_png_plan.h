@@ -1,5 +1,6 @@
 // ik_png_plan.h -- host-side bookkeeping of the parallel inflate (ik_inflate.h):
 // decoder lanes from chunk candidates, and the chain check that verifies them.
+// Also the Adam7 pass table of interlaced streams (adam7_plan).
 // Shared by the GPU PNG decoder (ik_png_decode.cpp) and its CPU model
 // (ik_png_model.cpp, CPU tests only).
 #pragma once
@@ -146,6 +147,40 @@ inline void offsets(const Lanes& L, std::vector<int64_t>& obase, uint64_t* total
         t += L.res[i].out_len;
     }
     *total = t;
+}
+
+// ---- Adam7 ----------------------------------------------------------------------
+// An interlaced stream's inflated bytes are its (up to) seven reduced images end to
+// end, each with its own filter byte per row; a pass without pixels is absent.
+// Pass p (0-based) holds the pixels (x0 + i dx, y0 + j dy) of the image.
+struct Adam7Pass {
+    int pass;                 // 0..6
+    uint32_t x0, y0, dx, dy;  // first column / row of the image and the steps
+    uint32_t pw, ph;          // the reduced image's size (both > 0)
+    uint64_t rowbytes;        // ceil(pw * bits_pp / 8)
+    uint64_t raw_off;         // its first filter byte in the inflated stream
+};
+
+// the non-empty passes of a w x h image of bits_pp bits per pixel, in stream
+// order; returns their number, the inflated length in *raw_total
+inline int adam7_plan(uint32_t w, uint32_t h, int bits_pp, Adam7Pass out[7], uint64_t* raw_total) {
+    static const uint8_t X0[7] = {0, 4, 0, 2, 0, 1, 0}, Y0[7] = {0, 0, 4, 0, 2, 0, 1};
+    static const uint8_t DX[7] = {8, 8, 4, 4, 2, 2, 1}, DY[7] = {8, 8, 8, 4, 4, 2, 2};
+    int n = 0;
+    uint64_t off = 0;
+    for (int p = 0; p < 7; ++p) {
+        const uint64_t pw = ((uint64_t)w + DX[p] - 1 - X0[p]) / DX[p], ph = ((uint64_t)h + DY[p] - 1 - Y0[p]) / DY[p];
+        if (!pw || !ph) continue;
+        Adam7Pass& a = out[n++];
+        a.pass = p;
+        a.x0 = X0[p]; a.y0 = Y0[p]; a.dx = DX[p]; a.dy = DY[p];
+        a.pw = (uint32_t)pw; a.ph = (uint32_t)ph;
+        a.rowbytes = (pw * (uint64_t)bits_pp + 7) / 8;
+        a.raw_off = off;
+        off += (a.rowbytes + 1) * ph;
+    }
+    if (raw_total) *raw_total = off;
+    return n;
 }
 
 }  // namespace pngplan
