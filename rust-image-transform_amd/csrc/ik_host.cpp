@@ -82,6 +82,7 @@ struct Arena {
 struct ThreadRes {
     std::map<int, hipStream_t> streams, copy_streams, prio_streams;
     std::map<int, hipEvent_t> prio_events;
+    std::map<int, std::array<hipEvent_t, 2>> fork_join;  // per device: an event records only on its own device's streams
     std::map<std::pair<int, int>, Arena> dev;  // (device, slot)
     Arena pinned[11];
     void release() {
@@ -103,6 +104,9 @@ struct ThreadRes {
         for (auto& kv : copy_streams) (void)hipStreamDestroy(kv.second);
         for (auto& kv : prio_streams) (void)hipStreamDestroy(kv.second);
         for (auto& kv : prio_events) (void)hipEventDestroy(kv.second);
+        for (auto& kv : fork_join)
+            for (hipEvent_t e : kv.second) (void)hipEventDestroy(e);
+        fork_join.clear();
         streams.clear();
         copy_streams.clear();
         prio_streams.clear();
@@ -294,7 +298,26 @@ bool thread_prio_stream(hipStream_t* out, hipEvent_t* ev) {
         r.prio_events[d] = e;
     }
     *out = it->second;
-    *ev = r.prio_events[d];
+    if (ev) *ev = r.prio_events[d];
+    return true;
+}
+
+bool thread_fork_join_events(hipEvent_t* fork, hipEvent_t* join) {
+    ThreadRes& r = tres();
+    const int d = current_device();
+    auto it = r.fork_join.find(d);
+    if (it == r.fork_join.end()) {
+        (void)hipSetDevice(d);
+        hipEvent_t f = nullptr, j = nullptr;
+        if (hipEventCreateWithFlags(&f, hipEventDisableTiming) != hipSuccess) return false;
+        if (hipEventCreateWithFlags(&j, hipEventDisableTiming) != hipSuccess) {
+            (void)hipEventDestroy(f);
+            return false;
+        }
+        it = r.fork_join.emplace(d, std::array<hipEvent_t, 2>{f, j}).first;
+    }
+    *fork = it->second[0];
+    *join = it->second[1];
     return true;
 }
 

@@ -24,6 +24,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cassert>
 #include <chrono>
 #include <condition_variable>
 #include <map>
@@ -49,6 +50,35 @@ namespace {
 inline uint32_t be32(const uint8_t* p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3]; }
 size_t up256(size_t v) { return (v + 255) & ~size_t(255); }
 
+// The layout of one block of memory, written once: take<T>(count) hands out the
+// next region (256-byte aligned) and notes the pointer that is to address it;
+// `cur` is then the block's size, and bind() sets the noted pointers once the
+// block exists.  So a table's size stands in one place, for the total and for
+// its pointer alike.
+struct Carver {
+    size_t cur = 0;
+    struct Slot { void* ptr; size_t off; };
+    static constexpr int kSlots = 24;
+    Slot slots[kSlots];
+    int nslots = 0;
+    template <typename T>
+    size_t take(size_t count, T** ptr = nullptr) {
+        const size_t o = cur;
+        cur += up256(sizeof(T) * count);
+        if (ptr) {
+            assert(nslots < kSlots);
+            slots[nslots++] = Slot{ptr, o};
+        }
+        return o;
+    }
+    void bind(uint8_t* base) {
+        for (int i = 0; i < nslots; ++i) {
+            uint8_t* p = base + slots[i].off;
+            std::memcpy(slots[i].ptr, &p, sizeof(p));  // (a T* of any T: object pointers share a representation)
+        }
+    }
+};
+
 struct PngJob {
     int idx = -1;                                   // stream index in the batch
     uint32_t w = 0, h = 0;
@@ -58,10 +88,8 @@ struct PngJob {
     uint64_t raw_total = 0;
     int rowbytes = 0;
     // layout: the file in the upload area's raw part, its zlib stream in the
-    // stream part, its staging copy (inputs the caller did not pin); the kernel
-    // stage's u16 symbols and filter types
+    // stream part, its staging copy (inputs the caller did not pin)
     size_t raw_off = 0, z_off = 0, stage_off = 0;
-    size_t o_u16 = 0, o_ft = 0;
     uint64_t nbits = 0;
     int chunk0 = 0, nchunks = 0;                     // its chunks in the batch chunk table
     pngplan::Lanes lanes;
@@ -250,7 +278,7 @@ bool parse_chunks(const std::vector<ChunkRef>& C, PngJob& J) {
 }
 
 struct HostTables {
-    std::vector<int> chunk_img, chunk_idx, pages, xst;
+    std::vector<int> pages, xst;
     std::vector<int64_t> cand, obase;
     std::vector<PngLaneDev> lanes;
     std::vector<std::pair<int, int>> who;
@@ -527,7 +555,6 @@ std::map<int, std::vector<double>> g_timing;
 // the upload stage's hand-off to the kernel stage
 struct PngBatchState {
     int device = 0;
-    int n = 0;
     std::vector<PngJob> jobs;
     std::vector<char> gpu;
     std::vector<PngJob*> J;
@@ -602,7 +629,6 @@ int png_upload_begin(const uint8_t* const* bytes, const size_t* lens, int n, Png
     up.n = n;
     PngBatchState& S = *st;
     S.device = current_device();
-    S.n = n;
     S.t0 = now_ms();
     S.jobs.assign(n, PngJob());
     S.gpu.assign(n, 0);
@@ -695,15 +721,17 @@ int png_upload_begin(const uint8_t* const* bytes, const size_t* lens, int n, Png
     }
     S.nchunks = nchunks;
     // (the pieces' dst offsets are area offsets: the stream area follows the raw one)
-    S.o_zs = raw;
-    const size_t o_pieces = raw + up256(zs);
-    const size_t o_chunks = o_pieces + up256(sizeof(PngGatherPiece) * pieces.size());
-    S.o_ftab = o_chunks + up256(sizeof(PngCrcChunk) * chunks.size());
-    S.o_fimg = S.o_ftab + up256(2 * sizeof(int) * nchunks);
-    const size_t o_pcrc = S.o_fimg + up256(sizeof(PngImgDev) * m);
-    S.o_err = o_pcrc + up256(2 * sizeof(uint32_t) * pieces.size());
-    S.o_cand = S.o_err + up256(sizeof(int) * m);
-    const size_t dev_bytes = S.o_cand + up256(sizeof(int64_t) * nchunks);
+    Carver lay;
+    lay.cur = raw;
+    S.o_zs = lay.take<uint8_t>(zs);
+    const size_t o_pieces = lay.take<PngGatherPiece>(pieces.size());
+    const size_t o_chunks = lay.take<PngCrcChunk>(chunks.size());
+    S.o_ftab = lay.take<int>(2 * (size_t)nchunks);
+    S.o_fimg = lay.take<PngImgDev>(m);
+    const size_t o_pcrc = lay.take<uint32_t>(2 * pieces.size());
+    S.o_err = lay.take<int>(m);
+    S.o_cand = lay.take<int64_t>(nchunks);
+    const size_t dev_bytes = lay.cur;
     const size_t tab_bytes = o_pcrc - o_pieces;  // pieces, chunks, search chunk table, search descriptors
     S.area = acquire_area(S.device);  // waits while two earlier batches' kernel stages hold both areas
     UploadArea* A = S.area;
@@ -848,908 +876,982 @@ static uint64_t lane_tok_capacity(uint64_t bits, bool big) {
     return png_wave_decoder() ? wave::region_capacity(bits, big) : infl::tok_capacity(bits, big);
 }
 
-int png_decode_finish(PngUpload& up, ik_image** outs, int* status, std::string* msgs) {
-    static const bool timing = getenv("IK_TIMING") != nullptr;
-    const bool wavedec = png_wave_decoder();
-    const double t0 = now_ms();
+// ---- the kernel stage ---------------------------------------------------------------
+// png_decode_finish is the list of its steps; each is a function over the batch's
+// stage state (PngStage), its device work area (PngWork) and its transfers (Xfer).
+namespace {
+
+// the fields of ik_png_last_timing (include/imagekit_hip.h)
+enum PngTim {
+    kTimUploadHostMs, kTimUploadDevMs, kTimDecodeMs, kTimExpandMs, kTimResolveMs, kTimUnfilterMs, kTimStageWallMs,
+    kTimRounds, kTimLanes, kTimSentToGpu, kTimGpuDecoded, kTimHostDecoded, kTimTokens, kTimFindMs, kTimGatherMs,
+    kTimCandidatesBackMs, kTimFindBeside
+};
+static_assert(kTimFindBeside + 1 == kPngTimingFields, "ik_png_last_timing's fields");
+
+// The stage's device memory and what it holds.  Work area (this thread's scratch
+// slot 2), laid out once by png_plan_work: per stream its u16 symbols and filter
+// types, the image entries and their flags, the lane tables (bounded by the chunk
+// count), row / page tables, the unfilter's tables, k_png_adam7's, and the token
+// area.  The expand units' tables (slot 5) are laid out by png_unit_tables.
+struct PngWork {
+    // image entries: one per stream, then one per pass image of the interlaced
+    // streams (a batch without those: M == m, n_il == 0)
+    int M = 0, n_il = 0;
+    size_t max_lanes = 0, max_units = 0, nrows = 0, npages = 0, nbands = 0, ngroups = 0;
+    uint64_t tok_total = 0, pieces_total = 0;  // the token area and the piece tables, in entries
+    uint64_t tok_used = 0, p_used = 0;         // handed out to lanes so far
+    uint8_t* dev = nullptr;
+    std::vector<size_t> o_u16, o_ft;  // per stream: its symbols and filter types in the area
+    PngImgDev *d_imgs = nullptr, *d_cls = nullptr;
+    int *d_err = nullptr, *d_xst = nullptr, *d_pages = nullptr;
+    PngLaneDev* d_lanes = nullptr;
+    infl::LaneResult* d_res = nullptr;
+    int64_t* d_obase = nullptr;
+    uint32_t* d_order = nullptr;
+    int2* d_rows = nullptr;
+    // unfilter: band-group table + per-image band offsets (staged together), then one
+    // progress counter per band and one ticket per class (zeroed: unf_zero bytes)
+    int2* d_groups = nullptr;
+    int* d_pbase = nullptr;
+    unsigned* d_prog = nullptr;
+    size_t unf_zero = 0;
+    PngA7Dev* d_a7 = nullptr;
+    uint2 *d_pieces = nullptr, *d_units = nullptr;  // the wave decoder's piece tables; its expand-unit records (parallel slots)
+    uint16_t* d_tok = nullptr;
+    // the units' tables: offsets (resolve's lane_obase), unit -> lane, expand status;
+    // and the direct-rows expand's marker list (png_direct_rows)
+    int64_t* d_uob = nullptr;
+    uint32_t* d_ulane = nullptr;
+    int* d_uxst = nullptr;
+    PngMarks marks;
+};
+
+struct PngStage {
+    PngUpload& up;
+    PngBatchState& S;
+    std::vector<PngJob*>& J;
+    const int m;
+    const hipStream_t s;
+    Events& ev;
+    // the large host tables are kept per thread between batches (clear() keeps
+    // the capacity): fresh multi-MB vectors cost page faults every batch
+    HostTables& ht;
+    const bool timing, wavedec;
+    int rc;
+    const double t0;
     double tim[kPngTimingFields] = {};
-    Events& ev = events();
-    auto rec = [&](int k, hipStream_t st) { if (ev.ok) (void)hipEventRecord(ev.e[k], st); };
-    auto reject = [&](PngJob& j, const char* why) {
+    double t1 = 0, t2 = 0, t3 = 0;   // candidates back; decode rounds from .. to
+    double mk[4] = {0, 0, 0, 0};     // host marks (IK_TIMING)
+    int rounds = 0, dropped = 0, overflows = 0;
+    bool pre = false;          // the block search was launched before this stage began
+    bool search_done = false;  // the next batch's block search was handed to the hook
+    std::vector<PngImgDev> hd{};               // the image entries
+    std::vector<std::pair<int, size_t>> pj{};  // (job, its first entry in ht.obase) of every verified job
+    // the wave decoder's expand units (ik_png_wave.h unit_starts): numbered lane by
+    // lane; an image's units are contiguous from uimg[k]
+    uint32_t nunits = 0;
+    std::vector<uint32_t> uimg{};
+    std::vector<PngA7Dev> ha7{};
+    uint32_t a7_blocks = 0;
+    int ne = 0;                  // image entries in use
+    std::vector<int> unf_job{};  // entry -> the job whose rows the unfilter takes from it (-1: an interlaced stream's own entry)
+    size_t nexp = 0;             // expand waves: units, or lanes
+    std::vector<int> herr{};     // the entries' resolve flags
+
+    void rec(int k) { if (ev.ok) (void)hipEventRecord(ev.e[k], s); }
+    void reject(PngJob& j, const char* why) {
         j.state = -1;
         if (timing) fprintf(stderr, "[png] stream %d (%ux%u) -> host decoder: %s\n", j.idx, j.w, j.h, why);
-    };
-    PngBatchState& S = *up.st;
-    const uint8_t* const* bytes = up.bytes;
-    const size_t* lens = up.lens;
-    const int n = up.n;
-    for (int i = 0; i < n; ++i) {
-        outs[i] = nullptr;
-        status[i] = IK_OK;
     }
-    double count_dev = 0;
-    std::vector<PngJob*>& J = S.J;
-    std::vector<char>& gpu = S.gpu;
-    const int m = (int)J.size();
-    hipStream_t s = thread_stream();
-    int rc = S.rc;
-    UploadArea* A = S.area;
-    if (m && !rc) {
-        // ---- the kernel stage's work area (this thread's) ----
-        size_t total = 0;
-        const int nchunks = S.nchunks;
-        // image entries: one per stream, then one per pass image of the interlaced
-        // streams (a batch without those: M == m, n_il == 0, and nothing below differs)
-        int M = m, n_il = 0;
-        for (PngJob* j : J) {
-            size_t ftb = j->h;  // filter types: one per row of the image, or of its pass images
-            if (j->interlaced) {
-                ftb = 0;
-                for (int q = 0; q < j->npass; ++q) ftb += j->pass[q].ph;
-                M += j->npass;
-                ++n_il;
-            }
-            j->o_u16 = total;
-            total += up256(2 * (j->raw_total + 64));
-            j->o_ft = total;
-            total += up256(ftb);
+    void next_search(hipEvent_t after) {  // the stage executor's hook, once per batch
+        up.on_next_search(after);
+        search_done = true;
+    }
+};
+
+// ---- step 1: the work area and the transfer area ----
+void png_plan_work(PngStage& T, PngWork& W, Xfer& X) {
+    const bool wavedec = T.wavedec;
+    Carver lay;
+    W.M = T.m;
+    for (PngJob* j : T.J) {
+        size_t ftb = j->h;  // filter types: one per row of the image, or of its pass images
+        if (j->interlaced) {
+            ftb = 0;
+            for (int q = 0; q < j->npass; ++q) ftb += j->pass[q].ph;
+            W.M += j->npass;
+            ++W.n_il;
         }
-        const size_t o_imgs = total;
-        total += up256(sizeof(PngImgDev) * M);
-        const size_t o_err = total;
-        total += up256(sizeof(int) * M);
-        const size_t o_dyn = total;  // lane tables, results, obase, rows, subtables: sized per round below
-        // the work area: lane tables (bounded by the chunk count), row / page
-        // tables, unfilter class descriptors, and the token area: a quarter token
-        // per compressed bit for every first-round lane, plus half again for lanes
-        // that decode again (a dropped successor, an overflow)
-        size_t max_lanes = 0;
-        uint64_t tok_total = 0;
-        for (PngJob* j : J) {
-            // (the wave decoder may split lanes at block boundaries: room for more)
-            max_lanes += (size_t)j->nchunks + (wavedec ? (size_t)j->nchunks / 4 + 16 : 0);
-            tok_total += lane_tok_capacity(j->nbits, false) + (uint64_t)j->nchunks * (lane_tok_capacity(0, false) +
-                                                                                      infl::kTokSlack);
+        W.o_u16.push_back(lay.take<uint16_t>(j->raw_total + 64));
+        W.o_ft.push_back(lay.take<uint8_t>(ftb));
+    }
+    // the token area: a quarter token per compressed bit for every first-round lane,
+    // plus half again for lanes that decode again (a dropped successor, an overflow)
+    for (PngJob* j : T.J) {
+        // (the wave decoder may split lanes at block boundaries: room for more)
+        W.max_lanes += (size_t)j->nchunks + (wavedec ? (size_t)j->nchunks / 4 + 16 : 0);
+        W.tok_total += lane_tok_capacity(j->nbits, false) + (uint64_t)j->nchunks * (lane_tok_capacity(0, false) +
+                                                                                    infl::kTokSlack);
+    }
+    W.tok_total += W.tok_total / 2 + 64;
+    // the wave decoder's piece tables: per lane wave::pieces_capacity(its bits) entries, handed out as
+    // the token regions are (a lane decoded again over a longer range gets a larger one)
+    if (wavedec) {
+        for (PngJob* j : T.J) W.pieces_total += wave::pieces_capacity(j->nbits) + 64ull * (uint64_t)j->nchunks;
+        W.pieces_total += W.pieces_total / 2 + 4096;
+    }
+    for (PngJob* j : T.J) {
+        W.npages += (j->raw_total >> kPngPageShift) + 1;
+        // (resolve and the unfilter take an interlaced stream pass image by pass image)
+        for (int q = 0; q < (j->interlaced ? j->npass : 1); ++q) {
+            const uint32_t hq = j->interlaced ? j->pass[q].ph : j->h;
+            W.nrows += hq;
+            W.nbands += ((size_t)hq + 63) / 64;
+            W.ngroups += (size_t)png_unfilter_groups((int)hq);
         }
-        tok_total += tok_total / 2 + 64;
-        // the wave decoder's piece tables: per lane wave::pieces_capacity(its bits) entries, handed out as
-        // the token regions are (a lane decoded again over a longer range gets a larger one)
-        uint64_t pieces_total = 0;
-        if (wavedec) {
-            for (PngJob* j : J) pieces_total += wave::pieces_capacity(j->nbits) + 64ull * (uint64_t)j->nchunks;
-            pieces_total += pieces_total / 2 + 4096;
-        }
-        const size_t pieces_bytes = up256(sizeof(uint2) * pieces_total);  // (twice: pieces, unit records)
-        size_t dyn = up256(sizeof(PngLaneDev) * max_lanes) + up256(sizeof(infl::LaneResult) * max_lanes) +
-                     up256(sizeof(int64_t) * max_lanes) + up256(2 * sizeof(int) * max_lanes) +
-                     up256(sizeof(uint32_t) * max_lanes) + up256(sizeof(PngImgDev) * M);
-        size_t nrows = 0, npages = 0, nbands = 0, ngroups = 0;
-        for (PngJob* j : J) {
-            npages += (j->raw_total >> kPngPageShift) + 1;
-            // (resolve and the unfilter take an interlaced stream pass image by pass image)
-            for (int q = 0; q < (j->interlaced ? j->npass : 1); ++q) {
-                const uint32_t hq = j->interlaced ? j->pass[q].ph : j->h;
-                nrows += hq;
-                nbands += ((size_t)hq + 63) / 64;
-                ngroups += (size_t)png_unfilter_groups((int)hq);
-            }
-        }
-        // unfilter: band-group table + per-image band offsets (staged), then one
-        // progress counter per band and one ticket per class (zeroed)
-        const size_t unf_tab = up256(sizeof(int2) * ngroups) + up256(sizeof(int) * M);
-        const size_t unf_zero = up256(sizeof(unsigned) * (nbands + 8));
-        const size_t a7_tab = up256(sizeof(PngA7Dev) * n_il);  // k_png_adam7's image table
-        dyn += up256(sizeof(int2) * nrows) + up256(sizeof(int) * npages) + unf_tab + unf_zero + a7_tab + 2 * pieces_bytes +
-               up256(2 * tok_total);
-        uint8_t* dev = scratch_slot(2, o_dyn + dyn);
-        if (!dev) rc = fail(IK_ERR_DEVICE, "cannot allocate the PNG batch work area (%zu bytes)", o_dyn + dyn);
-        PngLaneDev* d_lanes = nullptr;
-        infl::LaneResult* d_res = nullptr;
-        int64_t* d_obase = nullptr;
-        int* d_xst = nullptr;
-        uint32_t* d_order = nullptr;
-        PngImgDev* d_cls = nullptr;
-        int2* d_rows = nullptr;
-        int* d_pages = nullptr;
-        uint8_t* d_unf = nullptr;
-        PngA7Dev* d_a7 = nullptr;
-        uint2* d_pieces = nullptr;
-        uint2* d_units = nullptr;  // the wave decoder's expand-unit records (slots parallel to d_pieces)
-        uint16_t* d_tok = nullptr;
-        if (!rc) {
-            size_t o = o_dyn;
-            d_lanes = reinterpret_cast<PngLaneDev*>(dev + o);
-            o += up256(sizeof(PngLaneDev) * max_lanes);
-            d_res = reinterpret_cast<infl::LaneResult*>(dev + o);
-            o += up256(sizeof(infl::LaneResult) * max_lanes);
-            d_obase = reinterpret_cast<int64_t*>(dev + o);
-            o += up256(sizeof(int64_t) * max_lanes);
-            d_xst = reinterpret_cast<int*>(dev + o);
-            o += up256(2 * sizeof(int) * max_lanes);
-            d_order = reinterpret_cast<uint32_t*>(dev + o);
-            o += up256(sizeof(uint32_t) * max_lanes);
-            d_cls = reinterpret_cast<PngImgDev*>(dev + o);
-            o += up256(sizeof(PngImgDev) * M);
-            d_rows = reinterpret_cast<int2*>(dev + o);
-            o += up256(sizeof(int2) * nrows);
-            d_pages = reinterpret_cast<int*>(dev + o);
-            o += up256(sizeof(int) * npages);
-            d_unf = dev + o;
-            o += unf_tab + unf_zero;
-            d_a7 = reinterpret_cast<PngA7Dev*>(dev + o);
-            o += a7_tab;
-            d_pieces = pieces_bytes ? reinterpret_cast<uint2*>(dev + o) : nullptr;
-            o += pieces_bytes;
-            d_units = pieces_bytes ? reinterpret_cast<uint2*>(dev + o) : nullptr;
-            o += pieces_bytes;
-            d_tok = reinterpret_cast<uint16_t*>(dev + o);
-        }
-        uint64_t tok_used = 0;
-        // the small transfers go through the pinned area by copy kernels on this stream:
-        // one that falls back to the copy engine queues behind the next batch's PCIe
-        // upload (2.25 GB on the bench) and stalls this kernel stage for its length.
-        // The expand units' status (2 ints each): a unit holds kUnitMinTok tokens or
-        // ends its lane
-        const size_t max_units = wavedec ? (size_t)(tok_total / wave::kUnitMinTok) + max_lanes + 16 : 0;
-        Xfer X;
-        if (!rc && !X.init(2 * sizeof(PngLaneDev) * max_lanes + sizeof(infl::LaneResult) * max_lanes +
-                               sizeof(int64_t) * (max_lanes + nchunks) + 3 * sizeof(int) * max_lanes +
-                               2 * sizeof(int) * max_units +
-                               sizeof(int2) * (nrows + ngroups) + sizeof(int) * (npages + 4 * M) +
-                               3 * sizeof(PngImgDev) * M + sizeof(PngA7Dev) * n_il + 512 * (n_il ? 1 : 0) +
-                               2 * sizeof(int) * nchunks + (64u << 10), s))
-            rc = fail(IK_ERR_NOMEM, "cannot allocate pinned PNG transfer area");
-        // the kernels run under the device's kernel gate (ik_runtime.h)
-        gate_enter(kGateKernels);
-        // ---- image descriptors ----
-        std::vector<PngImgDev> hd(m);
-        hd.reserve(M);  // (the pass images' entries are appended once their streams are verified)
-        // the large host tables are kept per thread between batches (clear() keeps
-        // the capacity): fresh multi-MB vectors cost page faults every batch
-        static thread_local HostTables ht;
-        for (int k = 0; k < m && !rc; ++k) {
-            PngJob& j = *J[k];
-            PngImgDev& d = hd[k];
-            d.words = reinterpret_cast<const uint32_t*>(A->dev + S.o_zs + j.z_off);
-            d.bit0 = 16;
-            d.nbits = j.nbits;
-            d.u16 = reinterpret_cast<uint16_t*>(dev + j.o_u16);
-            d.raw_total = j.raw_total;
-            d.rowbytes = j.rowbytes;
-            d.H = (int)j.h;
-            d.bpp = j.bpp;
-            d.ft = dev + j.o_ft;
-        }
-        const PngImgDev* d_imgs = reinterpret_cast<const PngImgDev*>(dev + o_imgs);
-        // ---- the block search: launched here unless the kernel stage launched it
-        // beside the previous batch's unfilter (PngUpload::on_next_search); its
-        // candidates come from the upload area ----
-        hipError_t e = rc ? hipSuccess : X.h2d(dev + o_imgs, hd.data(), sizeof(PngImgDev) * m);
-        const bool pre = S.find_launched;
-        if (!rc && e == hipSuccess) {
-            png_find_launch(S, s);
-            rc = S.rc;
-        }
-        if (!rc && e == hipSuccess && A->ev[3]) e = hipStreamWaitEvent(s, A->ev[3], 0);
+    }
+    const size_t M = (size_t)W.M, max_lanes = W.max_lanes;
+    lay.take(M, &W.d_imgs);
+    lay.take(M, &W.d_err);
+    lay.take(max_lanes, &W.d_lanes);
+    lay.take(max_lanes, &W.d_res);
+    lay.take(max_lanes, &W.d_obase);
+    lay.take(2 * max_lanes, &W.d_xst);
+    lay.take(max_lanes, &W.d_order);
+    lay.take(M, &W.d_cls);
+    lay.take(W.nrows, &W.d_rows);
+    lay.take(W.npages, &W.d_pages);
+    lay.take(W.ngroups, &W.d_groups);
+    lay.take(M, &W.d_pbase);
+    const size_t o_prog = lay.take(W.nbands + 8, &W.d_prog);
+    W.unf_zero = lay.cur - o_prog;
+    lay.take((size_t)W.n_il, &W.d_a7);  // k_png_adam7's image table
+    lay.take(W.pieces_total, &W.d_pieces);
+    lay.take(W.pieces_total, &W.d_units);
+    lay.take(W.tok_total, &W.d_tok);
+    W.dev = scratch_slot(2, lay.cur);
+    if (!W.dev) {
+        T.rc = fail(IK_ERR_DEVICE, "cannot allocate the PNG batch work area (%zu bytes)", lay.cur);
+        return;
+    }
+    lay.bind(W.dev);
+    if (!W.pieces_total) W.d_pieces = W.d_units = nullptr;
+    // the small transfers go through the pinned area by copy kernels on this stream:
+    // one that falls back to the copy engine queues behind the next batch's PCIe
+    // upload (2.25 GB on the bench) and stalls this kernel stage for its length.
+    // The expand units' status (2 ints each): a unit holds kUnitMinTok tokens or
+    // ends its lane
+    W.max_units = wavedec ? (size_t)(W.tok_total / wave::kUnitMinTok) + max_lanes + 16 : 0;
+    const size_t nchunks = (size_t)T.S.nchunks;
+    const size_t lane_tabs = 2 * sizeof(PngLaneDev) * max_lanes + sizeof(infl::LaneResult) * max_lanes +
+                             sizeof(int64_t) * (max_lanes + nchunks) + 3 * sizeof(int) * max_lanes;
+    const size_t unit_status = 2 * sizeof(int) * W.max_units;
+    const size_t row_tabs = sizeof(int2) * (W.nrows + W.ngroups) + sizeof(int) * (W.npages + 4 * M);
+    const size_t img_tabs = 3 * sizeof(PngImgDev) * M;
+    const size_t adam7 = sizeof(PngA7Dev) * W.n_il + 512 * (W.n_il ? 1 : 0);
+    const size_t search = 2 * sizeof(int) * nchunks + (64u << 10);
+    if (!X.init(lane_tabs + unit_status + row_tabs + img_tabs + adam7 + search, T.s))
+        T.rc = fail(IK_ERR_NOMEM, "cannot allocate pinned PNG transfer area");
+}
+
 #ifdef IK_FIND_PROF
-        {
-            (void)hipStreamSynchronize(s);
-            unsigned long long pf[8] = {};
-            if (png_find_prof_read(pf) == hipSuccess && pf[5])
-                fprintf(stderr, "[find-prof] waves %llu: cycles/wave %.0f, flush cycles/wave %.0f (%.1f%%), flushes/wave %.2f, "
-                        "steps/wave %.1f, candidates/wave %.1f, kernel %.2f ms\n", pf[5], (double)pf[0] / pf[5],
-                        (double)pf[1] / pf[5], 100.0 * pf[1] / std::max(1.0, (double)pf[0]), (double)pf[2] / pf[5],
-                        (double)pf[3] / pf[5], (double)pf[4] / pf[5], ev_ms(8, 9));
-        }
+void report_find_prof(hipStream_t s) {
+    (void)hipStreamSynchronize(s);
+    unsigned long long pf[8] = {};
+    if (png_find_prof_read(pf) == hipSuccess && pf[5])
+        fprintf(stderr, "[find-prof] waves %llu: cycles/wave %.0f, flush cycles/wave %.0f (%.1f%%), flushes/wave %.2f, "
+                "steps/wave %.1f, candidates/wave %.1f, kernel %.2f ms\n", pf[5], (double)pf[0] / pf[5],
+                (double)pf[1] / pf[5], 100.0 * pf[1] / std::max(1.0, (double)pf[0]), (double)pf[2] / pf[5],
+                (double)pf[3] / pf[5], (double)pf[4] / pf[5], ev_ms(8, 9));
+}
 #endif
-        std::vector<int64_t>& cand = ht.cand;
-        cand.assign(nchunks, 0);
-        std::vector<int> crc_err(m, 0);
-        if (!rc && e == hipSuccess) e = X.d2h(cand.data(), A->dev + S.o_cand, sizeof(int64_t) * nchunks);
-        if (!rc && e == hipSuccess) {
-            e = launch_copy_words(reinterpret_cast<const uint32_t*>(A->dev + S.o_err),
-                                  reinterpret_cast<uint32_t*>(dev + o_err), (size_t)m, s);
-            if (e == hipSuccess) e = X.d2h(crc_err.data(), dev + o_err, sizeof(int) * m);
+
+// ---- step 2: the streams' image entries; the block search's candidates and the
+// upload's CRC flags come back (a CRC mismatch: the host decoder reports png's error) ----
+void png_search_results(PngStage& T, PngWork& W, Xfer& X) {
+    const int m = T.m;
+    int& rc = T.rc;
+    UploadArea* A = T.S.area;
+    T.hd.assign(m, PngImgDev());
+    T.hd.reserve(W.M);  // (the pass images' entries are appended once their streams are verified)
+    for (int k = 0; k < m && !rc; ++k) {
+        PngJob& j = *T.J[k];
+        PngImgDev& d = T.hd[k];
+        d.words = reinterpret_cast<const uint32_t*>(A->dev + T.S.o_zs + j.z_off);
+        d.bit0 = 16;
+        d.nbits = j.nbits;
+        d.u16 = reinterpret_cast<uint16_t*>(W.dev + W.o_u16[k]);
+        d.raw_total = j.raw_total;
+        d.rowbytes = j.rowbytes;
+        d.H = (int)j.h;
+        d.bpp = j.bpp;
+        d.ft = W.dev + W.o_ft[k];
+    }
+    // the block search: launched here unless the kernel stage launched it beside the
+    // previous batch's unfilter (PngUpload::on_next_search); its candidates come from
+    // the upload area
+    hipError_t e = rc ? hipSuccess : X.h2d(W.d_imgs, T.hd.data(), sizeof(PngImgDev) * m);
+    T.pre = T.S.find_launched;
+    if (!rc && e == hipSuccess) {
+        png_find_launch(T.S, T.s);
+        rc = T.S.rc;
+    }
+    if (!rc && e == hipSuccess && A->ev[3]) e = hipStreamWaitEvent(T.s, A->ev[3], 0);
+#ifdef IK_FIND_PROF
+    report_find_prof(T.s);
+#endif
+    std::vector<int64_t>& cand = T.ht.cand;
+    cand.assign(T.S.nchunks, 0);
+    std::vector<int> crc_err(m, 0);
+    if (!rc && e == hipSuccess) e = X.d2h(cand.data(), A->dev + T.S.o_cand, sizeof(int64_t) * T.S.nchunks);
+    if (!rc && e == hipSuccess) {
+        e = launch_copy_words(reinterpret_cast<const uint32_t*>(A->dev + T.S.o_err),
+                              reinterpret_cast<uint32_t*>(W.d_err), (size_t)m, T.s);
+        if (e == hipSuccess) e = X.d2h(crc_err.data(), W.d_err, sizeof(int) * m);
+    }
+    if (!rc && e != hipSuccess) rc = hip_fail(e, "PNG block search");
+    for (int k = 0; k < m; ++k)
+        if (crc_err[k]) T.reject(*T.J[k], "IDAT CRC");
+    T.t1 = now_ms();
+    T.tim[kTimCandidatesBackMs] = T.t1 - T.t0;  // (upload wait + search)
+}
+
+// ---- the decode rounds' lanes ----
+// What lane i of a job needs: its token region's capacity and, for the wave
+// decoder, its piece table's entries (0 for the lane decoder)
+struct LaneNeed { uint32_t cap, pieces; };
+LaneNeed lane_need(const PngJob& j, size_t i, uint64_t nbits, bool wavedec) {
+    const pngplan::Lanes& LL = j.lanes;
+    const uint64_t end = LL.stop[i] == ~0ull ? nbits : LL.stop[i];
+    const uint64_t bits = end > LL.start[i] ? end - LL.start[i] : 0;
+    return LaneNeed{(uint32_t)lane_tok_capacity(bits, LL.big[i] != 0), wavedec ? wave::pieces_capacity(bits) : 0u};
+}
+
+// lane i of stream k as a decode round launches it
+PngLaneDev decode_lane(const pngplan::Lanes& LL, size_t i, int k) {
+    PngLaneDev L{};
+    L.start = LL.start[i];
+    L.stop = LL.stop[i];
+    L.tbase = LL.tbase[i];
+    L.ntok = LL.tcap[i];
+    L.img = (uint32_t)k;
+    L.first = i == 0;
+    L.big = LL.big[i] ? 1u : 0u;
+    L.pbase = LL.pslot[i] < 0 ? 0 : (uint64_t)LL.pslot[i];
+    L.npieces = LL.pcap[i];
+    return L;
+}
+
+// lane i of verified stream k as expand takes it (ob: its output offset); the wave
+// decoder's tokens are the lane's pieces (piece table at its slot), expanded by units
+// from unit `ubase` of the batch
+PngLaneDev expand_lane(const pngplan::Lanes& LL, size_t i, int k, int64_t ob, bool wavedec, uint32_t ubase, uint32_t uimg) {
+    PngLaneDev L{};
+    L.tbase = LL.tbase[i];
+    L.obase = ob;
+    L.out_len = LL.res[i].out_len;
+    L.ntok = LL.res[i].ntok;
+    L.img = (uint32_t)k;
+    L.first = i == 0;
+    if (wavedec) {
+        L.pbase = (uint64_t)LL.pslot[i];
+        L.npieces = LL.res[i].pieces;
+        L.ubase = ubase;
+        L.uimg = uimg;
+        L.nunits = LL.res[i].units;
+    }
+    return L;
+}
+
+// where a job's lanes go: the next slot of the lane table, the next free token and
+// piece-table entry
+struct LaneCursors {
+    size_t lane = 0;
+    uint64_t tok = 0, pieces = 0;
+};
+
+// what a job's dirty lanes take of each (a lane keeps a region that is large enough)
+LaneCursors job_lanes_need(const PngJob& j, bool wavedec) {
+    LaneCursors c;
+    for (size_t i = 0; i < j.lanes.start.size(); ++i) {
+        if (!j.lanes.dirty[i]) continue;
+        const LaneNeed nd = lane_need(j, i, j.nbits, wavedec);
+        ++c.lane;
+        if (nd.cap > j.lanes.tcap[i]) c.tok += nd.cap + infl::kTokSlack;
+        if (nd.pieces > j.lanes.pcap[i]) c.pieces += nd.pieces;
+    }
+    return c;
+}
+
+// Job k's dirty lanes into the lane table (ht.lanes / ht.who, sized by the caller)
+// from the cursors on, each with a (larger) token region and piece table where its
+// own does not do.  Stops at a lane the areas have no room for and returns why
+// (the caller sends the job to the host decoder); nullptr when all went in.
+const char* build_job_lanes(PngJob& j, int k, bool wavedec, const PngWork& W, HostTables& ht, LaneCursors& c) {
+    pngplan::Lanes& LL = j.lanes;
+    for (size_t i = 0; i < LL.start.size(); ++i) {
+        if (!LL.dirty[i]) continue;
+        const LaneNeed nd = lane_need(j, i, j.nbits, wavedec);
+        if (nd.cap > LL.tcap[i]) {
+            const uint64_t need = nd.cap + infl::kTokSlack;
+            if (c.tok + need > W.tok_total) return "token area full";
+            LL.tbase[i] = c.tok;
+            LL.tcap[i] = nd.cap;
+            c.tok += need;
         }
-        if (!rc && e != hipSuccess) rc = hip_fail(e, "PNG block search");
-        for (int k = 0; k < m; ++k)
-            if (crc_err[k]) reject(*J[k], "IDAT CRC");  // the host decoder reports png's CRC error
-        const double t1 = now_ms();
-        tim[15] = t1 - t0;  // from the stage's start until the candidates are back (upload wait + search)
-        const double t2 = now_ms();
-        double mk[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // dev timing marks (IK_TIMING)
-        // the lane plans, one job per pool task (the decode waits on this host work)
+        if (nd.pieces > LL.pcap[i]) {
+            if (c.pieces + nd.pieces > W.pieces_total) return "piece tables full";
+            LL.pslot[i] = (int64_t)c.pieces;
+            LL.pcap[i] = nd.pieces;
+            c.pieces += nd.pieces;
+        }
+        ht.lanes[c.lane] = decode_lane(LL, i, k);
+        ht.who[c.lane] = {k, (int)i};
+        ++c.lane;
+    }
+    return nullptr;
+}
+
+// The lane table of the next round.  In the first round every lane of every live job
+// is new and the areas were sized for all of them: when the jobs' needs (prefix sums)
+// all fit, the jobs fill their parts at once, each from its own cursors.  Otherwise,
+// and in later rounds (the few lanes that overflowed or decode on past a dropped
+// successor), job by job from the running cursors, and a job that finds an area full
+// goes to the host decoder.
+void build_round_lanes(PngStage& T, PngWork& W, bool first) {
+    const int m = T.m;
+    std::vector<LaneCursors> at(m + 1);
+    at[0].tok = W.tok_used;
+    at[0].pieces = W.p_used;
+    for (int k = 0; k < m; ++k) {
+        const LaneCursors nd = T.J[k]->state ? LaneCursors() : job_lanes_need(*T.J[k], T.wavedec);
+        at[k + 1].lane = at[k].lane + nd.lane;
+        at[k + 1].tok = at[k].tok + nd.tok;
+        at[k + 1].pieces = at[k].pieces + nd.pieces;
+    }
+    T.ht.lanes.resize(at[m].lane);
+    T.ht.who.resize(at[m].lane);
+    if (!at[m].lane) return;
+    const bool fits = at[m].tok <= W.tok_total && at[m].lane <= W.max_lanes && at[m].pieces <= W.pieces_total;
+    LaneCursors c = at[0];
+    auto job = [&](int k, LaneCursors& cur) {
+        PngJob& j = *T.J[k];
+        if (j.state) return;
+        if (const char* why = build_job_lanes(j, k, T.wavedec, W, T.ht, cur)) T.reject(j, why);
+    };
+    if (first && fits) {
         parallel_for(m, 0, [&](int k) {
-            PngJob* j = J[k];
-            std::vector<int64_t> c(cand.begin() + j->chunk0, cand.begin() + j->chunk0 + j->nchunks);
-            pngplan::build(c, j->lanes);
+            LaneCursors cur = at[k];
+            job(k, cur);
         });
-        // ---- decode rounds: token streams; the host checks the lane chain ----
-        int rounds = 0, dropped = 0, overflows = 0;
-        bool search_done = false;  // the next batch's block search was handed to the hook
-        std::vector<PngLaneDev>& hl = ht.lanes;
-        std::vector<std::pair<int, int>>& who = ht.who;  // (job, lane) of each launched lane
-        std::vector<infl::LaneResult>& hres = ht.res;
-        std::vector<uint32_t>& lane_order = ht.order;  // launch slot -> lane (order_lanes)
-        hl.clear();
-        who.clear();
-        hres.clear();
-        // first round, in parallel: every lane of every live job is new, and the token
-        // area was sized for all of them, so each job's lanes and token regions go to
-        // fixed offsets (prefix sums over the jobs) and the jobs fill their parts at once
-        bool first_built = false;
-        uint64_t p_used = 0;  // piece-table entries handed out (the wave decoder)
-        {
-            std::vector<size_t> l0(m + 1, 0);
-            std::vector<uint64_t> t0(m + 1, 0), q0(m + 1, 0);
-            for (int k = 0; k < m; ++k) {
-                const PngJob& j = *J[k];
-                const pngplan::Lanes& LL = j.lanes;
-                size_t nl = 0;
-                uint64_t need = 0, pneed = 0;
-                if (!j.state)
-                    for (size_t i = 0; i < LL.start.size(); ++i) {
-                        if (!LL.dirty[i]) continue;
-                        const uint64_t end = LL.stop[i] == ~0ull ? j.nbits : LL.stop[i];
-                        const uint64_t bits = end > LL.start[i] ? end - LL.start[i] : 0;
-                        const uint32_t cap = (uint32_t)lane_tok_capacity(bits, LL.big[i] != 0);
-                        ++nl;
-                        if (cap > LL.tcap[i]) need += cap + infl::kTokSlack;
-                        if (wavedec && wave::pieces_capacity(bits) > LL.pcap[i]) pneed += wave::pieces_capacity(bits);
-                    }
-                l0[k + 1] = l0[k] + nl;
-                t0[k + 1] = t0[k] + need;
-                q0[k + 1] = q0[k] + pneed;
-            }
-            if (tok_used + t0[m] <= tok_total && l0[m] <= max_lanes && p_used + q0[m] <= pieces_total) {
-                hl.resize(l0[m]);
-                who.resize(l0[m]);
-                parallel_for(m, 0, [&](int k) {
-                    PngJob& j = *J[k];
-                    if (j.state) return;
-                    pngplan::Lanes& LL = j.lanes;
-                    size_t t = l0[k];
-                    uint64_t tu = tok_used + t0[k], pu = p_used + q0[k];
-                    for (size_t i = 0; i < LL.start.size(); ++i) {
-                        if (!LL.dirty[i]) continue;
-                        const uint64_t end = LL.stop[i] == ~0ull ? j.nbits : LL.stop[i];
-                        const uint64_t bits = end > LL.start[i] ? end - LL.start[i] : 0;
-                        const uint32_t cap = (uint32_t)lane_tok_capacity(bits, LL.big[i] != 0);
-                        if (cap > LL.tcap[i]) {
-                            LL.tbase[i] = tu;
-                            LL.tcap[i] = cap;
-                            tu += cap + infl::kTokSlack;
-                        }
-                        if (wavedec && wave::pieces_capacity(bits) > LL.pcap[i]) {
-                            LL.pslot[i] = (int64_t)pu;
-                            LL.pcap[i] = wave::pieces_capacity(bits);
-                            pu += LL.pcap[i];
-                        }
-                        PngLaneDev L{};
-                        L.start = LL.start[i];
-                        L.stop = LL.stop[i];
-                        L.tbase = LL.tbase[i];
-                        L.ntok = LL.tcap[i];
-                        L.img = (uint32_t)k;
-                        L.first = i == 0;
-                        L.big = LL.big[i] ? 1u : 0u;
-                        L.pbase = LL.pslot[i] < 0 ? 0 : (uint64_t)LL.pslot[i];
-                        L.npieces = LL.pcap[i];
-                        hl[t] = L;
-                        who[t] = {k, (int)i};
-                        ++t;
-                    }
-                });
-                tok_used += t0[m];
-                p_used += q0[m];
-                first_built = true;
-            }
-        }
-        while (!rc) {
-            if (!first_built) {
-                hl.clear();
-                who.clear();
-                for (int k = 0; k < m; ++k) {
-                    PngJob& j = *J[k];
-                    if (j.state) continue;
-                    pngplan::Lanes& LL = j.lanes;
-                    for (size_t i = 0; i < LL.start.size(); ++i) {
-                        if (!LL.dirty[i]) continue;
-                        const uint64_t end = LL.stop[i] == ~0ull ? j.nbits : LL.stop[i];
-                        const uint32_t cap = (uint32_t)lane_tok_capacity(end > LL.start[i] ? end - LL.start[i] : 0,
-                                                                         LL.big[i] != 0);
-                        if (cap > LL.tcap[i]) {  // a (larger) region from the area
-                            const uint64_t need = cap + infl::kTokSlack;
-                            if (tok_used + need > tok_total) { reject(j, "token area full"); break; }  // host decoder
-                            LL.tbase[i] = tok_used;
-                            LL.tcap[i] = cap;
-                            tok_used += need;
-                        }
-                        const uint32_t pneed = wavedec ? wave::pieces_capacity(end > LL.start[i] ? end - LL.start[i] : 0) : 0;
-                        if (pneed > LL.pcap[i]) {
-                            if (p_used + pneed > pieces_total) { reject(j, "piece tables full"); break; }  // host decoder
-                            LL.pslot[i] = (int64_t)p_used;
-                            LL.pcap[i] = pneed;
-                            p_used += pneed;
-                        }
-                        PngLaneDev L{};
-                        L.start = LL.start[i];
-                        L.stop = LL.stop[i];
-                        L.tbase = LL.tbase[i];
-                        L.ntok = LL.tcap[i];
-                        L.img = (uint32_t)k;
-                        L.first = i == 0;
-                        L.big = LL.big[i] ? 1u : 0u;
-                        L.pbase = LL.pslot[i] < 0 ? 0 : (uint64_t)LL.pslot[i];
-                        L.npieces = LL.pcap[i];
-                        hl.push_back(L);
-                        who.emplace_back(k, (int)i);
-                    }
-                }
-            }
-            first_built = false;
-            // lanes of a job that just fell back are dropped from the launch
-            if (!hl.empty()) {
-                size_t w = 0;
-                for (size_t t = 0; t < hl.size(); ++t)
-                    if (J[who[t].first]->state == 0) { hl[w] = hl[t]; who[w] = who[t]; ++w; }
-                hl.resize(w);
-                who.resize(w);
-            }
-            if (hl.empty()) break;
-            if (hl.size() > max_lanes) { rc = fail(IK_ERR_DEVICE, "PNG lane table overflow"); break; }
-            const bool ordered = order_lanes(hl, J, lane_order);
-            const size_t lb = sizeof(PngLaneDev) * hl.size();
-            if (X.h2d(d_lanes, hl.data(), lb) != hipSuccess ||
-                (ordered && X.h2d(d_order, lane_order.data(), sizeof(uint32_t) * hl.size()) != hipSuccess)) {
-                rc = fail(IK_ERR_DEVICE, "PNG lane table upload");
-                break;
-            }
-            hres.resize(hl.size());
-            if (!mk[0]) mk[0] = now_ms();  // plan built, lanes uploaded (first round)
-            rec(2, s);
-            // (IK_FIND_BESIDE: the next batch's block search beside this decode, on another queue)
-            if (!search_done && png_find_beside_decode() && up.on_next_search && ev.ok) {
-                (void)hipEventRecord(ev.e[11], s);
-                up.on_next_search(ev.e[11]);
-                search_done = true;
-            }
-            hipError_t e2 = wavedec ? launch_png_wave(d_imgs, d_lanes, ordered ? d_order : nullptr, (int)hl.size(), d_tok,
-                                                      d_pieces, d_units, d_res, s)
-                                    : launch_png_decode(d_imgs, d_lanes, ordered ? d_order : nullptr, (int)hl.size(), d_tok,
-                                                        d_res, s);
-            rec(3, s);
-            // the lane results come back behind the decode; the next batch's block
-            // search (the stage executor's hook) queues behind that copy, so it runs
-            // while this thread checks the lane chain and plans expand / resolve
-            size_t roff = ~size_t(0);
-            const size_t rbytes = sizeof(infl::LaneResult) * hl.size();
-            if (e2 == hipSuccess) e2 = X.d2h_start(d_res, rbytes, &roff, ev.ok ? ev.e[10] : nullptr);
-            if (e2 == hipSuccess && !search_done && up.on_next_search) {
-                up.on_next_search(nullptr);
-                search_done = true;
-            }
-            if (e2 == hipSuccess) e2 = X.d2h_finish(hres.data(), d_res, rbytes, roff, ev.ok ? ev.e[10] : nullptr);
-            if (e2 != hipSuccess) { rc = hip_fail(e2, "PNG inflate (decode)"); break; }
-            count_dev += ev_ms(2, 3);
+        c = at[m];
+    } else {
+        for (int k = 0; k < m; ++k) job(k, c);
+    }
+    T.ht.lanes.resize(c.lane);
+    T.ht.who.resize(c.lane);
+    W.tok_used = c.tok;
+    W.p_used = c.pieces;
+}
+
 #ifdef IK_WAVE_PROF
-            if (wavedec) {
-                unsigned long long pf[8] = {};
-                if (png_wave_prof_read(pf) == hipSuccess && pf[7])
-                    fprintf(stderr, "[wave-prof] lanes %llu: kcycles/lane total %.0f, codes %.0f (lengths %.0f), tables %.0f, "
-                            "staging %.0f, first passes %.0f, fix rounds %.0f, rest %.0f\n", pf[7], pf[0] / 1024.0 / pf[7],
-                            pf[6] / 1024.0 / pf[7],
-                            pf[1] / 1024.0 / pf[7], pf[2] / 1024.0 / pf[7], pf[3] / 1024.0 / pf[7], pf[4] / 1024.0 / pf[7],
-                            pf[5] / 1024.0 / pf[7],
-                            ((double)pf[0] - pf[1] - pf[2] - pf[3] - pf[4] - pf[5]) / 1024.0 / pf[7]);
-            }
+void report_wave_prof() {
+    unsigned long long pf[8] = {};
+    if (png_wave_prof_read(pf) == hipSuccess && pf[7])
+        fprintf(stderr, "[wave-prof] lanes %llu: kcycles/lane total %.0f, codes %.0f (lengths %.0f), tables %.0f, "
+                "staging %.0f, first passes %.0f, fix rounds %.0f, rest %.0f\n", pf[7], pf[0] / 1024.0 / pf[7],
+                pf[6] / 1024.0 / pf[7],
+                pf[1] / 1024.0 / pf[7], pf[2] / 1024.0 / pf[7], pf[3] / 1024.0 / pf[7], pf[4] / 1024.0 / pf[7],
+                pf[5] / 1024.0 / pf[7],
+                ((double)pf[0] - pf[1] - pf[2] - pf[3] - pf[4] - pf[5]) / 1024.0 / pf[7]);
+}
 #endif
-            ++rounds;
-            std::vector<char> again(m, 0);  // a job with overflowed lanes: those first, then the check
-            for (size_t t = 0; t < hl.size(); ++t) {
-                pngplan::Lanes& LL = J[who[t].first]->lanes;
-                const int i = who[t].second;
-                LL.res[i] = hres[t];
-                LL.dirty[i] = 0;
-                if (hres[t].status == infl::kLaneOverflow) {
-                    ++overflows;
-                    if (LL.big[i]) {
-                        LL.res[i].status = infl::kLaneCorrupt;  // past the exact bound too (see tok_capacity)
-                    } else {
-                        LL.big[i] = 1;
-                        LL.dirty[i] = 1;
-                        again[who[t].first] = 1;
-                    }
-                }
-            }
-            for (int k = 0; k < m; ++k) {
-                PngJob& j = *J[k];
-                if (j.state || again[k]) continue;
-                const size_t before = j.lanes.start.size();
-                const int st = pngplan::check(j.lanes);
-                dropped += (int)(before - j.lanes.start.size());
-                if (st == 0) j.state = 1;
-                else if (st < 0) reject(j, "lane chain check");
-            }
-        }
-        // the compressed streams are read for the last time (every decode round's
-        // results were synchronised): the next batch may upload into the area
-        (void)hipStreamSynchronize(s);
-        {
-            float ms = 0;
-            if (A->ev[3] && A->ev[4] && hipEventElapsedTime(&ms, A->ev[4], A->ev[3]) == hipSuccess) tim[13] = ms;
-            if (A->ev[0] && A->ev[2] && hipEventElapsedTime(&ms, A->ev[0], A->ev[2]) == hipSuccess) tim[1] = ms;
-            if (A->ev[1] && A->ev[2] && hipEventElapsedTime(&ms, A->ev[1], A->ev[2]) == hipSuccess) tim[14] = ms;
-        }
-        tim[16] = pre ? 1.0 : 0.0;
-        release_area(S.area);
-        const double t3 = now_ms();
-        // ---- offsets, output images, expand, resolve, unfilter ----
-        std::vector<int64_t>& hob = ht.obase;
-        std::vector<int>& hpages = ht.pages;
-        hob.clear();
-        hpages.clear();
-        hl.clear();
-        size_t npg = 0;                        // page-table entries so far
-        std::vector<std::pair<int, size_t>> pj;  // (job, its first entry in hob) of every verified job
-        // the wave decoder's expand units (ik_png_wave.h unit_starts): numbered lane by
-        // lane; an image's units are contiguous from uimg[k]
-        uint32_t nunits = 0;
-        std::vector<uint32_t> uimg(m, 0);
-        for (int k = 0; k < m && !rc; ++k) {
-            PngJob& j = *J[k];
-            if (j.state != 1) continue;
-            std::vector<int64_t> ob;
-            uint64_t tot = 0;
-            pngplan::offsets(j.lanes, ob, &tot);
-            if (tot != j.raw_total) { reject(j, "image data length"); continue; }  // png's error
-            if (wavedec) {
-                bool units_ok = true;
-                for (size_t i = 0; i < ob.size(); ++i) units_ok = units_ok && j.lanes.res[i].units > 0;
-                if (!units_ok) { reject(j, "expand units"); continue; }
-            }
-            if (j.expand) {  // unfiltered rows in a row image, then k_png_px into the output image
-                if (alloc_image((uint32_t)j.rowbytes, j.h, 1, &j.rows) ||
-                alloc_image(j.w, j.h, (uint32_t)j.out_c, &j.img, j.depth == 16 ? 2 : 1)) {
-                    reject(j, "image allocation");
-                    continue;
-                }
-            } else if (alloc_image(j.w, j.h, (uint32_t)j.bpp, &j.img)) {
-                reject(j, "image allocation");
-                continue;
-            }
-            if (j.interlaced) {
-                // the pass images' rows: one block from the image pool, each pass pitched
-                // and padded as alloc_image would (resolve stores whole 16-byte chunks,
-                // the unfilter reads its rows through a buffer descriptor)
-                size_t sb = 0;
-                for (int q = 0; q < j.npass; ++q) {
-                    j.pass_off[q] = sb;
-                    sb += pitch_for((uint32_t)j.pass[q].rowbytes, 1) * (size_t)j.pass[q].ph;
-                }
-                if (alloc_image(256, (uint32_t)(sb / 256), 1, &j.stage)) {
-                    reject(j, "image allocation");
-                    continue;
-                }
-            }
-            hd[k].obase = d_obase + hob.size();  // (the wave decoder's: its unit table, set below)
-            hd[k].page_lane = d_pages + npg;  // (the page table itself is built while expand runs)
-            hd[k].nlanes = (int)ob.size();
-            uimg[k] = nunits;
-            pj.emplace_back(k, hob.size());
-            npg += (j.raw_total >> kPngPageShift) + 1;
-            hd[k].dst = j.expand ? j.rows->d : j.img->d;
-            hd[k].pitch = j.expand ? j.rows->pitch : j.img->pitch;
-            hd[k].flags = reinterpret_cast<const int*>(dev + o_err) + k;
-            for (size_t i = 0; i < ob.size(); ++i) tim[12] += (double)j.lanes.res[i].ntok;
-            for (size_t i = 0; i < ob.size(); ++i) {
-                PngLaneDev L{};
-                L.tbase = j.lanes.tbase[i];
-                L.obase = ob[i];
-                L.out_len = j.lanes.res[i].out_len;
-                L.ntok = j.lanes.res[i].ntok;
-                L.img = (uint32_t)k;
-                L.first = i == 0;
-                if (wavedec) {  // the tokens are the lane's pieces (piece table at its slot), expanded by units
-                    L.pbase = (uint64_t)j.lanes.pslot[i];
-                    L.npieces = j.lanes.res[i].pieces;
-                    L.ubase = nunits;
-                    L.uimg = uimg[k];
-                    L.nunits = j.lanes.res[i].units;
-                    nunits += L.nunits;
-                }
-                hl.push_back(L);
-            }
-            if (wavedec) hd[k].nlanes = (int)(nunits - uimg[k]);
-            hob.insert(hob.end(), ob.begin(), ob.end());
-        }
-        // the units' tables: offsets (resolve's lane_obase), unit -> lane, expand status
-        int64_t* d_uob = nullptr;
-        uint32_t* d_ulane = nullptr;
-        int* d_uxst = nullptr;
-        // and the direct-rows expand's marker list (png_direct_rows): a slot per 16 output bytes
-        PngMarks marks;
-        if (!rc && wavedec && nunits) {
-            uint64_t raw_sum = 0;
-            for (const auto& q : pj) raw_sum += J[q.first]->raw_total;
-            // (at least 64 K entries per sub-list: a small batch's few units each take one)
-            const uint64_t mcap =
-                png_direct_rows() ? std::min<uint64_t>(std::max<uint64_t>(raw_sum / 16, 65536ull * kMarkLists), 0xFFFFFF00ull) : 0;
-            const size_t b0 = up256(sizeof(int64_t) * nunits), b1 = up256(sizeof(uint32_t) * nunits);
-            const size_t b2 = up256(2 * sizeof(int) * nunits),
-                         b3 = mcap ? up256(sizeof(uint32_t) * kMarkLists) + up256(sizeof(uint64_t) * mcap) : 0;
-            uint8_t* ua = scratch_slot(5, b0 + b1 + b2 + b3);
-            if (!ua) {
-                rc = fail(IK_ERR_DEVICE, "cannot allocate the PNG expand-unit tables (%u units)", nunits);
+
+// one round's results into the lane plans, then every job's chain check
+void check_round(PngStage& T) {
+    const int m = T.m;
+    const std::vector<std::pair<int, int>>& who = T.ht.who;
+    std::vector<char> again(m, 0);  // a job with overflowed lanes: those first, then the check
+    for (size_t t = 0; t < who.size(); ++t) {
+        pngplan::Lanes& LL = T.J[who[t].first]->lanes;
+        const int i = who[t].second;
+        LL.res[i] = T.ht.res[t];
+        LL.dirty[i] = 0;
+        if (T.ht.res[t].status == infl::kLaneOverflow) {
+            ++T.overflows;
+            if (LL.big[i]) {
+                LL.res[i].status = infl::kLaneCorrupt;  // past the exact bound too (see tok_capacity)
             } else {
-                d_uob = reinterpret_cast<int64_t*>(ua);
-                d_ulane = reinterpret_cast<uint32_t*>(ua + b0);
-                d_uxst = reinterpret_cast<int*>(ua + b0 + b1);
-                for (const auto& q : pj) hd[q.first].obase = d_uob + uimg[q.first];
-                if (mcap) {
-                    marks.count = reinterpret_cast<uint32_t*>(ua + b0 + b1 + b2);
-                    marks.list = reinterpret_cast<uint64_t*>(ua + b0 + b1 + b2 + up256(sizeof(uint32_t) * kMarkLists));
-                    marks.cap = (uint32_t)mcap;
-                }
+                LL.big[i] = 1;
+                LL.dirty[i] = 1;
+                again[who[t].first] = 1;
             }
         }
-        // the pass images of the verified interlaced streams: entries of their own
-        // behind the streams' (the stream's symbols, unit offsets and page table; their
-        // own rows, filter types, flags and place in the inflated bytes), and
-        // k_png_adam7's table of them
-        std::vector<PngA7Dev> ha7;
-        uint32_t a7_blocks = 0;
-        for (const auto& q : pj) {
-            PngJob& j = *J[q.first];
-            if (rc || !j.interlaced) continue;
-            j.pass_e0 = (int)hd.size();
-            PngA7Dev a{};
-            a.dst = hd[q.first].dst;
-            a.pitch = hd[q.first].pitch;
-            a.w = (int)j.w;
-            a.h = (int)j.h;
-            a.rowbytes = j.rowbytes;
-            a.bits = j.bits_pp;
-            a.nseg = (uint32_t)((j.rowbytes + kA7Threads * png_adam7_unit_bytes(j.bits_pp) - 1) /
-                                (kA7Threads * png_adam7_unit_bytes(j.bits_pp)));
-            a.blk0 = a7_blocks;
-            a7_blocks += a.nseg * j.h;
-            size_t fo = 0;
-            for (int t = 0; t < j.npass; ++t) {
-                const pngplan::Adam7Pass& P = j.pass[t];
-                PngImgDev d = hd[q.first];
-                d.raw0 = P.raw_off;
-                d.rowbytes = (int)P.rowbytes;
-                d.H = (int)P.ph;
-                d.ft = dev + j.o_ft + fo;
-                d.dst = j.stage->d + j.pass_off[t];
-                d.pitch = pitch_for((uint32_t)P.rowbytes, 1);
-                d.flags = reinterpret_cast<const int*>(dev + o_err) + hd.size();
-                fo += P.ph;
-                a.pass[P.pass].src = d.dst;
-                a.pass[P.pass].pitch = d.pitch;
-                a.pass[P.pass].rowbytes = d.rowbytes;
-                a.pass[P.pass].ph = d.H;
-                hd.push_back(d);
-            }
-            ha7.push_back(a);
+    }
+    for (int k = 0; k < m; ++k) {
+        PngJob& j = *T.J[k];
+        if (j.state || again[k]) continue;
+        const size_t before = j.lanes.start.size();
+        const int st = pngplan::check(j.lanes);
+        T.dropped += (int)(before - j.lanes.start.size());
+        if (st == 0) j.state = 1;
+        else if (st < 0) T.reject(j, "lane chain check");
+    }
+}
+
+// ---- step 3: decode rounds: token streams; the host checks the lane chain after
+// each.  Then the compressed streams have been read for the last time and the
+// upload area goes back ----
+void png_decode_rounds(PngStage& T, PngWork& W, Xfer& X) {
+    const int m = T.m;
+    int& rc = T.rc;
+    const hipStream_t s = T.s;
+    T.t2 = now_ms();
+    // the lane plans, one job per pool task (the decode waits on this host work)
+    parallel_for(m, 0, [&](int k) {
+        PngJob* j = T.J[k];
+        const std::vector<int64_t>& cand = T.ht.cand;
+        std::vector<int64_t> c(cand.begin() + j->chunk0, cand.begin() + j->chunk0 + j->nchunks);
+        pngplan::build(c, j->lanes);
+    });
+    std::vector<PngLaneDev>& hl = T.ht.lanes;
+    std::vector<std::pair<int, int>>& who = T.ht.who;  // (job, lane) of each launched lane
+    std::vector<infl::LaneResult>& hres = T.ht.res;
+    std::vector<uint32_t>& lane_order = T.ht.order;  // launch slot -> lane (order_lanes)
+    hres.clear();
+    while (!rc) {
+        build_round_lanes(T, W, T.rounds == 0);
+        // lanes of a job that just fell back are dropped from the launch
+        if (!hl.empty()) {
+            size_t w = 0;
+            for (size_t t = 0; t < hl.size(); ++t)
+                if (T.J[who[t].first]->state == 0) { hl[w] = hl[t]; who[w] = who[t]; ++w; }
+            hl.resize(w);
+            who.resize(w);
         }
-        const int ne = (int)hd.size();  // image entries in use
-        // entry -> the job whose rows the unfilter takes from it (-1: an interlaced stream's own entry)
-        std::vector<int> unf_job(ne, -1);
-        for (int k = 0; k < m; ++k)
-            if (!J[k]->interlaced) unf_job[k] = k;
-        for (const auto& q : pj)
-            if (!rc && J[q.first]->interlaced)
-                for (int t = 0; t < J[q.first]->npass; ++t) unf_job[J[q.first]->pass_e0 + t] = q.first;
-        const size_t nexp = wavedec ? (size_t)nunits : hl.size();  // expand waves: units, or lanes
-        mk[1] = now_ms();  // offsets, images, page tables, lane table built
-        std::vector<int2>& hrows = ht.rows;
-        std::vector<int>& hxst = ht.xst;
-        hrows.clear();
-        hxst.clear();
-        std::vector<int> herr(ne, 0);
-        if (!rc && !hl.empty()) {
-            // expand goes out first; the resolve pass's page and row tables are built
-            // on the host while it runs (stream order puts their uploads after it)
-            const size_t lb = sizeof(PngLaneDev) * hl.size();
-            hipError_t ue = X.h2d(d_lanes, hl.data(), lb);
-            if (ue == hipSuccess) ue = X.h2d(d_obase, hob.data(), sizeof(int64_t) * hob.size());
-            if (ue == hipSuccess) ue = X.h2d(dev + o_imgs, hd.data(), sizeof(PngImgDev) * ne);
-            if (ue == hipSuccess) ue = hipMemsetAsync(dev + o_err, 0, sizeof(int) * ne, s);
-            if (ue == hipSuccess && marks.count) ue = hipMemsetAsync(marks.count, 0, sizeof(uint32_t) * kMarkLists, s);
-            if (ue != hipSuccess) rc = hip_fail(ue, "PNG expand tables");
-            hxst.resize(2 * nexp);
-            mk[2] = now_ms();  // lane tables uploaded
-            // the next batch's block search (VALU-bound) beside this batch's expand,
-            // resolve and unfilter, which run at a raised wave priority (ik_png.hip
-            // raise_priority): the stage executor's hook
-            if (!rc && !search_done && up.on_next_search) {
-                up.on_next_search(nullptr);
-                search_done = true;
-            }
-            if (!rc) {
-                hipError_t e3 = hipSuccess;
-                rec(4, s);
-                if (wavedec) {
-                    // the units' tables and page tables (k_png_units), then one wave per unit
-                    if (e3 == hipSuccess) e3 = launch_png_units(d_imgs, d_lanes, (int)hl.size(), d_units, d_ulane, s);
-                    if (e3 == hipSuccess)
-                        e3 = launch_png_expand(d_imgs, d_lanes, (int)nunits, d_tok, d_uxst, s, d_pieces, d_units, d_ulane,
-                                               marks);
-                } else if (e3 == hipSuccess) {
-                    e3 = launch_png_expand(d_imgs, d_lanes, (int)hl.size(), d_tok, d_xst, s);
-                }
-                rec(5, s);
-                // page -> decoder that holds the page's first byte (resolve's lane lookup;
-                // the wave decoder's units: k_png_units built it)
-                for (const auto& q : pj) {
-                    const PngJob& j = *J[q.first];
-                    if (!wavedec) {
-                        const int64_t* ob = hob.data() + q.second;
-                        const size_t nl = (size_t)hd[q.first].nlanes;
-                        for (uint64_t pg = 0, ln = 0; pg <= (j.raw_total >> kPngPageShift); ++pg) {
-                            while (ln + 1 < nl && (uint64_t)ob[ln + 1] <= (pg << kPngPageShift)) ++ln;
-                            hpages.push_back((int)ln);
-                        }
-                    }
-                    if (j.interlaced) {  // pass rows: (pass-image entry, row of the pass)
-                        for (int t = 0; t < j.npass; ++t)
-                            for (uint32_t y = 0; y < j.pass[t].ph; ++y) hrows.push_back(make_int2(j.pass_e0 + t, (int)y));
-                        continue;
-                    }
-                    for (uint32_t y = 0; y < j.h; ++y) hrows.push_back(make_int2(q.first, (int)y));
-                }
-                if (e3 == hipSuccess && !wavedec) e3 = X.h2d(d_pages, hpages.data(), sizeof(int) * hpages.size());
-                if (e3 == hipSuccess) e3 = X.h2d(d_rows, hrows.data(), sizeof(int2) * hrows.size());
-                if (e3 == hipSuccess)
-                    e3 = marks.list ? launch_png_marks(d_imgs, marks, d_rows, (int)hrows.size(), reinterpret_cast<int*>(dev + o_err), s)
-                                    : launch_png_resolve(d_imgs, d_rows, (int)hrows.size(), reinterpret_cast<int*>(dev + o_err), s);
-                rec(6, s);
-#ifdef IK_PNG_DUMP  // dev experiment: every image's filtered rows and filter types before the unfilter
-                if (e3 == hipSuccess) {
-                    (void)hipStreamSynchronize(s);
-                    png_dump_store(J, hd, m);
-                }
+        if (hl.empty()) break;
+        if (hl.size() > W.max_lanes) { rc = fail(IK_ERR_DEVICE, "PNG lane table overflow"); break; }
+        const bool ordered = order_lanes(hl, T.J, lane_order);
+        const size_t lb = sizeof(PngLaneDev) * hl.size();
+        if (X.h2d(W.d_lanes, hl.data(), lb) != hipSuccess ||
+            (ordered && X.h2d(W.d_order, lane_order.data(), sizeof(uint32_t) * hl.size()) != hipSuccess)) {
+            rc = fail(IK_ERR_DEVICE, "PNG lane table upload");
+            break;
+        }
+        hres.resize(hl.size());
+        if (!T.mk[0]) T.mk[0] = now_ms();  // plan built, lanes uploaded (first round)
+        T.rec(2);
+        // (IK_FIND_BESIDE: the next batch's block search beside this decode, on another queue)
+        if (!T.search_done && png_find_beside_decode() && T.up.on_next_search && T.ev.ok) {
+            (void)hipEventRecord(T.ev.e[11], s);
+            T.next_search(T.ev.e[11]);
+        }
+        hipError_t e2 = T.wavedec ? launch_png_wave(W.d_imgs, W.d_lanes, ordered ? W.d_order : nullptr, (int)hl.size(),
+                                                    W.d_tok, W.d_pieces, W.d_units, W.d_res, s)
+                                  : launch_png_decode(W.d_imgs, W.d_lanes, ordered ? W.d_order : nullptr, (int)hl.size(),
+                                                      W.d_tok, W.d_res, s);
+        T.rec(3);
+        // the lane results come back behind the decode; the next batch's block
+        // search (the stage executor's hook) queues behind that copy, so it runs
+        // while this thread checks the lane chain and plans expand / resolve
+        size_t roff = ~size_t(0);
+        const size_t rbytes = sizeof(infl::LaneResult) * hl.size();
+        const hipEvent_t rev = T.ev.ok ? T.ev.e[10] : nullptr;
+        if (e2 == hipSuccess) e2 = X.d2h_start(W.d_res, rbytes, &roff, rev);
+        if (e2 == hipSuccess && !T.search_done && T.up.on_next_search) T.next_search(nullptr);
+        if (e2 == hipSuccess) e2 = X.d2h_finish(hres.data(), W.d_res, rbytes, roff, rev);
+        if (e2 != hipSuccess) { rc = hip_fail(e2, "PNG inflate (decode)"); break; }
+        T.tim[kTimDecodeMs] += ev_ms(2, 3);
+#ifdef IK_WAVE_PROF
+        if (T.wavedec) report_wave_prof();
 #endif
-                // unfilter (+ png's EXPAND), as a step of its own: the direct-rows path whose
-                // marker list overflowed runs resolve and this again (below)
-                auto unfilter_all = [&](hipError_t e3) -> hipError_t {
-                    // unfilter: one launch per bytes-per-pixel class, over that class's
-                    // images; a workgroup per 16 bands, its (image, group) by ticket
-                    if (e3 == hipSuccess) {
-                        std::vector<PngImgDev> cls;
-                        std::vector<int2> groups;
-                        std::vector<int> pbase;
-                        struct Range { int bpp, img0, grp0; };
-                        std::vector<Range> ranges;
-                        int band0 = 0;
-                        for (int bpp : {1, 2, 3, 4, 6, 8}) {
-                            const Range r{bpp, (int)cls.size(), (int)groups.size()};
-                            for (int k = 0; k < ne; ++k)
-                                if (unf_job[k] >= 0 && J[unf_job[k]]->state == 1 && hd[k].bpp == bpp) {
-                                    for (int g = 0; g < png_unfilter_groups(hd[k].H); ++g)
-                                        groups.push_back(make_int2((int)cls.size() - r.img0, g));
-                                    pbase.push_back(band0);
-                                    band0 += (hd[k].H + 63) / 64;
-                                    cls.push_back(hd[k]);
-                                }
-                            if ((int)cls.size() > r.img0) ranges.push_back(r);
-                        }
-                        const size_t gb = up256(sizeof(int2) * ngroups);
-                        std::vector<uint8_t> tabs(unf_tab, 0);
-                        std::memcpy(tabs.data(), groups.data(), sizeof(int2) * groups.size());
-                        std::memcpy(tabs.data() + gb, pbase.data(), sizeof(int) * pbase.size());
-                        e3 = X.h2d(d_unf, tabs.data(), unf_tab);
-                        unsigned* d_prog = reinterpret_cast<unsigned*>(d_unf + unf_tab);
-                        unsigned* d_ticket = d_prog + nbands;
-                        if (e3 == hipSuccess) e3 = hipMemsetAsync(d_prog, 0, unf_zero, s);
-                        if (e3 == hipSuccess) e3 = X.h2d(d_cls, cls.data(), sizeof(PngImgDev) * cls.size());
-                        const int2* d_groups = reinterpret_cast<const int2*>(d_unf);
-                        const int* d_pbase = reinterpret_cast<const int*>(d_unf + gb);
-                        // RGBA8 images of None / Sub / Up rows take the scan path, the others
-                        // the diagonal kernel; each skips the other's images, so the diagonal
-                        // one runs beside, on this thread's high-priority stream (fork / join
-                        // by events): 1.3 + 1.9 ms in turn -> 1.8-2.0 ms together
-                        static thread_local hipEvent_t fork_ev = nullptr, join_ev = nullptr;
-                        if (!fork_ev && (hipEventCreateWithFlags(&fork_ev, hipEventDisableTiming) != hipSuccess ||
-                                         hipEventCreateWithFlags(&join_ev, hipEventDisableTiming) != hipSuccess))
-                            fork_ev = join_ev = nullptr;
-                        hipStream_t side = nullptr;
-                        hipEvent_t side_ev = nullptr;
-                        if (fork_ev && !thread_prio_stream(&side, &side_ev)) side = nullptr;
-                        for (size_t r = 0; r < ranges.size() && e3 == hipSuccess; ++r) {
-                            const int g1 = r + 1 < ranges.size() ? ranges[r + 1].grp0 : (int)groups.size();
-                            const int g0 = ranges[r].grp0, i0 = ranges[r].img0;
-                            const int i1 = r + 1 < ranges.size() ? ranges[r + 1].img0 : (int)cls.size();
-                            const bool fork = side && ranges[r].bpp == 4;
-                            if (fork) {
-                                e3 = hipEventRecord(fork_ev, s);
-                                if (e3 == hipSuccess) e3 = hipStreamWaitEvent(side, fork_ev, 0);
-                            }
-                            if (e3 == hipSuccess)
-                                e3 = launch_png_unfilter(d_cls + i0, d_groups + g0, g1 - g0, d_pbase + i0, d_prog,
-                                                         d_ticket + r, ranges[r].bpp, fork ? side : s);
-                            if (e3 == hipSuccess && ranges[r].bpp == 4) e3 = launch_png_unfilter_su(d_cls + i0, i1 - i0, s);
-                            if (fork && e3 == hipSuccess) {
-                                e3 = hipEventRecord(join_ev, side);
-                                if (e3 == hipSuccess) e3 = hipStreamWaitEvent(s, join_ev, 0);
-                            }
-                        }
-                    }
-                    // the interlaced streams' pass images into their rows (one launch)
-                    if (e3 == hipSuccess && !ha7.empty()) {
-                        e3 = X.h2d(d_a7, ha7.data(), sizeof(PngA7Dev) * ha7.size());
-                        if (e3 == hipSuccess) e3 = launch_png_adam7(d_a7, (int)ha7.size(), a7_blocks, s);
-                    }
-                    // png's EXPAND for the palette / low-bit / tRNS images
-                    for (int k = 0; k < m && e3 == hipSuccess; ++k) {
-                        PngJob& j = *J[k];
-                        if (j.state != 1 || !j.expand || !j.rows) continue;
-                        j.px.src = j.rows->d;
-                        j.px.sp = j.rows->pitch;
-                        j.px.dst = j.img->d;
-                        j.px.dp = j.img->pitch;
-                        e3 = launch_png_px(j.px, s);
-                    }
-                    return e3;
-                };
-                e3 = unfilter_all(e3);
-                rec(7, s);
-#ifdef IK_EXP_PROF
-                {
-                    (void)hipStreamSynchronize(s);
-                    unsigned long long pf[8] = {};
-                    if (png_exp_prof_read(pf) == hipSuccess && pf[0])
-                        fprintf(stderr, "[exp-prof] waves %zu: kcycles/wave %.0f: token wait %.0f, scan %.0f, literals %.0f, "
-                                "matches %.0f, stores+sync %.0f, loop %.0f; batches/wave %.1f\n", nexp,
-                                pf[0] / 1024.0 / nexp, pf[6] / 1024.0 / nexp, pf[1] / 1024.0 / nexp, pf[2] / 1024.0 / nexp,
-                                pf[3] / 1024.0 / nexp, pf[4] / 1024.0 / nexp, pf[5] / 1024.0 / nexp, (double)pf[7] / nexp);
+        ++T.rounds;
+        check_round(T);
+    }
+    // the compressed streams are read for the last time (every decode round's
+    // results were synchronised): the next batch may upload into the area
+    (void)hipStreamSynchronize(s);
+    UploadArea* A = T.S.area;
+    float ms = 0;
+    if (A->ev[3] && A->ev[4] && hipEventElapsedTime(&ms, A->ev[4], A->ev[3]) == hipSuccess) T.tim[kTimFindMs] = ms;
+    if (A->ev[0] && A->ev[2] && hipEventElapsedTime(&ms, A->ev[0], A->ev[2]) == hipSuccess) T.tim[kTimUploadDevMs] = ms;
+    if (A->ev[1] && A->ev[2] && hipEventElapsedTime(&ms, A->ev[1], A->ev[2]) == hipSuccess) T.tim[kTimGatherMs] = ms;
+    T.tim[kTimFindBeside] = T.pre ? 1.0 : 0.0;
+    release_area(T.S.area);
+    T.t3 = now_ms();
+}
+
+// the units' tables (this thread's scratch slot 5)
+void png_unit_tables(PngStage& T, PngWork& W) {
+    uint64_t raw_sum = 0;
+    for (const auto& q : T.pj) raw_sum += T.J[q.first]->raw_total;
+    // (at least 64 K entries per sub-list: a small batch's few units each take one)
+    const uint64_t mcap =
+        png_direct_rows() ? std::min<uint64_t>(std::max<uint64_t>(raw_sum / 16, 65536ull * kMarkLists), 0xFFFFFF00ull) : 0;
+    Carver lay;
+    PngMarks marks;
+    lay.take((size_t)T.nunits, &W.d_uob);
+    lay.take((size_t)T.nunits, &W.d_ulane);
+    lay.take(2 * (size_t)T.nunits, &W.d_uxst);
+    if (mcap) {  // a slot per 16 output bytes
+        lay.take((size_t)kMarkLists, &marks.count);
+        lay.take((size_t)mcap, &marks.list);
+        marks.cap = (uint32_t)mcap;
+    }
+    uint8_t* ua = scratch_slot(5, lay.cur);
+    if (!ua) {
+        T.rc = fail(IK_ERR_DEVICE, "cannot allocate the PNG expand-unit tables (%u units)", T.nunits);
+        return;
+    }
+    lay.bind(ua);
+    W.marks = marks;
+    for (const auto& q : T.pj) T.hd[q.first].obase = W.d_uob + T.uimg[q.first];
+}
+
+// The pass images of the verified interlaced streams: entries of their own behind
+// the streams' (the stream's symbols, unit offsets and page table; their own rows,
+// filter types, flags and place in the inflated bytes), and k_png_adam7's table of them
+void png_pass_images(PngStage& T, PngWork& W) {
+    std::vector<PngImgDev>& hd = T.hd;
+    for (const auto& q : T.pj) {
+        PngJob& j = *T.J[q.first];
+        if (T.rc || !j.interlaced) continue;
+        j.pass_e0 = (int)hd.size();
+        PngA7Dev a{};
+        a.dst = hd[q.first].dst;
+        a.pitch = hd[q.first].pitch;
+        a.w = (int)j.w;
+        a.h = (int)j.h;
+        a.rowbytes = j.rowbytes;
+        a.bits = j.bits_pp;
+        a.nseg = (uint32_t)((j.rowbytes + kA7Threads * png_adam7_unit_bytes(j.bits_pp) - 1) /
+                            (kA7Threads * png_adam7_unit_bytes(j.bits_pp)));
+        a.blk0 = T.a7_blocks;
+        T.a7_blocks += a.nseg * j.h;
+        size_t fo = 0;
+        for (int t = 0; t < j.npass; ++t) {
+            const pngplan::Adam7Pass& P = j.pass[t];
+            PngImgDev d = hd[q.first];
+            d.raw0 = P.raw_off;
+            d.rowbytes = (int)P.rowbytes;
+            d.H = (int)P.ph;
+            d.ft = W.dev + W.o_ft[q.first] + fo;
+            d.dst = j.stage->d + j.pass_off[t];
+            d.pitch = pitch_for((uint32_t)P.rowbytes, 1);
+            d.flags = W.d_err + hd.size();
+            fo += P.ph;
+            a.pass[P.pass].src = d.dst;
+            a.pass[P.pass].pitch = d.pitch;
+            a.pass[P.pass].rowbytes = d.rowbytes;
+            a.pass[P.pass].ph = d.H;
+            hd.push_back(d);
+        }
+        T.ha7.push_back(a);
+    }
+}
+
+// a verified stream's images: the output, the rows png's EXPAND reads, the pass
+// images' rows; false when the pool has none (the stream goes to the host decoder)
+bool alloc_job_images(PngJob& j) {
+    if (j.expand) {  // unfiltered rows in a row image, then k_png_px into the output image
+        if (alloc_image((uint32_t)j.rowbytes, j.h, 1, &j.rows) ||
+            alloc_image(j.w, j.h, (uint32_t)j.out_c, &j.img, j.depth == 16 ? 2 : 1))
+            return false;
+    } else if (alloc_image(j.w, j.h, (uint32_t)j.bpp, &j.img)) {
+        return false;
+    }
+    if (j.interlaced) {
+        // the pass images' rows: one block from the image pool, each pass pitched
+        // and padded as alloc_image would (resolve stores whole 16-byte chunks,
+        // the unfilter reads its rows through a buffer descriptor)
+        size_t sb = 0;
+        for (int q = 0; q < j.npass; ++q) {
+            j.pass_off[q] = sb;
+            sb += pitch_for((uint32_t)j.pass[q].rowbytes, 1) * (size_t)j.pass[q].ph;
+        }
+        if (alloc_image(256, (uint32_t)(sb / 256), 1, &j.stage)) return false;
+    }
+    return true;
+}
+
+// ---- step 4: the verified jobs' tables: output offsets, the output / row /
+// pass-stage images, expand's lane table, the unit tables, the pass images' entries ----
+void png_verified_tables(PngStage& T, PngWork& W) {
+    const int m = T.m;
+    const bool wavedec = T.wavedec;
+    std::vector<PngImgDev>& hd = T.hd;
+    std::vector<int64_t>& hob = T.ht.obase;
+    std::vector<PngLaneDev>& hl = T.ht.lanes;
+    hob.clear();
+    T.ht.pages.clear();
+    hl.clear();
+    size_t npg = 0;  // page-table entries so far
+    T.uimg.assign(m, 0);
+    for (int k = 0; k < m && !T.rc; ++k) {
+        PngJob& j = *T.J[k];
+        if (j.state != 1) continue;
+        std::vector<int64_t> ob;
+        uint64_t tot = 0;
+        pngplan::offsets(j.lanes, ob, &tot);
+        if (tot != j.raw_total) { T.reject(j, "image data length"); continue; }  // png's error
+        if (wavedec) {
+            bool units_ok = true;
+            for (size_t i = 0; i < ob.size(); ++i) units_ok = units_ok && j.lanes.res[i].units > 0;
+            if (!units_ok) { T.reject(j, "expand units"); continue; }
+        }
+        if (!alloc_job_images(j)) { T.reject(j, "image allocation"); continue; }
+        hd[k].obase = W.d_obase + hob.size();  // (the wave decoder's: its unit table, set below)
+        hd[k].page_lane = W.d_pages + npg;  // (the page table itself is built while expand runs)
+        hd[k].nlanes = (int)ob.size();
+        T.uimg[k] = T.nunits;
+        T.pj.emplace_back(k, hob.size());
+        npg += (j.raw_total >> kPngPageShift) + 1;
+        hd[k].dst = j.expand ? j.rows->d : j.img->d;
+        hd[k].pitch = j.expand ? j.rows->pitch : j.img->pitch;
+        hd[k].flags = W.d_err + k;
+        for (size_t i = 0; i < ob.size(); ++i) T.tim[kTimTokens] += (double)j.lanes.res[i].ntok;
+        for (size_t i = 0; i < ob.size(); ++i) {
+            hl.push_back(expand_lane(j.lanes, i, k, ob[i], wavedec, T.nunits, T.uimg[k]));
+            T.nunits += hl.back().nunits;
+        }
+        if (wavedec) hd[k].nlanes = (int)(T.nunits - T.uimg[k]);
+        hob.insert(hob.end(), ob.begin(), ob.end());
+    }
+    if (!T.rc && wavedec && T.nunits) png_unit_tables(T, W);
+    png_pass_images(T, W);
+    T.ne = (int)hd.size();
+    T.unf_job.assign(T.ne, -1);
+    for (int k = 0; k < m; ++k)
+        if (!T.J[k]->interlaced) T.unf_job[k] = k;
+    for (const auto& q : T.pj)
+        if (!T.rc && T.J[q.first]->interlaced)
+            for (int t = 0; t < T.J[q.first]->npass; ++t) T.unf_job[T.J[q.first]->pass_e0 + t] = q.first;
+    T.nexp = wavedec ? (size_t)T.nunits : hl.size();
+    T.mk[1] = now_ms();  // offsets, images, page tables, lane table built
+}
+
+// resolve's tables, built on the host while expand runs: page -> decoder that holds
+// the page's first byte (the wave decoder's units: k_png_units built it), and the
+// rows: (image entry, row)
+void build_page_and_row_tables(PngStage& T) {
+    for (const auto& q : T.pj) {
+        const PngJob& j = *T.J[q.first];
+        if (!T.wavedec) {
+            const int64_t* ob = T.ht.obase.data() + q.second;
+            const size_t nl = (size_t)T.hd[q.first].nlanes;
+            for (uint64_t pg = 0, ln = 0; pg <= (j.raw_total >> kPngPageShift); ++pg) {
+                while (ln + 1 < nl && (uint64_t)ob[ln + 1] <= (pg << kPngPageShift)) ++ln;
+                T.ht.pages.push_back((int)ln);
+            }
+        }
+        if (j.interlaced) {  // pass rows: (pass-image entry, row of the pass)
+            for (int t = 0; t < j.npass; ++t)
+                for (uint32_t y = 0; y < j.pass[t].ph; ++y) T.ht.rows.push_back(make_int2(j.pass_e0 + t, (int)y));
+            continue;
+        }
+        for (uint32_t y = 0; y < j.h; ++y) T.ht.rows.push_back(make_int2(q.first, (int)y));
+    }
+}
+
+// Unfilter (+ the interlaced streams' gather, + png's EXPAND), as a step of its own:
+// the direct-rows path whose marker list overflowed runs resolve and this again.
+// One unfilter launch per bytes-per-pixel class, over that class's images; a
+// workgroup per 16 bands, its (image, group) by ticket.
+hipError_t png_unfilter_all(PngStage& T, PngWork& W, Xfer& X, hipError_t e3) {
+    const hipStream_t s = T.s;
+    if (e3 == hipSuccess) {
+        std::vector<PngImgDev> cls;
+        std::vector<int2> groups;
+        std::vector<int> pbase;
+        struct Range { int bpp, img0, grp0; };
+        std::vector<Range> ranges;
+        int band0 = 0;
+        for (int bpp : {1, 2, 3, 4, 6, 8}) {
+            const Range r{bpp, (int)cls.size(), (int)groups.size()};
+            for (int k = 0; k < T.ne; ++k)
+                if (T.unf_job[k] >= 0 && T.J[T.unf_job[k]]->state == 1 && T.hd[k].bpp == bpp) {
+                    for (int g = 0; g < png_unfilter_groups(T.hd[k].H); ++g)
+                        groups.push_back(make_int2((int)cls.size() - r.img0, g));
+                    pbase.push_back(band0);
+                    band0 += (T.hd[k].H + 63) / 64;
+                    cls.push_back(T.hd[k]);
                 }
+            if ((int)cls.size() > r.img0) ranges.push_back(r);
+        }
+        // (the group table and the band offsets go up as one staged block)
+        const size_t gb = (size_t)(reinterpret_cast<uint8_t*>(W.d_pbase) - reinterpret_cast<uint8_t*>(W.d_groups));
+        const size_t unf_tab = (size_t)(reinterpret_cast<uint8_t*>(W.d_prog) - reinterpret_cast<uint8_t*>(W.d_groups));
+        std::vector<uint8_t> tabs(unf_tab, 0);
+        std::memcpy(tabs.data(), groups.data(), sizeof(int2) * groups.size());
+        std::memcpy(tabs.data() + gb, pbase.data(), sizeof(int) * pbase.size());
+        e3 = X.h2d(W.d_groups, tabs.data(), unf_tab);
+        unsigned* d_ticket = W.d_prog + W.nbands;
+        if (e3 == hipSuccess) e3 = hipMemsetAsync(W.d_prog, 0, W.unf_zero, s);
+        if (e3 == hipSuccess) e3 = X.h2d(W.d_cls, cls.data(), sizeof(PngImgDev) * cls.size());
+        // RGBA8 images of None / Sub / Up rows take the scan path, the others
+        // the diagonal kernel; each skips the other's images, so the diagonal
+        // one runs beside, on this thread's high-priority stream (fork / join
+        // by this device's events): 1.3 + 1.9 ms in turn -> 1.8-2.0 ms together
+        hipStream_t side = nullptr;
+        hipEvent_t fork_ev = nullptr, join_ev = nullptr;
+        if (!thread_fork_join_events(&fork_ev, &join_ev) || !thread_prio_stream(&side, nullptr)) side = nullptr;
+        for (size_t r = 0; r < ranges.size() && e3 == hipSuccess; ++r) {
+            const int g1 = r + 1 < ranges.size() ? ranges[r + 1].grp0 : (int)groups.size();
+            const int g0 = ranges[r].grp0, i0 = ranges[r].img0;
+            const int i1 = r + 1 < ranges.size() ? ranges[r + 1].img0 : (int)cls.size();
+            const bool fork = side && ranges[r].bpp == 4;
+            if (fork) {
+                e3 = hipEventRecord(fork_ev, s);
+                if (e3 == hipSuccess) e3 = hipStreamWaitEvent(side, fork_ev, 0);
+            }
+            if (e3 == hipSuccess)
+                e3 = launch_png_unfilter(W.d_cls + i0, W.d_groups + g0, g1 - g0, W.d_pbase + i0, W.d_prog, d_ticket + r,
+                                         ranges[r].bpp, fork ? side : s);
+            if (e3 == hipSuccess && ranges[r].bpp == 4) e3 = launch_png_unfilter_su(W.d_cls + i0, i1 - i0, s);
+            if (fork && e3 == hipSuccess) {
+                e3 = hipEventRecord(join_ev, side);
+                if (e3 == hipSuccess) e3 = hipStreamWaitEvent(s, join_ev, 0);
+            }
+        }
+    }
+    // the interlaced streams' pass images into their rows (one launch)
+    if (e3 == hipSuccess && !T.ha7.empty()) {
+        e3 = X.h2d(W.d_a7, T.ha7.data(), sizeof(PngA7Dev) * T.ha7.size());
+        if (e3 == hipSuccess) e3 = launch_png_adam7(W.d_a7, (int)T.ha7.size(), T.a7_blocks, s);
+    }
+    // png's EXPAND for the palette / low-bit / tRNS images
+    for (int k = 0; k < T.m && e3 == hipSuccess; ++k) {
+        PngJob& j = *T.J[k];
+        if (j.state != 1 || !j.expand || !j.rows) continue;
+        j.px.src = j.rows->d;
+        j.px.sp = j.rows->pitch;
+        j.px.dst = j.img->d;
+        j.px.dp = j.img->pitch;
+        e3 = launch_png_px(j.px, s);
+    }
+    return e3;
+}
+
+#ifdef IK_EXP_PROF
+void report_exp_prof(hipStream_t s, size_t nexp) {
+    (void)hipStreamSynchronize(s);
+    unsigned long long pf[8] = {};
+    if (png_exp_prof_read(pf) == hipSuccess && pf[0])
+        fprintf(stderr, "[exp-prof] waves %zu: kcycles/wave %.0f: token wait %.0f, scan %.0f, literals %.0f, "
+                "matches %.0f, stores+sync %.0f, loop %.0f; batches/wave %.1f\n", nexp,
+                pf[0] / 1024.0 / nexp, pf[6] / 1024.0 / nexp, pf[1] / 1024.0 / nexp, pf[2] / 1024.0 / nexp,
+                pf[3] / 1024.0 / nexp, pf[4] / 1024.0 / nexp, pf[5] / 1024.0 / nexp, (double)pf[7] / nexp);
+}
 #endif
 #ifdef IK_UNF_PROF
-                {
-                    (void)hipStreamSynchronize(s);
-                    unsigned long long pf[8] = {};
-                    if (png_unf_prof_read(pf) == hipSuccess && pf[7])
-                        fprintf(stderr, "[unf-prof] waves %llu: cycles/wave above %.0f, fetch-issue %.0f, steps %.0f, publish "
-                                "%.0f, landed %.0f; unfilter %.2f ms\n", pf[7], (double)pf[0] / pf[7], (double)pf[1] / pf[7],
-                                (double)pf[2] / pf[7], (double)pf[3] / pf[7], (double)pf[4] / pf[7], ev_ms(6, 7));
-                }
+void report_unf_prof(hipStream_t s) {
+    (void)hipStreamSynchronize(s);
+    unsigned long long pf[8] = {};
+    if (png_unf_prof_read(pf) == hipSuccess && pf[7])
+        fprintf(stderr, "[unf-prof] waves %llu: cycles/wave above %.0f, fetch-issue %.0f, steps %.0f, publish "
+                "%.0f, landed %.0f; unfilter %.2f ms\n", pf[7], (double)pf[0] / pf[7], (double)pf[1] / pf[7],
+                (double)pf[2] / pf[7], (double)pf[3] / pf[7], (double)pf[4] / pf[7], ev_ms(6, 7));
+}
 #endif
-                uint32_t nmarks = 0, mcnt[kMarkLists];
-                bool mover = false;
-                if (e3 == hipSuccess && marks.count) {
-                    e3 = X.d2h(mcnt, marks.count, sizeof(mcnt));
-                    for (uint32_t q = 0; q < kMarkLists; ++q) {
-                        nmarks += mcnt[q];
-                        mover = mover || mcnt[q] > marks.cap / kMarkLists;
-                    }
-                }
-                if (e3 == hipSuccess && mover) {
-                    // the marker list overflowed (runs of copies across units, e.g. a flat
-                    // image): the rows from the u16 symbols after all, then the unfilter again
-                    if (timing) fprintf(stderr, "[png] %u window markers > list %u: resolve pass\n", nmarks, marks.cap);
-                    e3 = hipMemsetAsync(dev + o_err, 0, sizeof(int) * ne, s);
-                    if (e3 == hipSuccess)
-                        e3 = launch_png_resolve(d_imgs, d_rows, (int)hrows.size(), reinterpret_cast<int*>(dev + o_err), s);
-                    e3 = unfilter_all(e3);
-                }
-                if (timing && marks.count) fprintf(stderr, "[png] window markers %u (list %u)\n", nmarks, marks.cap);
-                if (e3 == hipSuccess) e3 = X.d2h(hxst.data(), wavedec ? d_uxst : d_xst, 2 * sizeof(int) * nexp);
-                if (e3 == hipSuccess) e3 = X.d2h(herr.data(), dev + o_err, sizeof(int) * ne);
-                for (int k = m; k < ne; ++k) herr[unf_job[k]] |= herr[k];  // a pass image's flags are its stream's
-                mk[3] = now_ms();  // expand .. unfilter done
-                if (e3 != hipSuccess) rc = hip_fail(e3, "PNG inflate (expand) / unfilter");
-                if (!rc) {
-                    tim[3] = ev_ms(4, 5);
-                    tim[4] = ev_ms(5, 6);
-                    tim[5] = ev_ms(6, 7);
-                }
-            }
-            if (!rc) {
-                size_t t = 0;
-                for (int k = 0; k < m; ++k) {
-                    PngJob& j = *J[k];
-                    if (j.state != 1) continue;
-                    const bool rows_ok = (herr[k] & 3) == 0;  // (bit 4: Average / Paeth rows, not an error)
-                    bool lanes_ok = true;
-                    for (size_t i = 0; i < j.lanes.start.size(); ++i) {
-                        const uint32_t nu = wavedec ? j.lanes.res[i].units : 1u;  // expand waves of this lane
-                        for (uint32_t u = 0; u < nu; ++u, ++t) {
-                            lanes_ok = lanes_ok && hxst[2 * t] == 0;
-                            if (timing && hxst[2 * t] != 0) {
-                                const infl::LaneResult& q = j.lanes.res[i];
-                                fprintf(stderr, "[png] stream %d lane %zu/%zu unit %u/%u: expand failed (start %llu stop %llu "
-                                        "end %llu out %llu tokens %u pieces %u blocks %u status %d)\n", j.idx, i,
-                                        j.lanes.start.size(), u, nu, (unsigned long long)j.lanes.start[i],
-                                        (unsigned long long)j.lanes.stop[i], (unsigned long long)q.end_bit,
-                                        (unsigned long long)q.out_len, q.ntok, q.pieces, q.blocks, q.status);
-                            }
-                        }
-                    }
-                    if (!rows_ok || !lanes_ok) reject(j, !lanes_ok ? "expand status" : "row filter bytes");
-                }
-            }
-        }
-        gate_leave(kGateKernels);  // unless the caller pinned it (transform_part: resize + encode next)
-        if (timing && !hl.empty()) {  // per-lane profile of the last decode round and the expand pass
-            double si = 0, sc = 0, sx = 0, mi = 0, mc = 0, mx = 0, sb = 0, mb = 0, ss = 0;
-            for (size_t t = 0; t < hres.size(); ++t) {
-                si += hres[t].iters; sc += hres[t].kcycles; sb += hres[t].blocks; ss += hres[t].kc_setup;
-                mi = std::max(mi, (double)hres[t].iters); mc = std::max(mc, (double)hres[t].kcycles);
-                mb = std::max(mb, (double)hres[t].blocks);
-            }
-            for (size_t t = 0; 2 * t + 1 < hxst.size(); ++t) {
-                sx += hxst[2 * t + 1];
-                mx = std::max(mx, (double)hxst[2 * t + 1]);
-            }
-            const double n1 = (double)std::max<size_t>(1, hres.size()), n2 = (double)std::max<size_t>(1, hxst.size() / 2);
-            fprintf(stderr, "[png] decode lanes %zu: iters mean %.0f max %.0f, blocks mean %.2f max %.0f, kcycles mean %.0f "
-                    "max %.0f (%.0f cycles/iter; setup kcycles mean %.0f); expand kcycles mean %.0f max %.0f\n",
-                    hres.size(), si / n1, mi, sb / n1, mb, sc / n1, mc, 1024.0 * sc / std::max(1.0, si), ss / n1, sx / n2,
-                    mx);
-        }
-        tim[0] = S.t_host;
-        tim[2] = count_dev;
-        tim[7] = rounds;
-        tim[8] = (double)hl.size();
-        tim[9] = m;
-        if (timing)
-            fprintf(stderr, "[png] t=%.1f %d streams (%d on the GPU): upload host %.2f ms, upload device %.2f ms (gather "
-                    "%.2f), waited+find %.2f ms (find %.2f), decode %.2f ms (%d rounds, %d dropped, %d overflows), "
-                    "expand+resolve+unfilter %.2f ms\n",
-                    fmod(t0, 1e5), n, m, tim[0], tim[1], tim[14], t1 - t0, tim[13], t3 - t2, rounds, dropped, overflows,
-                    now_ms() - t3);
-        if (timing)
-            fprintf(stderr, "[png] host: plan+lanes %.2f, (decode rounds) .. tables %.2f, rows+uploads %.2f, "
-                    "(expand..unfilter) %.2f, after %.2f ms\n", mk[0] - t2, mk[1] - t3, mk[2] - mk[1], mk[3] - mk[2],
-                    now_ms() - mk[3]);
+
+// ---- step 5: expand -> resolve (or the markers) -> unfilter + Adam7 + EXPAND, then
+// the status words come back ----
+void png_expand_unfilter(PngStage& T, PngWork& W, Xfer& X) {
+    int& rc = T.rc;
+    const hipStream_t s = T.s;
+    const bool wavedec = T.wavedec;
+    std::vector<PngLaneDev>& hl = T.ht.lanes;
+    std::vector<int2>& hrows = T.ht.rows;
+    std::vector<int>& hxst = T.ht.xst;
+    const int ne = T.ne;
+    const PngMarks& marks = W.marks;
+    hrows.clear();
+    hxst.clear();
+    T.herr.assign(ne, 0);
+    if (rc || hl.empty()) return;
+    // expand goes out first; the resolve pass's page and row tables are built
+    // on the host while it runs (stream order puts their uploads after it)
+    hipError_t ue = X.h2d(W.d_lanes, hl.data(), sizeof(PngLaneDev) * hl.size());
+    if (ue == hipSuccess) ue = X.h2d(W.d_obase, T.ht.obase.data(), sizeof(int64_t) * T.ht.obase.size());
+    if (ue == hipSuccess) ue = X.h2d(W.d_imgs, T.hd.data(), sizeof(PngImgDev) * ne);
+    if (ue == hipSuccess) ue = hipMemsetAsync(W.d_err, 0, sizeof(int) * ne, s);
+    if (ue == hipSuccess && marks.count) ue = hipMemsetAsync(marks.count, 0, sizeof(uint32_t) * kMarkLists, s);
+    if (ue != hipSuccess) rc = hip_fail(ue, "PNG expand tables");
+    hxst.resize(2 * T.nexp);
+    T.mk[2] = now_ms();  // lane tables uploaded
+    // the next batch's block search (VALU-bound) beside this batch's expand,
+    // resolve and unfilter, which run at a raised wave priority (ik_png.hip
+    // raise_priority): the stage executor's hook
+    if (!rc && !T.search_done && T.up.on_next_search) T.next_search(nullptr);
+    if (rc) return;
+    hipError_t e3 = hipSuccess;
+    T.rec(4);
+    if (wavedec) {
+        // the units' tables and page tables (k_png_units), then one wave per unit
+        e3 = launch_png_units(W.d_imgs, W.d_lanes, (int)hl.size(), W.d_units, W.d_ulane, s);
+        if (e3 == hipSuccess)
+            e3 = launch_png_expand(W.d_imgs, W.d_lanes, (int)T.nunits, W.d_tok, W.d_uxst, s, W.d_pieces, W.d_units,
+                                   W.d_ulane, marks);
+    } else {
+        e3 = launch_png_expand(W.d_imgs, W.d_lanes, (int)hl.size(), W.d_tok, W.d_xst, s);
     }
-    release_area(S.area);  // (error paths)
-    if (m) {
-        (void)hipStreamSynchronize(s);  // the row images are read
-        for (int k = 0; k < m; ++k) {
-            PngJob& j = *J[k];
-            if (j.rows) { ik_image_free(j.rows); j.rows = nullptr; }
-            if (j.stage) { ik_image_free(j.stage); j.stage = nullptr; }
-            if (!rc && j.state == 1) {
-                outs[j.idx] = j.img;
-                j.img = nullptr;
-            } else {
-                if (j.img) { ik_image_free(j.img); j.img = nullptr; }
-                gpu[j.idx] = 0;  // host decoder below
-            }
-        }
-        if (rc) {  // the device path failed as a whole: every stream on the host
-            for (int k = 0; k < m; ++k) gpu[J[k]->idx] = 0;
+    T.rec(5);
+    build_page_and_row_tables(T);
+    if (e3 == hipSuccess && !wavedec) e3 = X.h2d(W.d_pages, T.ht.pages.data(), sizeof(int) * T.ht.pages.size());
+    if (e3 == hipSuccess) e3 = X.h2d(W.d_rows, hrows.data(), sizeof(int2) * hrows.size());
+    if (e3 == hipSuccess)
+        e3 = marks.list ? launch_png_marks(W.d_imgs, marks, W.d_rows, (int)hrows.size(), W.d_err, s)
+                        : launch_png_resolve(W.d_imgs, W.d_rows, (int)hrows.size(), W.d_err, s);
+    T.rec(6);
+#ifdef IK_PNG_DUMP  // dev experiment: every image's filtered rows and filter types before the unfilter
+    if (e3 == hipSuccess) {
+        (void)hipStreamSynchronize(s);
+        png_dump_store(T.J, T.hd, T.m);
+    }
+#endif
+    e3 = png_unfilter_all(T, W, X, e3);
+    T.rec(7);
+#ifdef IK_EXP_PROF
+    report_exp_prof(s, T.nexp);
+#endif
+#ifdef IK_UNF_PROF
+    report_unf_prof(s);
+#endif
+    uint32_t nmarks = 0, mcnt[kMarkLists];
+    bool mover = false;
+    if (e3 == hipSuccess && marks.count) {
+        e3 = X.d2h(mcnt, marks.count, sizeof(mcnt));
+        for (uint32_t q = 0; q < kMarkLists; ++q) {
+            nmarks += mcnt[q];
+            mover = mover || mcnt[q] > marks.cap / kMarkLists;
         }
     }
-    // ---- host decoder: streams outside the GPU path, and GPU rejects ----
-    std::vector<int> host;
-    for (int i = 0; i < n; ++i)
-        if (!gpu[i]) host.push_back(i);
-    tim[11] = (double)host.size();
-    tim[10] = (double)(n - (int)host.size());
-    g_png_gpu_streams += (unsigned long long)(n - (int)host.size());
-    g_png_host_streams += (unsigned long long)host.size();
+    if (e3 == hipSuccess && mover) {
+        // the marker list overflowed (runs of copies across units, e.g. a flat
+        // image): the rows from the u16 symbols after all, then the unfilter again
+        if (T.timing) fprintf(stderr, "[png] %u window markers > list %u: resolve pass\n", nmarks, marks.cap);
+        e3 = hipMemsetAsync(W.d_err, 0, sizeof(int) * ne, s);
+        if (e3 == hipSuccess) e3 = launch_png_resolve(W.d_imgs, W.d_rows, (int)hrows.size(), W.d_err, s);
+        e3 = png_unfilter_all(T, W, X, e3);
+    }
+    if (T.timing && marks.count) fprintf(stderr, "[png] window markers %u (list %u)\n", nmarks, marks.cap);
+    if (e3 == hipSuccess) e3 = X.d2h(hxst.data(), wavedec ? W.d_uxst : W.d_xst, 2 * sizeof(int) * T.nexp);
+    if (e3 == hipSuccess) e3 = X.d2h(T.herr.data(), W.d_err, sizeof(int) * ne);
+    for (int k = T.m; k < ne; ++k) T.herr[T.unf_job[k]] |= T.herr[k];  // a pass image's flags are its stream's
+    T.mk[3] = now_ms();  // expand .. unfilter done
+    if (e3 != hipSuccess) rc = hip_fail(e3, "PNG inflate (expand) / unfilter");
+    if (!rc) {
+        T.tim[kTimExpandMs] = ev_ms(4, 5);
+        T.tim[kTimResolveMs] = ev_ms(5, 6);
+        T.tim[kTimUnfilterMs] = ev_ms(6, 7);
+    }
+}
+
+// ---- step 6: a verified job whose expand waves or rows reported trouble goes to
+// the host decoder ----
+void png_judge_jobs(PngStage& T) {
+    if (T.rc || T.ht.lanes.empty()) return;
+    const std::vector<int>& hxst = T.ht.xst;
+    size_t t = 0;
+    for (int k = 0; k < T.m; ++k) {
+        PngJob& j = *T.J[k];
+        if (j.state != 1) continue;
+        const bool rows_ok = (T.herr[k] & 3) == 0;  // (bit 4: Average / Paeth rows, not an error)
+        bool lanes_ok = true;
+        for (size_t i = 0; i < j.lanes.start.size(); ++i) {
+            const uint32_t nu = T.wavedec ? j.lanes.res[i].units : 1u;  // expand waves of this lane
+            for (uint32_t u = 0; u < nu; ++u, ++t) {
+                lanes_ok = lanes_ok && hxst[2 * t] == 0;
+                if (T.timing && hxst[2 * t] != 0) {
+                    const infl::LaneResult& q = j.lanes.res[i];
+                    fprintf(stderr, "[png] stream %d lane %zu/%zu unit %u/%u: expand failed (start %llu stop %llu "
+                            "end %llu out %llu tokens %u pieces %u blocks %u status %d)\n", j.idx, i,
+                            j.lanes.start.size(), u, nu, (unsigned long long)j.lanes.start[i],
+                            (unsigned long long)j.lanes.stop[i], (unsigned long long)q.end_bit,
+                            (unsigned long long)q.out_len, q.ntok, q.pieces, q.blocks, q.status);
+                }
+            }
+        }
+        if (!rows_ok || !lanes_ok) T.reject(j, !lanes_ok ? "expand status" : "row filter bytes");
+    }
+}
+
+// the stage's fields of ik_png_last_timing, and IK_TIMING's lines: the per-lane
+// profile of the last decode round and the expand pass, the stage's times, the host marks
+void png_stage_report(PngStage& T, int n) {
+    const std::vector<infl::LaneResult>& hres = T.ht.res;
+    const std::vector<int>& hxst = T.ht.xst;
+    double* tim = T.tim;
+    if (T.timing && !T.ht.lanes.empty()) {
+        double si = 0, sc = 0, sx = 0, mi = 0, mc = 0, mx = 0, sb = 0, mb = 0, ss = 0;
+        for (size_t t = 0; t < hres.size(); ++t) {
+            si += hres[t].iters; sc += hres[t].kcycles; sb += hres[t].blocks; ss += hres[t].kc_setup;
+            mi = std::max(mi, (double)hres[t].iters); mc = std::max(mc, (double)hres[t].kcycles);
+            mb = std::max(mb, (double)hres[t].blocks);
+        }
+        for (size_t t = 0; 2 * t + 1 < hxst.size(); ++t) {
+            sx += hxst[2 * t + 1];
+            mx = std::max(mx, (double)hxst[2 * t + 1]);
+        }
+        const double n1 = (double)std::max<size_t>(1, hres.size()), n2 = (double)std::max<size_t>(1, hxst.size() / 2);
+        fprintf(stderr, "[png] decode lanes %zu: iters mean %.0f max %.0f, blocks mean %.2f max %.0f, kcycles mean %.0f "
+                "max %.0f (%.0f cycles/iter; setup kcycles mean %.0f); expand kcycles mean %.0f max %.0f\n",
+                hres.size(), si / n1, mi, sb / n1, mb, sc / n1, mc, 1024.0 * sc / std::max(1.0, si), ss / n1, sx / n2,
+                mx);
+    }
+    tim[kTimUploadHostMs] = T.S.t_host;
+    tim[kTimRounds] = T.rounds;
+    tim[kTimLanes] = (double)T.ht.lanes.size();
+    tim[kTimSentToGpu] = T.m;
+    if (!T.timing) return;
+    fprintf(stderr, "[png] t=%.1f %d streams (%d on the GPU): upload host %.2f ms, upload device %.2f ms (gather "
+            "%.2f), waited+find %.2f ms (find %.2f), decode %.2f ms (%d rounds, %d dropped, %d overflows), "
+            "expand+resolve+unfilter %.2f ms\n",
+            fmod(T.t0, 1e5), n, T.m, tim[kTimUploadHostMs], tim[kTimUploadDevMs], tim[kTimGatherMs], T.t1 - T.t0,
+            tim[kTimFindMs], T.t3 - T.t2, T.rounds, T.dropped, T.overflows, now_ms() - T.t3);
+    fprintf(stderr, "[png] host: plan+lanes %.2f, (decode rounds) .. tables %.2f, rows+uploads %.2f, "
+            "(expand..unfilter) %.2f, after %.2f ms\n", T.mk[0] - T.t2, T.mk[1] - T.t3, T.mk[2] - T.mk[1],
+            T.mk[3] - T.mk[2], now_ms() - T.mk[3]);
+}
+
+// ---- step 7: the verified streams' images to the caller; the others (and every one
+// when the device path failed as a whole) to the host decoder ----
+void png_hand_out(PngStage& T, ik_image** outs) {
+    (void)hipStreamSynchronize(T.s);  // the row images are read
+    for (PngJob* jp : T.J) {
+        PngJob& j = *jp;
+        if (j.rows) { ik_image_free(j.rows); j.rows = nullptr; }
+        if (j.stage) { ik_image_free(j.stage); j.stage = nullptr; }
+        if (!T.rc && j.state == 1) {
+            outs[j.idx] = j.img;
+            j.img = nullptr;
+        } else {
+            if (j.img) { ik_image_free(j.img); j.img = nullptr; }
+            T.S.gpu[j.idx] = 0;
+        }
+    }
+}
+
+// the host decoder: streams outside the GPU path, and GPU rejects
+void png_host_decode(const PngUpload& up, const std::vector<int>& host, ik_image** outs, int* status, std::string* msgs) {
     parallel_for((int)host.size(), 0, [&](int k) {
         const int i = host[k];
         thread_local std::vector<uint8_t> px;
         uint32_t w = 0, h = 0, c = 0, dep = 1;
         // a device-resident file comes back to host memory for the host decoder
         std::vector<uint8_t> hb;
-        const uint8_t* src = bytes[i];
+        const uint8_t* src = up.bytes[i];
         if (up.dev) {
-            hb.resize(lens[i]);
-            if (lens[i] && hipMemcpy(hb.data(), bytes[i], lens[i], hipMemcpyDeviceToHost) != hipSuccess) {
+            hb.resize(up.lens[i]);
+            if (up.lens[i] && hipMemcpy(hb.data(), up.bytes[i], up.lens[i], hipMemcpyDeviceToHost) != hipSuccess) {
                 status[i] = hip_fail(hipErrorUnknown, "PNG device input copy");
                 if (msgs) msgs[i] = "PNG device input copy failed";
                 return;
             }
             src = hb.data();
         }
-        int st = decode_png(src, lens[i], w, h, c, px, &dep);
+        int st = decode_png(src, up.lens[i], w, h, c, px, &dep);
         if (!st) st = dep == 2 ? ik_image_from_host16(reinterpret_cast<const uint16_t*>(px.data()), w, h, c, &outs[i])
                                : ik_image_from_host(px.data(), w, h, c, &outs[i]);
         if (px.capacity() > (128u << 20)) std::vector<uint8_t>().swap(px);
@@ -1760,10 +1862,47 @@ int png_decode_finish(PngUpload& up, ik_image** outs, int* status, std::string* 
             msgs[i] = buf;
         }
     });
-    tim[6] = now_ms() - t0;
-    if (m) {
+}
+
+}  // namespace
+
+int png_decode_finish(PngUpload& up, ik_image** outs, int* status, std::string* msgs) {
+    static const bool timing = getenv("IK_TIMING") != nullptr;
+    static thread_local HostTables ht;
+    PngBatchState& S = *up.st;
+    const int n = up.n;
+    PngStage T{up, S, S.J, (int)S.J.size(), thread_stream(), events(), ht, timing, png_wave_decoder(), S.rc, now_ms()};
+    for (int i = 0; i < n; ++i) {
+        outs[i] = nullptr;
+        status[i] = IK_OK;
+    }
+    if (T.m && !T.rc) {
+        PngWork W;
+        Xfer X;
+        png_plan_work(T, W, X);
+        gate_enter(kGateKernels);  // the kernels run under the device's kernel gate (ik_runtime.h)
+        png_search_results(T, W, X);
+        png_decode_rounds(T, W, X);
+        png_verified_tables(T, W);
+        png_expand_unfilter(T, W, X);
+        png_judge_jobs(T);
+        gate_leave(kGateKernels);  // unless the caller pinned it (transform_part: resize + encode next)
+        png_stage_report(T, n);
+    }
+    release_area(S.area);  // (error paths)
+    if (T.m) png_hand_out(T, outs);
+    std::vector<int> host;
+    for (int i = 0; i < n; ++i)
+        if (!S.gpu[i]) host.push_back(i);
+    T.tim[kTimHostDecoded] = (double)host.size();
+    T.tim[kTimGpuDecoded] = (double)(n - (int)host.size());
+    g_png_gpu_streams += (unsigned long long)(n - (int)host.size());
+    g_png_host_streams += (unsigned long long)host.size();
+    png_host_decode(up, host, outs, status, msgs);
+    T.tim[kTimStageWallMs] = now_ms() - T.t0;
+    if (T.m) {
         std::lock_guard<std::mutex> lk(g_timing_mu);
-        g_timing[S.device].assign(tim, tim + kPngTimingFields);
+        g_timing[S.device].assign(T.tim, T.tim + kPngTimingFields);
     }
     if (timing) fprintf(stderr, "[png] decode_png_batch returns at t=%.1f\n", fmod(now_ms(), 1e5));
     up.st.reset();

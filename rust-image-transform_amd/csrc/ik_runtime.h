@@ -186,8 +186,12 @@ uint64_t request_cost(const uint8_t* b, size_t n, int64_t w, int64_t h, int fmt)
 hipStream_t thread_stream();  // per-thread, per-device non-blocking stream
 hipStream_t thread_copy_stream();  // a second one, for uploads that overlap the first's kernels
 // a third, at the highest priority, and an event to order it after the first (the
-// exact WebP coder's launches); false if it cannot be made
+// exact WebP coder's launches; ev may be null); false if it cannot be made
 bool thread_prio_stream(hipStream_t* s, hipEvent_t* ev);
+// two events (no timing) of the calling thread on its current device, to fork work
+// from one of its streams to another and join it back (the PNG unfilter); made on
+// first use on that device; false if they cannot be made
+bool thread_fork_join_events(hipEvent_t* fork, hipEvent_t* join);
 size_t pitch_for(uint32_t w, uint32_t c);
 uint8_t* scratch(size_t bytes);  // per-thread device scratch, valid until the next call
 // per-thread, per-device grow-only device arenas for batch work (slot 1: JPEG
