@@ -139,8 +139,11 @@ int ik_decode(const uint8_t *bytes, size_t len, ik_image **out, int *fmt_out);
 /* decode_image over n inputs at once (the /img handler under load).  Baseline
  * JPEG scans (with or without restart markers) are entropy-decoded together by
  * the self-synchronising GPU decoder (a few launches for the whole batch) and
- * reconstructed on the GPU; PNG streams go through the batched GPU inflate; other
- * inputs through ik_decode.  outs[i] / fmts[i] / status[i] per input (outs[i]
+ * reconstructed on the GPU; PNG streams go through the batched GPU inflate; lossy
+ * WebP files (no alpha, no animation) are parsed on the host workers and
+ * reconstructed together by one pair of GPU launches (IK_WEBP_DECODE=auto: when
+ * they total 3 MPix; the other WebP kinds by libwebp); inputs of any other kind get
+ * ik_decode's verdict.  outs[i] / fmts[i] / status[i] per input (outs[i]
  * NULL on failure; fmts and status may be NULL); returns the first failure or
  * IK_OK. */
 int ik_decode_batch(const uint8_t *const *bytes, const size_t *lens, uint32_t n, ik_image **outs,
@@ -186,6 +189,33 @@ int ik_png_counters(unsigned long long *out);
  * the inflated stream; *raw_total (may be NULL) = the inflated length.  Returns
  * the number of non-empty passes. */
 int ik_png_adam7_plan(uint32_t w, uint32_t h, int bits_pp, uint64_t *out, uint64_t *raw_total);
+/* process-wide counts of WebP streams decoded since load (ik_decode and the batch
+ * calls alike): out[0] reconstructed by the GPU decoder, out[1] handed to libwebp on
+ * the host (outside the GPU path, handed back by it, or by policy) */
+int ik_webp_counters(unsigned long long *out);
+/* the last batch with WebP inputs finished on the calling thread's device (n <= 10
+ * values): [0] wall ms of the host half (partition 0 + tokens of the lossy files,
+ * libwebp for the others, on the worker pool), [1] thread CPU ms of partition 0 +
+ * tokens summed over the files (core-ms), [2] staging copies + H2D ms, device ms
+ * (HIP events) of [3] reconstruction and loop filter [4] upsampling and colour,
+ * [5] images the GPU decoded, [6] images handed to libwebp, [7] macroblock rows
+ * launched, [8] the reconstruction grid (the largest of the sub-launches),
+ * [9] sub-launches */
+int ik_webp_last_timing(double *out, int n);
+/* the pixel total of a batch's lossy WebP files from which IK_WEBP_DECODE=auto
+ * takes the GPU batch path */
+unsigned long long ik_webp_gpu_min_batch_pixels(void);
+/* the launch plan of a batch of lossy WebP frames (no GPU needed): n frames of
+ * mb_w[i] x mb_h[i] macroblocks taking bytes[i] of device memory each.  order[k] is
+ * the request placed k-th (largest first: by MB rows, then by MBs, then by index);
+ * launch_lo (room for n + 1) lists the first k of each sub-launch and then n: the
+ * placed frames are cut where the next would take a sub-launch past cap_bytes, and a
+ * frame above the cap is alone in its own; row_start (n + 1 values) is the MB-row
+ * ticket of each placed frame's first row, restarting at 0 in each sub-launch, and
+ * row_start[n] the MB rows of the last sub-launch.  Returns the sub-launch count
+ * (0 for n = 0). */
+int ik_webp_batch_plan(const uint32_t *mb_w, const uint32_t *mb_h, const uint64_t *bytes, uint32_t n,
+                       uint64_t cap_bytes, uint32_t *order, uint32_t *row_start, uint32_t *launch_lo);
 /* process-wide JPEG counters: out[0] = streams whose entropy decoding ran on the
  * GPU (restart intervals or self-synchronising scans), out[1] = on the host */
 int ik_jpeg_counters(unsigned long long *out);

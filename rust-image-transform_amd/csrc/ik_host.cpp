@@ -1369,6 +1369,7 @@ static int decode_one(const uint8_t* bytes, size_t len, ik_image** out, int* fmt
         if (st == kVp8dHost) {
             if (webp_decode_mode() == 2)
                 return fail(IK_ERR_TRANSFORM, "IK_WEBP_DECODE=gpu: the GPU WebP decoder leaves this file to libwebp");
+            webp_count_host_decode();
             st = decode_webp(bytes, len, w, h, c, px);
         }
         break;
@@ -1406,7 +1407,9 @@ int decode_batch_dev(const uint8_t* const* bytes, const size_t* lens, uint32_t n
                      const uint8_t* const* sniff = nullptr, const JpegUpload* jup = nullptr) {
     std::vector<const uint8_t*> jb, pb, ph;
     std::vector<size_t> jl, pl;
-    std::vector<uint32_t> ji, pi, other;
+    std::vector<const uint8_t*> wb;
+    std::vector<size_t> wl;
+    std::vector<uint32_t> ji, pi, wi, other;
     for (uint32_t i = 0; i < n; ++i) {
         outs[i] = nullptr;
         st[i] = IK_OK;
@@ -1423,6 +1426,10 @@ int decode_batch_dev(const uint8_t* const* bytes, const size_t* lens, uint32_t n
             pl.push_back(lens[i]);
             ph.push_back(sniff ? sniff[i] : bytes[i]);
             pi.push_back(i);
+        } else if (f == Sniffed::WebP) {
+            wb.push_back(bytes[i]);
+            wl.push_back(lens[i]);
+            wi.push_back(i);
         } else {
             other.push_back(i);
         }
@@ -1446,11 +1453,23 @@ int decode_batch_dev(const uint8_t* const* bytes, const size_t* lens, uint32_t n
             msg[pi[k]] = pm[k];
         }
     }
-    parallel_for((int)other.size(), threads, [&](int k) {  // PNG / WebP / unknown: host decoders, in parallel
+    parallel_for((int)other.size(), threads, [&](int k) {  // unknown and unsupported formats: decode_image's verdicts
         const uint32_t i = other[k];
         st[i] = decode_one(bytes[i], lens[i], &outs[i], fmts ? &fmts[i] : nullptr);
         if (st[i]) msg[i] = t_err;
     });
+    if (!wi.empty()) {  // the batch's lossy WebP frames through one set of launches, the rest by libwebp
+        std::vector<ik_image*> wo(wi.size(), nullptr);
+        std::vector<int> ws(wi.size(), IK_OK);
+        std::vector<std::string> wm(wi.size());
+        decode_webp_batch(wb.data(), wl.data(), (int)wi.size(), wo.data(), ws.data(), wm.data(), threads);
+        for (size_t k = 0; k < wi.size(); ++k) {
+            outs[wi[k]] = wo[k];
+            st[wi[k]] = ws[k];
+            msg[wi[k]] = wm[k];
+            if (fmts && !ws[k]) fmts[wi[k]] = IK_FORMAT_WEBP;
+        }
+    }
     if (!ji.empty()) {
         std::vector<ik_image*> jo(ji.size(), nullptr);
         std::vector<int> js(ji.size(), IK_OK);

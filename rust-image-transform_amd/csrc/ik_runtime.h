@@ -297,6 +297,19 @@ int decode_webp(const uint8_t* b, size_t n, uint32_t& w, uint32_t& h, uint32_t& 
 // WebP kinds, anything its parser finds unusual, data that runs out.
 constexpr int kVp8dHost = -1000;
 int decode_webp_device(const uint8_t* b, size_t n, ik_image** out);
+void webp_count_host_decode();  // a WebP stream handed to decode_webp outside decode_webp_batch (ik_webp_counters)
+// decode_image over a batch's n WebP files: the lossy ones the GPU path takes are
+// parsed in parallel (partition 0 and the tokens, on up to `threads` threads) and
+// reconstructed together -- one staged area, one H2D, one k_vp8d_recon and one
+// k_vp8d_rgb launch over all of them (sub-launches past IK_VP8D_BATCH_BYTES, default
+// 256 MiB); the rest (alpha, lossless, animation, anything handed back, a frame whose
+// err word the device set) go to libwebp on the worker that found them.  IK_WEBP_DECODE
+// is read per batch: host = libwebp only; gpu = every lossy file takes the batch path
+// and a file left to libwebp is an error; auto = the batch path when its lossy files
+// total kWebpGpuMinBatchPixels pixels.  outs / status / msgs per file as decode_image
+// gives them; returns the first failure.
+int decode_webp_batch(const uint8_t* const* b, const size_t* lens, int n, ik_image** outs, int* status,
+                      std::string* msgs, int threads);
 // IK_WEBP_DECODE (read per call): 0 "host" (libwebp only), 2 "gpu" (every size; a file
 // the GPU path leaves to the host is an error instead: the tests' proof that it ran),
 // 1 otherwise (auto: the GPU path from 3 MPix, where it is faster than libwebp)

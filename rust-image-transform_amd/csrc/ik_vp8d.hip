@@ -1,17 +1,28 @@
 // ik_vp8d.hip -- device half of the GPU WebP (VP8 lossy) decoder (host half:
 // ik_vp8d_host.cpp, which also decodes the token partitions: an arithmetic-coded
 // stream, serial symbol by symbol -- one wave decoding it on the scalar unit ran at
-// 1/12 of a CPU core).  Two launches per batch of images:
+// 1/12 of a CPU core).  Two launches per batch of images (one image for
+// ik_decode, a batch's lossy files together for decode_webp_batch):
 //   k_vp8d_recon   prediction + inverse transforms + loop filter (frame_dec.c
-//                  ReconstructRow / DoFilter): one workgroup per image, one wave per MB
-//                  row, kReconWaves rows in flight, each two MBs behind the row above
-//                  (the unfiltered top row, the top-right samples and the filtered
-//                  pixels its edges touch are final by then); per wave an LDS work area
-//                  holds the MB being predicted and its filter window, so each pixel is
-//                  written to HBM once per MB.  Intra-4 MBs go by sub-block diagonals
-//                  (x + 2y: ten steps, a lane per pixel), the other blocks a lane each.
+//                  ReconstructRow / DoFilter): one-wave workgroups that take (image, MB
+//                  row) tickets in order over every image of the launch, so the rows in
+//                  flight are the grid's waves, spread over the images; a row runs two
+//                  MBs behind the row above it (the unfiltered top row, the top-right
+//                  samples and the filtered pixels its edges touch are final by then).
+//                  The launch plan (row_start: the ticket of each image's first row,
+//                  images largest first) maps a ticket to its image by binary search.
+//                  Per wave an LDS work area holds the MB being predicted and its filter
+//                  window, so each pixel is written to HBM once per MB.  Intra-4 MBs go
+//                  by sub-block diagonals (x + 2y: ten steps, a lane per pixel), the
+//                  other blocks a lane each.
 //   k_vp8d_rgb     fancy chroma upsampling + YUV -> RGB (io_dec.c EmitFancyRGB,
-//                  upsampling.c UPSAMPLE_FUNC, yuv.h VP8YuvToRgb) into the ik_image
+//                  upsampling.c UPSAMPLE_FUNC, yuv.h VP8YuvToRgb) into the ik_image: a
+//                  workgroup per row tile of the plan's tile table (about 1024 pixels of
+//                  one image: one row of a wide image, several of a narrow one)
+#include <atomic>
+#include <cstdlib>
+#include <cstring>
+
 #include <hip/hip_runtime.h>
 
 #include "ik_vp8d_gpu.h"
@@ -111,7 +122,20 @@ __device__ __forceinline__ int idct_pixel(const int16_t* q, int r, int c) {
 // ever waits for the row ticketed just before it, which a running wave holds: the
 // grid drains whatever the residency.  A row publishes its progress (MBs done) after
 // its stores of each MB; the row below starts MB x once the row above has done x + 2.
-__global__ __launch_bounds__(64) void k_vp8d_recon(const DImg* __restrict__ imgs, int n, uint32_t* __restrict__ ticket) {
+//
+// Over a batch the argument is the same, whatever the order of the images: ticket t is
+// row t - row_start[k] of the k-th placed image, so an image's rows hold consecutive
+// tickets, and the only row a row waits for -- the one above it in the same image -- is
+// ticket t - 1.  A wave draws a ticket only while it runs, and the counter hands them
+// out in order, so the wave that drew t - 1 is resident (or done) when t is drawn: it
+// never waits for a workgroup that has yet to be scheduled, with any grid and any
+// residency.  The first row of an image (t = row_start[k]) waits for nothing.  That is
+// what lets the plan place the largest images first: the order only decides which rows
+// are the launch's tail.  A row that gives up (err: the row above timed out or gave up)
+// takes the next ticket instead of leaving, so the other images' rows are all drawn;
+// the rows below it in its image see err and give up at once.
+__global__ __launch_bounds__(64) void k_vp8d_recon(const DImg* __restrict__ imgs, const uint32_t* __restrict__ row_start,
+                                                   int n, uint32_t* __restrict__ ticket) {
     __shared__ WaveLds L;
     __shared__ uint16_t s_tap[10 * 16];  // the predictor taps (a divergent index into them: LDS, not memory)
     const int lane = threadIdx.x;
@@ -126,15 +150,17 @@ __global__ __launch_bounds__(64) void k_vp8d_recon(const DImg* __restrict__ imgs
         uint32_t t = 0;
         if (lane == 0) t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         t = (uint32_t)ufl((int)t);
+        // the ticket's image: the last k with row_start[k] <= t (scalar loads)
+        const cptr<uint32_t> rs = (cptr<uint32_t>)row_start;
+        if (t >= rs[n]) return;
         int ii = 0;
-        uint32_t r0 = 0;
-        for (; ii < n; ++ii) {
-            r0 = ((cptr<DImg>)imgs)[ii].row0;
-            if (t < r0 + ((cptr<DImg>)imgs)[ii].rows) break;
+        for (int hi = n; hi - ii > 1;) {
+            const int mid = (ii + hi) >> 1;
+            if (rs[mid] <= t) ii = mid;
+            else hi = mid;
         }
-        if (ii == n) return;
         const cptr<DImg> di = (cptr<DImg>)imgs + ii;
-        const int mb_y = (int)(t - r0);
+        const int mb_y = (int)(t - rs[ii]);
         const cptr<DFrame> fr = (cptr<DFrame>)di->fr;
         // per-MB records as dwords (a byte through a scalar pointer becomes a vector
         // load and a wait per field)
@@ -172,17 +198,20 @@ __global__ __launch_bounds__(64) void k_vp8d_recon(const DImg* __restrict__ imgs
                 const uint32_t need = (uint32_t)min(mb_x + 2, mb_w);
                 if (seen < need) {
                     const uint64_t t_end = __builtin_amdgcn_s_memrealtime() + 400000000ull;  // 4 s
+                    bool gave_up = false;
                     for (;;) {
                         seen = (uint32_t)ufl((int)__hip_atomic_load(prog + mb_y - 1, __ATOMIC_RELAXED,
                                                                     __HIP_MEMORY_SCOPE_AGENT));
                         if (seen >= need) break;
-                        if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ||
+                        if (ufl((int)__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) ||
                             __builtin_amdgcn_s_memrealtime() > t_end) {
                             if (lane == 0) __hip_atomic_store(err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            return;
+                            gave_up = true;
+                            break;
                         }
                         __builtin_amdgcn_s_sleep(2);
                     }
+                    if (gave_up) break;  // this image is the host's; on to the next ticket
                 }
                 // the unfiltered row above (+ top-right) and the filter's top strip (rows
                 // 12..15 of the MB above, filtered), all sc1 loads
@@ -409,43 +438,91 @@ __global__ __launch_bounds__(64) void k_vp8d_recon(const DImg* __restrict__ imgs
     }
 }
 
-// fancy upsampling + colour: one workgroup per output row of one image
-__global__ __launch_bounds__(256) void k_vp8d_rgb(const DImg* __restrict__ imgs) {
-    const cptr<DImg> di = (cptr<DImg>)imgs + blockIdx.y;
+// fancy upsampling + colour: one workgroup per row tile (DTile: some rows of one image).
+// The block's threads split into 256 / L rows of L lanes, L the power of two that
+// covers the width (at most 256): a wide image gives a row all 256 threads, a narrow
+// one several rows at a time.
+__global__ __launch_bounds__(256) void k_vp8d_rgb(const DImg* __restrict__ imgs, const DTile* __restrict__ tiles) {
+    const cptr<uint32_t> tl = (cptr<uint32_t>)tiles + 3 * blockIdx.x;
+    const cptr<DImg> di = (cptr<DImg>)imgs + tl[0];
     const cptr<DFrame> fr = (cptr<DFrame>)di->fr;
-    const int w = fr->w, h = fr->h, r = blockIdx.x;
-    if (r >= h) return;
+    const int w = fr->w, h = fr->h;
+    const int r_end = min((int)(tl[1] + tl[2]), h);
     const int uvh = (h + 1) >> 1;
-    int nr, fr_;
-    if (r == 0) {
-        nr = fr_ = 0;
-    } else if (r & 1) {
-        nr = (r - 1) >> 1;
-        fr_ = min((r + 1) >> 1, uvh - 1);
-    } else {
-        nr = r >> 1;
-        fr_ = nr - 1;
-    }
-    const uint8_t* yrow = di->y + (size_t)r * di->ys;
-    const uint8_t *nu = di->u + (size_t)nr * di->uvs, *fu = di->u + (size_t)fr_ * di->uvs;
-    const uint8_t *nv = di->v + (size_t)nr * di->uvs, *fv = di->v + (size_t)fr_ * di->uvs;
-    uint8_t* out = di->out + (size_t)r * di->out_pitch;
-    for (int c = threadIdx.x; c < w; c += 256) {
-        const int yy = yrow[c], u = fancy_chroma(nu, fu, c, w), v = fancy_chroma(nv, fv, c, w);
-        out[3 * c + 0] = (uint8_t)yuv_r(yy, v);
-        out[3 * c + 1] = (uint8_t)yuv_g(yy, u, v);
-        out[3 * c + 2] = (uint8_t)yuv_b(yy, u);
+    const int sh = w >= 256 ? 8 : 32 - __clz(w - 1);  // (w = 1: __clz(0) = 32, one lane per row)
+    const int lanes = 1 << sh, step = 256 >> sh;
+    const int c0 = threadIdx.x & (lanes - 1);
+    for (int r = (int)tl[1] + ((int)threadIdx.x >> sh); r < r_end; r += step) {
+        int nr, fr_;
+        if (r == 0) {
+            nr = fr_ = 0;
+        } else if (r & 1) {
+            nr = (r - 1) >> 1;
+            fr_ = min((r + 1) >> 1, uvh - 1);
+        } else {
+            nr = r >> 1;
+            fr_ = nr - 1;
+        }
+        const uint8_t* yrow = di->y + (size_t)r * di->ys;
+        const uint8_t *nu = di->u + (size_t)nr * di->uvs, *fu = di->u + (size_t)fr_ * di->uvs;
+        const uint8_t *nv = di->v + (size_t)nr * di->uvs, *fv = di->v + (size_t)fr_ * di->uvs;
+        uint8_t* out = di->out + (size_t)r * di->out_pitch;
+        for (int c = c0; c < w; c += lanes) {
+            const int yy = yrow[c], u = fancy_chroma(nu, fu, c, w), v = fancy_chroma(nv, fv, c, w);
+            out[3 * c + 0] = (uint8_t)yuv_r(yy, v);
+            out[3 * c + 1] = (uint8_t)yuv_g(yy, u, v);
+            out[3 * c + 2] = (uint8_t)yuv_b(yy, u);
+        }
     }
 }
 
-hipError_t launch_vp8d_recon(const DImg* imgs, int n, uint32_t total_rows, uint32_t* ticket, hipStream_t s) {
-    // about one wave per CU: the rows in flight are bounded by the wavefront anyway
-    const uint32_t grid = total_rows < 256 ? total_rows : 256;
-    hipLaunchKernelGGL(k_vp8d_recon, dim3(grid), dim3(64), 0, s, imgs, n, ticket);
+// the waves of k_vp8d_recon a device holds at once: its occupancy per CU times the CUs
+// (asked once per device; 0 if the runtime does not say)
+static uint32_t resident_waves() {
+    static std::atomic<uint32_t> cache[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+    uint32_t v = cache[dev].load(std::memory_order_relaxed);
+    if (!v) {
+        int per_cu = 0, cus = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_vp8d_recon, 64, 0) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per_cu <= 0 || cus <= 0)
+            return 0;
+        v = (uint32_t)per_cu * (uint32_t)cus;
+        cache[dev].store(v, std::memory_order_relaxed);
+    }
+    return v;
+}
+
+hipError_t launch_vp8d_recon(const DImg* imgs, const uint32_t* row_start, int n, uint32_t total_rows, uint32_t* ticket,
+                             hipStream_t s, uint32_t* grid_used) {
+    // One image: about one wave per CU, the rows in flight are bounded by its wavefront
+    // anyway.  A batch: every wave the device can hold (the kernel's occupancy times the
+    // CU count; kReconBatchGrid if the runtime does not say) -- the rows of different
+    // images do not wait for each other, and the reconstruction of 64 1024x768 frames
+    // took 13.4 / 7.5 / 4.5 / 2.1 ms with 256 / 512 / 1024 / that many workgroups
+    // (profiles/webp_batch_notes.md).
+    uint32_t grid = 256;
+    if (n > 1) {
+        grid = resident_waves();
+        if (!grid) grid = kReconBatchGrid;
+    }
+    if (const char* e = getenv("IK_VP8D_GRID")) {  // dev switch: a number, or "occ" for the batch grid
+        if (!std::strcmp(e, "occ")) {
+            if (const uint32_t v = resident_waves()) grid = v;
+        } else if (const long v = atol(e); v > 0 && v <= (1 << 20)) {
+            grid = (uint32_t)v;
+        }
+    }
+    if (grid > total_rows) grid = total_rows;
+    if (grid_used) *grid_used = grid;
+    if (!grid) return hipSuccess;
+    hipLaunchKernelGGL(k_vp8d_recon, dim3(grid), dim3(64), 0, s, imgs, row_start, n, ticket);
     return hipGetLastError();
 }
-hipError_t launch_vp8d_rgb(const DImg* imgs, int n, int max_h, hipStream_t s) {
-    hipLaunchKernelGGL(k_vp8d_rgb, dim3(max_h, n), dim3(256), 0, s, imgs);
+hipError_t launch_vp8d_rgb(const DImg* imgs, const DTile* tiles, uint32_t ntiles, hipStream_t s) {
+    if (!ntiles) return hipSuccess;
+    hipLaunchKernelGGL(k_vp8d_rgb, dim3(ntiles), dim3(256), 0, s, imgs, tiles);
     return hipGetLastError();
 }
 

@@ -24,14 +24,29 @@ struct alignas(16) DImg {
     uint8_t* out;            // the ik_image's pixels (RGB)
     uint32_t ys, uvs;        // plane pitches
     uint32_t out_pitch;
-    uint32_t row0, rows;     // the launch's tickets of this image's MB rows: [row0, row0 + rows)
     uint32_t* prog;          // per MB row: MBs done (zeroed per launch)
     uint32_t* err;           // set when a row's wait times out (zeroed per launch)
 };
 
-// ticket: zeroed per launch; total_rows: the images' MB rows together
-hipError_t launch_vp8d_recon(const DImg* imgs, int n, uint32_t total_rows, uint32_t* ticket, hipStream_t s);
-hipError_t launch_vp8d_rgb(const DImg* imgs, int n, int max_h, hipStream_t s);
+// One block's work of the colour launch: rows [row0, row0 + rows) of image img
+struct DTile {
+    uint32_t img, row0, rows;
+};
+// the rows of a w-wide image that make one tile: about kRgbTilePixels pixels
+constexpr uint32_t kRgbTilePixels = 1024;
+inline uint32_t rgb_tile_rows(uint32_t w) { return w >= kRgbTilePixels ? 1 : kRgbTilePixels / w; }
+
+// The launch plan beside imgs (the images in plan order: ik_vp8d_plan.h): row_start[k]
+// is the ticket of image k's first MB row, row_start[n] the launch's MB rows.
+// ticket: zeroed per launch.  The grid is min(rows, 256) for one image and, for
+// several, min(rows, the waves the device holds at once: the kernel's occupancy times
+// the CU count; kReconBatchGrid if the runtime does not say).  IK_VP8D_GRID (dev
+// switch) forces a grid: a number, or "occ" for the batch's.  *grid_used (may be
+// null) is the grid.
+constexpr uint32_t kReconBatchGrid = 1024;
+hipError_t launch_vp8d_recon(const DImg* imgs, const uint32_t* row_start, int n, uint32_t total_rows, uint32_t* ticket,
+                             hipStream_t s, uint32_t* grid_used);
+hipError_t launch_vp8d_rgb(const DImg* imgs, const DTile* tiles, uint32_t ntiles, hipStream_t s);
 
 }  // namespace vp8d
 }  // namespace ik

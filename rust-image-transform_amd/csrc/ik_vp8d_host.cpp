@@ -14,14 +14,27 @@
 // Files it does not cover -- lossless (VP8L), alpha, animation, anything its parser
 // finds unusual, data that runs out -- go to the host decoder (decode_webp), which
 // then gives libwebp's answer, error message included.
+//
+// Two drivers over one launch sequence (run_launch): decode_webp_device, one file of
+// one ik_decode call, and decode_webp_batch, the lossy files of a batch call together
+// -- their host halves in parallel on the worker pool, then one staged area and one
+// pair of launches over all of them, laid out by the plan of ik_vp8d_plan.h.
+#include <algorithm>
+#include <array>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <ctime>
+#include <map>
+#include <mutex>
 #include <vector>
 
+#include "../../include/imagekit_hip.h"
 #include "ik_runtime.h"
 #include "ik_vp8d_gpu.h"
+#include "ik_vp8d_plan.h"
 
 namespace ik {
 
@@ -435,116 +448,444 @@ int webp_decode_mode() {  // IK_WEBP_DECODE: host / gpu (no host fallback: tests
 // (mb_w + 2 mb_h) MB steps of ~12-25 us; libwebp ~4 ms per MPix.
 constexpr uint64_t kWebpGpuMinPixels = 3000000;
 
-int decode_webp_device(const uint8_t* b, size_t n, ik_image** out) {
-    if (!webp_decode_mode()) return kVp8dHost;
-    size_t off = 0, len = 0;
-    uint32_t cw, ch;
-    if (!find_vp8(b, n, off, len, cw, ch)) return kVp8dHost;
-    const int mode = webp_decode_mode();
-    if (mode == 1) {
-        const uint32_t w = le16(b + off + 6) & 0x3fff, h = le16(b + off + 8) & 0x3fff;
-        if ((uint64_t)w * h < kWebpGpuMinPixels) return kVp8dHost;
+// auto, for a batch (decode_webp_batch): the device path when the batch's lossy files
+// total this many pixels.  Starts at the one-frame break-even: that many pixels spread
+// over several frames have a shorter critical path than one such frame and share one
+// set of launches, so the batch path cannot lose where the one-frame path won
+// (profiles/webp_batch_notes.md).
+constexpr uint64_t kWebpGpuMinBatchPixels = kWebpGpuMinPixels;
+
+namespace {
+
+std::atomic<unsigned long long> g_webp_gpu{0}, g_webp_host{0};  // ik_webp_counters
+
+// the last batch per device (ik_webp_last_timing)
+enum { kWtParseWallMs = 0, kWtParseCoreMs, kWtStageMs, kWtReconMs, kWtRgbMs, kWtGpuImages, kWtHostImages, kWtRows,
+       kWtGrid, kWtLaunches, kWtFields };
+std::mutex g_wtim_mu;
+std::map<int, std::array<double, kWtFields>> g_wtim;
+
+double now_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+double thread_cpu_ms() {
+    timespec ts;
+    if (clock_gettime(CLOCK_THREAD_CPUTIME_ID, &ts)) return 0;
+    return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
+}
+std::string last_msg() {
+    char buf[512];
+    ik_last_error(buf, sizeof(buf));
+    return buf;
+}
+
+// the host half of one accepted file
+struct Frame {
+    Parsed P;
+    Tokens T;
+    size_t bytes() const { return P.mbs.capacity() * sizeof(DMB) + (T.coef.capacity() + T.at.capacity()) * 4 + T.flags.capacity(); }
+};
+constexpr size_t kFrameKeepBytes = 16u << 20;  // host buffers kept between calls up to this much
+
+// One block of memory laid out once: take(bytes) hands out the next 256-byte aligned
+// region.  (ik_png_decode.cpp's Carver binds a fixed few named pointers; here the
+// regions are per image, so the offsets are kept instead.)
+struct Lay {
+    size_t cur = 0;
+    size_t take(size_t bytes) {
+        const size_t o = cur;
+        cur += up256(bytes);
+        return o;
     }
-    thread_local Parsed P;
-    thread_local Tokens T;
-    struct Trim {  // (per-thread buffers: released after frames over 16 MiB of them)
-        ~Trim() {
-            if (P.mbs.capacity() * sizeof(DMB) + T.coef.capacity() * 4 > (16u << 20)) {
-                std::vector<DMB>().swap(P.mbs);
-                std::vector<uint32_t>().swap(T.coef);
-                std::vector<uint32_t>().swap(T.at);
-                std::vector<uint8_t>().swap(T.flags);
-            }
+};
+struct FrameLay {
+    size_t fr, mb, flags, at, coef;  // staged: [DFrame][DMB x nmb][flags][entry starts][entries]
+    size_t y, u, v, top;             // device work: the planes, the two top rows
+};
+void lay_staged(Lay& L, const Frame& F, FrameLay& o) {
+    const size_t nmb = (size_t)F.P.fr.mb_w * F.P.fr.mb_h;
+    o.fr = L.take(sizeof(DFrame));
+    o.mb = L.take(nmb * sizeof(DMB));
+    o.flags = L.take(nmb);
+    o.at = L.take((nmb + 1) * 4);
+    o.coef = L.take(F.T.coef.size() * 4 + 4);
+}
+void lay_work(Lay& L, const Frame& F, FrameLay& o) {
+    const DFrame& fr = F.P.fr;
+    o.y = L.take((size_t)fr.mb_w * 16 * fr.mb_h * 16);
+    o.u = L.take((size_t)fr.mb_w * 8 * fr.mb_h * 8);
+    o.v = L.take((size_t)fr.mb_w * 8 * fr.mb_h * 8);
+    o.top = L.take((size_t)2 * fr.mb_w * 32);
+}
+uint32_t frame_tiles(const DFrame& fr) {
+    const uint32_t tr = rgb_tile_rows((uint32_t)fr.w);
+    return ((uint32_t)fr.h + tr - 1) / tr;
+}
+// what a frame adds to a launch's staged + work bytes (the sub-launch cap counts these)
+uint64_t frame_launch_bytes(const Frame& F) {
+    Lay L;
+    FrameLay o;
+    lay_staged(L, F, o);
+    lay_work(L, F, o);
+    return L.cur + sizeof(DImg) + 4 + (size_t)frame_tiles(F.P.fr) * sizeof(DTile) + 4 * (1 + (size_t)F.P.fr.mb_h);
+}
+
+struct LaunchTim {
+    double stage_ms = 0, recon_ms = 0, rgb_ms = 0;
+    uint32_t grid = 0;
+};
+
+// m parsed frames, in plan order (row_start: m + 1 tickets), through one set of
+// launches into new images: one H2D of the staged area
+//   [DImg x m][row_start][tiles] then per frame [DFrame][DMB x nmb][flags][entry starts][entries]
+// one memset of the sync words of the work area behind it
+//   [ticket, err per image, progress per MB row] then per frame [Y][U][V][top rows]
+// the two kernels, the err words back, one stream sync.  imgs[k]: the image, or null
+// where the device gave the frame up (a row's wait timed out: the device is too busy
+// or something is wrong; libwebp decides).  A failure frees every image.
+int run_launch(const Frame* const* F, const uint32_t* row_start, int m, ik_image** imgs, int threads, LaunchTim* tim) {
+    for (int k = 0; k < m; ++k) imgs[k] = nullptr;
+    const uint32_t total_rows = row_start[m];
+    uint32_t ntiles = 0;
+    for (int k = 0; k < m; ++k) ntiles += frame_tiles(F[k]->P.fr);
+    Lay L;
+    std::vector<FrameLay> o((size_t)m);
+    const size_t o_img = L.take(sizeof(DImg) * (size_t)m);
+    const size_t o_rs = L.take(4 * ((size_t)m + 1));
+    const size_t o_tiles = L.take(sizeof(DTile) * (size_t)ntiles);
+    for (int k = 0; k < m; ++k) lay_staged(L, *F[k], o[k]);
+    const size_t stage = L.cur;
+    const size_t sync_bytes = 4 * (1 + (size_t)m + total_rows);
+    const size_t o_sync = L.take(sync_bytes);
+    for (int k = 0; k < m; ++k) lay_work(L, *F[k], o[k]);
+    const size_t total = L.cur;
+
+    auto drop = [&] {
+        for (int k = 0; k < m; ++k) {
+            ik_image_free(imgs[k]);
+            imgs[k] = nullptr;
         }
-    } trim;
-    static const bool timing = getenv("IK_TIMING") != nullptr;  // dev: phase times to stderr
-    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t0 = timing ? now() : 0;
-    if (!parse_vp8(b, off, len, cw, ch, P)) return kVp8dHost;
-    const double t1 = timing ? now() : 0;
-    if (!decode_tokens(b, P, T)) return kVp8dHost;
-    const double t2 = timing ? now() : 0;
-    const DFrame& fr = P.fr;
-    const size_t nmb = (size_t)fr.mb_w * fr.mb_h;
-
-    // staged (one H2D): [DImg][DFrame][DMB x nmb][flags][entry starts][entries]
-    const size_t o_fr = up256(sizeof(DImg));
-    const size_t o_mb = o_fr + up256(sizeof(DFrame));
-    const size_t o_flags = o_mb + up256(nmb * sizeof(DMB));
-    const size_t o_at = o_flags + up256(nmb);
-    const size_t o_coef = o_at + up256((nmb + 1) * 4);
-    const size_t stage = o_coef + up256(T.coef.size() * 4 + 4);
-    // device work: [ticket, error, progress per MB row][Y][U][V][top rows]
-    const uint32_t ys = (uint32_t)fr.mb_w * 16, uvs = (uint32_t)fr.mb_w * 8;
-    const size_t o_sync = stage;
-    const size_t o_y = o_sync + up256(4 * (2 + (size_t)fr.mb_h));
-    const size_t o_u = o_y + up256((size_t)ys * fr.mb_h * 16);
-    const size_t o_v = o_u + up256((size_t)uvs * fr.mb_h * 8);
-    const size_t o_top = o_v + up256((size_t)uvs * fr.mb_h * 8);
-    const size_t total = o_top + up256((size_t)2 * fr.mb_w * 32);
-
-    ik_image* img = nullptr;
-    int st = alloc_image((uint32_t)fr.w, (uint32_t)fr.h, 3, &img);
-    if (st) return st;
+    };
+    for (int k = 0; k < m; ++k) {
+        const int st = alloc_image((uint32_t)F[k]->P.fr.w, (uint32_t)F[k]->P.fr.h, 3, &imgs[k]);
+        if (st) {
+            drop();
+            return st;
+        }
+    }
     uint8_t* d = scratch_slot(kScratchVp8d, total);
-    uint8_t* h = d ? pinned_slot(kPinnedVp8d, stage) : nullptr;
+    uint8_t* h = d ? pinned_slot(kPinnedVp8d, stage + up256(4 * (size_t)m)) : nullptr;  // (+ the err words, read back)
     if (!d || !h) {
-        ik_image_free(img);
+        drop();
         return d ? IK_ERR_NOMEM : fail(IK_ERR_DEVICE, "cannot allocate the WebP decoder's device work area");
     }
     hipStream_t s = thread_stream();
     (void)hipStreamSynchronize(s);  // (the pinned area may still feed an earlier copy)
-    DImg di{};
-    di.fr = reinterpret_cast<const DFrame*>(d + o_fr);
-    di.mbs = reinterpret_cast<const DMB*>(d + o_mb);
-    di.flags = d + o_flags;
-    di.coef_at = reinterpret_cast<const uint32_t*>(d + o_at);
-    di.coef = reinterpret_cast<const uint32_t*>(d + o_coef);
-    di.y = d + o_y;
-    di.u = d + o_u;
-    di.v = d + o_v;
-    di.top = d + o_top;
-    di.out = img->d;
-    di.ys = ys;
-    di.uvs = uvs;
-    di.out_pitch = (uint32_t)img->pitch;
-    di.row0 = 0;
-    di.rows = (uint32_t)fr.mb_h;
+    const double t0 = tim ? now_ms() : 0;
     uint32_t* const sync = reinterpret_cast<uint32_t*>(d + o_sync);
-    di.err = sync + 1;
-    di.prog = sync + 2;
-    std::memcpy(h, &di, sizeof(di));
-    std::memcpy(h + o_fr, &fr, sizeof(DFrame));
-    std::memcpy(h + o_mb, P.mbs.data(), nmb * sizeof(DMB));
-    std::memcpy(h + o_flags, T.flags.data(), nmb);
-    std::memcpy(h + o_at, T.at.data(), (nmb + 1) * 4);
-    if (!T.coef.empty()) std::memcpy(h + o_coef, T.coef.data(), T.coef.size() * 4);
-    const DImg* dimg = reinterpret_cast<const DImg*>(d);
-    const double t3 = timing ? now() : 0;
-    hipError_t e = hipMemcpyAsync(d, h, o_coef + T.coef.size() * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemsetAsync(sync, 0, 4 * (2 + (size_t)fr.mb_h), s);
-    if (timing && e == hipSuccess) e = hipStreamSynchronize(s);
-    const double t4 = timing ? now() : 0;
-    if (e == hipSuccess) e = launch_vp8d_recon(dimg, 1, (uint32_t)fr.mb_h, sync, s);
-    if (timing && e == hipSuccess) e = hipStreamSynchronize(s);
-    const double t5 = timing ? now() : 0;
-    if (e == hipSuccess) e = launch_vp8d_rgb(dimg, 1, fr.h, s);
-    uint32_t* const herr = reinterpret_cast<uint32_t*>(h + stage - 4);  // (the staged area's last word: free)
-    if (e == hipSuccess) e = hipMemcpyAsync(herr, sync + 1, 4, hipMemcpyDeviceToHost, s);
+    DImg* const himg = reinterpret_cast<DImg*>(h + o_img);
+    DTile* const htile = reinterpret_cast<DTile*>(h + o_tiles);
+    std::memcpy(h + o_rs, row_start, 4 * ((size_t)m + 1));
+    uint32_t prog0 = 0, tile0 = 0;
+    std::vector<uint32_t> first_tile((size_t)m);
+    for (int k = 0; k < m; ++k) {
+        const DFrame& fr = F[k]->P.fr;
+        DImg di{};
+        di.fr = reinterpret_cast<const DFrame*>(d + o[k].fr);
+        di.mbs = reinterpret_cast<const DMB*>(d + o[k].mb);
+        di.flags = d + o[k].flags;
+        di.coef_at = reinterpret_cast<const uint32_t*>(d + o[k].at);
+        di.coef = reinterpret_cast<const uint32_t*>(d + o[k].coef);
+        di.y = d + o[k].y;
+        di.u = d + o[k].u;
+        di.v = d + o[k].v;
+        di.top = d + o[k].top;
+        di.out = imgs[k]->d;
+        di.ys = (uint32_t)fr.mb_w * 16;
+        di.uvs = (uint32_t)fr.mb_w * 8;
+        di.out_pitch = (uint32_t)imgs[k]->pitch;
+        di.err = sync + 1 + k;
+        di.prog = sync + 1 + m + prog0;
+        prog0 += (uint32_t)fr.mb_h;
+        himg[k] = di;
+        first_tile[k] = tile0;
+        tile0 += frame_tiles(fr);
+    }
+    auto fill = [&](int k) {  // frame k's staged records and its tiles
+        const Frame& f = *F[k];
+        const DFrame& fr = f.P.fr;
+        const size_t nmb = (size_t)fr.mb_w * fr.mb_h;
+        std::memcpy(h + o[k].fr, &fr, sizeof(DFrame));
+        std::memcpy(h + o[k].mb, f.P.mbs.data(), nmb * sizeof(DMB));
+        std::memcpy(h + o[k].flags, f.T.flags.data(), nmb);
+        std::memcpy(h + o[k].at, f.T.at.data(), (nmb + 1) * 4);
+        if (!f.T.coef.empty()) std::memcpy(h + o[k].coef, f.T.coef.data(), f.T.coef.size() * 4);
+        const uint32_t tr = rgb_tile_rows((uint32_t)fr.w);
+        DTile* t = htile + first_tile[k];
+        for (uint32_t r = 0; r < (uint32_t)fr.h; r += tr) *t++ = DTile{(uint32_t)k, r, std::min(tr, (uint32_t)fr.h - r)};
+    };
+    if (m > 1) parallel_for(m, threads, fill);
+    else fill(0);
+
+    const DImg* dimg = reinterpret_cast<const DImg*>(d + o_img);
+    uint32_t* const herr = reinterpret_cast<uint32_t*>(h + stage);
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (tim) {
+        const EvPair &p = thread_events(2), &q = thread_events(3);
+        ev[0] = p.a, ev[1] = p.b, ev[2] = q.a, ev[3] = q.b;
+        ev_record(ev[0], s);
+    }
+    hipError_t e = hipMemcpyAsync(d, h, stage, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(sync, 0, sync_bytes, s);
+    if (tim) ev_record(ev[1], s);
+    uint32_t grid = 0;
+    if (e == hipSuccess)
+        e = launch_vp8d_recon(dimg, reinterpret_cast<const uint32_t*>(d + o_rs), m, total_rows, sync, s, &grid);
+    if (tim) ev_record(ev[2], s);
+    if (e == hipSuccess) e = launch_vp8d_rgb(dimg, reinterpret_cast<const DTile*>(d + o_tiles), ntiles, s);
+    if (tim) ev_record(ev[3], s);
+    if (e == hipSuccess) e = hipMemcpyAsync(herr, sync + 1, 4 * (size_t)m, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (timing)
-        fprintf(stderr, "vp8d %dx%d: parse %.3f tokens %.3f (%zu coefs) stage %.3f h2d %.3f recon %.3f rgb %.3f ms\n", fr.w,
-                fr.h, t1 - t0, t2 - t1, T.coef.size(), t3 - t2, t4 - t3, t5 - t4, now() - t5);
     if (e != hipSuccess) {
-        ik_image_free(img);
+        drop();
         return hip_fail(e, "WebP decode launches");
     }
-    if (*herr) {  // a row's wait timed out: the device is too busy or something is wrong; libwebp decides
-        ik_image_free(img);
-        return kVp8dHost;
+    if (tim) {
+        auto ms = [](hipEvent_t a, hipEvent_t b) {
+            float v = 0;
+            return a && b && hipEventElapsedTime(&v, a, b) == hipSuccess ? (double)v : 0.0;
+        };
+        tim->stage_ms += (now_ms() - t0) - ms(ev[1], ev[3]);  // staging copies and the H2D: the wall time less the kernels
+        tim->recon_ms += ms(ev[1], ev[2]);
+        tim->rgb_ms += ms(ev[2], ev[3]);
+        tim->grid = std::max(tim->grid, grid);
     }
+    for (int k = 0; k < m; ++k)
+        if (herr[k]) {
+            ik_image_free(imgs[k]);
+            imgs[k] = nullptr;
+        }
+    return IK_OK;
+}
+
+void trim_frame(Frame& f) {
+    if (f.bytes() > kFrameKeepBytes) f = Frame();
+}
+
+// libwebp's decode of one file into a new device image (what decode_image does with
+// a WebP file outside the GPU path)
+int host_one(const uint8_t* b, size_t n, ik_image** out) {
+    thread_local std::vector<uint8_t> px;
+    struct Trim {
+        ~Trim() { if (px.capacity() > (128u << 20)) std::vector<uint8_t>().swap(px); }
+    } trim;
+    ++g_webp_host;
+    uint32_t w = 0, h = 0, c = 0;
+    const int st = decode_webp(b, n, w, h, c, px);
+    return st ? st : ik_image_from_host(px.data(), w, h, c, out);
+}
+
+int left_to_libwebp() {
+    return fail(IK_ERR_TRANSFORM, "IK_WEBP_DECODE=gpu: the GPU WebP decoder leaves this file to libwebp");
+}
+
+}  // namespace
+
+void webp_count_host_decode() { ++g_webp_host; }
+
+int decode_webp_device(const uint8_t* b, size_t n, ik_image** out) {
+    const int mode = webp_decode_mode();
+    if (!mode) return kVp8dHost;
+    size_t off = 0, len = 0;
+    uint32_t cw, ch;
+    if (!find_vp8(b, n, off, len, cw, ch)) return kVp8dHost;
+    if (mode == 1) {
+        const uint32_t w = le16(b + off + 6) & 0x3fff, h = le16(b + off + 8) & 0x3fff;
+        if ((uint64_t)w * h < kWebpGpuMinPixels) return kVp8dHost;
+    }
+    thread_local Frame F;  // (per-thread buffers: released after frames over 16 MiB of them)
+    struct Trim {
+        ~Trim() { trim_frame(F); }
+    } trim;
+    if (!parse_vp8(b, off, len, cw, ch, F.P) || !decode_tokens(b, F.P, F.T)) return kVp8dHost;
+    const Frame* const fp = &F;
+    const uint32_t row_start[2] = {0, (uint32_t)F.P.fr.mb_h};
+    ik_image* img = nullptr;
+    const int st = run_launch(&fp, row_start, 1, &img, 1, nullptr);
+    if (st) return st;
+    if (!img) return kVp8dHost;
+    ++g_webp_gpu;
     *out = img;
     return IK_OK;
 }
 
+int decode_webp_batch(const uint8_t* const* b, const size_t* lens, int n, ik_image** outs, int* status,
+                      std::string* msgs, int threads) {
+    const int mode = webp_decode_mode();
+    const double t_begin = now_ms();
+    // the files the GPU path would take: a plain lossy frame in the container
+    struct Cand {
+        size_t off = 0, len = 0;
+        uint32_t cw = 0, ch = 0;
+        int frame = -1;  // its Frame in the pool, once parsed and accepted: -1 otherwise
+        double core_ms = 0;
+    };
+    std::vector<Cand> C((size_t)n);
+    std::vector<char> take((size_t)n, 0);
+    int ncand = 0;
+    if (mode) {
+        uint64_t px = 0;
+        for (int i = 0; i < n; ++i)
+            if (find_vp8(b[i], lens[i], C[i].off, C[i].len, C[i].cw, C[i].ch)) {
+                take[i] = 1;
+                ++ncand;
+                px += (uint64_t)(le16(b[i] + C[i].off + 6) & 0x3fff) * (le16(b[i] + C[i].off + 8) & 0x3fff);
+            }
+        if (mode == 1 && px < kWebpGpuMinBatchPixels) {
+            std::fill(take.begin(), take.end(), 0);
+            ncand = 0;
+        }
+    }
+    // the batch's host buffers: kept on the calling thread between batches, released
+    // at the batch's end once they hold more than the one-request path would keep
+    thread_local std::vector<Frame> pool;
+    struct Trim {
+        ~Trim() {
+            size_t sum = 0;
+            for (const Frame& f : pool) sum += f.bytes();
+            if (sum > kFrameKeepBytes) std::vector<Frame>().swap(pool);
+        }
+    } trim;
+    if (pool.size() < (size_t)ncand) pool.resize((size_t)ncand);
+    for (int i = 0, k = 0; i < n; ++i)
+        if (take[i]) C[i].frame = k++;
+    Frame* const frames = pool.data();  // (the workers below have pools of their own: this thread's, by address)
+    std::atomic<int> host_calls{0};
+
+    // host half, in parallel over the items: partition 0 and the tokens of the taken
+    // files; every other file, and any a parser hands back, to libwebp on the same worker
+    parallel_for(n, threads, [&](int i) {
+        outs[i] = nullptr;
+        status[i] = IK_OK;
+        if (take[i]) {
+            Frame& F = frames[C[i].frame];
+            const double c0 = thread_cpu_ms();
+            const bool ok = parse_vp8(b[i], C[i].off, C[i].len, C[i].cw, C[i].ch, F.P) && decode_tokens(b[i], F.P, F.T);
+            C[i].core_ms = thread_cpu_ms() - c0;
+            if (ok) return;
+            C[i].frame = -1;
+        }
+        status[i] = mode == 2 ? left_to_libwebp() : (++host_calls, host_one(b[i], lens[i], &outs[i]));
+        if (status[i]) msgs[i] = last_msg();
+    });
+    std::array<double, kWtFields> W{};
+    W[kWtParseWallMs] = now_ms() - t_begin;
+    for (int i = 0; i < n; ++i) W[kWtParseCoreMs] += C[i].core_ms;
+
+    // the accepted frames: planned (largest first, cut at the cap), then launched
+    std::vector<int> acc;  // request index of each accepted frame
+    for (int i = 0; i < n; ++i)
+        if (C[i].frame >= 0) acc.push_back(i);
+    const uint32_t na = (uint32_t)acc.size();
+    std::vector<int> retry;  // frames the device gave up
+    if (na) {
+        uint64_t cap = 256ull << 20;
+        if (const char* e = getenv("IK_VP8D_BATCH_BYTES")) {  // dev switch
+            const long long v = atoll(e);
+            if (v > 0) cap = (uint64_t)v;
+        }
+        std::vector<uint32_t> mw(na), mh(na), order(na), row_start(na + 1), lo(na + 1);
+        std::vector<uint64_t> bytes(na);
+        for (uint32_t a = 0; a < na; ++a) {
+            const Frame& F = frames[C[acc[a]].frame];
+            mw[a] = (uint32_t)F.P.fr.mb_w;
+            mh[a] = (uint32_t)F.P.fr.mb_h;
+            bytes[a] = frame_launch_bytes(F);
+        }
+        const int launches = webp_batch_plan(mw.data(), mh.data(), bytes.data(), na, cap, order.data(), row_start.data(),
+                                             lo.data());
+        LaunchTim tim;
+        std::vector<const Frame*> F;
+        std::vector<ik_image*> imgs;
+        std::vector<uint32_t> rs;
+        int failed = IK_OK;  // a failed launch fails its frames and every later launch's
+        std::string failed_msg;
+        for (int l = 0; l < launches; ++l) {
+            const uint32_t k0 = lo[l], m = lo[l + 1] - k0;
+            if (!failed) {
+                F.resize(m);
+                imgs.assign(m, nullptr);
+                rs.assign(row_start.begin() + k0, row_start.begin() + k0 + m);
+                rs.push_back(rs.back() + mh[order[k0 + m - 1]]);
+                for (uint32_t k = 0; k < m; ++k) F[k] = &frames[C[acc[order[k0 + k]]].frame];
+                failed = run_launch(F.data(), rs.data(), (int)m, imgs.data(), threads, &tim);
+                if (failed) failed_msg = last_msg();
+                else W[kWtRows] += rs.back();
+            }
+            for (uint32_t k = 0; k < m; ++k) {
+                const int i = acc[order[k0 + k]];
+                if (failed) {
+                    status[i] = failed;
+                    msgs[i] = failed_msg;
+                } else if (imgs[k]) {
+                    outs[i] = imgs[k];
+                    ++g_webp_gpu;
+                    W[kWtGpuImages] += 1;
+                } else {
+                    retry.push_back(i);
+                }
+            }
+        }
+        W[kWtStageMs] = tim.stage_ms;
+        W[kWtReconMs] = tim.recon_ms;
+        W[kWtRgbMs] = tim.rgb_ms;
+        W[kWtGrid] = tim.grid;
+        W[kWtLaunches] = launches;
+    }
+    parallel_for((int)retry.size(), threads, [&](int k) {
+        const int i = retry[(size_t)k];
+        status[i] = mode == 2 ? left_to_libwebp() : (++host_calls, host_one(b[i], lens[i], &outs[i]));
+        if (status[i]) msgs[i] = last_msg();
+    });
+    W[kWtHostImages] = host_calls.load();
+    {
+        std::lock_guard<std::mutex> lk(g_wtim_mu);
+        g_wtim[current_device()] = W;
+    }
+    if (getenv("IK_TIMING"))  // dev: the batch's phases to stderr
+        fprintf(stderr, "vp8d batch of %d: host half %.3f ms (%.3f core-ms) stage+h2d %.3f recon %.3f rgb %.3f ms, %d on the GPU, "
+                "%d MB rows, grid %d, %d launches\n", n, W[kWtParseWallMs], W[kWtParseCoreMs], W[kWtStageMs], W[kWtReconMs],
+                W[kWtRgbMs], (int)W[kWtGpuImages], (int)W[kWtRows], (int)W[kWtGrid], (int)W[kWtLaunches]);
+    int first = IK_OK;
+    for (int i = 0; i < n; ++i)
+        if (status[i] && !first) first = status[i];
+    return first;
+}
+
 }  // namespace ik
+
+extern "C" int ik_webp_counters(unsigned long long* out) {
+    if (!out) return ik::fail(IK_ERR_INVALID, "null pointer");
+    out[0] = ik::g_webp_gpu.load();
+    out[1] = ik::g_webp_host.load();
+    return IK_OK;
+}
+
+extern "C" int ik_webp_last_timing(double* out, int n) {
+    if (!out) return ik::fail(IK_ERR_INVALID, "null pointer");
+    std::array<double, ik::kWtFields> t{};
+    {
+        std::lock_guard<std::mutex> lk(ik::g_wtim_mu);
+        auto it = ik::g_wtim.find(ik::current_device());
+        if (it != ik::g_wtim.end()) t = it->second;
+    }
+    for (int i = 0; i < n; ++i) out[i] = i < ik::kWtFields ? t[(size_t)i] : 0.0;
+    return IK_OK;
+}
+
+extern "C" unsigned long long ik_webp_gpu_min_batch_pixels(void) { return ik::kWebpGpuMinBatchPixels; }
+
+extern "C" int ik_webp_batch_plan(const uint32_t* mb_w, const uint32_t* mb_h, const uint64_t* bytes, uint32_t n,
+                                  uint64_t cap_bytes, uint32_t* order, uint32_t* row_start, uint32_t* launch_lo) {
+    return ik::vp8d::webp_batch_plan(mb_w, mb_h, bytes, n, cap_bytes, order, row_start, launch_lo);
+}
