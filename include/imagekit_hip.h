@@ -410,6 +410,25 @@ int ik_webp_encode_exact_device(const uint8_t *dev_yuv, size_t yuv_stride, uint3
  * int16 coefficients, MCU-major, Y/Cb/Cr, natural order */
 int ik_jpeg_coeffs_device(const uint8_t *dev_src, uint32_t w, uint32_t h, uint32_t C,
                           size_t pitch, int quality, int16_t *dev_coef, void *hip_stream);
+/* the JPEG entropy coder on its own (k_jpeg_huff_enc), for parity tests: baseline
+ * Huffman coding of n images of w x h pixels whose int16 coefficients
+ * ([mcu][Y,Cb,Cr][64], natural order; the ik_jpeg_coeffs_device layout) lie
+ * coef_img_stride int16 units apart in device memory (16-byte aligned, the stride
+ * a multiple of 8: IK_ERR_INVALID otherwise).  One launch, the buffers laid out as
+ * encode_image's JPEG branch lays them out.  Image i's stuffed scan bytes (no
+ * header, no EOI) land in host_out + i * ik_jpeg_enc_capacity(w, h) and their
+ * count in host_len[i]; 0xffffffff there is the kernel's "does not fit" answer
+ * (twice the unstuffed bytes exceed the capacity), reported as is -- no host
+ * coder runs here.  host_out goes to the device before the launch, so bytes
+ * the kernel does not write (it stores whole 16-byte words) come back unchanged. */
+size_t ik_jpeg_enc_capacity(uint32_t w, uint32_t h);
+int ik_jpeg_huffman_device(const int16_t *dev_coef, size_t coef_img_stride, uint32_t n, uint32_t w,
+                           uint32_t h, uint8_t *host_out, uint32_t *host_len);
+/* process-wide JPEG encode counters: out[0] = images whose scan bytes
+ * k_jpeg_huff_enc wrote, out[1] = images the host coder wrote because their
+ * stream did not fit the GPU coder's buffer (ik_encode, ik_transform[_batch],
+ * ik_pipeline_*) */
+int ik_jpeg_enc_counters(unsigned long long *out);
 
 /* device memory helpers (so callers need no HIP headers) */
 int ik_dev_alloc(size_t bytes, void **dev_ptr);

@@ -515,7 +515,10 @@ int resize_mode() {
 namespace {
 std::mutex g_consts_mu;
 std::map<int, DeviceConsts*> g_consts;
+std::atomic<unsigned long long> g_jpeg_enc_gpu{0}, g_jpeg_enc_host{0};
 }  // namespace
+
+void jpeg_enc_count(bool gpu_coded) { (gpu_coded ? g_jpeg_enc_gpu : g_jpeg_enc_host) += 1; }
 
 const DeviceConsts* device_consts(int device) {
     std::mutex& mu = g_consts_mu;
@@ -631,8 +634,10 @@ int encode_device_front(const uint8_t* dev, uint32_t w, uint32_t h, uint32_t c, 
             rc = copy_d2h_2d((uint8_t*)coef.data(), cbytes, (const uint8_t*)dcoef, cbytes, cbytes, 1, s);
             if (rc) return rc;
             jpeg_write(coef.data(), (int)w, (int)h, qt, out);
+            jpeg_enc_count(false);
             return IK_OK;
         }
+        jpeg_enc_count(true);
         jpeg_header((int)w, (int)h, qt, out);
         const size_t hdr = out.size();
         out.resize(hdr + len + 2);
@@ -1230,12 +1235,13 @@ int jpeg_front_group(const std::vector<ik_image*>& imgs, int quality, std::vecto
         const uint32_t* lens = reinterpret_cast<const uint32_t*>(hp + p_len);
         for (size_t i = 0; i < m; ++i) {
             std::vector<uint8_t>& o = *out[b0 + i];
-            if (lens[i] == 0xffffffffu) {  // past the GPU coder's buffer: the single-image path (host coder)
+            if (lens[i] == 0xffffffffu) {  // past the GPU coder's buffer: the single-image path (host coder, counted there)
                 EncodePrep pp;
                 if (int rc = encode_device_front(imgs[b0 + i]->d, w, h, i0->c, i0->pitch, IK_FORMAT_JPEG, q, pp, o))
                     return rc;
                 continue;
             }
+            jpeg_enc_count(true);
             o.assign(hdr.begin(), hdr.end());
             o.insert(o.end(), hp + cap * i, hp + cap * i + lens[i]);
             o.push_back(0xFF);
@@ -2389,6 +2395,56 @@ int ik_jpeg_coeffs_device(const uint8_t* dev_src, uint32_t w, uint32_t h, uint32
     if (int rc = copy_h2d_2d(dq, 128, qt, 128, 128, 1, s)) return rc;
     IK_HIP(launch_jpeg_coeffs(dev_src, (int)w, (int)h, (int)C, pitch, 0, dq, dev_coef, 0, 1, s));
     IK_HIP(hipStreamSynchronize(s));
+    return IK_OK;
+}
+
+size_t ik_jpeg_enc_capacity(uint32_t w, uint32_t h) { return jpeg_enc_cap((int)w, (int)h); }
+
+int ik_jpeg_huffman_device(const int16_t* dev_coef, size_t coef_img_stride, uint32_t n, uint32_t w, uint32_t h,
+                           uint8_t* host_out, uint32_t* host_len) {
+    IK_API_ENTER();
+    if (!dev_coef || !host_out || !host_len || !n || !w || !h || w > 65535 || h > 65535)
+        return fail(IK_ERR_INVALID, "bad arguments");
+    const DeviceConsts* dc = device_consts(current_device());
+    if (!dc) return fail(IK_ERR_DEVICE, "cannot upload JPEG tables");
+    hipStream_t s = thread_stream();
+    if (!s) return fail(IK_ERR_DEVICE, "cannot create HIP stream");
+    const size_t nmcu = (size_t)((w + 7) / 8) * ((h + 7) / 8);
+    if (n > 1 && coef_img_stride < nmcu * 3 * 64) return fail(IK_ERR_INVALID, "coefficient stride too small");
+    // [Huffman work: words + staging][stuffed streams][lengths], as encode_device_front lays them out
+    const size_t cap = jpeg_enc_cap((int)w, (int)h);
+    const size_t o_off = 2 * cap * n, l_off = o_off + cap * n;
+    uint8_t* dw = scratch(l_off + sizeof(uint32_t) * n);
+    if (!dw) return fail(IK_ERR_DEVICE, "cannot allocate device scratch");
+    JpegEncArgs a{};
+    a.coef = dev_coef;
+    a.coef_img_stride = coef_img_stride;
+    a.nmcu = (int)nmcu;
+    a.huff = dc->jpeg_huff;
+    a.work = dw;
+    a.work_img_bytes = 2 * cap;
+    a.words_bytes = cap;
+    a.out = dw + o_off;
+    a.out_img_stride = cap;
+    a.out_cap = cap;
+    a.out_len = reinterpret_cast<uint32_t*>(dw + l_off);
+    // the caller's bytes go up first, so whatever the kernel leaves alone comes back as it was
+    if (int rc = copy_h2d_2d(dw + o_off, cap * n, host_out, cap * n, cap * n, 1, s)) return rc;
+    const hipError_t e = launch_jpeg_huff_enc(a, (int)n, s);
+    if (e == hipErrorInvalidValue)
+        return fail(IK_ERR_INVALID, "coefficients must be 16-byte aligned and their stride a multiple of 8");
+    if (e != hipSuccess) return hip_fail(e, "jpeg huffman");
+    IK_HIP(hipStreamSynchronize(s));
+    if (int rc = copy_d2h_2d(reinterpret_cast<uint8_t*>(host_len), 4 * (size_t)n, dw + l_off, 4 * (size_t)n,
+                             4 * (size_t)n, 1, s))
+        return rc;
+    return copy_d2h_2d(host_out, cap * n, dw + o_off, cap * n, cap * n, 1, s);
+}
+
+int ik_jpeg_enc_counters(unsigned long long* out) {
+    if (!out) return fail(IK_ERR_INVALID, "null pointer");
+    out[0] = g_jpeg_enc_gpu.load();
+    out[1] = g_jpeg_enc_host.load();
     return IK_OK;
 }
 

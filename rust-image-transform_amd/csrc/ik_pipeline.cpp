@@ -261,6 +261,7 @@ int host_stage(ik_pipeline* p, const ik_pipeline::Slot& s, uint8_t* out, size_t 
             std::memcpy(o.data() + p->jpeg_hdr.size(), s.h_jpeg + p->jcap * (size_t)i, len);
             o[o.size() - 2] = 0xFF;
             o[o.size() - 1] = 0xD9;
+            jpeg_enc_count(true);
         } else {  // did not fit the GPU coder's buffer: coefficients back, host coder
             std::vector<int16_t> coef(p->stage_bytes / sizeof(int16_t));
             if (hipMemcpy(coef.data(), s.d_stage + p->stage_bytes * (size_t)i, p->stage_bytes,
@@ -270,6 +271,7 @@ int host_stage(ik_pipeline* p, const ik_pipeline::Slot& s, uint8_t* out, size_t 
                 return;
             }
             jpeg_write(coef.data(), (int)p->nw, (int)p->nh, p->qt, p->outs[i]);
+            jpeg_enc_count(false);
         }
     });
     p->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

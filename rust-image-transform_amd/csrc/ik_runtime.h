@@ -226,6 +226,9 @@ int avif_encode_yuv444(const uint8_t* planes /* Y, U, V, A */, bool has_alpha, i
 void jpeg_write(const int16_t* coef, int w, int h, const uint8_t qt[128], std::vector<uint8_t>& out);
 void jpeg_header(int w, int h, const uint8_t qt[128], std::vector<uint8_t>& out);  // SOI .. SOS
 void jpeg_huff_u32(uint32_t t[4 * 256]);  // ldc, lac, cdc, cac: code << 8 | size
+// which coder wrote an encoded JPEG's scan bytes (ik_jpeg_enc_counters): k_jpeg_huff_enc
+// or, for a stream past its buffer, the host coder jpeg_write
+void jpeg_enc_count(bool gpu_coded);
 
 // the WebP coder encode_image uses unless ik_set_webp_encoder / IK_WEBP_ENCODER says
 // otherwise (ik_webp_gpu.cpp)
