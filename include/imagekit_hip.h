@@ -140,9 +140,11 @@ int ik_decode(const uint8_t *bytes, size_t len, ik_image **out, int *fmt_out);
  * JPEG scans (with or without restart markers) are entropy-decoded together by
  * the self-synchronising GPU decoder (a few launches for the whole batch) and
  * reconstructed on the GPU; PNG streams go through the batched GPU inflate; lossy
- * WebP files (no alpha, no animation) are parsed on the host workers and
- * reconstructed together by one pair of GPU launches (IK_WEBP_DECODE=auto: when
- * they total 3 MPix; the other WebP kinds by libwebp); inputs of any other kind get
+ * WebP files (no animation; with an alpha plane only under
+ * ik_set_webp_alpha_decode(IK_WEBP_ALPHA_GPU), which is off by default) are parsed on
+ * the host workers and reconstructed together by one set of GPU launches
+ * (IK_WEBP_DECODE=auto: when they total 3 MPix; the other WebP kinds by libwebp);
+ * inputs of any other kind get
  * ik_decode's verdict.  outs[i] / fmts[i] / status[i] per input (outs[i]
  * NULL on failure; fmts and status may be NULL); returns the first failure or
  * IK_OK. */
@@ -193,15 +195,37 @@ int ik_png_adam7_plan(uint32_t w, uint32_t h, int bits_pp, uint64_t *out, uint64
  * calls alike): out[0] reconstructed by the GPU decoder, out[1] handed to libwebp on
  * the host (outside the GPU path, handed back by it, or by policy) */
 int ik_webp_counters(unsigned long long *out);
-/* the last batch with WebP inputs finished on the calling thread's device (n <= 10
+/* the last batch with WebP inputs finished on the calling thread's device (n <= 13
  * values): [0] wall ms of the host half (partition 0 + tokens of the lossy files,
  * libwebp for the others, on the worker pool), [1] thread CPU ms of partition 0 +
  * tokens summed over the files (core-ms), [2] staging copies + H2D ms, device ms
  * (HIP events) of [3] reconstruction and loop filter [4] upsampling and colour,
  * [5] images the GPU decoded, [6] images handed to libwebp, [7] macroblock rows
  * launched, [8] the reconstruction grid (the largest of the sub-launches),
- * [9] sub-launches */
+ * [9] sub-launches, [10] device ms of the alpha planes' un-filtering, [11] thread CPU
+ * ms of reading the alpha planes on the host (core-ms; not part of [1]), [12] images
+ * with an alpha plane among [5] */
 int ik_webp_last_timing(double *out, int n);
+/* Where a lossy WebP file that carries an alpha plane (VP8X with the alpha flag and
+ * one ALPH chunk) is decoded.  IK_WEBP_ALPHA_HOST, the default: by libwebp on the
+ * host, whatever IK_WEBP_DECODE says.  IK_WEBP_ALPHA_GPU: such a file is a lossy file
+ * like any other for the GPU decoder -- under IK_WEBP_DECODE=auto its pixels count
+ * toward the 3 MPix thresholds, =gpu forces it there, =host keeps it away; the host
+ * reads the plane (raw, or lossless-coded through libwebp), the device undoes its
+ * prediction filter and writes RGBA.  Off by default because the plane's entropy
+ * decode stays on the host and its un-filtering is one wave per plane: until it is
+ * measured faster than libwebp at the sizes auto sends, the default stays.
+ * Process-wide; -1 returns to the environment, IK_WEBP_ALPHA_DECODE=host|gpu, which
+ * is read per call like IK_WEBP_DECODE. */
+typedef enum { IK_WEBP_ALPHA_HOST = 0, IK_WEBP_ALPHA_GPU = 1 } ik_webp_alpha_decode;
+int ik_set_webp_alpha_decode(int where);
+int ik_get_webp_alpha_decode(void);
+/* the host half of that path alone (no GPU needed): the alpha plane of a file the GPU
+ * decoder would take, still filtered -- *filter 0 none, 1 horizontal, 2 vertical,
+ * 3 gradient; *compression 0 raw, 1 lossless -- w * h bytes into plane (cap: its
+ * size).  IK_ERR_UNSUPPORTED for a file the GPU path leaves to libwebp. */
+int ik_webp_alpha_plane(const uint8_t *bytes, size_t len, uint8_t *plane, size_t cap, uint32_t *w, uint32_t *h,
+                        int *filter, int *compression);
 /* the pixel total of a batch's lossy WebP files from which IK_WEBP_DECODE=auto
  * takes the GPU batch path */
 unsigned long long ik_webp_gpu_min_batch_pixels(void);

@@ -423,4 +423,17 @@ int decode_webp(const uint8_t* b, size_t n, uint32_t& W, uint32_t& H, uint32_t& 
     return IK_OK;
 }
 
+bool webp_lossless_green(const uint8_t* b, size_t n, uint32_t w, uint32_t h, uint8_t* plane) {
+    const WebPDec& d = webp_dec();
+    if (!d.rgba || !d.wfree) return false;
+    int gw = 0, gh = 0;
+    uint8_t* p = d.rgba(b, n, &gw, &gh);
+    if (!p) return false;
+    const bool ok = gw > 0 && gh > 0 && (uint32_t)gw == w && (uint32_t)gh == h;
+    if (ok)
+        for (size_t i = 0, px = (size_t)w * h; i < px; ++i) plane[i] = p[4 * i + 1];
+    d.wfree(p);
+    return ok;
+}
+
 }  // namespace ik

@@ -293,8 +293,13 @@ constexpr int kPngTimingFields = 17;  // ik_png_last_timing
 bool host_pinned(const void* p, size_t n);
 bool png_gpu_enabled(size_t raw_bytes);  // IK_PNG_GPU / IK_PNG_GPU_MIN policy
 int decode_webp(const uint8_t* b, size_t n, uint32_t& w, uint32_t& h, uint32_t& c, std::vector<uint8_t>& px);
-// WebP lossy ("VP8 ", no alpha, no animation) on the GPU (ik_vp8d_host.cpp + ik_vp8d.hip):
-// the host parses the headers and partition 0, the device decodes the tokens,
+// libwebp's WebPDecodeRGBA of a w x h lossless file, its green channel alone into plane
+// (w * h bytes): how the GPU path reads a lossless-coded alpha plane (ik_vp8d_host.cpp).
+// false: the decode failed or gave another size.
+bool webp_lossless_green(const uint8_t* b, size_t n, uint32_t w, uint32_t h, uint8_t* plane);
+// WebP lossy ("VP8 ", no animation; with an alpha plane only under
+// IK_WEBP_ALPHA_DECODE=gpu) on the GPU (ik_vp8d_host.cpp + ik_vp8d.hip):
+// the host parses the headers and partition 0 and decodes the tokens, the device
 // reconstructs, loop-filters and converts to RGB straight into a new device image.
 // Returns kVp8dHost (nothing recorded) for files it leaves to decode_webp: other
 // WebP kinds, anything its parser finds unusual, data that runs out.
@@ -303,9 +308,10 @@ int decode_webp_device(const uint8_t* b, size_t n, ik_image** out);
 void webp_count_host_decode();  // a WebP stream handed to decode_webp outside decode_webp_batch (ik_webp_counters)
 // decode_image over a batch's n WebP files: the lossy ones the GPU path takes are
 // parsed in parallel (partition 0 and the tokens, on up to `threads` threads) and
-// reconstructed together -- one staged area, one H2D, one k_vp8d_recon and one
-// k_vp8d_rgb launch over all of them (sub-launches past IK_VP8D_BATCH_BYTES, default
-// 256 MiB); the rest (alpha, lossless, animation, anything handed back, a frame whose
+// reconstructed together -- one staged area, one H2D, one k_vp8d_recon, one
+// k_vp8d_alpha where a taken file's alpha plane is filtered and one k_vp8d_rgb launch
+// over all of them (sub-launches past IK_VP8D_BATCH_BYTES, default 256 MiB); the rest
+// (alpha unless IK_WEBP_ALPHA_DECODE=gpu, lossless, animation, anything handed back, a frame whose
 // err word the device set) go to libwebp on the worker that found them.  IK_WEBP_DECODE
 // is read per batch: host = libwebp only; gpu = every lossy file takes the batch path
 // and a file left to libwebp is an error; auto = the batch path when its lossy files

@@ -119,7 +119,8 @@ struct DSeg {  // per segment: VP8ParseQuant's matrices; PrecomputeFilterStrengt
 };
 
 // one frame: geometry, filter, token partitions (offsets into the file bytes),
-// segments and coefficient probabilities ([type][band][ctx] rows of 11, padded to 16)
+// segments and coefficient probabilities ([type][band][ctx] rows of 11, padded to 16);
+// then what an ALPH chunk adds (set after parse_vp8: 3 channels, no plane, without one)
 struct alignas(16) DFrame {
     int32_t w, h, mb_w, mb_h;
     int32_t filter_type;  // 0 none, 1 simple, 2 normal (libwebp dec->filter_type_)
@@ -129,7 +130,25 @@ struct alignas(16) DFrame {
     uint32_t part_off[8], part_end[8];
     DSeg seg[4];
     uint8_t proba[4 * 8 * 3 * 16];
+    int32_t channels;      // of the output image: 3 (RGB), or 4 (RGBA) with an alpha plane
+    int32_t alpha_filter;  // the plane's prediction filter: 0 none, 1 horizontal, 2 vertical, 3 gradient
+    uint32_t alpha_off;    // the plane's offset in the frame's staged data (its pitch: alpha_pitch(w))
+    uint32_t pad1;
 };
+
+// The alpha plane's filters (libwebp dsp/filters.c, the *Unfilter_C functions): the
+// prediction of pixel (x, y) from the un-filtered left / above / above-left
+// neighbours; the un-filtered value is (in + prediction) & 255
+IK_HD int alpha_pred(int filter, int x, int y, int left, int above, int above_left) {
+    // row 0 from the left ((0, 0) from 0), column 0 from above; as selects: the device
+    // walks a plane's rows a lane each, and the rule is in its serial chain
+    const int g = left + above - above_left;
+    int p = filter == 1 ? left : filter == 2 ? above : g < 0 ? 0 : g > 255 ? 255 : g;
+    p = x == 0 ? above : p;
+    return y == 0 ? (x == 0 ? 0 : left) : p;
+}
+// the staged plane's row pitch: whole 16-byte pieces, so a line moves in aligned pieces
+IK_HD uint32_t alpha_pitch(uint32_t w) { return (w + 15u) & ~15u; }
 
 // ---- reconstruction helpers (BPS-pitched, as ik_vp8x.h) ----
 // the 4x4 block (bx, by) of the size x size prediction of mode m (DC 0, TM 1, V 2, H 3)

@@ -2,7 +2,8 @@
 // ik_vp8d_host.cpp, which also decodes the token partitions: an arithmetic-coded
 // stream, serial symbol by symbol -- one wave decoding it on the scalar unit ran at
 // 1/12 of a CPU core).  Two launches per batch of images (one image for
-// ik_decode, a batch's lossy files together for decode_webp_batch):
+// ik_decode, a batch's lossy files together for decode_webp_batch), and between them a
+// third when a file's alpha plane (its ALPH chunk, IK_WEBP_ALPHA_DECODE=gpu) is filtered:
 //   k_vp8d_recon   prediction + inverse transforms + loop filter (frame_dec.c
 //                  ReconstructRow / DoFilter): one-wave workgroups that take (image, MB
 //                  row) tickets in order over every image of the launch, so the rows in
@@ -15,13 +16,19 @@
 //                  window, so each pixel is written to HBM once per MB.  Intra-4 MBs go
 //                  by sub-block diagonals (x + 2y: ten steps, a lane per pixel), the
 //                  other blocks a lane each.
+//   k_vp8d_alpha   the alpha plane's prediction filter undone in place (alpha_dec.c
+//                  ALPHDecode -> filters.c HorizontalUnfilter_C / VerticalUnfilter_C /
+//                  GradientUnfilter_C): a wave per filtered plane, a lane per row of a
+//                  64-row band, the lanes one column apart
 //   k_vp8d_rgb     fancy chroma upsampling + YUV -> RGB (io_dec.c EmitFancyRGB,
 //                  upsampling.c UPSAMPLE_FUNC, yuv.h VP8YuvToRgb) into the ik_image: a
 //                  workgroup per row tile of the plan's tile table (about 1024 pixels of
-//                  one image: one row of a wide image, several of a narrow one)
+//                  one image: one row of a wide image, several of a narrow one); the
+//                  RGBA instantiation adds the un-filtered alpha
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include <hip/hip_runtime.h>
 
@@ -438,10 +445,89 @@ __global__ __launch_bounds__(64) void k_vp8d_recon(const DImg* __restrict__ imgs
     }
 }
 
+// The alpha plane's prediction filter undone in place: a wave per plane (which: the
+// launch's images that have a filtered one), band after band of 64 rows from the top.
+// The gradient filter's clip makes a row serial and each pixel wait for the one above
+// it, so lane r owns row r of the band and runs skewed, at column t - r on step t:
+// "above" is what lane r - 1 produced one step earlier (one DPP shift down the wave),
+// "above-left" the lane's own previous "above", "left" its own previous output.  Lane 0
+// takes its "above" from the band before, whose last row this wave has written back:
+// 64 columns of it per chunk in one load, handed out by readlane.  The horizontal and
+// vertical filters share the walk.  Nothing waits for another wave; the loop bounds are
+// w and h: (w + 63) steps, rounded up to whole chunks, per band.
+//
+// The band goes through LDS in chunks of 64 columns, whole lines in 16-byte pieces (the
+// plane's pitch is a multiple of 16), as a ring of two slots per row: chunk j's steps
+// touch columns 64 j - 63 .. 64 j + 63, so before them slot j & 1 gives the columns of
+// chunk j - 2, which the last lane left at step 64 j - 2, back to memory and takes those
+// of chunk j.  A lane reads its next input before it writes this step's output.
+constexpr int kAlphaRing = 128;                 // columns of a row in LDS: two slots of 64
+constexpr int kAlphaLdsPitch = kAlphaRing + 16;  // (a row's 16-byte pieces stay aligned)
+
+__global__ __launch_bounds__(64) void k_vp8d_alpha(const DImg* __restrict__ imgs, const uint32_t* __restrict__ which) {
+    __shared__ __attribute__((aligned(16))) uint8_t ring[64 * kAlphaLdsPitch];
+    const int lane = threadIdx.x;
+    const cptr<DImg> di = (cptr<DImg>)imgs + ((cptr<uint32_t>)which)[blockIdx.x];
+    const cptr<DFrame> fr = (cptr<DFrame>)di->fr;
+    const int w = fr->w, h = fr->h, filter = fr->alpha_filter;
+    const size_t ap = alpha_pitch((uint32_t)w);
+    uint8_t* const A = di->alpha;
+    uint8_t* const mine = ring + lane * kAlphaLdsPitch;
+    const int nchunk = (w + 63 + 63) >> 6;  // steps 0 .. w + 62
+    for (int r0 = 0; r0 < h; r0 += 64) {
+        const int y = r0 + lane;
+        const bool live = y < h;
+        int left = 0, up_prev = 0, out = 0;
+        for (int j = 0; j < nchunk + 2; ++j) {
+            // slot j & 1: chunk j - 2 out, chunk j in; a row of the slot is 4 pieces
+            const int pc = 16 * (lane & 3);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int rr = (lane >> 2) + 16 * i;
+                uint4* const l = reinterpret_cast<uint4*>(ring + rr * kAlphaLdsPitch + (j & 1) * 64 + pc);
+                if (r0 + rr < h) {
+                    uint8_t* const g = A + (size_t)(r0 + rr) * ap + pc;
+                    if (j >= 2 && 64 * (j - 2) + pc < w) *reinterpret_cast<uint4*>(g + 64 * (j - 2)) = *l;
+                    if (j < nchunk && 64 * j + pc < w) *l = *reinterpret_cast<const uint4*>(g + 64 * j);
+                }
+            }
+            if (j >= nchunk) continue;
+            // the row above the band, columns 64 j .. 64 j + 63 (lane 0's "above")
+            int pv = 0;
+            if (r0 > 0 && 64 * j + lane < w) pv = A[(size_t)(r0 - 1) * ap + 64 * j + lane];
+            WSYNC();
+            auto steps = [&](auto f) {  // (the filter, wave-uniform, as a constant of the loop)
+                int in = mine[(64 * j - lane) & (kAlphaRing - 1)];
+                for (int s = 0; s < 64; ++s) {
+                    const int c = 64 * j + s - lane;
+                    const int next = mine[(c + 1) & (kAlphaRing - 1)];
+                    const int a0 = __builtin_amdgcn_readlane(pv, s);
+                    const int up = __builtin_amdgcn_update_dpp(a0, out, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+                    out = (in + alpha_pred(decltype(f)::value, c, y, left, up, up_prev)) & 255;
+                    if (live && c >= 0 && c < w) mine[c & (kAlphaRing - 1)] = (uint8_t)out;
+                    left = out;
+                    up_prev = up;
+                    in = next;
+                }
+            };
+            if (filter == 1) steps(std::integral_constant<int, 1>());
+            else if (filter == 2) steps(std::integral_constant<int, 2>());
+            else steps(std::integral_constant<int, 3>());
+            WSYNC();
+        }
+        // the band's last row is the next band's "above": its stores have left
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+}
+
 // fancy upsampling + colour: one workgroup per row tile (DTile: some rows of one image).
 // The block's threads split into 256 / L rows of L lanes, L the power of two that
 // covers the width (at most 256): a wide image gives a row all 256 threads, a narrow
-// one several rows at a time.
+// one several rows at a time.  kRgba: the launch has images with an alpha plane, which
+// get RGBA pixels (libwebp's WebPDecodeRGBA: the same RGB, not premultiplied).
+template <bool kRgba>
 __global__ __launch_bounds__(256) void k_vp8d_rgb(const DImg* __restrict__ imgs, const DTile* __restrict__ tiles) {
     const cptr<uint32_t> tl = (cptr<uint32_t>)tiles + 3 * blockIdx.x;
     const cptr<DImg> di = (cptr<DImg>)imgs + tl[0];
@@ -467,6 +553,15 @@ __global__ __launch_bounds__(256) void k_vp8d_rgb(const DImg* __restrict__ imgs,
         const uint8_t *nu = di->u + (size_t)nr * di->uvs, *fu = di->u + (size_t)fr_ * di->uvs;
         const uint8_t *nv = di->v + (size_t)nr * di->uvs, *fv = di->v + (size_t)fr_ * di->uvs;
         uint8_t* out = di->out + (size_t)r * di->out_pitch;
+        if (kRgba && fr->channels == 4) {  // (image pitches are multiples of 256: a pixel is one aligned word)
+            const uint8_t* arow = di->alpha + (size_t)r * alpha_pitch((uint32_t)w);
+            for (int c = c0; c < w; c += lanes) {
+                const int yy = yrow[c], u = fancy_chroma(nu, fu, c, w), v = fancy_chroma(nv, fv, c, w);
+                reinterpret_cast<uint32_t*>(out)[c] = (uint32_t)yuv_r(yy, v) | (uint32_t)yuv_g(yy, u, v) << 8 |
+                                                      (uint32_t)yuv_b(yy, u) << 16 | (uint32_t)arow[c] << 24;
+            }
+            continue;
+        }
         for (int c = c0; c < w; c += lanes) {
             const int yy = yrow[c], u = fancy_chroma(nu, fu, c, w), v = fancy_chroma(nv, fv, c, w);
             out[3 * c + 0] = (uint8_t)yuv_r(yy, v);
@@ -520,9 +615,15 @@ hipError_t launch_vp8d_recon(const DImg* imgs, const uint32_t* row_start, int n,
     hipLaunchKernelGGL(k_vp8d_recon, dim3(grid), dim3(64), 0, s, imgs, row_start, n, ticket);
     return hipGetLastError();
 }
-hipError_t launch_vp8d_rgb(const DImg* imgs, const DTile* tiles, uint32_t ntiles, hipStream_t s) {
+hipError_t launch_vp8d_alpha(const DImg* imgs, const uint32_t* which, uint32_t n, hipStream_t s) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_vp8d_alpha, dim3(n), dim3(64), 0, s, imgs, which);
+    return hipGetLastError();
+}
+hipError_t launch_vp8d_rgb(const DImg* imgs, const DTile* tiles, uint32_t ntiles, bool rgba, hipStream_t s) {
     if (!ntiles) return hipSuccess;
-    hipLaunchKernelGGL(k_vp8d_rgb, dim3(ntiles), dim3(256), 0, s, imgs, tiles);
+    if (rgba) hipLaunchKernelGGL(k_vp8d_rgb<true>, dim3(ntiles), dim3(256), 0, s, imgs, tiles);
+    else hipLaunchKernelGGL(k_vp8d_rgb<false>, dim3(ntiles), dim3(256), 0, s, imgs, tiles);
     return hipGetLastError();
 }
 

@@ -21,11 +21,13 @@ struct alignas(16) DImg {
     const uint8_t* flags;    // per MB: 1 = some coefficient is non-zero (libwebp !skip)
     uint8_t *y, *u, *v;
     uint8_t* top;
-    uint8_t* out;            // the ik_image's pixels (RGB)
+    uint8_t* out;            // the ik_image's pixels (RGB; RGBA where fr->channels is 4)
     uint32_t ys, uvs;        // plane pitches
     uint32_t out_pitch;
     uint32_t* prog;          // per MB row: MBs done (zeroed per launch)
     uint32_t* err;           // set when a row's wait times out (zeroed per launch)
+    uint8_t* alpha;          // fr->channels == 4: the staged alpha plane (alpha_pitch(w) apart, as
+                             // filtered by fr->alpha_filter; k_vp8d_alpha un-filters it in place)
 };
 
 // One block's work of the colour launch: rows [row0, row0 + rows) of image img
@@ -46,7 +48,10 @@ inline uint32_t rgb_tile_rows(uint32_t w) { return w >= kRgbTilePixels ? 1 : kRg
 constexpr uint32_t kReconBatchGrid = 1024;
 hipError_t launch_vp8d_recon(const DImg* imgs, const uint32_t* row_start, int n, uint32_t total_rows, uint32_t* ticket,
                              hipStream_t s, uint32_t* grid_used);
-hipError_t launch_vp8d_rgb(const DImg* imgs, const DTile* tiles, uint32_t ntiles, hipStream_t s);
+// which[0 .. n): the launch's images whose alpha plane has a filter to undo (a wave each)
+hipError_t launch_vp8d_alpha(const DImg* imgs, const uint32_t* which, uint32_t n, hipStream_t s);
+// rgba: some image of the launch has four channels
+hipError_t launch_vp8d_rgb(const DImg* imgs, const DTile* tiles, uint32_t ntiles, bool rgba, hipStream_t s);
 
 }  // namespace vp8d
 }  // namespace ik

@@ -15,6 +15,15 @@
 // finds unusual, data that runs out -- go to the host decoder (decode_webp), which
 // then gives libwebp's answer, error message included.
 //
+// Alpha behind a switch (IK_WEBP_ALPHA_DECODE=gpu / ik_set_webp_alpha_decode; off by
+// default, so that without it nothing changes and because whether it pays has to be
+// measured per size first, profiles/webp_alpha_notes.md): a lossy file with one ALPH
+// chunk is the same frame plus an 8-bit plane.  The host reads the plane as the
+// encoder filtered it -- raw bytes, or a lossless stream decoded by libwebp itself as
+// the VP8L file it would be with a header in front (alpha_plane) -- and the device
+// undoes the prediction filter (k_vp8d_alpha) and writes RGBA, WebPDecodeRGBA's pixels
+// (tests/test_webp_alpha_host.py, tests/test_gpu_webp_alpha.py).
+//
 // Two drivers over one launch sequence (run_launch): decode_webp_device, one file of
 // one ik_decode call, and decode_webp_batch, the lossy files of a batch call together
 // -- their host halves in parallel on the worker pool, then one staged area and one
@@ -46,11 +55,21 @@ uint32_t le16(const uint8_t* p) { return p[0] | (uint32_t)p[1] << 8; }
 uint32_t le24(const uint8_t* p) { return le16(p) | (uint32_t)p[2] << 16; }
 uint32_t le32(const uint8_t* p) { return le24(p) | (uint32_t)p[3] << 24; }
 
-// the "VP8 " payload of a simple file, or of an extended one without alpha or
-// animation (libwebp webp_dec.c ParseRIFF / ParseVP8X / ParseOptionalChunks /
-// ParseVP8Header); false: leave the file to the host decoder
-bool find_vp8(const uint8_t* b, size_t n, size_t& off, size_t& len, uint32_t& cw, uint32_t& ch) {
-    cw = ch = 0;
+// where a file's frame lies: the "VP8 " payload, the canvas size an extended header
+// gives (0: none), and the ALPH payload (alen 0: the file has none)
+struct Chunks {
+    size_t off = 0, len = 0;
+    uint32_t cw = 0, ch = 0;
+    size_t aoff = 0, alen = 0;
+};
+
+// the "VP8 " payload of a simple file, or of an extended one without animation and,
+// unless with_alpha, without alpha (libwebp webp_dec.c ParseRIFF / ParseVP8X /
+// ParseOptionalChunks / ParseVP8Header).  with_alpha: the alpha flag and exactly one
+// ALPH chunk before the frame go together; either without the other, or a second
+// chunk, is not taken.  false: leave the file to the host decoder
+bool find_vp8(const uint8_t* b, size_t n, bool with_alpha, Chunks& c) {
+    c = Chunks();
     if (n < 20 || std::memcmp(b, "RIFF", 4) || std::memcmp(b + 8, "WEBP", 4)) return false;
     const size_t riff = le32(b + 4);
     if (riff < 12 || riff + 8 > n) return false;
@@ -61,25 +80,75 @@ bool find_vp8(const uint8_t* b, size_t n, size_t& off, size_t& len, uint32_t& cw
         const size_t sz = le32(b + p + 4);
         if (sz < 10 || p + 8 + sz > end) return false;
         const uint8_t flags = b[p + 8];
-        if (flags & (0x10 | 0x02)) return false;  // alpha, animation
-        cw = 1 + le24(b + p + 12);
-        ch = 1 + le24(b + p + 15);
+        if (flags & 0x02) return false;  // animation
+        const bool alpha = flags & 0x10;
+        if (alpha && !with_alpha) return false;
+        c.cw = 1 + le24(b + p + 12);
+        c.ch = 1 + le24(b + p + 15);
         p += 8 + sz + (sz & 1);
+        bool have_alph = false;
         for (;;) {
             if (p + 8 > end) return false;
             if (!std::memcmp(b + p, "VP8 ", 4)) break;
-            if (!std::memcmp(b + p, "VP8L", 4) || !std::memcmp(b + p, "ALPH", 4) || !std::memcmp(b + p, "ANIM", 4) ||
-                !std::memcmp(b + p, "ANMF", 4))
+            if (!std::memcmp(b + p, "VP8L", 4) || !std::memcmp(b + p, "ANIM", 4) || !std::memcmp(b + p, "ANMF", 4))
                 return false;
             const size_t csz = le32(b + p + 4);
+            if (!std::memcmp(b + p, "ALPH", 4)) {
+                if (!alpha || have_alph || !csz || csz > end - (p + 8)) return false;
+                have_alph = true;
+                c.aoff = p + 8;
+                c.alen = csz;
+            }
+            if (csz > end - (p + 8)) return false;
             p += 8 + csz + (csz & 1);
         }
+        if (alpha != have_alph) return false;
     } else if (std::memcmp(b + p, "VP8 ", 4)) {
         return false;
     }
-    len = le32(b + p + 4);
-    off = p + 8;
-    return len >= 10 && off + len <= end;
+    c.len = le32(b + p + 4);
+    c.off = p + 8;
+    return c.len >= 10 && c.off + c.len <= end;
+}
+// the frame size its header gives (c.len >= 10)
+uint32_t frame_w(const uint8_t* b, const Chunks& c) { return le16(b + c.off + 6) & 0x3fff; }
+uint32_t frame_h(const uint8_t* b, const Chunks& c) { return le16(b + c.off + 8) & 0x3fff; }
+
+// The filtered alpha plane of an ALPH payload a[0 .. alen) for a w x h frame (libwebp
+// alpha_dec.c ALPHInit / ALPHDecode): the header byte -- bits 0-1 the compression (0 raw,
+// 1 lossless), 2-3 the filter, 4-5 the pre-processing (which changes nothing on the
+// decoding side), 6-7 reserved -- then w * h raw bytes, or a VP8L image stream without
+// its 5-byte header whose green channel is the plane.  The stream goes to libwebp as
+// the lossless file it would be with that header (VP8LDecodeAlphaHeader enters the same
+// DecodeImageStream at the same bit); its entropy code is as serial as the VP8 tokens.
+// false: libwebp would refuse it, or it is safer that libwebp decides.
+bool alpha_plane(const uint8_t* a, size_t alen, uint32_t w, uint32_t h, std::vector<uint8_t>& plane, int& filter,
+                 int& compression) {
+    if (alen < 1 || !w || !h) return false;
+    compression = a[0] & 3;
+    filter = (a[0] >> 2) & 3;
+    if (compression > 1 || ((a[0] >> 4) & 3) > 1 || (a[0] >> 6) > 1) return false;
+    const size_t px = (size_t)w * h;
+    if (compression == 0) {
+        if (alen - 1 < px) return false;
+        plane.assign(a + 1, a + 1 + px);
+        return true;
+    }
+    const size_t body = alen - 1, chunk = 5 + body;
+    const size_t file = 20 + chunk + (chunk & 1);
+    uint8_t hd[25] = {'R', 'I', 'F', 'F', 0, 0, 0, 0, 'W', 'E', 'B', 'P', 'V', 'P', '8', 'L'};
+    auto put32 = [&](int at, uint32_t v) {
+        for (int k = 0; k < 4; ++k) hd[at + k] = (uint8_t)(v >> (8 * k));
+    };
+    put32(4, (uint32_t)(file - 8));
+    put32(16, (uint32_t)chunk);
+    hd[20] = 0x2f;  // the VP8L signature, then 14 bits width - 1, 14 bits height - 1, alpha, version 0
+    put32(21, (w - 1) | (h - 1) << 14 | 1u << 28);
+    std::vector<uint8_t> f(file, 0);
+    std::copy(hd, hd + 25, f.begin());
+    std::copy(a + 1, a + 1 + body, f.begin() + 25);
+    plane.resize(px);
+    return webp_lossless_green(f.data(), f.size(), w, h, plane.data());
 }
 
 struct Parsed {
@@ -441,6 +510,20 @@ int webp_decode_mode() {  // IK_WEBP_DECODE: host / gpu (no host fallback: tests
     return 1;
 }
 
+// Whether a lossy file with an alpha plane is the GPU path's (IK_WEBP_ALPHA_GPU) or
+// libwebp's (IK_WEBP_ALPHA_HOST, the default): ik_set_webp_alpha_decode's value, else
+// IK_WEBP_ALPHA_DECODE=host|gpu, read per call as IK_WEBP_DECODE is.  Off by default:
+// the alpha plane's entropy decode stays on the host and its un-filtering is one wave
+// per plane, so whether the device path wins has to be measured per size first
+// (profiles/webp_alpha_notes.md).
+std::atomic<int> g_webp_alpha{-1};
+int webp_alpha_mode() {
+    const int v = g_webp_alpha.load(std::memory_order_relaxed);
+    if (v >= 0) return v;
+    const char* e = getenv("IK_WEBP_ALPHA_DECODE");
+    return e && !std::strcmp(e, "gpu") ? IK_WEBP_ALPHA_GPU : IK_WEBP_ALPHA_HOST;
+}
+
 // auto: the device path from this many pixels on.  Measured per frame (decode_image,
 // one request; profiles/r06_webp_decode.log): 4096x4096 39.6 ms against libwebp's 62.2,
 // 3000x2000 16.9 / 19.5, 2560x1440 11.4 / 12.0, 1920x1080 7.3 / 7.1, 512x512 1.65 / 0.93.
@@ -461,7 +544,7 @@ std::atomic<unsigned long long> g_webp_gpu{0}, g_webp_host{0};  // ik_webp_count
 
 // the last batch per device (ik_webp_last_timing)
 enum { kWtParseWallMs = 0, kWtParseCoreMs, kWtStageMs, kWtReconMs, kWtRgbMs, kWtGpuImages, kWtHostImages, kWtRows,
-       kWtGrid, kWtLaunches, kWtFields };
+       kWtGrid, kWtLaunches, kWtAlphaMs, kWtAlphaCoreMs, kWtAlphaImages, kWtFields };
 std::mutex g_wtim_mu;
 std::map<int, std::array<double, kWtFields>> g_wtim;
 
@@ -483,8 +566,28 @@ std::string last_msg() {
 struct Frame {
     Parsed P;
     Tokens T;
-    size_t bytes() const { return P.mbs.capacity() * sizeof(DMB) + (T.coef.capacity() + T.at.capacity()) * 4 + T.flags.capacity(); }
+    std::vector<uint8_t> alpha;  // P.fr.channels == 4: the filtered alpha plane, w * h
+    size_t bytes() const {
+        return P.mbs.capacity() * sizeof(DMB) + (T.coef.capacity() + T.at.capacity()) * 4 + T.flags.capacity() +
+               alpha.capacity();
+    }
 };
+// the whole host half of one file: partition 0, the tokens and, with an ALPH chunk
+// (c.alen), the filtered alpha plane; false: the file is libwebp's.  *alpha_ms (may be
+// null) gets the thread CPU ms of the alpha plane alone.
+bool host_half(const uint8_t* b, const Chunks& c, Frame& F, double* alpha_ms) {
+    if (!parse_vp8(b, c.off, c.len, c.cw, c.ch, F.P) || !decode_tokens(b, F.P, F.T)) return false;
+    DFrame& fr = F.P.fr;
+    fr.channels = 3;
+    if (!c.alen) return true;
+    const double c0 = alpha_ms ? thread_cpu_ms() : 0;
+    int filter = 0, compression = 0;
+    if (!alpha_plane(b + c.aoff, c.alen, (uint32_t)fr.w, (uint32_t)fr.h, F.alpha, filter, compression)) return false;
+    fr.channels = 4;
+    fr.alpha_filter = filter;
+    if (alpha_ms) *alpha_ms = thread_cpu_ms() - c0;
+    return true;
+}
 constexpr size_t kFrameKeepBytes = 16u << 20;  // host buffers kept between calls up to this much
 
 // One block of memory laid out once: take(bytes) hands out the next 256-byte aligned
@@ -499,16 +602,18 @@ struct Lay {
     }
 };
 struct FrameLay {
-    size_t fr, mb, flags, at, coef;  // staged: [DFrame][DMB x nmb][flags][entry starts][entries]
-    size_t y, u, v, top;             // device work: the planes, the two top rows
+    size_t fr, mb, flags, at, coef, alpha;  // staged: [DFrame][DMB x nmb][flags][entry starts][entries][alpha plane]
+    size_t y, u, v, top;                    // device work: the planes, the two top rows
 };
 void lay_staged(Lay& L, const Frame& F, FrameLay& o) {
-    const size_t nmb = (size_t)F.P.fr.mb_w * F.P.fr.mb_h;
+    const DFrame& fr = F.P.fr;
+    const size_t nmb = (size_t)fr.mb_w * fr.mb_h;
     o.fr = L.take(sizeof(DFrame));
     o.mb = L.take(nmb * sizeof(DMB));
     o.flags = L.take(nmb);
     o.at = L.take((nmb + 1) * 4);
     o.coef = L.take(F.T.coef.size() * 4 + 4);
+    o.alpha = fr.channels == 4 ? L.take((size_t)alpha_pitch((uint32_t)fr.w) * fr.h) : 0;
 }
 void lay_work(Lay& L, const Frame& F, FrameLay& o) {
     const DFrame& fr = F.P.fr;
@@ -527,20 +632,22 @@ uint64_t frame_launch_bytes(const Frame& F) {
     FrameLay o;
     lay_staged(L, F, o);
     lay_work(L, F, o);
-    return L.cur + sizeof(DImg) + 4 + (size_t)frame_tiles(F.P.fr) * sizeof(DTile) + 4 * (1 + (size_t)F.P.fr.mb_h);
+    return L.cur + sizeof(DImg) + 4 + 4 + (size_t)frame_tiles(F.P.fr) * sizeof(DTile) + 4 * (1 + (size_t)F.P.fr.mb_h);
 }
 
 struct LaunchTim {
-    double stage_ms = 0, recon_ms = 0, rgb_ms = 0;
+    double stage_ms = 0, recon_ms = 0, alpha_ms = 0, rgb_ms = 0;
     uint32_t grid = 0;
 };
 
 // m parsed frames, in plan order (row_start: m + 1 tickets), through one set of
 // launches into new images: one H2D of the staged area
-//   [DImg x m][row_start][tiles] then per frame [DFrame][DMB x nmb][flags][entry starts][entries]
+//   [DImg x m][row_start][tiles][the images with a filtered alpha plane] then per frame
+//   [DFrame][DMB x nmb][flags][entry starts][entries][alpha plane, rows alpha_pitch(w) apart]
 // one memset of the sync words of the work area behind it
 //   [ticket, err per image, progress per MB row] then per frame [Y][U][V][top rows]
-// the two kernels, the err words back, one stream sync.  imgs[k]: the image, or null
+// the kernels (reconstruction, the alpha filters where a plane has one, colour), the
+// err words back, one stream sync.  imgs[k]: the image, or null
 // where the device gave the frame up (a row's wait timed out: the device is too busy
 // or something is wrong; libwebp decides).  A failure frees every image.
 int run_launch(const Frame* const* F, const uint32_t* row_start, int m, ik_image** imgs, int threads, LaunchTim* tim) {
@@ -553,6 +660,7 @@ int run_launch(const Frame* const* F, const uint32_t* row_start, int m, ik_image
     const size_t o_img = L.take(sizeof(DImg) * (size_t)m);
     const size_t o_rs = L.take(4 * ((size_t)m + 1));
     const size_t o_tiles = L.take(sizeof(DTile) * (size_t)ntiles);
+    const size_t o_which = L.take(4 * (size_t)m);
     for (int k = 0; k < m; ++k) lay_staged(L, *F[k], o[k]);
     const size_t stage = L.cur;
     const size_t sync_bytes = 4 * (1 + (size_t)m + total_rows);
@@ -567,7 +675,7 @@ int run_launch(const Frame* const* F, const uint32_t* row_start, int m, ik_image
         }
     };
     for (int k = 0; k < m; ++k) {
-        const int st = alloc_image((uint32_t)F[k]->P.fr.w, (uint32_t)F[k]->P.fr.h, 3, &imgs[k]);
+        const int st = alloc_image((uint32_t)F[k]->P.fr.w, (uint32_t)F[k]->P.fr.h, (uint32_t)F[k]->P.fr.channels, &imgs[k]);
         if (st) {
             drop();
             return st;
@@ -586,11 +694,18 @@ int run_launch(const Frame* const* F, const uint32_t* row_start, int m, ik_image
     DImg* const himg = reinterpret_cast<DImg*>(h + o_img);
     DTile* const htile = reinterpret_cast<DTile*>(h + o_tiles);
     std::memcpy(h + o_rs, row_start, 4 * ((size_t)m + 1));
-    uint32_t prog0 = 0, tile0 = 0;
+    uint32_t prog0 = 0, tile0 = 0, nwhich = 0;
+    bool rgba = false;
+    uint32_t* const hwhich = reinterpret_cast<uint32_t*>(h + o_which);
     std::vector<uint32_t> first_tile((size_t)m);
     for (int k = 0; k < m; ++k) {
         const DFrame& fr = F[k]->P.fr;
         DImg di{};
+        if (fr.channels == 4) {
+            rgba = true;
+            di.alpha = d + o[k].alpha;
+            if (fr.alpha_filter) hwhich[nwhich++] = (uint32_t)k;
+        }
         di.fr = reinterpret_cast<const DFrame*>(d + o[k].fr);
         di.mbs = reinterpret_cast<const DMB*>(d + o[k].mb);
         di.flags = d + o[k].flags;
@@ -620,6 +735,11 @@ int run_launch(const Frame* const* F, const uint32_t* row_start, int m, ik_image
         std::memcpy(h + o[k].flags, f.T.flags.data(), nmb);
         std::memcpy(h + o[k].at, f.T.at.data(), (nmb + 1) * 4);
         if (!f.T.coef.empty()) std::memcpy(h + o[k].coef, f.T.coef.data(), f.T.coef.size() * 4);
+        if (fr.channels == 4) {  // the plane's rows, alpha_pitch(w) apart
+            reinterpret_cast<DFrame*>(h + o[k].fr)->alpha_off = (uint32_t)(o[k].alpha - o[k].fr);
+            const size_t w = (size_t)fr.w, ap = alpha_pitch((uint32_t)fr.w);
+            for (size_t r = 0; r < (size_t)fr.h; ++r) std::memcpy(h + o[k].alpha + r * ap, f.alpha.data() + r * w, w);
+        }
         const uint32_t tr = rgb_tile_rows((uint32_t)fr.w);
         DTile* t = htile + first_tile[k];
         for (uint32_t r = 0; r < (uint32_t)fr.h; r += tr) *t++ = DTile{(uint32_t)k, r, std::min(tr, (uint32_t)fr.h - r)};
@@ -629,11 +749,10 @@ int run_launch(const Frame* const* F, const uint32_t* row_start, int m, ik_image
 
     const DImg* dimg = reinterpret_cast<const DImg*>(d + o_img);
     uint32_t* const herr = reinterpret_cast<uint32_t*>(h + stage);
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // after: the alpha kernel, the memset, recon, rgb
     if (tim) {
         const EvPair &p = thread_events(2), &q = thread_events(3);
         ev[0] = p.a, ev[1] = p.b, ev[2] = q.a, ev[3] = q.b;
-        ev_record(ev[0], s);
     }
     hipError_t e = hipMemcpyAsync(d, h, stage, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(sync, 0, sync_bytes, s);
@@ -642,7 +761,9 @@ int run_launch(const Frame* const* F, const uint32_t* row_start, int m, ik_image
     if (e == hipSuccess)
         e = launch_vp8d_recon(dimg, reinterpret_cast<const uint32_t*>(d + o_rs), m, total_rows, sync, s, &grid);
     if (tim) ev_record(ev[2], s);
-    if (e == hipSuccess) e = launch_vp8d_rgb(dimg, reinterpret_cast<const DTile*>(d + o_tiles), ntiles, s);
+    if (e == hipSuccess && nwhich) e = launch_vp8d_alpha(dimg, reinterpret_cast<const uint32_t*>(d + o_which), nwhich, s);
+    if (tim) ev_record(ev[0], s);
+    if (e == hipSuccess) e = launch_vp8d_rgb(dimg, reinterpret_cast<const DTile*>(d + o_tiles), ntiles, rgba, s);
     if (tim) ev_record(ev[3], s);
     if (e == hipSuccess) e = hipMemcpyAsync(herr, sync + 1, 4 * (size_t)m, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -657,7 +778,8 @@ int run_launch(const Frame* const* F, const uint32_t* row_start, int m, ik_image
         };
         tim->stage_ms += (now_ms() - t0) - ms(ev[1], ev[3]);  // staging copies and the H2D: the wall time less the kernels
         tim->recon_ms += ms(ev[1], ev[2]);
-        tim->rgb_ms += ms(ev[2], ev[3]);
+        tim->alpha_ms += ms(ev[2], ev[0]);
+        tim->rgb_ms += ms(ev[0], ev[3]);
         tim->grid = std::max(tim->grid, grid);
     }
     for (int k = 0; k < m; ++k)
@@ -696,18 +818,14 @@ void webp_count_host_decode() { ++g_webp_host; }
 int decode_webp_device(const uint8_t* b, size_t n, ik_image** out) {
     const int mode = webp_decode_mode();
     if (!mode) return kVp8dHost;
-    size_t off = 0, len = 0;
-    uint32_t cw, ch;
-    if (!find_vp8(b, n, off, len, cw, ch)) return kVp8dHost;
-    if (mode == 1) {
-        const uint32_t w = le16(b + off + 6) & 0x3fff, h = le16(b + off + 8) & 0x3fff;
-        if ((uint64_t)w * h < kWebpGpuMinPixels) return kVp8dHost;
-    }
+    Chunks c;
+    if (!find_vp8(b, n, webp_alpha_mode() == IK_WEBP_ALPHA_GPU, c)) return kVp8dHost;
+    if (mode == 1 && (uint64_t)frame_w(b, c) * frame_h(b, c) < kWebpGpuMinPixels) return kVp8dHost;
     thread_local Frame F;  // (per-thread buffers: released after frames over 16 MiB of them)
     struct Trim {
         ~Trim() { trim_frame(F); }
     } trim;
-    if (!parse_vp8(b, off, len, cw, ch, F.P) || !decode_tokens(b, F.P, F.T)) return kVp8dHost;
+    if (!host_half(b, c, F, nullptr)) return kVp8dHost;
     const Frame* const fp = &F;
     const uint32_t row_start[2] = {0, (uint32_t)F.P.fr.mb_h};
     ik_image* img = nullptr;
@@ -723,23 +841,24 @@ int decode_webp_batch(const uint8_t* const* b, const size_t* lens, int n, ik_ima
                       std::string* msgs, int threads) {
     const int mode = webp_decode_mode();
     const double t_begin = now_ms();
-    // the files the GPU path would take: a plain lossy frame in the container
+    // the files the GPU path would take: a plain lossy frame in the container (with an
+    // alpha plane beside it under IK_WEBP_ALPHA_DECODE=gpu)
     struct Cand {
-        size_t off = 0, len = 0;
-        uint32_t cw = 0, ch = 0;
+        Chunks c;
         int frame = -1;  // its Frame in the pool, once parsed and accepted: -1 otherwise
-        double core_ms = 0;
+        double core_ms = 0, alpha_ms = 0;
     };
     std::vector<Cand> C((size_t)n);
     std::vector<char> take((size_t)n, 0);
     int ncand = 0;
     if (mode) {
+        const bool with_alpha = webp_alpha_mode() == IK_WEBP_ALPHA_GPU;
         uint64_t px = 0;
         for (int i = 0; i < n; ++i)
-            if (find_vp8(b[i], lens[i], C[i].off, C[i].len, C[i].cw, C[i].ch)) {
+            if (find_vp8(b[i], lens[i], with_alpha, C[i].c)) {
                 take[i] = 1;
                 ++ncand;
-                px += (uint64_t)(le16(b[i] + C[i].off + 6) & 0x3fff) * (le16(b[i] + C[i].off + 8) & 0x3fff);
+                px += (uint64_t)frame_w(b[i], C[i].c) * frame_h(b[i], C[i].c);
             }
         if (mode == 1 && px < kWebpGpuMinBatchPixels) {
             std::fill(take.begin(), take.end(), 0);
@@ -770,8 +889,8 @@ int decode_webp_batch(const uint8_t* const* b, const size_t* lens, int n, ik_ima
         if (take[i]) {
             Frame& F = frames[C[i].frame];
             const double c0 = thread_cpu_ms();
-            const bool ok = parse_vp8(b[i], C[i].off, C[i].len, C[i].cw, C[i].ch, F.P) && decode_tokens(b[i], F.P, F.T);
-            C[i].core_ms = thread_cpu_ms() - c0;
+            const bool ok = host_half(b[i], C[i].c, F, &C[i].alpha_ms);
+            C[i].core_ms = thread_cpu_ms() - c0 - C[i].alpha_ms;
             if (ok) return;
             C[i].frame = -1;
         }
@@ -780,7 +899,10 @@ int decode_webp_batch(const uint8_t* const* b, const size_t* lens, int n, ik_ima
     });
     std::array<double, kWtFields> W{};
     W[kWtParseWallMs] = now_ms() - t_begin;
-    for (int i = 0; i < n; ++i) W[kWtParseCoreMs] += C[i].core_ms;
+    for (int i = 0; i < n; ++i) {
+        W[kWtParseCoreMs] += C[i].core_ms;
+        W[kWtAlphaCoreMs] += C[i].alpha_ms;
+    }
 
     // the accepted frames: planned (largest first, cut at the cap), then launched
     std::vector<int> acc;  // request index of each accepted frame
@@ -831,6 +953,7 @@ int decode_webp_batch(const uint8_t* const* b, const size_t* lens, int n, ik_ima
                     outs[i] = imgs[k];
                     ++g_webp_gpu;
                     W[kWtGpuImages] += 1;
+                    if (F[k]->P.fr.channels == 4) W[kWtAlphaImages] += 1;
                 } else {
                     retry.push_back(i);
                 }
@@ -839,6 +962,7 @@ int decode_webp_batch(const uint8_t* const* b, const size_t* lens, int n, ik_ima
         W[kWtStageMs] = tim.stage_ms;
         W[kWtReconMs] = tim.recon_ms;
         W[kWtRgbMs] = tim.rgb_ms;
+        W[kWtAlphaMs] = tim.alpha_ms;
         W[kWtGrid] = tim.grid;
         W[kWtLaunches] = launches;
     }
@@ -884,6 +1008,33 @@ extern "C" int ik_webp_last_timing(double* out, int n) {
 }
 
 extern "C" unsigned long long ik_webp_gpu_min_batch_pixels(void) { return ik::kWebpGpuMinBatchPixels; }
+
+extern "C" int ik_set_webp_alpha_decode(int where) {
+    if (where != -1 && where != IK_WEBP_ALPHA_HOST && where != IK_WEBP_ALPHA_GPU)
+        return ik::fail(IK_ERR_INVALID, "ik_set_webp_alpha_decode: IK_WEBP_ALPHA_HOST, IK_WEBP_ALPHA_GPU or -1");
+    ik::g_webp_alpha.store(where, std::memory_order_relaxed);
+    return IK_OK;
+}
+extern "C" int ik_get_webp_alpha_decode(void) { return ik::webp_alpha_mode(); }
+
+extern "C" int ik_webp_alpha_plane(const uint8_t* bytes, size_t len, uint8_t* plane, size_t cap, uint32_t* w, uint32_t* h,
+                                   int* filter, int* compression) {
+    if (!bytes || !w || !h || !filter || !compression) return ik::fail(IK_ERR_INVALID, "null pointer");
+    ik::Chunks c;
+    if (!ik::find_vp8(bytes, len, true, c) || !c.alen)
+        return ik::fail(IK_ERR_UNSUPPORTED, "not a lossy WebP file with one alpha plane: left to libwebp");
+    const uint32_t fw = ik::frame_w(bytes, c), fh = ik::frame_h(bytes, c);
+    if (!fw || !fh || fw != c.cw || fh != c.ch)
+        return ik::fail(IK_ERR_UNSUPPORTED, "the canvas is not the frame: left to libwebp");
+    std::vector<uint8_t> a;
+    if (!ik::alpha_plane(bytes + c.aoff, c.alen, fw, fh, a, *filter, *compression))
+        return ik::fail(IK_ERR_UNSUPPORTED, "the GPU path leaves this alpha plane to libwebp");
+    *w = fw;
+    *h = fh;
+    if (a.size() > cap || (!plane && !a.empty())) return ik::fail(IK_ERR_INVALID, "the plane needs w * h bytes");
+    std::memcpy(plane, a.data(), a.size());
+    return IK_OK;
+}
 
 extern "C" int ik_webp_batch_plan(const uint32_t* mb_w, const uint32_t* mb_h, const uint64_t* bytes, uint32_t n,
                                   uint64_t cap_bytes, uint32_t* order, uint32_t* row_start, uint32_t* launch_lo) {

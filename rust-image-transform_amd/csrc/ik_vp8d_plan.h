@@ -10,7 +10,8 @@
 namespace ik {
 namespace vp8d {
 
-// n images of mb_w[i] x mb_h[i] macroblocks that take bytes[i] of staged + work memory.
+// n images of mb_w[i] x mb_h[i] macroblocks that take bytes[i] of staged + work memory
+// (a frame's staged alpha plane included, so the cap holds for RGBA frames too).
 //   order[k]      the request placed k-th: largest first, by MB rows, then by MBs, then
 //                 by request index, so a launch's last tickets are short rows
 //   launch_lo     the first k of each sub-launch, then n (room for n + 1 values): the
