@@ -501,7 +501,7 @@ static int up_libjpeg(const uint8_t *p, int pw, int dw, int dh, int fh, int fv, 
     if (fh == 2 && fv == 1) {
         const uint8_t *ip = ROW(ys);
         const int X = xs >> 1;
-        if (dw == 1) return ip[0];
+        if (dw <= 2) return ip[X]; /* jinit_upsampler: fancy only above two samples, else h2v1_upsample */
         if (!(xs & 1)) return X == 0 ? ip[0] : (ip[X] * 3 + ip[X - 1] + 1) >> 2;
         return X == dw - 1 ? ip[X] : (ip[X] * 3 + ip[X + 1] + 2) >> 2;
     }
@@ -509,7 +509,7 @@ static int up_libjpeg(const uint8_t *p, int pw, int dw, int dh, int fh, int fv, 
         const int Y = ys >> 1, X = xs >> 1;
         const uint8_t *i0 = ROW(Y), *i1 = ROW((ys & 1) ? Y + 1 : Y - 1);
         const int ths = i0[X] * 3 + i1[X];
-        if (dw == 1) return (xs & 1) ? (ths * 4 + 7) >> 4 : (ths * 4 + 8) >> 4;
+        if (dw <= 2) return i0[X]; /* h2v2_upsample: replication, as above */
         if (!(xs & 1)) {
             if (X == 0) return (ths * 4 + 8) >> 4;
             return (ths * 3 + i0[X - 1] * 3 + i1[X - 1] + 8) >> 4;

@@ -100,7 +100,7 @@ __device__ __forceinline__ int upsampled(const JpegGeom& g, int ci, int x, int y
     if (fh == 2 && fv == 1) {  // h2v1_fancy_upsample
         const uint8_t* ip = row(ys);
         const int X = xs >> 1;
-        if (dw == 1) return ip[0];
+        if (dw <= 2) return ip[X];  // jinit_upsampler: fancy only above two samples, else h2v1_upsample
         if (!(xs & 1)) return X == 0 ? ip[0] : (ip[X] * 3 + ip[X - 1] + 1) >> 2;
         return X == dw - 1 ? ip[X] : (ip[X] * 3 + ip[X + 1] + 2) >> 2;
     }
@@ -109,7 +109,7 @@ __device__ __forceinline__ int upsampled(const JpegGeom& g, int ci, int x, int y
         const uint8_t* i0 = row(Y);
         const uint8_t* i1 = row((ys & 1) ? Y + 1 : Y - 1);
         const int thiss = i0[X] * 3 + i1[X];
-        if (dw == 1) return (xs & 1) ? (thiss * 4 + 7) >> 4 : (thiss * 4 + 8) >> 4;
+        if (dw <= 2) return i0[X];  // h2v2_upsample: replication, as above
         if (!(xs & 1)) {
             if (X == 0) return (thiss * 4 + 8) >> 4;
             const int lasts = i0[X - 1] * 3 + i1[X - 1];
