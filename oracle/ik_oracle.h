@@ -96,6 +96,12 @@ int iko_vp8_modes(const uint8_t *y, const uint8_t *u, const uint8_t *v, int w, i
 long iko_vp8_encode(const uint8_t *y, const uint8_t *u, const uint8_t *v, int w, int h, float quality,
                     const uint8_t *seg, int num_segments, int update_map, const int *probs, const int *quant,
                     const int *fstr, int dq_uv_dc, int dq_uv_ac, uint8_t **out);
+/* the same, plus a census of the coded levels: levels[4][4], per coefficient type (0 i16-AC,
+ * 1 i16-DC, 2 chroma, 3 i4) the number of non-zero levels in 1..67, in 68..2046 and at
+ * 2047, and the largest level */
+long iko_vp8_encode_levels(const uint8_t *y, const uint8_t *u, const uint8_t *v, int w, int h, float quality,
+                           const uint8_t *seg, int num_segments, int update_map, const int *probs, const int *quant,
+                           const int *fstr, int dq_uv_dc, int dq_uv_ac, uint8_t **out, uint32_t *levels);
 
 /* the reference CPU transform (resize_image + encode_image) on a decoded 8-bit
  * image: fmt 0=jpeg 1=webp.  Used as bench.py's cpu_baseline "port". */

@@ -179,6 +179,11 @@ static int add_token(int bit, uint32_t id, uint32_t* s) {
 
 static void add_const(int bit, int prob) { put_token(((uint32_t)bit << 15) | (1u << 14) | (uint32_t)prob); }
 
+/* optional census of the coded levels (iko_vp8_encode_levels): per coefficient type
+ * (0 i16-AC, 1 i16-DC, 2 chroma, 3 i4) the count of non-zero levels <= MAX_VARIABLE_LEVEL,
+ * of those up to MAX_LEVEL - 1, of those at MAX_LEVEL, and the largest level; NULL = off */
+static uint32_t (*g_levels)[4];
+
 #define TOKEN_ID(t, b, ctx) (11u * ((ctx) + 3u * ((b) + 8u * (t))))
 static const uint8_t kCat3[] = {173, 148, 140, 0};
 static const uint8_t kCat4[] = {176, 155, 140, 135, 0};
@@ -200,6 +205,10 @@ static int record_coeff_tokens(Proba* P, int ctx, const Residual* r) {
             base_id = TOKEN_ID(t, kEncBands[n], 0);
             s = P->stats[t][kEncBands[n]][0];
             continue;
+        }
+        if (g_levels) {
+            ++g_levels[t][v <= MAX_VARIABLE_LEVEL ? 0 : v < MAX_LEVEL ? 1 : 2];
+            if (v > g_levels[t][3]) g_levels[t][3] = v;
         }
         if (!add_token(v > 1, base_id + 2, s + 2)) {
             base_id = TOKEN_ID(t, kEncBands[n], 1);
@@ -1431,4 +1440,17 @@ long iko_vp8_encode(const uint8_t* y, const uint8_t* u, const uint8_t* v, int w,
     free(ym); free(bm); free(uvm);
     *out = o;
     return (long)total;
+}
+
+/* iko_vp8_encode, and what its token walk coded: levels[4][4], per coefficient type the
+ * number of non-zero levels in 1..67, 68..2046 and at 2047, and the largest level */
+long iko_vp8_encode_levels(const uint8_t* y, const uint8_t* u, const uint8_t* v, int w, int h, float quality,
+                           const uint8_t* seg, int num_segments, int update_map, const int* probs, const int* quant,
+                           const int* fstr, int dq_uv_dc, int dq_uv_ac, uint8_t** out, uint32_t* levels) {
+    memset(levels, 0, 16 * sizeof(*levels));
+    g_levels = (uint32_t(*)[4])levels;
+    const long n = iko_vp8_encode(y, u, v, w, h, quality, seg, num_segments, update_map, probs, quant, fstr, dq_uv_dc,
+                                  dq_uv_ac, out);
+    g_levels = NULL;
+    return n;
 }

@@ -12,7 +12,8 @@ diffusion on at <= 98, off above).  The segment set-up is the restated first sta
 
 The last tests close the loop: the restated filter levels, header, modes, token
 partition and RIFF container are the same *file* WebPEncodeRGB writes, byte for byte --
-the whole reference WebP coder restated, the model a GPU coder is checked against."""
+the whole reference WebP coder restated, the model a GPU coder is checked against --
+also on tests/vp8_content.py's chosen patterns and strip / epoch-edge geometries."""
 import ctypes
 import os
 import re
@@ -22,6 +23,7 @@ import pytest
 
 import ikutil
 import oracle_vp8
+import vp8_content
 import vp8_parse
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -79,23 +81,33 @@ def test_modes_and_probabilities_equal_libwebp(orc, wh, pat, q):
         assert bad.size == 0, f"{w}x{h} {pat} q{q}: {name} differs first at {bad[0].tolist()} ({len(bad)} entries)"
 
 
-def restated_webp(orc, y, u, v, q):
+def restated_webp(orc, y, u, v, q, levels=None):
     """The whole file, restated: oracle_vp8's segment set-up + vp8_modes.c's decisions,
-    filter levels, token partition and RIFF container (iko_vp8_encode)."""
+    filter levels, token partition and RIFF container (iko_vp8_encode).  levels: an optional
+    (4, 4) uint32 array that receives the coded levels' census (iko_vp8_encode_levels): per
+    coefficient type the number of non-zero levels in 1..67, 68..2046 and at 2047, and the
+    largest level."""
     h, w = y.shape
     a = oracle_vp8.analyze(y, u, v, q)
     lib = orc.lib
-    lib.iko_vp8_encode.restype = ctypes.c_long
-    lib.iko_vp8_encode.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_float] + [ctypes.c_void_p] + \
+    argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_float] + [ctypes.c_void_p] + \
         [ctypes.c_int] * 2 + [ctypes.c_void_p] * 3 + [ctypes.c_int] * 2 + [ctypes.c_void_p]
+    lib.iko_vp8_encode.restype = lib.iko_vp8_encode_levels.restype = ctypes.c_long
+    lib.iko_vp8_encode.argtypes = argtypes
+    lib.iko_vp8_encode_levels.argtypes = argtypes + [ctypes.c_void_p]
     seg = np.ascontiguousarray(a["segments"].reshape(-1).astype(np.uint8))
     arr = lambda x: np.ascontiguousarray(np.array(x, np.int32))  # noqa: E731
     probs, quant, fstr = arr(a["probs"]), arr(a["quant"]), arr(a["fstrength_pre"])
     y, u, v = (np.ascontiguousarray(t) for t in (y, u, v))
     out = ctypes.POINTER(ctypes.c_uint8)()
-    n = lib.iko_vp8_encode(y.ctypes.data, u.ctypes.data, v.ctypes.data, w, h, q, seg.ctypes.data, a["num_segments"],
-                           int(a["update_map"]), probs.ctypes.data, quant.ctypes.data, fstr.ctypes.data, a["uv_dc"],
-                           a["uv_ac"], ctypes.byref(out))
+    args = (y.ctypes.data, u.ctypes.data, v.ctypes.data, w, h, q, seg.ctypes.data, a["num_segments"],
+            int(a["update_map"]), probs.ctypes.data, quant.ctypes.data, fstr.ctypes.data, a["uv_dc"], a["uv_ac"],
+            ctypes.byref(out))
+    if levels is None:
+        n = lib.iko_vp8_encode(*args)
+    else:
+        assert levels.shape == (4, 4) and levels.dtype == np.uint32 and levels.flags.c_contiguous
+        n = lib.iko_vp8_encode_levels(*args, levels.ctypes.data)
     assert n > 0
     b = ctypes.string_at(out, n)
     lib.iko_free(out)
@@ -111,6 +123,27 @@ def test_whole_file_equals_libwebp(orc, wh, pat, q):
     w, h = wh
     rgb = ikutil.synth(w, h, 3, seed=5 * w + h, pattern=pat)
     assert restated_webp(orc, *orc.libwebp_import_yuv(rgb), q) == orc.webp_encode_rgb(rgb, q)
+
+
+# the content the GPU coder is judged by (tests/test_gpu_vp8x_content.py): flat, striped,
+# diagonal and saturated frames, and frames one macroblock wide or high or ending on an
+# epoch edge of the probability refresh -- a GPU mismatch there with this test green is
+# the kernels' own
+@pytest.mark.parametrize("name", vp8_content.PATTERN_NAMES)
+def test_whole_file_on_chosen_content(orc, name):
+    rgb = vp8_content.pattern(name, 64, 48)
+    yuv = orc.libwebp_import_yuv(rgb)
+    for q in (1.0, 98.0, 99.0, 100.0):
+        assert restated_webp(orc, *yuv, q) == orc.webp_encode_rgb(rgb, q), f"{name} q{q}"
+
+
+@pytest.mark.parametrize("wh", vp8_content.STRIPS, ids=lambda wh: f"{wh[0]}x{wh[1]}")
+@pytest.mark.parametrize("name", ["S", "flat_in_noise"])
+def test_whole_file_on_strips_and_epoch_edges(orc, wh, name):
+    rgb = vp8_content.geometry_image(name, *wh)
+    yuv = orc.libwebp_import_yuv(rgb)
+    for q in (1.0, 98.0, 99.0, 100.0):
+        assert restated_webp(orc, *yuv, q) == orc.webp_encode_rgb(rgb, q), f"{wh[0]}x{wh[1]} {name} q{q}"
 
 
 def test_golden_webp_bytes(orc):

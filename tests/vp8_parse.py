@@ -188,3 +188,54 @@ def parse(webp: bytes) -> dict:
     out.update(mb_w=mbw, mb_h=mbh, segments=segs, skip=skip, is_i4=is_i4, ymode=ymode, bmodes=bmodes, uvmode=uvmode,
                overrun=bd.pos > len(bd.d) + 2)
     return out
+
+
+I4_NAMES = ["DC", "TM", "VE", "HE", "RD", "VR", "LD", "VL", "HD", "HU"]
+I16_NAMES = ["DC", "TM", "V", "H"]
+
+
+def diagnose(got: bytes, want: bytes) -> str:
+    """Where two WebP files of one frame part: the first macroblock, in raster order, whose
+    segment, luma mode, sub-block modes or chroma mode differ; else the first header field or
+    coefficient probability that differs; else that only the tokens do."""
+    if got == want:
+        return "files equal"
+    n = min(len(got), len(want))
+    at = next((i for i in range(n) if got[i] != want[i]), n)
+    head = f"differs at byte {at} ({len(got)} vs {len(want)} bytes)"
+    e = parse(want)
+    try:
+        g = parse(got)
+    except Exception as ex:  # the wrong file need not even parse
+        return f"{head}; the file does not parse: {type(ex).__name__}: {ex}"
+    if (g["width"], g["height"]) != (e["width"], e["height"]):
+        return f"{head}; frame size {g['width']}x{g['height']}, expected {e['width']}x{e['height']}"
+    for key in ("segment", "filter", "quant"):
+        if g[key] != e[key]:
+            return f"{head}; {key} header {g[key]}, expected {e[key]}"
+    mb_w, mb_h = e["mb_w"], e["mb_h"]
+
+    def luma(r, my, mx):
+        if r["is_i4"][my, mx]:
+            return "i4 [" + " ".join(I4_NAMES[m] for m in r["bmodes"][4 * my:4 * my + 4, 4 * mx:4 * mx + 4].reshape(-1)) + "]"
+        return "i16 " + I16_NAMES[r["ymode"][my, mx]]
+
+    for my in range(mb_h):
+        for mx in range(mb_w):
+            what = []
+            if g["segments"][my, mx] != e["segments"][my, mx]:
+                what.append(f"segment {g['segments'][my, mx]}, expected {e['segments'][my, mx]}")
+            if luma(g, my, mx) != luma(e, my, mx):
+                what.append(f"luma {luma(g, my, mx)}, expected {luma(e, my, mx)}")
+            if g["uvmode"][my, mx] != e["uvmode"][my, mx]:
+                what.append(f"chroma {I16_NAMES[g['uvmode'][my, mx]]}, expected {I16_NAMES[e['uvmode'][my, mx]]}")
+            if what:
+                return f"{head}; first at macroblock {my * mb_w + mx} (x {mx}, y {my}) of {mb_w}x{mb_h}: " + "; ".join(what)
+    bad = [i for i, (a, b) in enumerate(zip(g["coeff_updates"], e["coeff_updates"])) if a != b]
+    if bad:
+        i = bad[0]
+        return (f"{head}; every decision equal, {len(bad)} coefficient probabilities differ, first index {i} "
+                f"(type {i // 264}, band {i // 33 % 8}, ctx {i // 11 % 3}, node {i % 11}): "
+                f"{g['coeff_updates'][i]}, expected {e['coeff_updates'][i]} (-1: not updated)")
+    return f"{head}; every decision and probability equal: the tokens differ (first partition {g['first_part_size']} bytes, " \
+           f"expected {e['first_part_size']})"
