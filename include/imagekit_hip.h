@@ -430,6 +430,45 @@ int ik_vp8_analyze_device(const uint8_t *dev_yuv, size_t yuv_stride, uint32_t n,
  * outs[i] / out_lens[i] receive each file (library-allocated, ik_buf_free). */
 int ik_webp_encode_exact_device(const uint8_t *dev_yuv, size_t yuv_stride, uint32_t n, uint32_t w, uint32_t h,
                                 int quality, uint8_t **outs, size_t *out_lens);
+/* the exact WebP coder over images of mixed sizes and qualities, in one set of launches:
+ * item i is w x h device YUV420 planes (the ik_webp_yuv420_device layout) at dev_yuv,
+ * anywhere in device memory, coded at its own quality (clamped to [1,100]).  Every file is
+ * the one ik_webp_encode_exact_device writes for that image alone.  w, h <= 16383 and
+ * n <= 65535; a bad item (a zero or oversized side, a null plane) is IK_ERR_INVALID
+ * before anything is launched, with outs untouched.  Items that all share one geometry
+ * and quality go through the uniform call (one geometry never takes two code paths).
+ * outs[i] / out_lens[i] as above: every file is allocated, or on a failure none is. */
+typedef struct {
+    const uint8_t *dev_yuv;
+    uint32_t w, h;
+    int quality;
+} ik_webp_exact_item;
+int ik_webp_encode_exact_items(const ik_webp_exact_item *items, uint32_t n, uint8_t **outs, size_t *out_lens);
+/* the ticket table of that call for n images of w[i] x h[i] pixels (no GPU needed), in
+ * the kernel's format: bit 63 = an epoch's statistics fold, bits 48..55 the image's
+ * epoch, bits 32..47 the image, bits 0..31 the macroblock (raster index in its image).
+ * Each image keeps the single-image order (epochs at libwebp's probability refreshes,
+ * macroblocks by diagonal mb_x + 2 mb_y, then the epoch's fold); the images are merged
+ * step by step (a step = one diagonal or one fold of an image).  Returns the ticket
+ * count and writes the first min(count, cap) tickets to tasks (may be NULL when cap is
+ * 0) and the launch's workgroup count to *grid (may be NULL); -1 on a bad argument. */
+long long ik_webp_exact_plan(const uint32_t *w, const uint32_t *h, uint32_t n, uint64_t *tasks, size_t cap,
+                             uint32_t *grid);
+/* where ik_transform_batch codes the WebP requests that form no same-geometry group the
+ * uniform exact call takes (encoder IK_WEBP_AUTO or IK_WEBP_EXACT):
+ * IK_WEBP_MIXED_HOST (the default): as before -- libwebp on host threads under AUTO, the
+ *   exact coder image by image under EXACT;
+ * IK_WEBP_MIXED_GPU: when a batch holds enough of them (32, provisional), all of them
+ *   through one batched colour launch and one mixed exact call (ik_webp_encode_exact_items'
+ *   path); the same files either way.
+ * ik_set_webp_mixed(-1) returns to the environment: IK_WEBP_MIXED=host|gpu, read per batch. */
+typedef enum { IK_WEBP_MIXED_HOST = 0, IK_WEBP_MIXED_GPU = 1 } ik_webp_mixed;
+int ik_set_webp_mixed(int where);
+int ik_get_webp_mixed(void);
+/* process-wide WebP encode counters: out[0] = images coded by the uniform exact call,
+ * out[1] = images coded by the mixed exact call, out[2] = images coded by libwebp on
+ * the host, out[3] = mixed exact calls made */
+int ik_webp_enc_counters(unsigned long long *out);
 /* the JPEG front end (to_rgb8 + RGB->YCbCr + FDCT + quantise) on the device:
  * int16 coefficients, MCU-major, Y/Cb/Cr, natural order */
 int ik_jpeg_coeffs_device(const uint8_t *dev_src, uint32_t w, uint32_t h, uint32_t C,

@@ -171,6 +171,7 @@ int webp_encode_yuv420(const uint8_t* y, const uint8_t* u, const uint8_t* v, int
     api.writer_clear(wrt);
     api.picture_free(pic);  // planes are ours: memory_ is NULL, nothing of ours is freed
     if (!ok) return fail(IK_ERR_TRANSFORM, "WebPEncode failed (error %d)", code);
+    webp_enc_count(2, 1);
     return IK_OK;
 }
 

@@ -84,7 +84,7 @@ struct ThreadRes {
     std::map<int, hipEvent_t> prio_events;
     std::map<int, std::array<hipEvent_t, 2>> fork_join;  // per device: an event records only on its own device's streams
     std::map<std::pair<int, int>, Arena> dev;  // (device, slot)
-    Arena pinned[11];
+    Arena pinned[12];
     void release() {
         for (auto& kv : streams) (void)hipStreamSynchronize(kv.second);
         for (auto& kv : copy_streams) (void)hipStreamSynchronize(kv.second);
@@ -1109,6 +1109,50 @@ static int webp_exact_group(const std::vector<ik_image*>& imgs, int quality, std
     return IK_OK;
 }
 
+// The exact coder for a batch's WebP requests of mixed sizes and qualities
+// (IK_WEBP_MIXED_GPU): one colour launch over a table of the images into device
+// memory, then all of them through one webp_encode_exact_mixed call -- the files are
+// final, no host coder runs.  8-bit images of at most 16383 x 16383 on one device.
+static int webp_exact_mixed_group(const std::vector<ik_image*>& imgs, const std::vector<int>& quality,
+                                  std::vector<std::vector<uint8_t>*>& outs) {
+    const size_t n = imgs.size();
+    DeviceGuard g(imgs[0]->device);
+    const DeviceConsts* dc = device_consts(current_device());
+    if (!dc) return fail(IK_ERR_DEVICE, "cannot upload WebP tables");
+    hipStream_t s = thread_stream();
+    if (!s) return fail(IK_ERR_DEVICE, "cannot create HIP stream");
+    std::vector<size_t> at(n);
+    size_t total = 0;
+    int max_w = 0, max_h = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const size_t w = imgs[i]->w, h = imgs[i]->h;
+        at[i] = total;
+        total += ((w * h + 2 * ((w + 1) / 2) * ((h + 1) / 2)) + 255) & ~size_t(255);
+        max_w = std::max(max_w, (int)w);
+        max_h = std::max(max_h, (int)h);
+    }
+    uint8_t* dyuv = scratch_slot(kScratchMixedPlanes, total + sizeof(WebpYuvItem) * n);
+    WebpYuvItem* htab = reinterpret_cast<WebpYuvItem*>(pinned_slot(kPinnedMixedTab, sizeof(WebpYuvItem) * n));
+    if (!dyuv || !htab) return fail(IK_ERR_DEVICE, "cannot allocate the mixed WebP planes");
+    (void)hipStreamSynchronize(s);  // nothing pending reads the pinned table
+    std::vector<ExactItem> items(n);
+    for (size_t i = 0; i < n; ++i) {
+        htab[i] = WebpYuvItem{imgs[i]->d, dyuv + at[i], imgs[i]->pitch, (int32_t)imgs[i]->w, (int32_t)imgs[i]->h,
+                              (int32_t)imgs[i]->c, 0};
+        const int q = quality[i];
+        items[i] = ExactItem{dyuv + at[i], (int)imgs[i]->w, (int)imgs[i]->h, q < 1 ? 1 : (q > 100 ? 100 : q)};
+    }
+    WebpYuvItem* dtab = reinterpret_cast<WebpYuvItem*>(dyuv + total);
+    hipError_t e = hipMemcpyAsync(dtab, htab, sizeof(WebpYuvItem) * n, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = launch_webp_yuv420_items(dtab, (int)n, max_w, max_h, dc->gamma_to_lin, dc->lin_to_gamma, s);
+    if (e != hipSuccess) return hip_fail(e, "webp yuv420 (mixed group)");
+    std::vector<std::vector<uint8_t>> files;
+    if (int rc = webp_encode_exact_mixed(items.data(), (int)n, files)) return rc;
+    for (size_t i = 0; i < n; ++i) outs[i]->swap(files[i]);
+    return IK_OK;
+}
+
 int webp_front_group(const std::vector<ik_image*>& imgs, int quality, std::vector<EncodePrep*>& prep) {
     const size_t n = imgs.size();
     if (!n) return IK_OK;
@@ -1654,6 +1698,10 @@ static void transform_decode_phase(const uint8_t* const* bytes, const size_t* le
 
 // IK_WEBP_AUTO: smallest same-geometry group that the exact GPU coder takes
 constexpr size_t kAutoExactMinGroup = 32;
+// IK_WEBP_MIXED_GPU: fewest WebP requests outside those groups that one mixed exact call
+// takes (provisional: the uniform rule's figure, until the two are measured against each
+// other -- profiles/webp_mixed_notes.md)
+constexpr size_t kAutoMixedMin = 32;
 
 // Device half, post stage: resize, the encoders' device front ends (under the
 // post gate, so a batch's resize runs beside the next batch's decode kernels);
@@ -1683,6 +1731,19 @@ static void transform_post_phase(const int64_t* w, const int64_t* h, const int* 
     // one launch (resize_group); the rest, image by image below
     std::vector<ik_image*> rsz(m, nullptr);
     std::vector<char> fronted(m, 0);  // encode front end already run (batched WebP colour conversion)
+    // IK_WEBP_MIXED_GPU (read once for the batch): the WebP requests that no uniform exact
+    // group takes keep their resized image (kept[k]) and are coded together below, when
+    // the batch can hold kAutoMixedMin of them at all; at IK_WEBP_MIXED_HOST nothing is kept
+    std::vector<ik_image*> kept(m, nullptr);
+    bool mixed = false;
+    size_t mixed_min = kAutoMixedMin;  // (EXACT: any two, as its uniform groups)
+    if (webp_mixed_mode() == IK_WEBP_MIXED_GPU && default_webp_encoder() != IK_WEBP_LIBWEBP) {
+        if (default_webp_encoder() == IK_WEBP_EXACT) mixed_min = 2;
+        size_t cand = 0;
+        for (uint32_t k = 0; k < m; ++k)
+            cand += !ds[k] && imgs[k] && imgs[k]->depth == 1 && fmt[idx[k]] == IK_FORMAT_WEBP;
+        mixed = cand >= mixed_min;
+    }
     {
         std::map<std::tuple<uint32_t, uint32_t, uint32_t, size_t, int, uint32_t, uint32_t>, std::vector<uint32_t>> groups;
         for (uint32_t k = 0; k < m; ++k) {
@@ -1731,6 +1792,7 @@ static void transform_post_phase(const int64_t* w, const int64_t* h, const int* 
                         }
                     continue;
                 }
+                if (mixed) continue;  // with the batch's other WebP requests, below
                 if (webp_front_group(im, qv.first, pp) == IK_OK)
                     for (uint32_t k : qv.second) fronted[k] = 1;
             }
@@ -1756,7 +1818,11 @@ static void transform_post_phase(const int64_t* w, const int64_t* h, const int* 
         const auto t0 = std::chrono::steady_clock::now();
         int r = rs ? IK_OK : ik_resize(imgs[k], w[i], h[i], filter, &rs);
         const auto t1 = std::chrono::steady_clock::now();
-        if (!r && !fronted[k]) r = encode_image_front(rs, fmt[i], quality[i], prep[k], bytes_out[k]);
+        if (!r && !fronted[k] && mixed && fmt[i] == IK_FORMAT_WEBP && rs->depth == 1 && rs->w && rs->h &&
+            rs->w <= 16383 && rs->h <= 16383) {
+            (void)hipStreamSynchronize(thread_stream());  // this thread's resize is done: another's stream reads it
+            kept[k] = rs;
+        } else if (!r && !fronted[k]) r = encode_image_front(rs, fmt[i], quality[i], prep[k], bytes_out[k]);
         if (timing) {
             const auto t2 = std::chrono::steady_clock::now();
             std::lock_guard<std::mutex> lk(tmu);
@@ -1764,10 +1830,40 @@ static void transform_post_phase(const int64_t* w, const int64_t* h, const int* 
             t_front += std::chrono::duration<double, std::milli>(t2 - t1).count();
         }
         if (r) { errs[i] = last_error_str(); st[i] = r; prep[k].done = true; }
-        if (rs && rs != imgs[k]) ik_image_free(rs);
-        ik_image_free(imgs[k]);
+        if (rs && rs != imgs[k] && rs != kept[k]) ik_image_free(rs);
+        if (imgs[k] != kept[k]) ik_image_free(imgs[k]);
         imgs[k] = nullptr;
     });
+    if (mixed) {
+        // one colour launch and one mixed exact call for the kept requests; fewer than
+        // the minimum of them (the uniform groups took the rest), or a failed call: the
+        // existing front end, image by image
+        std::vector<uint32_t> ks;
+        for (uint32_t k = 0; k < m; ++k)
+            if (kept[k]) ks.push_back(k);
+        bool coded = false;
+        if (ks.size() >= mixed_min) {
+            std::vector<ik_image*> im;
+            std::vector<int> qs;
+            std::vector<std::vector<uint8_t>*> oo;
+            for (uint32_t k : ks) { im.push_back(kept[k]); qs.push_back(quality[idx[k]]); oo.push_back(&bytes_out[k]); }
+            const auto t0 = std::chrono::steady_clock::now();
+            coded = webp_exact_mixed_group(im, qs, oo) == IK_OK;
+            t_front += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+        parallel_for((int)ks.size(), threads, [&](int j) {
+            const uint32_t k = ks[(size_t)j], i = idx[k];
+            if (coded) {
+                prep[k].fmt = IK_FORMAT_WEBP;
+                prep[k].done = true;  // the files are final: no host coder
+            } else if (int r = encode_image_front(kept[k], fmt[i], quality[i], prep[k], bytes_out[k])) {
+                errs[i] = last_error_str();
+                st[i] = r;
+                prep[k].done = true;
+            }
+            ik_image_free(kept[k]);
+        });
+    }
     batch_timing_commit(current_device(), true);
     gate_pin(kGatePost, false);
     std::vector<ik_image*>().swap(hp.imgs);

@@ -108,6 +108,16 @@ hipError_t launch_webp_yuv420(const uint8_t* src, int w, int h, int C, size_t pi
                               size_t yuv_img_stride, int n, const uint16_t* gamma_to_lin,
                               const int* lin_to_gamma, hipStream_t s,
                               const uint64_t* src_tab = nullptr /* per-image bases instead of img_stride */);
+// the same conversion over n images of different sizes in one launch: a device table of
+// these (grid.z = image; max_w / max_h: the largest of the table's sizes)
+struct WebpYuvItem {
+    const uint8_t* src;  // pixels, rows pitch bytes apart
+    uint8_t* yuv;        // Y, U, V planes back to back
+    size_t pitch;
+    int32_t w, h, C, pad;
+};
+hipError_t launch_webp_yuv420_items(const WebpYuvItem* items, int n, int max_w, int max_h,
+                                    const uint16_t* gamma_to_lin, const int* lin_to_gamma, hipStream_t s);
 // n images; planes (Y, U, V, A: w*h each) plane_img_stride apart; transparent[n]
 // zeroed here, then set to 1 for every image with an alpha < 255
 hipError_t launch_avif_yuv444(const uint8_t* src, int w, int h, int C, size_t pitch, size_t img_stride,

@@ -734,13 +734,10 @@ __device__ __forceinline__ int lin_to_gamma(const int* __restrict__ tab, uint32_
     return (y + 64) >> 7;
 }
 
-__global__ __launch_bounds__(kThreads) void k_webp_yuv420(const uint8_t* __restrict__ src, int w,
-                                                          int h, int C, size_t pitch,
-                                                          size_t img_stride, uint8_t* __restrict__ Y,
-                                                          size_t yuv_img_stride,
-                                                          const uint16_t* __restrict__ g2l,
-                                                          const int* __restrict__ l2g,
-                                                          const uint64_t* __restrict__ src_tab) {
+// one image's planes: base its pixels, y_img its Y plane (U and V follow)
+__device__ __forceinline__ void webp_yuv420_image(const uint8_t* __restrict__ base, int w, int h, int C, size_t pitch,
+                                                  uint8_t* __restrict__ y_img, const uint16_t* __restrict__ g2l,
+                                                  const int* __restrict__ l2g) {
     __shared__ uint16_t s_g2l[256];
     __shared__ int s_l2g[33];
     for (int t = threadIdx.x; t < 256; t += kThreads) s_g2l[t] = g2l[t];
@@ -749,11 +746,7 @@ __global__ __launch_bounds__(kThreads) void k_webp_yuv420(const uint8_t* __restr
     const int uvw = (w + 1) >> 1, uvh = (h + 1) >> 1;
     const int cx = blockIdx.x * 64 + (threadIdx.x & 63);
     const int cy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    const int img = blockIdx.z;
     if (cx >= uvw || cy >= uvh) return;
-    const uint8_t* __restrict__ base =
-        src_tab ? reinterpret_cast<const uint8_t*>(src_tab[img]) : src + (size_t)img * img_stride;
-    uint8_t* __restrict__ y_img = Y + (size_t)img * yuv_img_stride;
     uint8_t* __restrict__ u_img = y_img + (size_t)w * h;
     uint8_t* __restrict__ v_img = u_img + (size_t)uvw * uvh;
     const int x0 = 2 * cx, y0 = 2 * cy;
@@ -791,6 +784,37 @@ __global__ __launch_bounds__(kThreads) void k_webp_yuv420(const uint8_t* __restr
     }
     u_img[(size_t)cy * uvw + cx] = (uint8_t)webp_clip_uv(-9719 * sum[0] - 19081 * sum[1] + 28800 * sum[2]);
     v_img[(size_t)cy * uvw + cx] = (uint8_t)webp_clip_uv(28800 * sum[0] - 24116 * sum[1] - 4684 * sum[2]);
+}
+
+__global__ __launch_bounds__(kThreads) void k_webp_yuv420(const uint8_t* __restrict__ src, int w,
+                                                          int h, int C, size_t pitch,
+                                                          size_t img_stride, uint8_t* __restrict__ Y,
+                                                          size_t yuv_img_stride,
+                                                          const uint16_t* __restrict__ g2l,
+                                                          const int* __restrict__ l2g,
+                                                          const uint64_t* __restrict__ src_tab) {
+    const int img = blockIdx.z;
+    const uint8_t* __restrict__ base =
+        src_tab ? reinterpret_cast<const uint8_t*>(src_tab[img]) : src + (size_t)img * img_stride;
+    webp_yuv420_image(base, w, h, C, pitch, Y + (size_t)img * yuv_img_stride, g2l, l2g);
+}
+
+// images of different sizes in one launch (grid.z = image): size, channels, pitch, source
+// and planes per image from a table; a thread past its own image's extent leaves
+__global__ __launch_bounds__(kThreads) void k_webp_yuv420_items(const WebpYuvItem* __restrict__ items,
+                                                                const uint16_t* __restrict__ g2l,
+                                                                const int* __restrict__ l2g) {
+    const WebpYuvItem& it = items[blockIdx.z];
+    webp_yuv420_image(it.src, it.w, it.h, it.C, it.pitch, it.yuv, g2l, l2g);
+}
+
+hipError_t launch_webp_yuv420_items(const WebpYuvItem* items, int n, int max_w, int max_h,
+                                    const uint16_t* gamma_to_lin, const int* lin_to_gamma_tab, hipStream_t s) {
+    if (n < 1 || n > 65535 || max_w < 1 || max_h < 1) return hipErrorInvalidValue;
+    const int uvw = (max_w + 1) >> 1, uvh = (max_h + 1) >> 1;
+    dim3 grid((uvw + 63) / 64, (uvh + 3) / 4, n);
+    hipLaunchKernelGGL(k_webp_yuv420_items, grid, dim3(kThreads), 0, s, items, gamma_to_lin, lin_to_gamma_tab);
+    return hipGetLastError();
 }
 
 hipError_t launch_webp_yuv420(const uint8_t* src, int w, int h, int C, size_t pitch,

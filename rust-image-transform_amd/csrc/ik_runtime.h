@@ -197,9 +197,12 @@ uint8_t* scratch(size_t bytes);  // per-thread device scratch, valid until the n
 // per-thread, per-device grow-only device arenas for batch work (slot 1: JPEG
 // batch decode, slot 2: PNG batch decode); valid until the next call with that slot
 uint8_t* scratch_slot(int slot, size_t bytes);
-uint8_t* pinned_slot(int slot, size_t bytes);  // per-thread grow-only pinned host arenas (slots 0..10)
+uint8_t* pinned_slot(int slot, size_t bytes);  // per-thread grow-only pinned host arenas (slots 0..11)
 // the exact WebP coder's arenas: its device work area; its constants in, its records out
 constexpr int kScratchExact = 8, kPinnedExactIn = 8, kPinnedExactOut = 9;
+// the mixed exact call's: same-geometry planes gathered a common stride apart; a batch's
+// planes and colour-conversion table (device) and that table's staging (pinned)
+constexpr int kScratchExactGather = 10, kScratchMixedPlanes = 11, kPinnedMixedTab = 11;
 // the WebP (VP8) decoder's: its device work area and its staged file + headers
 constexpr int kScratchVp8d = 9, kPinnedVp8d = 10;
 int copy_h2d_2d(uint8_t* dst, size_t dpitch, const uint8_t* src, size_t spitch, size_t width,
@@ -237,6 +240,19 @@ int default_webp_encoder();
 // the exact coder (ik_vp8x_host.cpp): libwebp's files from n device YUV420 images
 int webp_encode_exact(const uint8_t* d_yuv, size_t yuv_stride, int n, int w, int h, int quality,
                       std::vector<std::vector<uint8_t>>& outs);
+// the same over images of mixed sizes and qualities (device planes anywhere), in one set
+// of launches; items that share one geometry and quality go through webp_encode_exact
+struct ExactItem {
+    const uint8_t* yuv;
+    int w, h, quality;
+};
+int webp_encode_exact_mixed(const ExactItem* items, int n, std::vector<std::vector<uint8_t>>& outs);
+// where a batch's WebP requests outside the uniform groups are coded (ik_set_webp_mixed /
+// IK_WEBP_MIXED, read per batch): IK_WEBP_MIXED_HOST or IK_WEBP_MIXED_GPU
+int webp_mixed_mode();
+// ik_webp_enc_counters: 0 = images by the uniform exact call, 1 = by the mixed exact
+// call, 2 = by libwebp on the host, 3 = mixed calls
+void webp_enc_count(int which, unsigned long long n);
 // its first stages alone (ik_vp8_analyze_device): segment analysis and set-up on the
 // device, the segment map and headers into host memory
 int vp8_analyze_setup(const uint8_t* d_yuv, size_t yuv_stride, int n, int w, int h, float quality, uint8_t* seg,

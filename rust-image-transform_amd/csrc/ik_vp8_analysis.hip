@@ -58,17 +58,16 @@ __device__ __forceinline__ void ftransform4(const int* d, int* out) {
 }  // namespace
 
 // Per MB: alpha[] (final mixed susceptibility, 0..255) and uva[] (best chroma
-// alpha, unclipped, as MBAnalyze accumulates it).
-__global__ __launch_bounds__(64) void k_vp8_analyze(const uint8_t* __restrict__ yuv, size_t yuv_stride, int w,
-                                                    int h, int mb_w, int mb_h, uint8_t* __restrict__ alpha,
-                                                    uint16_t* __restrict__ uva) {
+// alpha, unclipped, as MBAnalyze accumulates it).  One MB of the image whose planes
+// start at Y; o: the MB's index in alpha[] / uva[].
+__device__ __forceinline__ void analyze_mb(const uint8_t* __restrict__ Y, int w, int h, int mb_w, int mb, size_t o,
+                                           uint8_t* __restrict__ alpha, uint16_t* __restrict__ uva) {
     __shared__ uint8_t s_src[3][16][16];  // Y 16x16; U, V 8x8 (in the first 8 rows / columns)
     __shared__ int s_left[3][16], s_top[3][16], s_tl[3];
     __shared__ int s_hist[4][32];  // luma DC, luma TM, chroma DC, chroma TM
-    const int mb = blockIdx.x, img = blockIdx.y, l = threadIdx.x;
+    const int l = threadIdx.x;
     const int mx = mb % mb_w, my = mb / mb_w;
     const int uw = (w + 1) >> 1, uh = (h + 1) >> 1;
-    const uint8_t* Y = yuv + (size_t)img * yuv_stride;
     const uint8_t* U = Y + (size_t)w * h;
     const uint8_t* V = U + (size_t)uw * uh;
     // stage: 256 + 2 x 64 source samples (6 per lane), the neighbours (clamped
@@ -160,21 +159,36 @@ __global__ __launch_bounds__(64) void k_vp8_analyze(const uint8_t* __restrict__ 
     if (l == 0) {
         const int a16 = max(s_hist[0][0], s_hist[1][0]), auv = max(s_hist[2][0], s_hist[3][0]);
         const int mixed = (3 * a16 + auv + 2) >> 2;
-        const size_t o = (size_t)img * mb_w * mb_h + mb;
         alpha[o] = (uint8_t)clampi(255 - mixed, 0, 255);
         uva[o] = (uint16_t)auv;
     }
 }
 
-// One workgroup per image: AssignSegments' k-means (analysis_enc.c).
-__global__ __launch_bounds__(256) void k_vp8_kmeans(const uint8_t* __restrict__ alpha, const uint16_t* __restrict__ uva,
-                                                    int nmb, uint8_t* __restrict__ seg, SegRecord* __restrict__ rec) {
+__global__ __launch_bounds__(64) void k_vp8_analyze(const uint8_t* __restrict__ yuv, size_t yuv_stride, int w,
+                                                    int h, int mb_w, int mb_h, uint8_t* __restrict__ alpha,
+                                                    uint16_t* __restrict__ uva) {
+    const int mb = blockIdx.x, img = blockIdx.y;
+    analyze_mb(yuv + (size_t)img * yuv_stride, w, h, mb_w, mb, (size_t)img * mb_w * mb_h + mb, alpha, uva);
+}
+
+// images of different sizes: grid.x runs to the largest image's MB count, a workgroup
+// past its own image's leaves at once (before any barrier)
+__global__ __launch_bounds__(64) void k_vp8_analyze_mixed(const ImgDesc* __restrict__ imgs, uint8_t* __restrict__ alpha,
+                                                          uint16_t* __restrict__ uva) {
+    const ImgDesc& d = imgs[blockIdx.y];
+    const int mb = blockIdx.x;
+    if (mb >= d.mb_w * d.mb_h) return;
+    analyze_mb(d.yuv, d.w, d.h, d.mb_w, mb, (size_t)d.mb0 + mb, alpha, uva);
+}
+
+// One workgroup per image: AssignSegments' k-means (analysis_enc.c).  A / UV / seg: the
+// image's nmb entries.
+__device__ __forceinline__ void kmeans_image(const uint8_t* __restrict__ A, const uint16_t* __restrict__ UV, int nmb,
+                                             uint8_t* __restrict__ seg, SegRecord* __restrict__ rec) {
     __shared__ int s_h[256];
     __shared__ int s_map[256];
     __shared__ unsigned long long s_sum[2][256];
-    const int img = blockIdx.x, t = threadIdx.x;
-    const uint8_t* A = alpha + (size_t)img * nmb;
-    const uint16_t* UV = uva + (size_t)img * nmb;
+    const int t = threadIdx.x;
     s_h[t] = 0;
     s_map[t] = 0;
     __syncthreads();
@@ -233,10 +247,24 @@ __global__ __launch_bounds__(256) void k_vp8_kmeans(const uint8_t* __restrict__ 
         r.nmb = nmb;
         r.alpha_sum = ta;
         r.uv_alpha_sum = tu;
-        rec[img] = r;
+        *rec = r;
     }
     __syncthreads();
-    for (int i = t; i < nmb; i += 256) seg[(size_t)img * nmb + i] = (uint8_t)s_map[A[i]];
+    for (int i = t; i < nmb; i += 256) seg[i] = (uint8_t)s_map[A[i]];
+}
+
+__global__ __launch_bounds__(256) void k_vp8_kmeans(const uint8_t* __restrict__ alpha, const uint16_t* __restrict__ uva,
+                                                    int nmb, uint8_t* __restrict__ seg, SegRecord* __restrict__ rec) {
+    const size_t o = (size_t)blockIdx.x * nmb;
+    kmeans_image(alpha + o, uva + o, nmb, seg + o, rec + blockIdx.x);
+}
+
+__global__ __launch_bounds__(256) void k_vp8_kmeans_mixed(const ImgDesc* __restrict__ imgs,
+                                                          const uint8_t* __restrict__ alpha,
+                                                          const uint16_t* __restrict__ uva, uint8_t* __restrict__ seg,
+                                                          SegRecord* __restrict__ rec) {
+    const ImgDesc& d = imgs[blockIdx.x];
+    kmeans_image(alpha + d.mb0, uva + d.mb0, d.mb_w * d.mb_h, seg + d.mb0, rec + blockIdx.x);
 }
 
 hipError_t launch_vp8_analysis(const uint8_t* yuv, size_t yuv_stride, int n, int w, int h, uint8_t* alpha,
@@ -245,6 +273,14 @@ hipError_t launch_vp8_analysis(const uint8_t* yuv, size_t yuv_stride, int n, int
     if (n < 1 || nmb < 1 || n > 65535) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_vp8_analyze, dim3(nmb, n), dim3(64), 0, s, yuv, yuv_stride, w, h, mb_w, mb_h, alpha, uva);
     hipLaunchKernelGGL(k_vp8_kmeans, dim3(n), dim3(256), 0, s, alpha, uva, nmb, seg, rec);
+    return hipGetLastError();
+}
+
+hipError_t launch_vp8_analysis_mixed(const ImgDesc* imgs, int n, int max_nmb, uint8_t* alpha, uint16_t* uva,
+                                     uint8_t* seg, SegRecord* rec, hipStream_t s) {
+    if (n < 1 || max_nmb < 1 || n > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_vp8_analyze_mixed, dim3(max_nmb, n), dim3(64), 0, s, imgs, alpha, uva);
+    hipLaunchKernelGGL(k_vp8_kmeans_mixed, dim3(n), dim3(256), 0, s, imgs, alpha, uva, seg, rec);
     return hipGetLastError();
 }
 

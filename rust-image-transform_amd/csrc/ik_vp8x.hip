@@ -22,6 +22,11 @@
 // drains whatever the residency; every wait is bounded (a timeout sets the error word
 // and the grid drains).
 //
+// k_vp8x_run_mixed is the same loop over images of different sizes and qualities: a task
+// takes its image's geometry, epoch bounds and array bases from a descriptor table
+// (ik_vp8_gpu.h ImgDesc), and the tickets are the images' own orders merged step by step
+// (ik_vp8x_host.cpp), which keeps every dependency on a smaller ticket.
+//
 // Hand-offs (MI355X_MICROARCH.md, inter-workgroup visibility, recipe R1): the payload
 // -- an MB's edge record (XEdge) and decision record (XMB), a fold's statistics,
 // probabilities and level costs -- is stored write-through (sc1, 16-byte stores),
@@ -1053,11 +1058,36 @@ __device__ bool poll_ge(const uint32_t* f, uint32_t want, uint32_t* err, uint64_
     }
 }
 
+// The image of a mixed call's task as the MB and fold bodies see it: the call's arrays
+// moved to the image's own parts, its planes and geometry from its descriptor -- the
+// bodies then run it as image 0 of a call of one.  All wave-uniform.
+__device__ __forceinline__ XArgs image_args(const XArgs& a, const XImg& d, int img) {
+    XArgs b = a;
+    b.yuv = d.yuv;
+    b.yuv_stride = 0;
+    b.w = d.w;
+    b.h = d.h;
+    b.mb_w = d.mb_w;
+    b.mb_h = d.mb_h;
+    b.mbs = a.mbs + d.mb0;
+    b.edges = a.edges + d.mb0;
+    b.seg = a.seg + d.mb0;
+    b.segs = a.segs + (size_t)img * 4;
+    b.lc = a.lc + (size_t)img * kCostRows * kLevelTab;
+    b.pr = a.pr + (size_t)img * 1056;
+    b.stats = a.stats + (size_t)img * 1056;
+    b.max_edge = a.max_edge + (size_t)img * 4;
+    b.use_derr = d.use_derr;
+    return b;
+}
+
 // The whole call's decisions and statistics folds, one launch (see the file header).
-__global__ __launch_bounds__(kNT) void k_vp8x_run(XArgs a, XRun r) {
-    __shared__ XLds S;
-    __shared__ uint64_t s_task;
-    __shared__ int s_ok;
+// MIXED: the images differ in size and quality; a task takes its image's geometry,
+// epoch bounds and array bases from the descriptor table instead of the call's XArgs
+// (k_vp8x_run_mixed).  The uniform instantiation is k_vp8x_run as it always was.
+template <bool MIXED>
+__device__ __forceinline__ void run_tasks(const XArgs& a, const XRun& r, const XImg* __restrict__ imgs, XLds& S,
+                                          uint64_t& s_task, int& s_ok) {
 #ifndef IK_VP8X_STAMPS
     // gfx950 allocates LDS in units of 1,280 B, 128 to a CU: at 24 units this workgroup
     // shares a CU with 8 workgroups of the PNG wave decoder (ik_png.hip: 13 each)
@@ -1089,7 +1119,20 @@ __global__ __launch_bounds__(kNT) void k_vp8x_run(XArgs a, XRun r) {
                 const int mb = (int)(uint32_t)task;
                 // 4 s per wait (s_memrealtime counts at 100 MHz); a call takes tens of ms
                 const uint64_t t_end = __builtin_amdgcn_s_memrealtime() + 400000000ull;
-                if (task >> 63) {  // the fold of epoch e: its MBs decided, the previous fold's statistics in place
+                if constexpr (MIXED) {  // the same waits on the image's own bounds, geometry and words
+                    const XImg& d = imgs[img];
+                    const int* bounds = r.bounds + d.bnd0;
+                    if (task >> 63) {
+                        ok = poll_ge(r.cnt + d.ep0 + e, (uint32_t)(bounds[e + 1] - bounds[e]), err, t_end);
+                        if (ok && e > 0) ok = poll_ge(r.ready + d.ep0 + e, 1u, err, t_end);
+                    } else {
+                        const int mx = mb % d.mb_w, my = mb / d.mb_w;
+                        const uint32_t* done = r.done + d.mb0;
+                        if (e > 0) ok = poll_ge(r.ready + d.ep0 + e, 1u, err, t_end);
+                        if (ok && mx > 0) ok = poll_ge(done + mb - 1, 1u, err, t_end);
+                        if (ok && my > 0) ok = poll_ge(done + mb - d.mb_w + (mx < d.mb_w - 1 ? 1 : 0), 1u, err, t_end);
+                    }
+                } else if (task >> 63) {  // the fold of epoch e: its MBs decided, the previous fold's statistics in place
                     ok = poll_ge(r.cnt + (size_t)img * r.nep + e, (uint32_t)(r.bounds[e + 1] - r.bounds[e]), err, t_end);
                     if (ok && e > 0) ok = poll_ge(r.ready + (size_t)img * r.nep + e, 1u, err, t_end);
                 } else {  // an MB: its epoch's level costs, its left and top-right (or top) neighbours
@@ -1127,13 +1170,31 @@ __global__ __launch_bounds__(kNT) void k_vp8x_run(XArgs a, XRun r) {
         // lane-derived address of the MB body out of the task loop (255 VGPRs, not 98)
         int lt = threadIdx.x;
         asm volatile("" : "+v"(lt));
-        if (task >> 63) fold_body(a, img, r.bounds[e], r.bounds[e + 1], S.f, lt);
-        else mb_body(a, img, (int)(uint32_t)task, S.m, lt, stm);
+        if constexpr (MIXED) {
+            // (the table is written before the launch and only read here)
+            const XImg& d = imgs[img];
+            const XArgs ai = image_args(a, d, img);
+            const int* bounds = r.bounds + d.bnd0;
+            if (task >> 63) fold_body(ai, 0, bounds[e], bounds[e + 1], S.f, lt);
+            else mb_body(ai, 0, (int)(uint32_t)task, S.m, lt, stm);
+        } else {
+            if (task >> 63) fold_body(a, img, r.bounds[e], r.bounds[e + 1], S.f, lt);
+            else mb_body(a, img, (int)(uint32_t)task, S.m, lt, stm);
+        }
         // the payload's write-through stores have completed before the flag
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (l == 0) {
-            if (task >> 63) {
+            if constexpr (MIXED) {  // the image's own words
+                const XImg& d = imgs[img];
+                if (task >> 63) {
+                    if (e + 1 < (int)d.nep)
+                        __hip_atomic_store(r.ready + d.ep0 + e + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                } else {
+                    __hip_atomic_store(r.done + d.mb0 + (uint32_t)task, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_fetch_add(r.cnt + d.ep0 + e, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            } else if (task >> 63) {
                 if (e + 1 < (int)r.nep)
                     __hip_atomic_store(r.ready + (size_t)img * r.nep + e + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             } else {
@@ -1152,16 +1213,31 @@ __global__ __launch_bounds__(kNT) void k_vp8x_run(XArgs a, XRun r) {
     }
 }
 
+// (the LDS is declared in the kernels: the uniform one's layout is what it always was)
+__global__ __launch_bounds__(kNT) void k_vp8x_run(XArgs a, XRun r) {
+    __shared__ XLds S;
+    __shared__ uint64_t s_task;
+    __shared__ int s_ok;
+    run_tasks<false>(a, r, nullptr, S, s_task, s_ok);
+}
+
+__global__ __launch_bounds__(kNT) void k_vp8x_run_mixed(XArgs a, XRun r, const XImg* __restrict__ imgs) {
+    __shared__ XLds S;
+    __shared__ uint64_t s_task;
+    __shared__ int s_ok;
+    run_tasks<true>(a, r, imgs, S, s_task, s_ok);
+}
+
 // The segment set-up (libwebp VP8SetSegmentParams + SimplifySegments + the segment
 // map's tree probabilities; restated from the host's vp8_segment_setup) and the
 // initial coding state of every image: one wave per image.  qtab[s_alpha + 127] is
 // the segment quantiser for a segment alpha at this quality (libwebp's pow(), computed
-// on the host with the same libm).
-__global__ __launch_bounds__(64) void k_vp8x_setup(XArgs a, const vp8::SegRecord* recs, const uint8_t* kseg,
-                                                   const int* qtab, ik_vp8_segment_header* hdrs) {
+// on the host with the same libm).  nmb: the image's MBs, mb0: its first index in the
+// per-MB arrays.
+__device__ __forceinline__ void setup_image(const XArgs& a, int img, int nmb, size_t mb0, const vp8::SegRecord* recs,
+                                            const uint8_t* kseg, const int* qtab, ik_vp8_segment_header* hdrs) {
     constexpr int nb = 4, sns = 50, filter_strength = 60;
-    const int img = blockIdx.x, l = threadIdx.x;
-    const int nmb = a.mb_w * a.mb_h;
+    const int l = threadIdx.x;
     __shared__ int s_map[nb], s_cnt[nb], s_nfinal, s_reset;
     __shared__ ik_vp8_segment_header s_hd;
     auto clip = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
@@ -1212,8 +1288,8 @@ __global__ __launch_bounds__(64) void k_vp8x_setup(XArgs a, const vp8::SegRecord
     }
     __syncthreads();
     const int nfinal = s_nfinal;
-    uint8_t* seg = a.seg + (size_t)img * nmb;
-    const uint8_t* ks = kseg + (size_t)img * nmb;
+    uint8_t* seg = a.seg + mb0;
+    const uint8_t* ks = kseg + mb0;
     for (int i = l; i < nmb; i += 64) {
         const int v = nfinal < nb ? s_map[ks[i]] : ks[i];
         seg[i] = (uint8_t)v;
@@ -1244,6 +1320,21 @@ __global__ __launch_bounds__(64) void k_vp8x_setup(XArgs a, const vp8::SegRecord
     if (l < nb) a.max_edge[img * nb + l] = 0;
 }
 
+__global__ __launch_bounds__(64) void k_vp8x_setup(XArgs a, const vp8::SegRecord* recs, const uint8_t* kseg,
+                                                   const int* qtab, ik_vp8_segment_header* hdrs) {
+    const int img = blockIdx.x, nmb = a.mb_w * a.mb_h;
+    setup_image(a, img, nmb, (size_t)img * nmb, recs, kseg, qtab, hdrs);
+}
+
+// the mixed call's: the image's MB count, base and quantiser table from its descriptor
+__global__ __launch_bounds__(64) void k_vp8x_setup_mixed(XArgs a, const XImg* __restrict__ imgs,
+                                                         const vp8::SegRecord* recs, const uint8_t* kseg,
+                                                         const int* qtabs, ik_vp8_segment_header* hdrs) {
+    const int img = blockIdx.x;
+    const XImg& d = imgs[img];
+    setup_image(a, img, d.mb_w * d.mb_h, d.mb0, recs, kseg, qtabs + 255 * (size_t)d.qtab, hdrs);
+}
+
 hipError_t launch_vp8x_setup(const XArgs& a, const vp8::SegRecord* rec, const uint8_t* kseg, const int* qtab,
                              ik_vp8_segment_header* hdr, int n, hipStream_t s) {
     hipLaunchKernelGGL(k_vp8x_setup, dim3(n), dim3(64), 0, s, a, rec, kseg, qtab, hdr);
@@ -1253,6 +1344,18 @@ hipError_t launch_vp8x_setup(const XArgs& a, const vp8::SegRecord* rec, const ui
 hipError_t launch_vp8x_run(const XArgs& a, const XRun& r, int grid, hipStream_t s) {
     if (grid <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_vp8x_run, dim3(grid), dim3(kNT), 0, s, a, r);
+    return hipGetLastError();
+}
+
+hipError_t launch_vp8x_setup_mixed(const XArgs& a, const XImg* imgs, const vp8::SegRecord* rec, const uint8_t* kseg,
+                                   const int* qtabs, ik_vp8_segment_header* hdr, int n, hipStream_t s) {
+    hipLaunchKernelGGL(k_vp8x_setup_mixed, dim3(n), dim3(64), 0, s, a, imgs, rec, kseg, qtabs, hdr);
+    return hipGetLastError();
+}
+
+hipError_t launch_vp8x_run_mixed(const XArgs& a, const XRun& r, const XImg* imgs, int grid, hipStream_t s) {
+    if (grid <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_vp8x_run_mixed, dim3(grid), dim3(kNT), 0, s, a, r, imgs);
     return hipGetLastError();
 }
 

@@ -57,5 +57,16 @@ hipError_t launch_vp8x_setup(const XArgs& a, const vp8::SegRecord* rec, const ui
                              ik_vp8_segment_header* hdr, int n, hipStream_t s);
 hipError_t launch_vp8x_run(const XArgs& a, const XRun& r, int grid, hipStream_t s);
 
+// The mixed call (images of different sizes and qualities): a.yuv / a.w / a.h / a.mb_w /
+// a.mb_h / a.use_derr are unused, each image's come from its descriptor, with the
+// first index of its MBs in mbs / edges / seg / done (mb0), of its epochs in cnt /
+// ready (ep0) and in the concatenated bounds (bnd0); r.nep is unused.  A ticket's
+// epoch and MB fields count within its image.  qtabs: one 255-entry table per
+// distinct quality of the call.
+using XImg = vp8::ImgDesc;
+hipError_t launch_vp8x_setup_mixed(const XArgs& a, const XImg* imgs, const vp8::SegRecord* rec, const uint8_t* kseg,
+                                   const int* qtabs, ik_vp8_segment_header* hdr, int n, hipStream_t s);
+hipError_t launch_vp8x_run_mixed(const XArgs& a, const XRun& r, const XImg* imgs, int grid, hipStream_t s);
+
 }  // namespace vp8x
 }  // namespace ik

@@ -13,6 +13,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <map>
+#include <utility>
 #include <vector>
 
 #include "../../include/imagekit_hip.h"
@@ -219,30 +221,29 @@ void write_file(int w, int h, const XMB* mbs, const uint8_t* probas, const ik_vp
     std::memcpy(o + 30 + b0.buf.size(), b1.buf.data(), b1.buf.size());
 }
 
-// The call's schedule, cached per thread for its geometry: epochs at libwebp's
-// probability refreshes; tickets in (epoch, diagonal, image) order, each epoch's folds
-// after its MBs.  Diagonals are found by one counting pass per epoch.
-struct XSchedule {
-    int w = 0, h = 0, n = 0;
-    std::vector<int> bounds;
-    std::vector<uint64_t> tasks;
-    int grid = 0;
+// One geometry's ticket order, as steps: epochs at libwebp's probability refreshes
+// (M = max(nmb / 8, 96), bounds M, 2M+1, ...); inside an epoch the MBs by diagonal
+// mb_x + 2 mb_y (one counting pass per epoch), then the epoch's fold.  A step is one
+// diagonal that holds MBs, or one fold; every dependency of a ticket lies in an earlier
+// step.  Tickets carry the epoch and the MB, image 0.
+struct GeomSteps {
+    std::vector<int> bounds;        // nep + 1 raster bounds of the epochs
+    std::vector<uint64_t> tasks;    // the geometry's tickets in order
+    std::vector<uint32_t> step_lo;  // steps + 1: each step's first ticket, then the ticket count
 };
 
-const XSchedule& exact_schedule(int w, int h, int n) {
-    static thread_local XSchedule sc;
-    if (sc.w == w && sc.h == h && sc.n == n) return sc;
-    const int mb_w = (w + 15) / 16, mb_h = (h + 15) / 16, nmb = mb_w * mb_h;
+void build_geometry_steps(int mb_w, int mb_h, GeomSteps& g) {
+    const int nmb = mb_w * mb_h;
     const int M = (nmb >> 3) < 96 ? 96 : (nmb >> 3);
-    sc.bounds.assign(1, 0);
-    for (int k = M; k < nmb; k += M + 1) sc.bounds.push_back(k);
-    sc.bounds.push_back(nmb);
-    sc.tasks.clear();
-    sc.tasks.reserve((size_t)n * (nmb + sc.bounds.size()));
-    int widest = 1;
+    g.bounds.assign(1, 0);
+    for (int k = M; k < nmb; k += M + 1) g.bounds.push_back(k);
+    g.bounds.push_back(nmb);
+    g.tasks.clear();
+    g.tasks.reserve((size_t)nmb + g.bounds.size());
+    g.step_lo.clear();
     std::vector<int> first, list;
-    for (size_t e = 0; e + 1 < sc.bounds.size(); ++e) {
-        const int k0 = sc.bounds[e], k1 = sc.bounds[e + 1];
+    for (size_t e = 0; e + 1 < g.bounds.size(); ++e) {
+        const int k0 = g.bounds[e], k1 = g.bounds[e + 1];
         // (an epoch that starts mid-row holds MBs of smaller diagonals in its next row)
         int d0 = 1 << 30, d1 = -1;
         for (int k = k0; k < k1; ++k) {
@@ -258,18 +259,91 @@ const XSchedule& exact_schedule(int w, int h, int n) {
         const uint64_t ep = (uint64_t)e << 48;
         for (int d = 0; d <= d1 - d0; ++d) {
             const int a = first[(size_t)d], b = first[(size_t)d + 1];
-            widest = std::max(widest, (b - a) * n);
-            for (int i = 0; i < n; ++i)
-                for (int j = a; j < b; ++j) sc.tasks.push_back(ep | ((uint64_t)i << 32) | (uint32_t)list[(size_t)j]);
+            if (a == b) continue;  // (a diagonal between an epoch's two rows may hold none of its MBs)
+            g.step_lo.push_back((uint32_t)g.tasks.size());
+            for (int j = a; j < b; ++j) g.tasks.push_back(ep | (uint32_t)list[(size_t)j]);
         }
-        for (int i = 0; i < n; ++i) sc.tasks.push_back((1ull << 63) | ep | ((uint64_t)i << 32));
+        g.step_lo.push_back((uint32_t)g.tasks.size());
+        g.tasks.push_back((1ull << 63) | ep);
     }
-    // resident workgroups: the widest diagonal's MBs (every workgroup more would hold
-    // LDS and registers that another batch's decode kernels beside the coder lose)
-    // (IK_VP8X_GRID: a multiple of that, e.g. 0.5 -- dev A/B)
+    g.step_lo.push_back((uint32_t)g.tasks.size());
+}
+
+// the steps of a geometry, cached per thread (emptied by begin_schedule when it has
+// grown past kGeomCacheMax: references stay valid until the next begin_schedule)
+constexpr size_t kGeomCacheMax = 256;
+std::map<std::pair<int, int>, GeomSteps>& geometry_cache() {
+    static thread_local std::map<std::pair<int, int>, GeomSteps> cache;
+    return cache;
+}
+void begin_schedule() {
+    if (geometry_cache().size() > kGeomCacheMax) geometry_cache().clear();
+}
+const GeomSteps& geometry_steps(int w, int h) {
+    const int mb_w = (w + 15) / 16, mb_h = (h + 15) / 16;
+    auto it = geometry_cache().find({mb_w, mb_h});
+    if (it == geometry_cache().end()) {
+        it = geometry_cache().emplace(std::make_pair(mb_w, mb_h), GeomSteps()).first;
+        build_geometry_steps(mb_w, mb_h, it->second);
+    }
+    return it->second;
+}
+
+// The call's tickets: the images' steps merged step by step -- step 0 of every image
+// (in image order), then step 1 of every image, ...; an image out of steps adds nothing.
+// Each image keeps its own order, and a ticket's dependencies (earlier steps of its own
+// image) hold smaller tickets, so the lowest unfinished ticket can always run.  Returns
+// the widest merged step's ticket count.
+int merge_steps(const std::vector<const GeomSteps*>& g, std::vector<uint64_t>& tasks) {
+    size_t total = 0;
+    for (const GeomSteps* p : g) total += p->tasks.size();
+    tasks.clear();
+    tasks.reserve(total);
+    std::vector<uint32_t> live(g.size());
+    for (size_t i = 0; i < g.size(); ++i) live[i] = (uint32_t)i;
+    size_t widest = 1;
+    for (size_t step = 0; !live.empty(); ++step) {
+        const size_t at = tasks.size();
+        size_t keep = 0;
+        for (uint32_t i : live) {
+            const GeomSteps& s = *g[i];
+            if (step + 1 >= s.step_lo.size()) continue;  // out of steps
+            for (uint32_t t = s.step_lo[step]; t < s.step_lo[step + 1]; ++t) tasks.push_back(s.tasks[t] | ((uint64_t)i << 32));
+            live[keep++] = i;
+        }
+        live.resize(keep);
+        widest = std::max(widest, tasks.size() - at);
+    }
+    return (int)std::min<size_t>(widest, 1u << 30);
+}
+
+// resident workgroups: the widest step's tickets (every workgroup more would hold
+// LDS and registers that another batch's decode kernels beside the coder lose)
+// (IK_VP8X_GRID: a multiple of that, e.g. 0.5 -- dev A/B)
+int schedule_grid(int widest, size_t ntasks) {
     static const double mul = getenv("IK_VP8X_GRID") ? atof(getenv("IK_VP8X_GRID")) : 1.0;
     const int want = std::max(1, (int)(std::max(mul, 0.05) * widest));
-    sc.grid = (int)std::min<size_t>(std::min(want, 2048), sc.tasks.size());
+    return (int)std::min<size_t>(std::min(want, 2048), ntasks);
+}
+
+// The uniform call's schedule, cached per thread for its geometry: n images of one
+// geometry merged -- tickets in (epoch, diagonal, image) order, each epoch's folds
+// after its MBs.
+struct XSchedule {
+    int w = 0, h = 0, n = 0;
+    std::vector<int> bounds;
+    std::vector<uint64_t> tasks;
+    int grid = 0;
+};
+
+const XSchedule& exact_schedule(int w, int h, int n) {
+    static thread_local XSchedule sc;
+    if (sc.w == w && sc.h == h && sc.n == n) return sc;
+    begin_schedule();
+    const GeomSteps& g = geometry_steps(w, h);
+    sc.bounds = g.bounds;
+    const int widest = merge_steps(std::vector<const GeomSteps*>((size_t)n, &g), sc.tasks);
+    sc.grid = schedule_grid(widest, sc.tasks.size());
     sc.w = w;
     sc.h = h;
     sc.n = n;
@@ -398,6 +472,167 @@ int webp_encode_exact(const uint8_t* d_yuv, size_t yuv_stride, int n, int w, int
         for (int sg = 0; sg < 4; ++sg) segs[sg] = setup_segment(hdr[i].quant[sg], hdr[i].dq_uv_dc, hdr[i].dq_uv_ac, 50);
         write_file(w, h, mbs + (size_t)nmb * i, pr + (size_t)1056 * i, hdr[i], me + (size_t)4 * i, segs, outs[i]);
     });
+    webp_enc_count(0, (unsigned long long)n);
+    return IK_OK;
+}
+
+// n images of their own sizes and qualities, their planes anywhere in device memory,
+// in one set of launches: a descriptor per image (ik_vp8_gpu.h ImgDesc) goes up with
+// the constants, the per-MB arrays are sized by the sum of the images' MBs, the
+// per-epoch ones by the sum of their epochs, and the tickets are the images' steps
+// merged (merge_steps).  Stream handling as webp_encode_exact.  Images that all share
+// one geometry and quality go through webp_encode_exact itself, so a geometry never
+// takes two code paths.
+int webp_encode_exact_mixed(const ExactItem* items, int n, std::vector<std::vector<uint8_t>>& outs) {
+    if (!items || n < 1 || n > 65535) return fail(IK_ERR_INVALID, "bad mixed WebP call of %d images", n);
+    bool same = true;
+    for (int i = 0; i < n; ++i) {
+        const ExactItem& it = items[i];
+        if (!it.yuv || it.w < 1 || it.h < 1 || it.w > 16383 || it.h > 16383 || it.quality < 1 || it.quality > 100)
+            return fail(IK_ERR_INVALID, "bad WebP item %d: %dx%d at quality %d%s", i, it.w, it.h, it.quality,
+                        it.yuv ? "" : ", null planes");
+        same = same && it.w == items[0].w && it.h == items[0].h && it.quality == items[0].quality;
+    }
+    if (same) {
+        const int w = items[0].w, h = items[0].h;
+        const size_t ysz = (size_t)w * h + 2 * (size_t)((w + 1) / 2) * ((h + 1) / 2);
+        // evenly spaced planes as they lie; others gathered a common stride apart
+        bool even = n == 1 || (items[1].yuv > items[0].yuv && (size_t)(items[1].yuv - items[0].yuv) >= ysz);
+        const size_t step = n > 1 && even ? (size_t)(items[1].yuv - items[0].yuv) : 0;
+        for (int i = 2; i < n && even; ++i) even = items[i].yuv == items[0].yuv + step * i;
+        if (even) return webp_encode_exact(items[0].yuv, step, n, w, h, items[0].quality, outs);
+        hipStream_t ts = thread_stream();
+        if (!ts) return fail(IK_ERR_DEVICE, "cannot create HIP stream");
+        const size_t stride = (ysz + 255) & ~(size_t)255;
+        uint8_t* g = scratch_slot(kScratchExactGather, stride * n);
+        if (!g) return fail(IK_ERR_DEVICE, "cannot allocate the gathered planes (%zu bytes)", stride * n);
+        for (int i = 0; i < n; ++i) IK_HIP(hipMemcpyAsync(g + stride * i, items[i].yuv, ysz, hipMemcpyDeviceToDevice, ts));
+        return webp_encode_exact(g, stride, n, w, h, items[0].quality, outs);
+    }
+    hipStream_t ts = thread_stream();
+    if (!ts) return fail(IK_ERR_DEVICE, "cannot create HIP stream");
+    hipStream_t s = ts;
+    hipEvent_t ev = nullptr;
+    if (thread_prio_stream(&s, &ev) && s != ts) {
+        IK_HIP(hipEventRecord(ev, ts));
+        IK_HIP(hipStreamWaitEvent(s, ev, 0));
+    } else {
+        s = ts;
+    }
+    // the descriptors, the concatenated epoch bounds, one quantiser table per quality
+    begin_schedule();
+    std::vector<const GeomSteps*> geom((size_t)n);
+    std::vector<XImg> desc((size_t)n);
+    std::vector<int> bounds, quals;
+    size_t tot_mb = 0, tot_ep = 0, tot_tasks = 0;
+    int max_nmb = 0;
+    for (int i = 0; i < n; ++i) {
+        const ExactItem& it = items[i];
+        const GeomSteps& g = geometry_steps(it.w, it.h);
+        geom[(size_t)i] = &g;
+        XImg& d = desc[(size_t)i];
+        d.yuv = it.yuv;
+        d.w = it.w;
+        d.h = it.h;
+        d.mb_w = (it.w + 15) / 16;
+        d.mb_h = (it.h + 15) / 16;
+        d.mb0 = (uint32_t)tot_mb;
+        d.ep0 = (uint32_t)tot_ep;
+        d.bnd0 = (uint32_t)bounds.size();
+        d.nep = (uint32_t)g.bounds.size() - 1;
+        size_t qi = std::find(quals.begin(), quals.end(), it.quality) - quals.begin();
+        if (qi == quals.size()) quals.push_back(it.quality);
+        d.qtab = (uint32_t)qi;
+        d.use_derr = it.quality <= 98;  // ERROR_DIFFUSION_QUALITY
+        bounds.insert(bounds.end(), g.bounds.begin(), g.bounds.end());
+        const int nmb = d.mb_w * d.mb_h;
+        max_nmb = std::max(max_nmb, nmb);
+        tot_mb += (size_t)nmb;
+        tot_ep += d.nep;
+        tot_tasks += g.tasks.size();
+        if (tot_mb > 0x7fffffffu || tot_tasks > 0x7fffffffu)
+            return fail(IK_ERR_INVALID, "mixed WebP call of more than 2^31 macroblocks");
+    }
+    static thread_local std::vector<uint64_t> tasks;
+    const int widest = merge_steps(geom, tasks);
+    const int grid = schedule_grid(widest, tasks.size());
+    // device buffers (one allocation, 256-byte aligned parts); the hand-off words first,
+    // zeroed by one memset per call
+    size_t off = 0;
+    auto part = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t sync_words = 4 + tot_mb + 2 * tot_ep;
+    const size_t o_sync = part(4 * sync_words);
+    const size_t sync_bytes = off;
+    const size_t o_alpha = part(tot_mb), o_uva = part(tot_mb * 2), o_kseg = part(tot_mb);
+    const size_t o_rec = part(sizeof(vp8::SegRecord) * n), o_hdr = part(sizeof(ik_vp8_segment_header) * n);
+    const size_t o_mbs = part(sizeof(XMB) * tot_mb), o_edges = part(sizeof(XEdge) * tot_mb);
+    const size_t o_seg = part(tot_mb), o_segs = part(sizeof(XSeg) * 4 * n);
+    const size_t o_lc = part(2ull * kCostRows * kLevelTab * n), o_pr = part(1056ull * n), o_st = part(4ull * 1056 * n);
+    const size_t o_me = part(16ull * n);
+    const size_t o_qtab = part(4 * 255 * quals.size()), o_bounds = part(4 * bounds.size());
+    const size_t o_desc = part(sizeof(XImg) * n), o_tasks = part(8 * tasks.size());
+    uint8_t* d = scratch_slot(kScratchExact, off);
+    if (!d) return fail(IK_ERR_DEVICE, "cannot allocate the exact coder's work area (%zu bytes)", off);
+    const size_t const_bytes = off - o_qtab;
+    uint8_t* hc = pinned_slot(kPinnedExactIn, const_bytes);
+    if (!hc) return IK_ERR_NOMEM;
+    for (size_t k = 0; k < quals.size(); ++k) segment_quant_table((float)quals[k], reinterpret_cast<int*>(hc) + 255 * k);
+    std::memcpy(hc + (o_bounds - o_qtab), bounds.data(), 4 * bounds.size());
+    std::memcpy(hc + (o_desc - o_qtab), desc.data(), sizeof(XImg) * n);
+    std::memcpy(hc + (o_tasks - o_qtab), tasks.data(), 8 * tasks.size());
+    IK_HIP(hipMemcpyAsync(d + o_qtab, hc, const_bytes, hipMemcpyHostToDevice, s));
+    IK_HIP(hipMemsetAsync(d + o_sync, 0, sync_bytes, s));
+    XArgs a{};  // (planes and geometry: per image, from the descriptors)
+    a.mbs = (XMB*)(d + o_mbs);
+    a.edges = (XEdge*)(d + o_edges);
+    a.seg = d + o_seg;
+    a.segs = (XSeg*)(d + o_segs);
+    a.lc = (uint16_t*)(d + o_lc);
+    a.pr = d + o_pr;
+    a.stats = (uint32_t*)(d + o_st);
+    a.max_edge = (int*)(d + o_me);
+    XRun r{};
+    r.tasks = (const uint64_t*)(d + o_tasks);
+    r.ntasks = (uint32_t)tasks.size();
+    r.bounds = (const int*)(d + o_bounds);
+    r.sync = (uint32_t*)(d + o_sync);
+    r.done = r.sync + 4;
+    r.cnt = r.done + tot_mb;
+    r.ready = r.cnt + tot_ep;
+    const XImg* dimgs = (const XImg*)(d + o_desc);
+    IK_HIP(vp8::launch_vp8_analysis_mixed(dimgs, n, max_nmb, d + o_alpha, (uint16_t*)(d + o_uva), d + o_kseg,
+                                          (vp8::SegRecord*)(d + o_rec), s));
+    IK_HIP(launch_vp8x_setup_mixed(a, dimgs, (const vp8::SegRecord*)(d + o_rec), d + o_kseg, (const int*)(d + o_qtab),
+                                   (ik_vp8_segment_header*)(d + o_hdr), n, s));
+    IK_HIP(launch_vp8x_run_mixed(a, r, dimgs, grid, s));
+    // the records back, as in webp_encode_exact; the files on the host, each with its own w, h
+    const size_t rec_bytes = sizeof(XMB) * tot_mb;
+    const size_t o_hpr = rec_bytes, o_hme = o_hpr + 1056ull * n, o_hhd = o_hme + 16ull * n;
+    const size_t o_herr = o_hhd + sizeof(ik_vp8_segment_header) * n, hbytes = o_herr + 16;
+    uint8_t* hp = pinned_slot(kPinnedExactOut, hbytes);
+    if (!hp) return IK_ERR_NOMEM;
+    IK_HIP(hipMemcpyAsync(hp, d + o_mbs, rec_bytes, hipMemcpyDeviceToHost, s));
+    IK_HIP(hipMemcpyAsync(hp + o_hpr, d + o_pr, 1056ull * n, hipMemcpyDeviceToHost, s));
+    IK_HIP(hipMemcpyAsync(hp + o_hme, d + o_me, 16ull * n, hipMemcpyDeviceToHost, s));
+    IK_HIP(hipMemcpyAsync(hp + o_hhd, d + o_hdr, sizeof(ik_vp8_segment_header) * n, hipMemcpyDeviceToHost, s));
+    IK_HIP(hipMemcpyAsync(hp + o_herr, d + o_sync, 8, hipMemcpyDeviceToHost, s));
+    IK_HIP(hipStreamSynchronize(s));
+    uint32_t err_word = 0;
+    std::memcpy(&err_word, hp + o_herr + 4, 4);
+    if (err_word) return fail(IK_ERR_DEVICE, "exact WebP coder: a dependency wait timed out on the device");
+    const XMB* mbs = reinterpret_cast<const XMB*>(hp);
+    const uint8_t* pr = hp + o_hpr;
+    const int* me = reinterpret_cast<const int*>(hp + o_hme);
+    const ik_vp8_segment_header* hdr = reinterpret_cast<const ik_vp8_segment_header*>(hp + o_hhd);
+    outs.resize(n);
+    parallel_for(n, n < 16 ? n : 16, [&](int i) {
+        XSeg segs[4];
+        for (int sg = 0; sg < 4; ++sg) segs[sg] = setup_segment(hdr[i].quant[sg], hdr[i].dq_uv_dc, hdr[i].dq_uv_ac, 50);
+        write_file(items[i].w, items[i].h, mbs + desc[(size_t)i].mb0, pr + (size_t)1056 * i, hdr[i], me + (size_t)4 * i,
+                   segs, outs[i]);
+    });
+    webp_enc_count(1, (unsigned long long)n);
+    webp_enc_count(3, 1);
     return IK_OK;
 }
 
@@ -473,4 +708,57 @@ extern "C" int ik_webp_encode_exact_device(const uint8_t* dev_yuv, size_t yuv_st
         out_lens[i] = files[i].size();
     }
     return IK_OK;
+}
+
+extern "C" int ik_webp_encode_exact_items(const ik_webp_exact_item* items, uint32_t n, uint8_t** outs,
+                                          size_t* out_lens) {
+    IK_API_ENTER();
+    if (!items || !outs || !out_lens) return fail(IK_ERR_INVALID, "null pointer");
+    if (n < 1 || n > 65535) return fail(IK_ERR_INVALID, "bad WebP item count %u", n);
+    std::vector<ExactItem> it(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!items[i].dev_yuv || items[i].w < 1 || items[i].h < 1 || items[i].w > 16383 || items[i].h > 16383)
+            return fail(IK_ERR_INVALID, "bad WebP item %u: %ux%u%s", i, items[i].w, items[i].h,
+                        items[i].dev_yuv ? "" : ", null planes");
+        const int q = items[i].quality;
+        it[i] = ExactItem{items[i].dev_yuv, (int)items[i].w, (int)items[i].h, q < 1 ? 1 : (q > 100 ? 100 : q)};
+    }
+    std::vector<std::vector<uint8_t>> files;
+    if (int rc = webp_encode_exact_mixed(it.data(), (int)n, files)) return rc;
+    std::vector<uint8_t*> mem(n, nullptr);
+    for (uint32_t i = 0; i < n; ++i) {
+        mem[i] = (uint8_t*)malloc(files[i].size() ? files[i].size() : 1);
+        if (!mem[i]) {
+            for (uint32_t j = 0; j < i; ++j) free(mem[j]);
+            return fail(IK_ERR_NOMEM, "out of host memory");
+        }
+        std::memcpy(mem[i], files[i].data(), files[i].size());
+    }
+    for (uint32_t i = 0; i < n; ++i) {
+        outs[i] = mem[i];
+        out_lens[i] = files[i].size();
+    }
+    return IK_OK;
+}
+
+extern "C" long long ik_webp_exact_plan(const uint32_t* w, const uint32_t* h, uint32_t n, uint64_t* tasks, size_t cap,
+                                        uint32_t* grid) {
+    if (!w || !h || n < 1 || n > 65535 || (cap && !tasks)) {
+        fail(IK_ERR_INVALID, "bad WebP plan arguments");
+        return -1;
+    }
+    begin_schedule();
+    std::vector<const GeomSteps*> geom(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (w[i] < 1 || h[i] < 1 || w[i] > 16383 || h[i] > 16383) {
+            fail(IK_ERR_INVALID, "bad WebP plan size %ux%u", w[i], h[i]);
+            return -1;
+        }
+        geom[i] = &geometry_steps((int)w[i], (int)h[i]);
+    }
+    std::vector<uint64_t> t;
+    const int widest = merge_steps(geom, t);
+    if (grid) *grid = (uint32_t)schedule_grid(widest, t.size());
+    if (cap) std::memcpy(tasks, t.data(), 8 * std::min(cap, t.size()));
+    return (long long)t.size();
 }

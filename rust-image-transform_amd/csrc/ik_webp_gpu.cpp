@@ -17,8 +17,19 @@ namespace ik {
 namespace {
 
 std::atomic<int> g_webp_encoder{-1};  // -1 = not yet read from IK_WEBP_ENCODER
+std::atomic<int> g_webp_mixed{-1};    // -1 = IK_WEBP_MIXED decides, read per batch
+std::atomic<unsigned long long> g_webp_enc[4];  // ik_webp_enc_counters
 
 }  // namespace
+
+int webp_mixed_mode() {
+    const int m = g_webp_mixed.load();
+    if (m >= 0) return m;
+    const char* s = getenv("IK_WEBP_MIXED");
+    return (s && (!strcmp(s, "gpu") || !strcmp(s, "1"))) ? IK_WEBP_MIXED_GPU : IK_WEBP_MIXED_HOST;
+}
+
+void webp_enc_count(int which, unsigned long long n) { g_webp_enc[which] += n; }
 
 int default_webp_encoder() {
     int e = g_webp_encoder.load();
@@ -49,6 +60,21 @@ int ik_set_webp_encoder(int encoder) {
 }
 
 int ik_get_webp_encoder(void) { return default_webp_encoder(); }
+
+int ik_set_webp_mixed(int where) {
+    if (where != -1 && where != IK_WEBP_MIXED_HOST && where != IK_WEBP_MIXED_GPU)
+        return fail(IK_ERR_INVALID, "bad WebP mixed-batch coder %d", where);
+    g_webp_mixed.store(where);
+    return IK_OK;
+}
+
+int ik_get_webp_mixed(void) { return webp_mixed_mode(); }
+
+int ik_webp_enc_counters(unsigned long long* out) {
+    if (!out) return fail(IK_ERR_INVALID, "null pointer");
+    for (int k = 0; k < 4; ++k) out[k] = g_webp_enc[k].load();
+    return IK_OK;
+}
 
 int ik_vp8_analyze_device(const uint8_t* dev_yuv, size_t yuv_stride, uint32_t n, uint32_t w, uint32_t h,
                           float quality, uint8_t* seg, ik_vp8_segment_header* hdr) {

@@ -20,6 +20,12 @@ _lib = None
 u8p = ctypes.POINTER(ctypes.c_uint8)
 c_img_p = ctypes.c_void_p
 
+
+class WebpExactItem(ctypes.Structure):
+    """ik_webp_exact_item: one image of ik_webp_encode_exact_items."""
+    _fields_ = [("dev_yuv", ctypes.c_void_p), ("w", ctypes.c_uint32), ("h", ctypes.c_uint32), ("quality", ctypes.c_int)]
+
+
 # (name, restype, argtypes) for every entry point declared in include/imagekit_hip.h
 SIGNATURES = [
     ("ik_init", ctypes.c_int, [ctypes.c_int]),
@@ -58,6 +64,11 @@ SIGNATURES = [
     ("ik_get_webp_encoder", ctypes.c_int, []),
     ("ik_pipeline_set_webp_encoder", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     ("ik_webp_encode_exact_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    ("ik_webp_encode_exact_items", ctypes.c_int, [ctypes.POINTER(WebpExactItem), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
+    ("ik_webp_exact_plan", ctypes.c_longlong, [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32)]),
+    ("ik_set_webp_mixed", ctypes.c_int, [ctypes.c_int]),
+    ("ik_get_webp_mixed", ctypes.c_int, []),
+    ("ik_webp_enc_counters", ctypes.c_int, [ctypes.POINTER(ctypes.c_ulonglong)]),
     ("ik_vp8_analyze_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
     ("ik_pipeline_create", ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
     ("ik_pipeline_run", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),

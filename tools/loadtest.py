@@ -26,6 +26,7 @@ about S seconds, before anything touches the GPU.
 Usage: python tools/loadtest.py [--requests 10000 --batch 64 --sources 8 --threads 16 --clients 4]
 """
 import argparse
+import ctypes
 import io
 import json
 import os
@@ -197,6 +198,7 @@ def main():
             pend = (tb, p)
 
     barrier()
+    cpu0 = os.times()
     t0 = time.perf_counter()
     ts = [threading.Thread(target=client) for _ in range(max(1, args.clients))]
     for t in ts:
@@ -204,6 +206,11 @@ def main():
     for t in ts:
         t.join()
     elapsed = time.perf_counter() - t0
+    cpu1 = os.times()
+    # this process' CPU time (user + system, every thread) over the timed wall time
+    cores_busy = ((cpu1.user - cpu0.user) + (cpu1.system - cpu0.system)) / elapsed
+    enc = (ctypes.c_ulonglong * 4)()
+    lib.ik_webp_enc_counters(enc)
     barrier()
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local}" if torch.cuda.is_available() else "cpu")
@@ -221,6 +228,10 @@ def main():
             "decoded_mpix_per_s": round(args.requests * S * S / elapsed / 1e6, 1),
             "output_bytes_per_request": out_bytes // max(1, len(mine)),
             "host_threads_per_gpu": args.threads,
+            "host_cores_busy": round(cores_busy, 2),  # (rank 0's process)
+            "webp_mixed": "gpu" if lib.ik_get_webp_mixed() == 1 else "host",
+            "webp_enc_counters": {"uniform_exact": enc[0], "mixed_exact": enc[1], "libwebp_host": enc[2],
+                                  "mixed_calls": enc[3]},
             "filter": "lanczos3 (the reference's)",
             "pipelined": bool(args.pipeline),
             "dispatch": (f"in-library dynamic queue over {ndev} logical device(s), {args.clients} client threads"
