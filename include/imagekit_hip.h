@@ -427,7 +427,8 @@ int ik_vp8_analyze_device(const uint8_t *dev_yuv, size_t yuv_stride, uint32_t n,
  * decisions on the device (a wavefront per probability-refresh epoch), the bitstream on
  * the host -- the file WebPEncodeRGB writes for these planes at this quality.  n images
  * of w x h device YUV420 planes (the ik_webp_yuv420_device layout) yuv_stride apart;
- * outs[i] / out_lens[i] receive each file (library-allocated, ik_buf_free). */
+ * outs[i] / out_lens[i] receive each file (library-allocated, ik_buf_free).  All or
+ * nothing: on a failure no file is left to free and outs / out_lens are not written. */
 int ik_webp_encode_exact_device(const uint8_t *dev_yuv, size_t yuv_stride, uint32_t n, uint32_t w, uint32_t h,
                                 int quality, uint8_t **outs, size_t *out_lens);
 /* the exact WebP coder over images of mixed sizes and qualities, in one set of launches:
@@ -437,7 +438,8 @@ int ik_webp_encode_exact_device(const uint8_t *dev_yuv, size_t yuv_stride, uint3
  * n <= 65535; a bad item (a zero or oversized side, a null plane) is IK_ERR_INVALID
  * before anything is launched, with outs untouched.  Items that all share one geometry
  * and quality go through the uniform call (one geometry never takes two code paths).
- * outs[i] / out_lens[i] as above: every file is allocated, or on a failure none is. */
+ * outs[i] / out_lens[i] as above, all or nothing: on a failure no file is left to free
+ * and outs / out_lens are not written. */
 typedef struct {
     const uint8_t *dev_yuv;
     uint32_t w, h;

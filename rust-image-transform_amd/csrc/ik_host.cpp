@@ -554,7 +554,7 @@ const DeviceConsts* device_consts(int device) {
 // AV1 coding by libavif/aom on the host.
 int encode_device_front(const uint8_t* dev, uint32_t w, uint32_t h, uint32_t c, size_t pitch, int fmt, int quality,
                         EncodePrep& p, std::vector<uint8_t>& out) {
-    const int q = quality < 1 ? 1 : (quality > 100 ? 100 : quality);
+    const int q = clamp_quality(quality);
     p.fmt = fmt;
     p.q = q;
     p.w = w;
@@ -566,8 +566,7 @@ int encode_device_front(const uint8_t* dev, uint32_t w, uint32_t h, uint32_t c, 
         if (w > 16383 || h > 16383) return fail(IK_ERR_TRANSFORM, "WebP dimensions %ux%u exceed 16383", w, h);
         const DeviceConsts* dc = device_consts(current_device());
         if (!dc) return fail(IK_ERR_DEVICE, "cannot upload WebP tables");
-        const size_t uvw = (w + 1) / 2, uvh = (h + 1) / 2;
-        const size_t bytes = (size_t)w * h + 2 * uvw * uvh;
+        const size_t bytes = yuv420_bytes(w, h);
         if (default_webp_encoder() == IK_WEBP_EXACT) {  // (read once: a concurrent switch cannot mix paths)
             uint8_t* dyuv = scratch(bytes);
             if (!dyuv) return fail(IK_ERR_DEVICE, "cannot allocate device scratch");
@@ -1089,7 +1088,7 @@ static int webp_exact_group(const std::vector<ik_image*>& imgs, int quality, std
     const DeviceConsts* dc = device_consts(current_device());
     if (!dc) return fail(IK_ERR_DEVICE, "cannot upload WebP tables");
     const uint32_t w = i0->w, h = i0->h;
-    const size_t uvw = (w + 1) / 2, uvh = (h + 1) / 2, bytes = (size_t)w * h + 2 * uvw * uvh;
+    const size_t bytes = yuv420_bytes(w, h);
     const size_t stride = (bytes + 255) & ~size_t(255);
     hipStream_t s = thread_stream();
     uint8_t* dyuv = scratch(stride * n + 16 * n + 256);
@@ -1103,7 +1102,7 @@ static int webp_exact_group(const std::vector<ik_image*>& imgs, int quality, std
                                dc->gamma_to_lin, dc->lin_to_gamma, s, dtab);
     if (e != hipSuccess) return hip_fail(e, "webp yuv420 (exact group)");
     std::vector<std::vector<uint8_t>> files;
-    const int q = quality < 1 ? 1 : (quality > 100 ? 100 : quality);
+    const int q = clamp_quality(quality);
     if (int rc = webp_encode_exact(dyuv, stride, (int)n, (int)w, (int)h, q, files)) return rc;
     for (size_t i = 0; i < n; ++i) outs[i]->swap(files[i]);
     return IK_OK;
@@ -1127,7 +1126,7 @@ static int webp_exact_mixed_group(const std::vector<ik_image*>& imgs, const std:
     for (size_t i = 0; i < n; ++i) {
         const size_t w = imgs[i]->w, h = imgs[i]->h;
         at[i] = total;
-        total += ((w * h + 2 * ((w + 1) / 2) * ((h + 1) / 2)) + 255) & ~size_t(255);
+        total += (yuv420_bytes(w, h) + 255) & ~size_t(255);
         max_w = std::max(max_w, (int)w);
         max_h = std::max(max_h, (int)h);
     }
@@ -1139,8 +1138,7 @@ static int webp_exact_mixed_group(const std::vector<ik_image*>& imgs, const std:
     for (size_t i = 0; i < n; ++i) {
         htab[i] = WebpYuvItem{imgs[i]->d, dyuv + at[i], imgs[i]->pitch, (int32_t)imgs[i]->w, (int32_t)imgs[i]->h,
                               (int32_t)imgs[i]->c, 0};
-        const int q = quality[i];
-        items[i] = ExactItem{dyuv + at[i], (int)imgs[i]->w, (int)imgs[i]->h, q < 1 ? 1 : (q > 100 ? 100 : q)};
+        items[i] = ExactItem{dyuv + at[i], (int)imgs[i]->w, (int)imgs[i]->h, clamp_quality(quality[i])};
     }
     WebpYuvItem* dtab = reinterpret_cast<WebpYuvItem*>(dyuv + total);
     hipError_t e = hipMemcpyAsync(dtab, htab, sizeof(WebpYuvItem) * n, hipMemcpyHostToDevice, s);
@@ -1163,7 +1161,7 @@ int webp_front_group(const std::vector<ik_image*>& imgs, int quality, std::vecto
     const DeviceConsts* dc = device_consts(current_device());
     if (!dc) return fail(IK_ERR_DEVICE, "cannot upload WebP tables");
     const uint32_t w = i0->w, h = i0->h;
-    const size_t uvw = (w + 1) / 2, uvh = (h + 1) / 2, bytes = (size_t)w * h + 2 * uvw * uvh;
+    const size_t bytes = yuv420_bytes(w, h);
     const size_t stride = (bytes + 255) & ~size_t(255);
     std::shared_ptr<uint8_t> blk = pinned_block(stride * n + 16 * n + 256);
     uint8_t* hp = blk.get();
@@ -1183,7 +1181,7 @@ int webp_front_group(const std::vector<ik_image*>& imgs, int quality, std::vecto
                                (int)n, dc->gamma_to_lin, dc->lin_to_gamma, s, dtab);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return hip_fail(e, "webp yuv420 (batched)");
-    const int q = quality < 1 ? 1 : (quality > 100 ? 100 : quality);
+    const int q = clamp_quality(quality);
     for (size_t i = 0; i < n; ++i) {
         EncodePrep& p = *prep[i];
         p.fmt = IK_FORMAT_WEBP;
@@ -1217,7 +1215,7 @@ int jpeg_front_group(const std::vector<ik_image*>& imgs, int quality, std::vecto
     DeviceGuard g(i0->device);
     const DeviceConsts* dc = device_consts(current_device());
     if (!dc) return fail(IK_ERR_DEVICE, "cannot upload JPEG tables");
-    const int q = quality < 1 ? 1 : (quality > 100 ? 100 : quality);
+    const int q = clamp_quality(quality);
     const uint32_t w = i0->w, h = i0->h;
     uint8_t qt[128];
     jpeg_quant_tables(q, qt);
@@ -1695,13 +1693,6 @@ static void transform_decode_phase(const uint8_t* const* bytes, const size_t* le
                 std::chrono::duration<double, std::milli>(tg1 - tg0).count(),
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tg1).count());
 }
-
-// IK_WEBP_AUTO: smallest same-geometry group that the exact GPU coder takes
-constexpr size_t kAutoExactMinGroup = 32;
-// IK_WEBP_MIXED_GPU: fewest WebP requests outside those groups that one mixed exact call
-// takes (provisional: the uniform rule's figure, until the two are measured against each
-// other -- profiles/webp_mixed_notes.md)
-constexpr size_t kAutoMixedMin = 32;
 
 // Device half, post stage: resize, the encoders' device front ends (under the
 // post gate, so a batch's resize runs beside the next batch's decode kernels);
@@ -2485,7 +2476,7 @@ int ik_jpeg_coeffs_device(const uint8_t* dev_src, uint32_t w, uint32_t h, uint32
     if (!dev_src || !dev_coef || !w || !h || C < 1 || C > 4) return fail(IK_ERR_INVALID, "bad arguments");
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : thread_stream();
     uint8_t qt[128];
-    jpeg_quant_tables(quality < 1 ? 1 : quality > 100 ? 100 : quality, qt);
+    jpeg_quant_tables(clamp_quality(quality), qt);
     uint8_t* dq = scratch(128);
     if (!dq) return fail(IK_ERR_DEVICE, "cannot allocate device scratch");
     if (int rc = copy_h2d_2d(dq, 128, qt, 128, 128, 1, s)) return rc;

@@ -310,10 +310,10 @@ int ik_pipeline_create(uint32_t W, uint32_t H, uint32_t C, uint32_t nw, uint32_t
         return rc;
     }
     *out = p;
-    // EXACT, or AUTO with batches of 32+ frames (the rule of a batch's same-geometry
-    // groups, ik_host.cpp kAutoExactMinGroup)
+    // EXACT, or AUTO with batches of kAutoExactMinGroup frames (the rule of a batch's
+    // same-geometry groups)
     const int enc = default_webp_encoder();
-    if (fmt == IK_FORMAT_WEBP && (enc == IK_WEBP_EXACT || (enc == IK_WEBP_AUTO && max_batch >= 32)))
+    if (fmt == IK_FORMAT_WEBP && (enc == IK_WEBP_EXACT || (enc == IK_WEBP_AUTO && max_batch >= kAutoExactMinGroup)))
         return ik_pipeline_set_webp_encoder(p, IK_WEBP_EXACT);
     return IK_OK;
 }
@@ -327,7 +327,7 @@ int pipeline_create(uint32_t W, uint32_t H, uint32_t C, uint32_t nw, uint32_t nh
     IK_HIP(hipSetDevice(p->device));
     p->W = W; p->H = H; p->C = C; p->nw = nw; p->nh = nh; p->max_batch = max_batch;
     p->filter = filter; p->fmt = fmt;
-    p->quality = quality < 1 ? 1 : quality > 100 ? 100 : quality;
+    p->quality = clamp_quality(quality);
     IK_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
     IK_HIP(hipStreamCreateWithFlags(&p->stream2, hipStreamNonBlocking));
     for (auto& sl : p->slot)
@@ -336,8 +336,7 @@ int pipeline_create(uint32_t W, uint32_t H, uint32_t C, uint32_t nw, uint32_t nh
     p->r_img_stride = p->r_pitch * nh;
     IK_HIP(hipMalloc(&p->d_resized, p->r_img_stride * max_batch + 16));
     if (fmt == IK_FORMAT_WEBP) {
-        const size_t uvw = (nw + 1) / 2, uvh = (nh + 1) / 2;
-        p->stage_bytes = (size_t)nw * nh + 2 * uvw * uvh;
+        p->stage_bytes = yuv420_bytes(nw, nh);
     } else if (fmt == IK_FORMAT_AVIF) {  // Y, U, V, A planes (4:4:4), 256-B aligned per image
         p->stage_bytes = (4 * (size_t)nw * nh + 255) & ~(size_t)255;
         for (auto& sl : p->slot) {

@@ -237,6 +237,16 @@ void jpeg_enc_count(bool gpu_coded);
 // otherwise (ik_webp_gpu.cpp)
 constexpr int kDefaultWebpEncoder = IK_WEBP_AUTO;
 int default_webp_encoder();
+// IK_WEBP_AUTO: smallest same-geometry group (ik_host.cpp), and smallest max_batch of a
+// pipeline (ik_pipeline.cpp), that the exact GPU coder takes
+constexpr size_t kAutoExactMinGroup = 32;
+// IK_WEBP_MIXED_GPU: fewest WebP requests outside those groups that one mixed exact call
+// takes (provisional: the uniform rule's figure, until the two are measured against each
+// other -- profiles/webp_mixed_notes.md)
+constexpr size_t kAutoMixedMin = 32;
+// encode_image's quality range, and the bytes of a w x h image's YUV420 planes
+inline int clamp_quality(int q) { return q < 1 ? 1 : (q > 100 ? 100 : q); }
+inline size_t yuv420_bytes(size_t w, size_t h) { return w * h + 2 * ((w + 1) / 2) * ((h + 1) / 2); }
 // the exact coder (ik_vp8x_host.cpp): libwebp's files from n device YUV420 images
 int webp_encode_exact(const uint8_t* d_yuv, size_t yuv_stride, int n, int w, int h, int quality,
                       std::vector<std::vector<uint8_t>>& outs);

@@ -363,21 +363,83 @@ void segment_quant_table(float quality, int* qtab) {
     }
 }
 
-}  // namespace
+// What a call holds, in the units its arrays are sized by.  The uniform call is the
+// mixed one with mb = n * nmb, ep = n * nep, one quantiser table, one geometry's bounds
+// and no descriptors.
+struct XTotals {
+    size_t n, mb, ep;      // images, their macroblocks, their epochs
+    size_t quals, bounds;  // 255-entry quantiser tables (distinct qualities), epoch-bound entries
+    size_t desc_bytes;     // the descriptor table (the mixed call's)
+    size_t tasks;          // tickets
+};
 
-// n images of w x h YUV420 planes on the device (yuv_stride bytes apart) -> the WebP
-// files libwebp's WebPEncodeRGB writes at this quality.  Device work on the thread's
-// coder stream (ordered after its main stream, which produced the planes): segment
-// analysis, set-up, ONE persistent launch for every decision and statistics fold,
-// the records back; then the files on the host.
-int webp_encode_exact(const uint8_t* d_yuv, size_t yuv_stride, int n, int w, int h, int quality,
-                      std::vector<std::vector<uint8_t>>& outs) {
-    if (n < 1 || n > 65535 || w < 1 || h < 1 || w > 16383 || h > 16383)
-        return fail(IK_ERR_INVALID, "bad WebP shape %dx%d x %d", w, h, n);
+// A call's device work area (kScratchExact): one allocation, every field the offset of a
+// 256-byte aligned part.  The hand-off words lie first (one memset zeroes them per
+// call), the constants last in the order they are staged (one upload).  Without `run`
+// (vp8_analyze_setup) the parts only k_vp8x_run uses -- sync, mbs, edges, bounds, desc,
+// tasks -- are empty, and an empty part moves no offset after it.
+struct WorkArea {
+    size_t sync, alpha, uva, kseg, rec, hdr, mbs, edges, seg, segs, lc, pr, st, me, qtab, bounds, desc, tasks;
+    size_t sync_bytes, bytes;  // the zeroed part, the whole area
+};
+
+WorkArea work_area(const XTotals& t, bool run) {
+    WorkArea L{};
+    auto part = [&](size_t bytes) { const size_t o = L.bytes; L.bytes += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t r = run ? 1 : 0;
+    L.sync = part(r * 4 * (4 + t.mb + 2 * t.ep));
+    L.sync_bytes = L.bytes;
+    L.alpha = part(t.mb), L.uva = part(t.mb * 2), L.kseg = part(t.mb);
+    L.rec = part(sizeof(vp8::SegRecord) * t.n), L.hdr = part(sizeof(ik_vp8_segment_header) * t.n);
+    L.mbs = part(r * sizeof(XMB) * t.mb), L.edges = part(r * sizeof(XEdge) * t.mb);
+    L.seg = part(t.mb), L.segs = part(sizeof(XSeg) * 4 * t.n);
+    L.lc = part(2ull * kCostRows * kLevelTab * t.n), L.pr = part(1056ull * t.n), L.st = part(4ull * 1056 * t.n);
+    L.me = part(16ull * t.n);
+    L.qtab = part(4 * 255 * t.quals), L.bounds = part(r * 4 * t.bounds);
+    L.desc = part(r * t.desc_bytes), L.tasks = part(r * 8 * t.tasks);
+    return L;
+}
+
+// The fields of XArgs and XRun that every call fills alike, from the work area at d
+// (r null: the call has no run-only parts; a.mbs and a.edges stay null)
+void fill_args(uint8_t* d, const WorkArea& L, const XTotals& t, XArgs& a, XRun* r) {
+    a.seg = d + L.seg;
+    a.segs = (XSeg*)(d + L.segs);
+    a.lc = (uint16_t*)(d + L.lc);
+    a.pr = d + L.pr;
+    a.stats = (uint32_t*)(d + L.st);
+    a.max_edge = (int*)(d + L.me);
+    if (!r) return;
+    a.mbs = (XMB*)(d + L.mbs);
+    a.edges = (XEdge*)(d + L.edges);
+    r->tasks = (const uint64_t*)(d + L.tasks);
+    r->ntasks = (uint32_t)t.tasks;
+    r->bounds = (const int*)(d + L.bounds);
+    r->sync = (uint32_t*)(d + L.sync);
+    r->done = r->sync + 4;
+    r->cnt = r->done + t.mb;
+    r->ready = r->cnt + t.ep;
+}
+
+// XArgs of n images of one geometry, a common stride apart (the mixed call's come per
+// image from its descriptors)
+XArgs uniform_args(const uint8_t* d_yuv, size_t yuv_stride, int w, int h) {
+    XArgs a{};
+    a.yuv = d_yuv;
+    a.yuv_stride = yuv_stride;
+    a.w = w;
+    a.h = h;
+    a.mb_w = (w + 15) / 16;
+    a.mb_h = (h + 15) / 16;
+    return a;
+}
+
+// The coder's stream: the thread's highest-priority one, so its launch is dispatched
+// ahead of another batch's decode kernels, ordered by an event after the thread's main
+// stream, which produced the planes; that main stream itself where there is no other.
+int coder_stream(hipStream_t* out) {
     hipStream_t ts = thread_stream();
     if (!ts) return fail(IK_ERR_DEVICE, "cannot create HIP stream");
-    // the coder's stream: the highest priority, so its launch is dispatched ahead of
-    // another batch's decode kernels; ordered after the caller's stream by an event
     hipStream_t s = ts;
     hipEvent_t ev = nullptr;
     if (thread_prio_stream(&s, &ev) && s != ts) {
@@ -386,78 +448,50 @@ int webp_encode_exact(const uint8_t* d_yuv, size_t yuv_stride, int n, int w, int
     } else {
         s = ts;
     }
-    const int mb_w = (w + 15) / 16, mb_h = (h + 15) / 16, nmb = mb_w * mb_h;
-    const float q = (float)quality;
-    const XSchedule& sc = exact_schedule(w, h, n);
-    const int nep = (int)sc.bounds.size() - 1;
-    // device buffers (one allocation, 256-byte aligned parts); the hand-off words first,
-    // zeroed by one memset per call
-    size_t off = 0;
-    auto part = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t sync_words = 4 + (size_t)n * nmb + 2ull * n * nep;
-    const size_t o_sync = part(4 * sync_words);
-    const size_t sync_bytes = off;
-    const size_t o_alpha = part((size_t)nmb * n), o_uva = part((size_t)nmb * n * 2), o_kseg = part((size_t)nmb * n);
-    const size_t o_rec = part(sizeof(vp8::SegRecord) * n), o_hdr = part(sizeof(ik_vp8_segment_header) * n);
-    const size_t o_mbs = part(sizeof(XMB) * nmb * n), o_edges = part(sizeof(XEdge) * nmb * n);
-    const size_t o_seg = part((size_t)nmb * n), o_segs = part(sizeof(XSeg) * 4 * n);
-    const size_t o_lc = part(2ull * kCostRows * kLevelTab * n), o_pr = part(1056ull * n), o_st = part(4ull * 1056 * n);
-    const size_t o_me = part(16ull * n);
-    const size_t o_qtab = part(4 * 255), o_bounds = part(4 * sc.bounds.size()), o_tasks = part(8 * sc.tasks.size());
-    uint8_t* d = scratch_slot(kScratchExact, off);
-    if (!d) return fail(IK_ERR_DEVICE, "cannot allocate the exact coder's work area (%zu bytes)", off);
-    // the constants: quantiser table, epoch bounds, tickets (through pinned staging)
-    const size_t const_bytes = off - o_qtab;
+    *out = s;
+    return IK_OK;
+}
+
+// The call's constants through pinned staging in one upload -- a quantiser table per
+// quality, the epoch bounds, the descriptors (t.desc_bytes of them, may be none), the
+// tickets -- and the hand-off words zeroed, on s.
+int upload_constants(uint8_t* d, const WorkArea& L, const XTotals& t, const int* quals, const int* bounds,
+                     const XImg* desc, const uint64_t* tasks, hipStream_t s) {
+    const size_t const_bytes = L.bytes - L.qtab;
     uint8_t* hc = pinned_slot(kPinnedExactIn, const_bytes);
     if (!hc) return IK_ERR_NOMEM;
-    segment_quant_table(q, reinterpret_cast<int*>(hc));
-    std::memcpy(hc + (o_bounds - o_qtab), sc.bounds.data(), 4 * sc.bounds.size());
-    std::memcpy(hc + (o_tasks - o_qtab), sc.tasks.data(), 8 * sc.tasks.size());
-    IK_HIP(hipMemcpyAsync(d + o_qtab, hc, const_bytes, hipMemcpyHostToDevice, s));
-    IK_HIP(hipMemsetAsync(d + o_sync, 0, sync_bytes, s));
-    XArgs a{};
-    a.yuv = d_yuv;
-    a.yuv_stride = yuv_stride;
-    a.w = w;
-    a.h = h;
-    a.mb_w = mb_w;
-    a.mb_h = mb_h;
-    a.mbs = (XMB*)(d + o_mbs);
-    a.edges = (XEdge*)(d + o_edges);
-    a.seg = d + o_seg;
-    a.segs = (XSeg*)(d + o_segs);
-    a.lc = (uint16_t*)(d + o_lc);
-    a.pr = d + o_pr;
-    a.stats = (uint32_t*)(d + o_st);
-    a.max_edge = (int*)(d + o_me);
-    a.use_derr = q <= 98.f;  // ERROR_DIFFUSION_QUALITY
-    XRun r{};
-    r.tasks = (const uint64_t*)(d + o_tasks);
-    r.ntasks = (uint32_t)sc.tasks.size();
-    r.nep = (uint32_t)nep;
-    r.bounds = (const int*)(d + o_bounds);
-    r.sync = (uint32_t*)(d + o_sync);
-    r.done = r.sync + 4;
-    r.cnt = r.done + (size_t)n * nmb;
-    r.ready = r.cnt + (size_t)n * nep;
-    // 1. segment analysis (ik_vp8_analysis.hip), 2. set-up, 3. every decision and fold
-    IK_HIP(vp8::launch_vp8_analysis(d_yuv, yuv_stride, n, w, h, d + o_alpha, (uint16_t*)(d + o_uva), d + o_kseg,
-                                    (vp8::SegRecord*)(d + o_rec), s));
-    IK_HIP(launch_vp8x_setup(a, (const vp8::SegRecord*)(d + o_rec), d + o_kseg, (const int*)(d + o_qtab),
-                             (ik_vp8_segment_header*)(d + o_hdr), n, s));
-    IK_HIP(launch_vp8x_run(a, r, sc.grid, s));
-    // 4. the records back (~830 B per MB), the final probabilities, the filter-edge
-    // maxima, the headers and the error word; the files on the host
-    const size_t rec_bytes = sizeof(XMB) * (size_t)nmb * n;
+    for (size_t k = 0; k < t.quals; ++k) segment_quant_table((float)quals[k], reinterpret_cast<int*>(hc) + 255 * k);
+    std::memcpy(hc + (L.bounds - L.qtab), bounds, 4 * t.bounds);
+    if (t.desc_bytes) std::memcpy(hc + (L.desc - L.qtab), desc, t.desc_bytes);
+    std::memcpy(hc + (L.tasks - L.qtab), tasks, 8 * t.tasks);
+    IK_HIP(hipMemcpyAsync(d + L.qtab, hc, const_bytes, hipMemcpyHostToDevice, s));
+    IK_HIP(hipMemsetAsync(d + L.sync, 0, L.sync_bytes, s));
+    return IK_OK;
+}
+
+// Where image i's file comes from: its size and its first record
+struct ImgAt {
+    int w, h;
+    size_t mb0;
+};
+
+// After k_vp8x_run: the records back (~830 B per MB), the final probabilities, the
+// filter-edge maxima, the headers and the error word; then the files on the host,
+// image i's from at(i).
+template <class At>
+int read_back_and_write(const uint8_t* d, const WorkArea& L, const XTotals& t, hipStream_t s, At at,
+                        std::vector<std::vector<uint8_t>>& outs) {
+    const int n = (int)t.n;
+    const size_t rec_bytes = sizeof(XMB) * t.mb;
     const size_t o_hpr = rec_bytes, o_hme = o_hpr + 1056ull * n, o_hhd = o_hme + 16ull * n;
     const size_t o_herr = o_hhd + sizeof(ik_vp8_segment_header) * n, hbytes = o_herr + 16;
     uint8_t* hp = pinned_slot(kPinnedExactOut, hbytes);
     if (!hp) return IK_ERR_NOMEM;
-    IK_HIP(hipMemcpyAsync(hp, d + o_mbs, rec_bytes, hipMemcpyDeviceToHost, s));
-    IK_HIP(hipMemcpyAsync(hp + o_hpr, d + o_pr, 1056ull * n, hipMemcpyDeviceToHost, s));
-    IK_HIP(hipMemcpyAsync(hp + o_hme, d + o_me, 16ull * n, hipMemcpyDeviceToHost, s));
-    IK_HIP(hipMemcpyAsync(hp + o_hhd, d + o_hdr, sizeof(ik_vp8_segment_header) * n, hipMemcpyDeviceToHost, s));
-    IK_HIP(hipMemcpyAsync(hp + o_herr, d + o_sync, 8, hipMemcpyDeviceToHost, s));
+    IK_HIP(hipMemcpyAsync(hp, d + L.mbs, rec_bytes, hipMemcpyDeviceToHost, s));
+    IK_HIP(hipMemcpyAsync(hp + o_hpr, d + L.pr, 1056ull * n, hipMemcpyDeviceToHost, s));
+    IK_HIP(hipMemcpyAsync(hp + o_hme, d + L.me, 16ull * n, hipMemcpyDeviceToHost, s));
+    IK_HIP(hipMemcpyAsync(hp + o_hhd, d + L.hdr, sizeof(ik_vp8_segment_header) * n, hipMemcpyDeviceToHost, s));
+    IK_HIP(hipMemcpyAsync(hp + o_herr, d + L.sync, 8, hipMemcpyDeviceToHost, s));
     IK_HIP(hipStreamSynchronize(s));
     uint32_t err_word = 0;
     std::memcpy(&err_word, hp + o_herr + 4, 4);
@@ -470,19 +504,56 @@ int webp_encode_exact(const uint8_t* d_yuv, size_t yuv_stride, int n, int w, int
     parallel_for(n, n < 16 ? n : 16, [&](int i) {
         XSeg segs[4];
         for (int sg = 0; sg < 4; ++sg) segs[sg] = setup_segment(hdr[i].quant[sg], hdr[i].dq_uv_dc, hdr[i].dq_uv_ac, 50);
-        write_file(w, h, mbs + (size_t)nmb * i, pr + (size_t)1056 * i, hdr[i], me + (size_t)4 * i, segs, outs[i]);
+        const ImgAt g = at(i);
+        write_file(g.w, g.h, mbs + g.mb0, pr + (size_t)1056 * i, hdr[i], me + (size_t)4 * i, segs, outs[i]);
     });
+    return IK_OK;
+}
+
+}  // namespace
+
+// n images of w x h YUV420 planes on the device (yuv_stride bytes apart) -> the WebP
+// files libwebp's WebPEncodeRGB writes at this quality.  Device work on the thread's
+// coder stream: segment analysis, set-up, ONE persistent launch for every decision and
+// statistics fold, the records back; then the files on the host.
+int webp_encode_exact(const uint8_t* d_yuv, size_t yuv_stride, int n, int w, int h, int quality,
+                      std::vector<std::vector<uint8_t>>& outs) {
+    if (n < 1 || n > 65535 || w < 1 || h < 1 || w > 16383 || h > 16383)
+        return fail(IK_ERR_INVALID, "bad WebP shape %dx%d x %d", w, h, n);
+    hipStream_t s = nullptr;
+    if (int rc = coder_stream(&s)) return rc;
+    const XSchedule& sc = exact_schedule(w, h, n);
+    XArgs a = uniform_args(d_yuv, yuv_stride, w, h);
+    a.use_derr = quality <= 98;  // ERROR_DIFFUSION_QUALITY
+    const size_t nmb = (size_t)a.mb_w * a.mb_h, nep = sc.bounds.size() - 1;
+    const XTotals t{(size_t)n, nmb * n, nep * n, 1, sc.bounds.size(), 0, sc.tasks.size()};
+    const WorkArea L = work_area(t, true);
+    uint8_t* d = scratch_slot(kScratchExact, L.bytes);
+    if (!d) return fail(IK_ERR_DEVICE, "cannot allocate the exact coder's work area (%zu bytes)", L.bytes);
+    if (int rc = upload_constants(d, L, t, &quality, sc.bounds.data(), nullptr, sc.tasks.data(), s)) return rc;
+    XRun r{};
+    fill_args(d, L, t, a, &r);
+    r.nep = (uint32_t)nep;
+    // 1. segment analysis (ik_vp8_analysis.hip), 2. set-up, 3. every decision and fold
+    IK_HIP(vp8::launch_vp8_analysis(d_yuv, yuv_stride, n, w, h, d + L.alpha, (uint16_t*)(d + L.uva), d + L.kseg,
+                                    (vp8::SegRecord*)(d + L.rec), s));
+    IK_HIP(launch_vp8x_setup(a, (const vp8::SegRecord*)(d + L.rec), d + L.kseg, (const int*)(d + L.qtab),
+                             (ik_vp8_segment_header*)(d + L.hdr), n, s));
+    IK_HIP(launch_vp8x_run(a, r, sc.grid, s));
+    if (int rc = read_back_and_write(d, L, t, s, [&](int i) { return ImgAt{w, h, nmb * i}; }, outs)) return rc;
     webp_enc_count(0, (unsigned long long)n);
     return IK_OK;
 }
 
 // n images of their own sizes and qualities, their planes anywhere in device memory,
-// in one set of launches: a descriptor per image (ik_vp8_gpu.h ImgDesc) goes up with
-// the constants, the per-MB arrays are sized by the sum of the images' MBs, the
-// per-epoch ones by the sum of their epochs, and the tickets are the images' steps
-// merged (merge_steps).  Stream handling as webp_encode_exact.  Images that all share
-// one geometry and quality go through webp_encode_exact itself, so a geometry never
-// takes two code paths.
+// in one set of launches.  Images that all share one geometry and quality go through
+// webp_encode_exact itself (gathered first when their planes are unevenly spaced), so a
+// geometry never takes two code paths.  For the rest this is webp_encode_exact's driver
+// with other totals: the per-MB arrays sized by the sum of the images' MBs, the
+// per-epoch ones by the sum of their epochs, a quantiser table per distinct quality, the
+// tickets the images' steps merged (merge_steps).  What it alone has is the descriptor
+// per image (ik_vp8_gpu.h ImgDesc), which goes up with the constants and gives the
+// table-driven kernels each image's planes, geometry and first indices.
 int webp_encode_exact_mixed(const ExactItem* items, int n, std::vector<std::vector<uint8_t>>& outs) {
     if (!items || n < 1 || n > 65535) return fail(IK_ERR_INVALID, "bad mixed WebP call of %d images", n);
     bool same = true;
@@ -495,7 +566,7 @@ int webp_encode_exact_mixed(const ExactItem* items, int n, std::vector<std::vect
     }
     if (same) {
         const int w = items[0].w, h = items[0].h;
-        const size_t ysz = (size_t)w * h + 2 * (size_t)((w + 1) / 2) * ((h + 1) / 2);
+        const size_t ysz = yuv420_bytes(w, h);
         // evenly spaced planes as they lie; others gathered a common stride apart
         bool even = n == 1 || (items[1].yuv > items[0].yuv && (size_t)(items[1].yuv - items[0].yuv) >= ysz);
         const size_t step = n > 1 && even ? (size_t)(items[1].yuv - items[0].yuv) : 0;
@@ -509,17 +580,9 @@ int webp_encode_exact_mixed(const ExactItem* items, int n, std::vector<std::vect
         for (int i = 0; i < n; ++i) IK_HIP(hipMemcpyAsync(g + stride * i, items[i].yuv, ysz, hipMemcpyDeviceToDevice, ts));
         return webp_encode_exact(g, stride, n, w, h, items[0].quality, outs);
     }
-    hipStream_t ts = thread_stream();
-    if (!ts) return fail(IK_ERR_DEVICE, "cannot create HIP stream");
-    hipStream_t s = ts;
-    hipEvent_t ev = nullptr;
-    if (thread_prio_stream(&s, &ev) && s != ts) {
-        IK_HIP(hipEventRecord(ev, ts));
-        IK_HIP(hipStreamWaitEvent(s, ev, 0));
-    } else {
-        s = ts;
-    }
-    // the descriptors, the concatenated epoch bounds, one quantiser table per quality
+    hipStream_t s = nullptr;
+    if (int rc = coder_stream(&s)) return rc;
+    // the descriptors, the concatenated epoch bounds, the distinct qualities
     begin_schedule();
     std::vector<const GeomSteps*> geom((size_t)n);
     std::vector<XImg> desc((size_t)n);
@@ -556,86 +619,26 @@ int webp_encode_exact_mixed(const ExactItem* items, int n, std::vector<std::vect
     static thread_local std::vector<uint64_t> tasks;
     const int widest = merge_steps(geom, tasks);
     const int grid = schedule_grid(widest, tasks.size());
-    // device buffers (one allocation, 256-byte aligned parts); the hand-off words first,
-    // zeroed by one memset per call
-    size_t off = 0;
-    auto part = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t sync_words = 4 + tot_mb + 2 * tot_ep;
-    const size_t o_sync = part(4 * sync_words);
-    const size_t sync_bytes = off;
-    const size_t o_alpha = part(tot_mb), o_uva = part(tot_mb * 2), o_kseg = part(tot_mb);
-    const size_t o_rec = part(sizeof(vp8::SegRecord) * n), o_hdr = part(sizeof(ik_vp8_segment_header) * n);
-    const size_t o_mbs = part(sizeof(XMB) * tot_mb), o_edges = part(sizeof(XEdge) * tot_mb);
-    const size_t o_seg = part(tot_mb), o_segs = part(sizeof(XSeg) * 4 * n);
-    const size_t o_lc = part(2ull * kCostRows * kLevelTab * n), o_pr = part(1056ull * n), o_st = part(4ull * 1056 * n);
-    const size_t o_me = part(16ull * n);
-    const size_t o_qtab = part(4 * 255 * quals.size()), o_bounds = part(4 * bounds.size());
-    const size_t o_desc = part(sizeof(XImg) * n), o_tasks = part(8 * tasks.size());
-    uint8_t* d = scratch_slot(kScratchExact, off);
-    if (!d) return fail(IK_ERR_DEVICE, "cannot allocate the exact coder's work area (%zu bytes)", off);
-    const size_t const_bytes = off - o_qtab;
-    uint8_t* hc = pinned_slot(kPinnedExactIn, const_bytes);
-    if (!hc) return IK_ERR_NOMEM;
-    for (size_t k = 0; k < quals.size(); ++k) segment_quant_table((float)quals[k], reinterpret_cast<int*>(hc) + 255 * k);
-    std::memcpy(hc + (o_bounds - o_qtab), bounds.data(), 4 * bounds.size());
-    std::memcpy(hc + (o_desc - o_qtab), desc.data(), sizeof(XImg) * n);
-    std::memcpy(hc + (o_tasks - o_qtab), tasks.data(), 8 * tasks.size());
-    IK_HIP(hipMemcpyAsync(d + o_qtab, hc, const_bytes, hipMemcpyHostToDevice, s));
-    IK_HIP(hipMemsetAsync(d + o_sync, 0, sync_bytes, s));
+    const XTotals t{(size_t)n, tot_mb, tot_ep, quals.size(), bounds.size(), sizeof(XImg) * n, tasks.size()};
+    const WorkArea L = work_area(t, true);
+    uint8_t* d = scratch_slot(kScratchExact, L.bytes);
+    if (!d) return fail(IK_ERR_DEVICE, "cannot allocate the exact coder's work area (%zu bytes)", L.bytes);
+    if (int rc = upload_constants(d, L, t, quals.data(), bounds.data(), desc.data(), tasks.data(), s)) return rc;
     XArgs a{};  // (planes and geometry: per image, from the descriptors)
-    a.mbs = (XMB*)(d + o_mbs);
-    a.edges = (XEdge*)(d + o_edges);
-    a.seg = d + o_seg;
-    a.segs = (XSeg*)(d + o_segs);
-    a.lc = (uint16_t*)(d + o_lc);
-    a.pr = d + o_pr;
-    a.stats = (uint32_t*)(d + o_st);
-    a.max_edge = (int*)(d + o_me);
     XRun r{};
-    r.tasks = (const uint64_t*)(d + o_tasks);
-    r.ntasks = (uint32_t)tasks.size();
-    r.bounds = (const int*)(d + o_bounds);
-    r.sync = (uint32_t*)(d + o_sync);
-    r.done = r.sync + 4;
-    r.cnt = r.done + tot_mb;
-    r.ready = r.cnt + tot_ep;
-    const XImg* dimgs = (const XImg*)(d + o_desc);
-    IK_HIP(vp8::launch_vp8_analysis_mixed(dimgs, n, max_nmb, d + o_alpha, (uint16_t*)(d + o_uva), d + o_kseg,
-                                          (vp8::SegRecord*)(d + o_rec), s));
-    IK_HIP(launch_vp8x_setup_mixed(a, dimgs, (const vp8::SegRecord*)(d + o_rec), d + o_kseg, (const int*)(d + o_qtab),
-                                   (ik_vp8_segment_header*)(d + o_hdr), n, s));
+    fill_args(d, L, t, a, &r);
+    const XImg* dimgs = (const XImg*)(d + L.desc);
+    IK_HIP(vp8::launch_vp8_analysis_mixed(dimgs, n, max_nmb, d + L.alpha, (uint16_t*)(d + L.uva), d + L.kseg,
+                                          (vp8::SegRecord*)(d + L.rec), s));
+    IK_HIP(launch_vp8x_setup_mixed(a, dimgs, (const vp8::SegRecord*)(d + L.rec), d + L.kseg, (const int*)(d + L.qtab),
+                                   (ik_vp8_segment_header*)(d + L.hdr), n, s));
     IK_HIP(launch_vp8x_run_mixed(a, r, dimgs, grid, s));
-    // the records back, as in webp_encode_exact; the files on the host, each with its own w, h
-    const size_t rec_bytes = sizeof(XMB) * tot_mb;
-    const size_t o_hpr = rec_bytes, o_hme = o_hpr + 1056ull * n, o_hhd = o_hme + 16ull * n;
-    const size_t o_herr = o_hhd + sizeof(ik_vp8_segment_header) * n, hbytes = o_herr + 16;
-    uint8_t* hp = pinned_slot(kPinnedExactOut, hbytes);
-    if (!hp) return IK_ERR_NOMEM;
-    IK_HIP(hipMemcpyAsync(hp, d + o_mbs, rec_bytes, hipMemcpyDeviceToHost, s));
-    IK_HIP(hipMemcpyAsync(hp + o_hpr, d + o_pr, 1056ull * n, hipMemcpyDeviceToHost, s));
-    IK_HIP(hipMemcpyAsync(hp + o_hme, d + o_me, 16ull * n, hipMemcpyDeviceToHost, s));
-    IK_HIP(hipMemcpyAsync(hp + o_hhd, d + o_hdr, sizeof(ik_vp8_segment_header) * n, hipMemcpyDeviceToHost, s));
-    IK_HIP(hipMemcpyAsync(hp + o_herr, d + o_sync, 8, hipMemcpyDeviceToHost, s));
-    IK_HIP(hipStreamSynchronize(s));
-    uint32_t err_word = 0;
-    std::memcpy(&err_word, hp + o_herr + 4, 4);
-    if (err_word) return fail(IK_ERR_DEVICE, "exact WebP coder: a dependency wait timed out on the device");
-    const XMB* mbs = reinterpret_cast<const XMB*>(hp);
-    const uint8_t* pr = hp + o_hpr;
-    const int* me = reinterpret_cast<const int*>(hp + o_hme);
-    const ik_vp8_segment_header* hdr = reinterpret_cast<const ik_vp8_segment_header*>(hp + o_hhd);
-    outs.resize(n);
-    parallel_for(n, n < 16 ? n : 16, [&](int i) {
-        XSeg segs[4];
-        for (int sg = 0; sg < 4; ++sg) segs[sg] = setup_segment(hdr[i].quant[sg], hdr[i].dq_uv_dc, hdr[i].dq_uv_ac, 50);
-        write_file(items[i].w, items[i].h, mbs + desc[(size_t)i].mb0, pr + (size_t)1056 * i, hdr[i], me + (size_t)4 * i,
-                   segs, outs[i]);
-    });
+    auto at = [&](int i) { return ImgAt{items[i].w, items[i].h, desc[(size_t)i].mb0}; };
+    if (int rc = read_back_and_write(d, L, t, s, at, outs)) return rc;
     webp_enc_count(1, (unsigned long long)n);
     webp_enc_count(3, 1);
     return IK_OK;
 }
-
 
 // The exact coder's first two stages alone (ik_vp8_analyze_device): libwebp's segment
 // analysis and the segment set-up on the device, the final segment map and headers
@@ -644,39 +647,25 @@ int vp8_analyze_setup(const uint8_t* d_yuv, size_t yuv_stride, int n, int w, int
                       ik_vp8_segment_header* hdr) {
     hipStream_t s = thread_stream();
     if (!s) return fail(IK_ERR_DEVICE, "cannot create HIP stream");
-    const int mb_w = (w + 15) / 16, mb_h = (h + 15) / 16, nmb = mb_w * mb_h;
-    size_t off = 0;
-    auto part = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_alpha = part((size_t)nmb * n), o_uva = part((size_t)nmb * n * 2), o_kseg = part((size_t)nmb * n);
-    const size_t o_rec = part(sizeof(vp8::SegRecord) * n), o_hdr = part(sizeof(ik_vp8_segment_header) * n);
-    const size_t o_seg = part((size_t)nmb * n), o_segs = part(sizeof(XSeg) * 4 * n);
-    const size_t o_lc = part(2ull * kCostRows * kLevelTab * n), o_pr = part(1056ull * n), o_st = part(4ull * 1056 * n);
-    const size_t o_me = part(16ull * n), o_qtab = part(4 * 255);
-    uint8_t* d = scratch_slot(kScratchExact, off);
-    if (!d) return fail(IK_ERR_DEVICE, "cannot allocate the segment analysis' work area (%zu bytes)", off);
+    XArgs a = uniform_args(d_yuv, yuv_stride, w, h);
+    XTotals t{};
+    t.n = (size_t)n;
+    t.mb = (size_t)a.mb_w * a.mb_h * n;
+    t.quals = 1;
+    const WorkArea L = work_area(t, false);
+    uint8_t* d = scratch_slot(kScratchExact, L.bytes);
+    if (!d) return fail(IK_ERR_DEVICE, "cannot allocate the segment analysis' work area (%zu bytes)", L.bytes);
     uint8_t* hc = pinned_slot(kPinnedExactIn, 4 * 255);
     if (!hc) return IK_ERR_NOMEM;
-    segment_quant_table(quality, reinterpret_cast<int*>(hc));
-    IK_HIP(hipMemcpyAsync(d + o_qtab, hc, 4 * 255, hipMemcpyHostToDevice, s));
-    XArgs a{};
-    a.yuv = d_yuv;
-    a.yuv_stride = yuv_stride;
-    a.w = w;
-    a.h = h;
-    a.mb_w = mb_w;
-    a.mb_h = mb_h;
-    a.seg = d + o_seg;
-    a.segs = (XSeg*)(d + o_segs);
-    a.lc = (uint16_t*)(d + o_lc);
-    a.pr = d + o_pr;
-    a.stats = (uint32_t*)(d + o_st);
-    a.max_edge = (int*)(d + o_me);
-    IK_HIP(vp8::launch_vp8_analysis(d_yuv, yuv_stride, n, w, h, d + o_alpha, (uint16_t*)(d + o_uva), d + o_kseg,
-                                    (vp8::SegRecord*)(d + o_rec), s));
-    IK_HIP(launch_vp8x_setup(a, (const vp8::SegRecord*)(d + o_rec), d + o_kseg, (const int*)(d + o_qtab),
-                             (ik_vp8_segment_header*)(d + o_hdr), n, s));
-    IK_HIP(hipMemcpyAsync(seg, d + o_seg, (size_t)nmb * n, hipMemcpyDeviceToHost, s));
-    IK_HIP(hipMemcpyAsync(hdr, d + o_hdr, sizeof(ik_vp8_segment_header) * n, hipMemcpyDeviceToHost, s));
+    segment_quant_table(quality, reinterpret_cast<int*>(hc));  // (a float here: staged apart from upload_constants)
+    IK_HIP(hipMemcpyAsync(d + L.qtab, hc, 4 * 255, hipMemcpyHostToDevice, s));
+    fill_args(d, L, t, a, nullptr);
+    IK_HIP(vp8::launch_vp8_analysis(d_yuv, yuv_stride, n, w, h, d + L.alpha, (uint16_t*)(d + L.uva), d + L.kseg,
+                                    (vp8::SegRecord*)(d + L.rec), s));
+    IK_HIP(launch_vp8x_setup(a, (const vp8::SegRecord*)(d + L.rec), d + L.kseg, (const int*)(d + L.qtab),
+                             (ik_vp8_segment_header*)(d + L.hdr), n, s));
+    IK_HIP(hipMemcpyAsync(seg, d + L.seg, t.mb, hipMemcpyDeviceToHost, s));
+    IK_HIP(hipMemcpyAsync(hdr, d + L.hdr, sizeof(ik_vp8_segment_header) * n, hipMemcpyDeviceToHost, s));
     IK_HIP(hipStreamSynchronize(s));
     return IK_OK;
 }
@@ -685,29 +674,35 @@ int vp8_analyze_setup(const uint8_t* d_yuv, size_t yuv_stride, int n, int w, int
 
 using namespace ik;
 
+// The files as malloc'd C outputs, all or nothing: on an allocation failure nothing is
+// left for the caller to free and outs / out_lens are not written.
+static int files_to_c_outputs(const std::vector<std::vector<uint8_t>>& files, uint8_t** outs, size_t* out_lens) {
+    const size_t n = files.size();
+    std::vector<uint8_t*> mem(n, nullptr);
+    for (size_t i = 0; i < n; ++i) {
+        mem[i] = (uint8_t*)malloc(files[i].size() ? files[i].size() : 1);
+        if (!mem[i]) {
+            for (size_t j = 0; j < i; ++j) free(mem[j]);
+            return fail(IK_ERR_NOMEM, "out of host memory");
+        }
+        std::memcpy(mem[i], files[i].data(), files[i].size());
+    }
+    for (size_t i = 0; i < n; ++i) {
+        outs[i] = mem[i];
+        out_lens[i] = files[i].size();
+    }
+    return IK_OK;
+}
+
 extern "C" int ik_webp_encode_exact_device(const uint8_t* dev_yuv, size_t yuv_stride, uint32_t n, uint32_t w,
                                            uint32_t h, int quality, uint8_t** outs, size_t* out_lens) {
     IK_API_ENTER();
     if (!dev_yuv || !outs || !out_lens) return fail(IK_ERR_INVALID, "null pointer");
-    const int q = quality < 1 ? 1 : (quality > 100 ? 100 : quality);
-    const size_t ysz = (size_t)w * h + 2 * (size_t)((w + 1) / 2) * ((h + 1) / 2);
+    const size_t ysz = yuv420_bytes(w, h);
     if (n > 1 && yuv_stride < ysz) return fail(IK_ERR_INVALID, "image stride %zu under the planes' %zu bytes", yuv_stride, ysz);
     std::vector<std::vector<uint8_t>> files;
-    if (int rc = webp_encode_exact(dev_yuv, yuv_stride, (int)n, (int)w, (int)h, q, files)) return rc;
-    for (uint32_t i = 0; i < n; ++i) {
-        outs[i] = (uint8_t*)malloc(files[i].size() ? files[i].size() : 1);
-        if (!outs[i]) {
-            for (uint32_t j = 0; j < i; ++j) {
-                free(outs[j]);
-                outs[j] = nullptr;
-                out_lens[j] = 0;
-            }
-            return fail(IK_ERR_NOMEM, "out of host memory");
-        }
-        std::memcpy(outs[i], files[i].data(), files[i].size());
-        out_lens[i] = files[i].size();
-    }
-    return IK_OK;
+    if (int rc = webp_encode_exact(dev_yuv, yuv_stride, (int)n, (int)w, (int)h, clamp_quality(quality), files)) return rc;
+    return files_to_c_outputs(files, outs, out_lens);
 }
 
 extern "C" int ik_webp_encode_exact_items(const ik_webp_exact_item* items, uint32_t n, uint8_t** outs,
@@ -720,25 +715,11 @@ extern "C" int ik_webp_encode_exact_items(const ik_webp_exact_item* items, uint3
         if (!items[i].dev_yuv || items[i].w < 1 || items[i].h < 1 || items[i].w > 16383 || items[i].h > 16383)
             return fail(IK_ERR_INVALID, "bad WebP item %u: %ux%u%s", i, items[i].w, items[i].h,
                         items[i].dev_yuv ? "" : ", null planes");
-        const int q = items[i].quality;
-        it[i] = ExactItem{items[i].dev_yuv, (int)items[i].w, (int)items[i].h, q < 1 ? 1 : (q > 100 ? 100 : q)};
+        it[i] = ExactItem{items[i].dev_yuv, (int)items[i].w, (int)items[i].h, clamp_quality(items[i].quality)};
     }
     std::vector<std::vector<uint8_t>> files;
     if (int rc = webp_encode_exact_mixed(it.data(), (int)n, files)) return rc;
-    std::vector<uint8_t*> mem(n, nullptr);
-    for (uint32_t i = 0; i < n; ++i) {
-        mem[i] = (uint8_t*)malloc(files[i].size() ? files[i].size() : 1);
-        if (!mem[i]) {
-            for (uint32_t j = 0; j < i; ++j) free(mem[j]);
-            return fail(IK_ERR_NOMEM, "out of host memory");
-        }
-        std::memcpy(mem[i], files[i].data(), files[i].size());
-    }
-    for (uint32_t i = 0; i < n; ++i) {
-        outs[i] = mem[i];
-        out_lens[i] = files[i].size();
-    }
-    return IK_OK;
+    return files_to_c_outputs(files, outs, out_lens);
 }
 
 extern "C" long long ik_webp_exact_plan(const uint32_t* w, const uint32_t* h, uint32_t n, uint64_t* tasks, size_t cap,

@@ -84,7 +84,7 @@ int ik_vp8_analyze_device(const uint8_t* dev_yuv, size_t yuv_stride, uint32_t n,
         return fail(IK_ERR_INVALID, "bad VP8 analysis shape %ux%u x %u", w, h, n);
     if (!(quality >= 0.f)) quality = 0.f;
     if (quality > 100.f) quality = 100.f;
-    const size_t ysz = (size_t)w * h + 2 * (size_t)((w + 1) / 2) * ((h + 1) / 2);
+    const size_t ysz = yuv420_bytes(w, h);
     if (n > 1 && yuv_stride < ysz) return fail(IK_ERR_INVALID, "image stride %zu under the planes' %zu bytes", yuv_stride, ysz);
     return vp8_analyze_setup(dev_yuv, yuv_stride, (int)n, (int)w, (int)h, quality, seg, hdr);
 }

@@ -28,14 +28,15 @@ def _planes_bytes(w, h):
     return w * h + 2 * ((w + 1) // 2) * ((h + 1) // 2)
 
 
-def _device_planes(ik, imgs):
+def _device_planes(ik, imgs, gaps=None):
     """Every image through ik_webp_yuv420_device into one device buffer, each at a
-    256-byte aligned offset of its own; returns (buffer, addresses)."""
+    256-byte aligned offset of its own, gaps[i] more bytes (a multiple of 256) left free
+    after image i; returns (buffer, addresses)."""
     offs, total = [], 0
-    for img in imgs:
+    for i, img in enumerate(imgs):
         h, w, _ = img.shape
         offs.append(total)
-        total += (_planes_bytes(w, h) + 255) // 256 * 256
+        total += (_planes_bytes(w, h) + 255) // 256 * 256 + (gaps[i] if gaps and i < len(gaps) else 0)
     dy = ctypes.c_void_p()
     assert ik.ik_dev_alloc(total, ctypes.byref(dy)) == 0
     for img, off in zip(imgs, offs):
@@ -53,10 +54,10 @@ def _device_planes(ik, imgs):
     return dy, [dy.value + o for o in offs]
 
 
-def encode_items(ik, imgs, qs):
+def encode_items(ik, imgs, qs, gaps=None):
     """The files of ik_webp_encode_exact_items for imgs[i] at quality qs[i]."""
     n = len(imgs)
-    dy, addr = _device_planes(ik, imgs)
+    dy, addr = _device_planes(ik, imgs, gaps)
     items = (_lib.WebpExactItem * n)()
     for i, img in enumerate(imgs):
         items[i] = _lib.WebpExactItem(addr[i], img.shape[1], img.shape[0], int(qs[i]))
@@ -142,6 +143,47 @@ def test_delegation_to_the_uniform_call(ik, oracle):
     assert (c2[0] - c1[0], c2[1] - c1[1], c2[3] - c1[3]) == (0, 5, 1), "one quality differs: the mixed call"
     for k, (img, q) in enumerate(zip(imgs, qs)):
         check(got[k], oracle.webp_encode_rgb(img, float(q)), f"image {k} q{q}")
+
+
+def test_gathered_planes(ik, oracle):
+    # one geometry and quality, planes 1024, 1280, 1024 and 1792 bytes apart: the mixed
+    # call gathers them a common stride apart and hands them to the uniform call
+    imgs = [ikutil.synth(33, 20, 3, seed=60 + s, pattern="SN"[s & 1]) for s in range(5)]
+    c0 = counters(ik)
+    got = encode_items(ik, imgs, [80] * 5, gaps=[0, 256, 0, 768])
+    c1 = counters(ik)
+    for k, img in enumerate(imgs):
+        check(got[k], oracle.webp_encode_rgb(img, 80.0), f"gathered image {k}")
+    assert (c1[0] - c0[0], c1[1] - c0[1], c1[3] - c0[3]) == (5, 0, 0), "the uniform call, no mixed call"
+
+
+def test_calls_share_one_work_area(ik, oracle):
+    # the uniform call, the mixed call and ik_vp8_analyze_device in turn on one thread: one
+    # scratch slot, one pair of pinned slots, one schedule cache and one host driver
+    from test_gpu_vp8_analysis import analyze, check as check_analysis
+    uni = [ikutil.synth(33, 20, 3, seed=70 + s, pattern="SNS"[s]) for s in range(3)]
+    uwant = [oracle.webp_encode_rgb(img, 80.0) for img in uni]
+    # 176x160: 110 MBs, over 96, so two epochs (bounds 0, 96, 110)
+    mixed = [uni[0], ikutil.synth(20, 33, 3, seed=73, pattern="N"), ikutil.synth(176, 160, 3, seed=74, pattern="S")]
+    mq = [80, 99, 25]
+
+    def uniform_call(what):
+        got = encode_exact(ik, uni, 80)
+        for k, (g, w) in enumerate(zip(got, uwant)):
+            check(g, w, f"{what}, image {k}")
+        return got
+
+    first = uniform_call("first uniform call")
+    c0 = counters(ik)
+    for k, g in enumerate(encode_items(ik, mixed, mq)):
+        check(g, oracle.webp_encode_rgb(mixed[k], float(mq[k])), f"mixed call, image {k}")
+    c1 = counters(ik)
+    assert (c1[1] - c0[1], c1[3] - c0[3]) == (3, 1), "three sizes: one mixed call"
+    second = uniform_call("uniform call after the mixed one (cached schedule)")
+    for k, a in enumerate(analyze(ik, uni, 80.0)):
+        check_analysis(a, vp8_parse.parse(uwant[k]), f"analysis between the calls, image {k}")
+    third = uniform_call("uniform call after the analysis")
+    assert first == second == third
 
 
 def test_work_area_growth(ik, oracle, mixed_set):
