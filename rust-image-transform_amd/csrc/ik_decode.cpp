@@ -173,7 +173,7 @@ bool unfilter(uint8_t* data, size_t h, size_t rowbytes, size_t bpp, std::vector<
 }  // namespace
 
 int decode_png(const uint8_t* b, size_t n, uint32_t& W, uint32_t& H, uint32_t& C, std::vector<uint8_t>& px,
-               uint32_t* depth_out) {
+               uint32_t* depth_out, bool zlib_only) {
     size_t pos = 8;
     uint32_t w = 0, h = 0;
     int depth = 0, ctype = -1, interlace = 0;
@@ -251,7 +251,7 @@ int decode_png(const uint8_t* b, size_t n, uint32_t& W, uint32_t& H, uint32_t& C
     }
     std::vector<uint8_t>& raw = scratch.raw;
     raw.resize(raw_total);  // contents are overwritten by the inflate (or the decode fails)
-    if (!inflate_exact_libdeflate(idat, raw)) {
+    if (zlib_only || !inflate_exact_libdeflate(idat, raw)) {
         z_stream zs{};
         if (inflateInit(&zs) != Z_OK) return fail(IK_ERR_TRANSFORM, "zlib init failed");
         zs.next_in = idat.data();

@@ -94,6 +94,7 @@ struct PngJob {
     int chunk0 = 0, nchunks = 0;                     // its chunks in the batch chunk table
     pngplan::Lanes lanes;
     int state = 0;                                   // 0 running, 1 verified, -1 host fallback
+    bool suspect = false;                            // the fallback's reason lies in the stream (not in this batch's areas)
     ik_image* img = nullptr;
     // png's EXPAND (palette -> RGB(A), gray below 8 bits -> 8 bits, tRNS -> alpha):
     // the unfiltered rows land in `rows` (rowbytes wide) and k_png_px writes the
@@ -960,8 +961,10 @@ struct PngStage {
     std::vector<int> herr{};     // the entries' resolve flags
 
     void rec(int k) { if (ev.ok) (void)hipEventRecord(ev.e[k], s); }
-    void reject(PngJob& j, const char* why) {
+    // no_room: the batch's areas had no room for a stream that may well be valid
+    void reject(PngJob& j, const char* why, bool no_room = false) {
         j.state = -1;
+        j.suspect = !no_room;
         if (timing) fprintf(stderr, "[png] stream %d (%ux%u) -> host decoder: %s\n", j.idx, j.w, j.h, why);
     }
     void next_search(hipEvent_t after) {  // the stage executor's hook, once per batch
@@ -1238,7 +1241,7 @@ void build_round_lanes(PngStage& T, PngWork& W, bool first) {
     auto job = [&](int k, LaneCursors& cur) {
         PngJob& j = *T.J[k];
         if (j.state) return;
-        if (const char* why = build_job_lanes(j, k, T.wavedec, W, T.ht, cur)) T.reject(j, why);
+        if (const char* why = build_job_lanes(j, k, T.wavedec, W, T.ht, cur)) T.reject(j, why, true);
     };
     if (first && fits) {
         parallel_for(m, 0, [&](int k) {
@@ -1500,7 +1503,7 @@ void png_verified_tables(PngStage& T, PngWork& W) {
             for (size_t i = 0; i < ob.size(); ++i) units_ok = units_ok && j.lanes.res[i].units > 0;
             if (!units_ok) { T.reject(j, "expand units"); continue; }
         }
-        if (!alloc_job_images(j)) { T.reject(j, "image allocation"); continue; }
+        if (!alloc_job_images(j)) { T.reject(j, "image allocation", true); continue; }
         hd[k].obase = W.d_obase + hob.size();  // (the wave decoder's: its unit table, set below)
         hd[k].page_lane = W.d_pages + npg;  // (the page table itself is built while expand runs)
         hd[k].nlanes = (int)ob.size();
@@ -1834,7 +1837,10 @@ void png_hand_out(PngStage& T, ik_image** outs) {
 }
 
 // the host decoder: streams outside the GPU path, and GPU rejects
-void png_host_decode(const PngUpload& up, const std::vector<int>& host, ik_image** outs, int* status, std::string* msgs) {
+// (rejected[i]: the GPU path found stream i corrupt -- zlib judges it; a stream the batch's
+// areas had no room for takes libdeflate like any other)
+void png_host_decode(const PngUpload& up, const std::vector<int>& host, const std::vector<char>& rejected, ik_image** outs,
+                     int* status, std::string* msgs) {
     parallel_for((int)host.size(), 0, [&](int k) {
         const int i = host[k];
         thread_local std::vector<uint8_t> px;
@@ -1851,7 +1857,7 @@ void png_host_decode(const PngUpload& up, const std::vector<int>& host, ik_image
             }
             src = hb.data();
         }
-        int st = decode_png(src, up.lens[i], w, h, c, px, &dep);
+        int st = decode_png(src, up.lens[i], w, h, c, px, &dep, rejected[i] != 0);
         if (!st) st = dep == 2 ? ik_image_from_host16(reinterpret_cast<const uint16_t*>(px.data()), w, h, c, &outs[i])
                                : ik_image_from_host(px.data(), w, h, c, &outs[i]);
         if (px.capacity() > (128u << 20)) std::vector<uint8_t>().swap(px);
@@ -1898,7 +1904,10 @@ int png_decode_finish(PngUpload& up, ik_image** outs, int* status, std::string* 
     T.tim[kTimGpuDecoded] = (double)(n - (int)host.size());
     g_png_gpu_streams += (unsigned long long)(n - (int)host.size());
     g_png_host_streams += (unsigned long long)host.size();
-    png_host_decode(up, host, outs, status, msgs);
+    std::vector<char> rejected(n, 0);
+    for (const PngJob* j : T.J)
+        if (j->state == -1 && j->suspect) rejected[j->idx] = 1;
+    png_host_decode(up, host, rejected, outs, status, msgs);
     T.tim[kTimStageWallMs] = now_ms() - T.t0;
     if (T.m) {
         std::lock_guard<std::mutex> lk(g_timing_mu);

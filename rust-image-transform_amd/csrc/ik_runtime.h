@@ -273,9 +273,11 @@ enum class Sniffed { Png, Jpeg, Gif, WebP, Tiff, Bmp, Ico, Hdr, Avif, OpenExr, Q
 Sniffed guess_format(const uint8_t* b, size_t n);
 const char* format_name(Sniffed f);
 // depth (optional): 16-bit streams decode to native-endian u16 samples (*depth = 2);
-// without it they are unsupported
+// without it they are unsupported.  zlib_only: inflate with zlib, not libdeflate (a stream
+// the GPU path found corrupt: libdeflate accepts code lengths whose last repeat overruns
+// HLIT + HDIST, zlib and the GPU path do not)
 int decode_png(const uint8_t* b, size_t n, uint32_t& w, uint32_t& h, uint32_t& c, std::vector<uint8_t>& px,
-               uint32_t* depth = nullptr);
+               uint32_t* depth = nullptr, bool zlib_only = false);
 uint32_t png_chunk_crc(const uint8_t* type, const uint8_t* data, size_t len);  // CRC-32 of type + data
 // PNG on the GPU (ik_png_decode.cpp + ik_png.hip): inflate + unfilter of n streams
 // in one set of launches, straight into new device images; streams the GPU path

@@ -29,6 +29,7 @@ import pytest
 from PIL import Image
 
 import ikutil
+from deflate_writer import deflate_blocks  # the block walk (RFC 1951), grown into a token walker there
 from imagekit import ImageFormat, decode_image, transform_batch, transform_batch_submit
 
 pytestmark = pytest.mark.gpu
@@ -45,104 +46,6 @@ def window_bits():
 
 
 W = window_bits()
-
-# ---- a DEFLATE block walk (RFC 1951): every block's (type, header bit, body bit, end bit) ----
-_LEXT = [0] * 8 + [1] * 4 + [2] * 4 + [3] * 4 + [4] * 4 + [5] * 4 + [0]
-_DEXT = [0, 0, 0, 0] + [k for k in range(1, 14) for _ in (0, 1)]
-_CLORD = [16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15]
-
-
-def _table(lens):
-    """entry at the next 15 stream bits (first bit lowest): symbol << 4 | code length"""
-    count = [0] * 16
-    for n in lens:
-        count[n] += 1
-    count[0] = 0
-    nxt, code = [0] * 16, 0
-    for b in range(1, 16):
-        code = (code + count[b - 1]) << 1
-        nxt[b] = code
-    tab = [0] * 32768
-    for s, n in enumerate(lens):
-        if n:
-            c = nxt[n]
-            nxt[n] += 1
-            r = int(format(c, "0%db" % n)[::-1], 2)
-            tab[r::1 << n] = [(s << 4) | n] * (32768 >> n)
-    return tab
-
-
-def deflate_blocks(z, max_blocks=None):
-    """The blocks of zlib stream z: (btype, header bit, first body bit, bit past the
-    end-of-block code / the stored bytes); bit positions from the stream's first byte."""
-    buf = z + b"\0" * 8
-
-    def bits(pos, n):
-        return (int.from_bytes(buf[pos >> 3:(pos >> 3) + 4], "little") >> (pos & 7)) & ((1 << n) - 1)
-
-    pos, out = 16, []
-    while True:
-        hdr, final, bt = pos, bits(pos, 1), bits(pos + 1, 2)
-        pos += 3
-        assert bt != 3
-        if bt == 0:
-            pos = (pos + 7) & ~7
-            n = bits(pos, 16)
-            assert n ^ 0xFFFF == bits(pos + 16, 16)
-            body = pos + 32
-            pos = body + 8 * n
-        else:
-            if bt == 1:
-                ll, dl = [8] * 144 + [9] * 112 + [7] * 24 + [8] * 8, [5] * 30
-            else:
-                hlit, hdist, hclen = bits(pos, 5) + 257, bits(pos + 5, 5) + 1, bits(pos + 10, 4) + 4
-                pos += 14
-                cl = [0] * 19
-                for i in range(hclen):
-                    cl[_CLORD[i]] = bits(pos, 3)
-                    pos += 3
-                ct, lens = _table(cl), []
-                while len(lens) < hlit + hdist:
-                    e = ct[bits(pos, 15)]
-                    assert e
-                    s = e >> 4
-                    pos += e & 15
-                    if s < 16:
-                        lens.append(s)
-                    elif s == 16:
-                        lens += [lens[-1]] * (3 + bits(pos, 2))
-                        pos += 2
-                    elif s == 17:
-                        lens += [0] * (3 + bits(pos, 3))
-                        pos += 3
-                    else:
-                        lens += [0] * (11 + bits(pos, 7))
-                        pos += 7
-                assert len(lens) == hlit + hdist
-                ll, dl = lens[:hlit], lens[hlit:]
-            lt, dt = _table(ll), _table(dl)
-            body = pos
-            while True:
-                e = lt[bits(pos, 15)]
-                assert e
-                s = e >> 4
-                pos += e & 15
-                if s < 256:
-                    continue
-                if s == 256:
-                    break
-                pos += _LEXT[s - 257]
-                e = dt[bits(pos, 15)]
-                assert e
-                pos += (e & 15) + _DEXT[e >> 4]
-        out.append((bt, hdr, body, pos))
-        if final:
-            assert ((pos + 7) >> 3) + 4 == len(z), "the walk must end at the Adler-32"
-            break
-        if max_blocks and len(out) >= max_blocks:
-            break
-    return out
-
 
 # ---- the streams ----
 def _chunk(t, d):

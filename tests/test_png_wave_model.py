@@ -8,7 +8,11 @@ check, expand and marker resolution after it), against zlib.
 decode_image on a PNG (reference src/transform.rs:31 -> png 0.18) inflates the
 IDAT zlib stream.  Bar: bytes identical to zlib.decompress for every stream
 shape zlib produces (dynamic, fixed and stored blocks, every level and
-strategy, tiny blocks), planted false candidates and corrupt streams."""
+strategy, tiny blocks), planted false candidates and corrupt streams.  The
+bar does not stop at zlib's shapes: the streams only other writers send
+(distances up to 32768, 48-bit steps, slow-path blocks, one distance code or
+none, the header's extremes, empty blocks) are deflate_streams.py's, run
+through this model by test_png_streams_model.py."""
 import ctypes
 import io
 import os
