@@ -243,6 +243,41 @@ int ik_webp_batch_plan(const uint32_t *mb_w, const uint32_t *mb_h, const uint64_
 /* process-wide JPEG counters: out[0] = streams whose entropy decoding ran on the
  * GPU (restart intervals or self-synchronising scans), out[1] = on the host */
 int ik_jpeg_counters(unsigned long long *out);
+/* process-wide counters of the JPEG files of device-resident batches
+ * (ik_transform_batch_submit_device): out[0] = taken in place, out[1] = copied back
+ * to the host before parsing, out[2] = taken in place but copied back later for the
+ * host decoder (these count in out[0] too) */
+int ik_jpeg_device_counters(unsigned long long *out);
+/* device time (HIP events, ms) of the last marker-walk launch of a device-resident
+ * batch, process-wide; 0 before the first */
+double ik_jpeg_device_walk_ms(void);
+/* Where the baseline JPEG files of a device-resident batch are read from.
+ * IK_JPEG_DEVICE_INPLACE, the default: where they lie.  IK_JPEG_DEVICE_COPY: every
+ * JPEG is copied back to the host at submit, as before in-place decoding existed
+ * (for A/B runs; the outputs are identical).  Process-wide; -1 returns to the
+ * environment, IK_JPEG_DEVICE=inplace|copy, which is read per batch. */
+typedef enum { IK_JPEG_DEVICE_COPY = 0, IK_JPEG_DEVICE_INPLACE = 1 } ik_jpeg_device;
+int ik_set_jpeg_device(int where);
+int ik_get_jpeg_device(void);
+/* The marker walk behind in-place decoding, run on host bytes (no GPU needed; the
+ * same code as the kernel's).  skeleton (cap >= IK_JPEG_SKELETON_BYTES) receives SOI
+ * and, verbatim and in order, the DQT, DHT, SOFn, DRI, APP0 and APP14 segments and
+ * the first SOS header -- itself a JPEG header the parser reads; every other segment
+ * is stepped over.  verdict: 0 in place, 1 copy back, 2 malformed (copied back:
+ * the host parser words the error).  reason: 0 none, 1 not one SOF0/SOF1 8-bit
+ * frame, 2 first scan under 4 KiB, 3 no SOS, 4 skeleton too large, 5 the first SOS
+ * names fewer components than the frame, 6 bytes between segments, 7 a segment
+ * length past the file's end, 8 no SOI.  entropy_offset: the first scan's first
+ * byte (0 when no SOS was reached); eoi_offset: the last FF D9 among the file's
+ * last 4 KiB and not before the scan, else len. */
+#define IK_JPEG_SKELETON_BYTES 4096
+typedef struct {
+    int verdict, reason;
+    int sof_marker;            /* 0xC0..0xCF, 0 = none */
+    uint32_t skeleton_len;
+    uint64_t entropy_offset, eoi_offset;
+} ik_jpeg_walk_info;
+int ik_jpeg_walk_host(const uint8_t *bytes, size_t len, uint8_t *skeleton, size_t cap, ik_jpeg_walk_info *info);
 
 /* resize_image (src/transform.rs:62-90).  w/h < 0 mean None.  Both None returns
  * the input unchanged (*out == img); otherwise a new image (img is not freed:
@@ -348,9 +383,17 @@ int ik_transform_batch_wait(uint64_t ticket);
  * of one device: dev_bytes[i] are device addresses (hipMalloc / ik_dev_alloc),
  * valid until the wait returns.  The batch runs on the device that holds them.
  * PNG files are walked, gathered, CRC-checked and decoded on the GPU where they
- * lie (no PCIe transfer of the compressed bytes); any other item, and a PNG the
- * GPU path does not take, is copied back to host memory first.  Outputs, status
- * and errors as ik_transform_batch_submit; wait with ik_transform_batch_wait.
+ * lie (no PCIe transfer of the compressed bytes).  Baseline JPEG files (one SOF0 /
+ * SOF1 frame, 8 bits, every component in a first scan of 4 KiB or more) are decoded
+ * in place too: a marker walk on the GPU brings back only the table and frame
+ * segments (a few hundred bytes) and two offsets, the host parser reads those, and
+ * the self-synchronising decoder reads the scan from the caller's memory -- nothing
+ * at or past dev_bytes[i] + lens[i] is read.  Such a file is copied back later, and
+ * alone, when the GPU decoder hands it to the host decoder (further scans, a stray
+ * marker, a bad code).  Any other item -- other JPEG kinds, WebP, AVIF, malformed
+ * files -- and a PNG the GPU path does not take is copied back to host memory
+ * first.  The outputs are the same bytes either way (ik_set_jpeg_device).  Outputs,
+ * status and errors as ik_transform_batch_submit; wait with ik_transform_batch_wait.
  * (The reference's handlers receive bodies in host memory, src/lib.rs:175-191;
  * this entry serves callers that already hold them on the device.) */
 int ik_transform_batch_submit_device(const uint8_t *const *dev_bytes, const size_t *lens, uint32_t n,

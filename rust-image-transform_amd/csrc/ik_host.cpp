@@ -27,6 +27,7 @@
 #include "../../include/imagekit_hip.h"
 #include "ik_png.h"
 #include "ik_runtime.h"
+#include "ik_jpeg_walk.h"
 
 namespace ik {
 
@@ -1444,8 +1445,8 @@ static std::string last_error_str() { return t_err; }
 // message (the decoder's own, as TransformError(e.to_string()) carries it).  up:
 // the batch's PNG streams' upload, already issued (png_upload_begin), or null
 // sniff: null, or a host copy of each item's first bytes (sniff_len(i) of them) when
-// bytes holds device addresses for the PNG items (device-resident inputs: every
-// other item is a host copy already)
+// bytes holds device addresses for the PNG items and the JPEG items taken in place
+// (device-resident inputs: every other item is a host copy already)
 static size_t sniff_len(const uint8_t* const* sniff, const uint8_t* const* bytes, const size_t* lens, uint32_t i) {
     return sniff && sniff[i] != bytes[i] ? std::min<size_t>(lens[i], 64) : lens[i];
 }
@@ -1647,8 +1648,8 @@ static void png_items(const uint8_t* const* bytes, const size_t* lens, const uin
         }
 }
 
-// the JPEG requests among idx, host inputs only (device-resident batches copy
-// their non-PNG items to the host first)
+// the JPEG requests among idx, host inputs only (a device-resident batch's JPEG
+// items are read where they lie or were copied to the host at submit: no upload)
 static void jpeg_items(const uint8_t* const* bytes, const size_t* lens, const std::vector<uint32_t>& idx,
                        std::vector<const uint8_t*>& jb, std::vector<size_t>& jl) {
     jb.clear();
@@ -1929,11 +1930,16 @@ struct Ticket {
     std::condition_variable cv;
     int pending = 0;
     // device-resident inputs (ik_transform_batch_submit_device): the request array
-    // the stages read (PNG items: the caller's device addresses; others: host
-    // copies), the host copies, and each item's sniff bytes
+    // the stages read (PNG items and the JPEG items taken in place: the caller's
+    // device addresses; others: host copies), the host copies, and each item's
+    // sniff bytes
     std::vector<const uint8_t*> eff, sniff;
     std::vector<std::vector<uint8_t>> hcopy;
     std::vector<uint8_t> heads;
+    // its baseline JPEG items decoded where they lie: what the marker walk brought
+    // back (by device address), and the skeletons' bytes
+    JpegInPlaceMap jin;
+    std::vector<uint8_t> jskel;
 };
 
 // one device's share of a ticket
@@ -2004,6 +2010,8 @@ private:
                 if (!p->sniff) {
                     jpeg_items(p->bytes, p->lens, p->hp.idx, p->jb, p->jl);
                     if (!p->jb.empty()) jpeg_upload_begin(p->jb.data(), p->jl.data(), (int)p->jb.size(), p->jup);
+                } else if (!p->t->jin.empty()) {
+                    p->jup.inplace = &p->t->jin;  // (no upload: the decoder reads the caller's memory)
                 }
                 {
                     std::lock_guard<std::mutex> lk(mu_);
@@ -2293,9 +2301,12 @@ int ik_transform_batch_submit_device(const uint8_t* const* dev_bytes, const size
     t->heads.assign(64 * (size_t)n, 0);
     {
         DeviceGuard g(phys);
-        // the first 64 bytes of every file, through pinned memory
+        // the first 64 bytes of every file, through pinned memory (the block also
+        // holds the JPEG marker walk's table, records and skeleton slots, below)
         const size_t o_files = (64 * (size_t)n + 255) & ~size_t(255);
-        uint8_t* pin = pinned_slot(7, o_files + 2 * sizeof(uint64_t) * n);
+        const size_t o_jrecs = o_files + 2 * sizeof(uint64_t) * n;
+        const size_t o_jskel = (o_jrecs + sizeof(jwalk::Rec) * n + 255) & ~size_t(255);
+        uint8_t* pin = pinned_slot(7, o_jskel + (size_t)jwalk::kSlot * n);
         void* dp = nullptr;
         if (!pin || hipHostGetDevicePointer(&dp, pin, 0) != hipSuccess || !dp)
             return fail(IK_ERR_NOMEM, "cannot allocate pinned memory for the input headers");
@@ -2309,11 +2320,63 @@ int ik_transform_batch_submit_device(const uint8_t* const* dev_bytes, const size
         IK_HIP(launch_copy_heads(df, df + n, (int)n, reinterpret_cast<uint8_t*>(dp), s));
         IK_HIP(hipStreamSynchronize(s));
         std::memcpy(t->heads.data(), pin, 64 * (size_t)n);
+        // The JPEG files: a marker walk on the GPU brings back each one's skeleton
+        // (table and frame segments), two offsets and a verdict; those it passes stay
+        // where they are, the decoder reads their scans from the caller's memory.
+        std::vector<uint32_t> ji;
+        for (uint32_t i = 0; i < n; ++i)
+            if (dev_bytes[i] && guess_format(t->heads.data() + 64 * (size_t)i, std::min<size_t>(lens[i], 64)) == Sniffed::Jpeg)
+                ji.push_back(i);
+        const size_t nj = ji.size();
+        std::vector<char> in_place(n, 0);
+        if (nj && jpeg_device_inplace()) {
+            for (size_t k = 0; k < nj; ++k) {  // (the kernel above has finished with the table)
+                files[k] = (uint64_t)(uintptr_t)dev_bytes[ji[k]];
+                files[nj + k] = lens[ji[k]];
+            }
+            uint8_t* dpin = reinterpret_cast<uint8_t*>(dp);
+            EvPair& ev = thread_events(0);
+            ev_record(ev.a, s);
+            IK_HIP(launch_jpeg_walk(df, df + nj, (int)nj, dpin + o_jskel, dpin + o_jrecs, s));
+            ev_record(ev.b, s);
+            IK_HIP(hipStreamSynchronize(s));
+            jpeg_device_walk_ms(ev_pair_ms(ev));
+            const jwalk::Rec* recs = reinterpret_cast<const jwalk::Rec*>(pin + o_jrecs);
+            size_t total = 0;
+            for (size_t k = 0; k < nj; ++k)
+                if (recs[k].verdict == jwalk::kInPlace) total += recs[k].skel_len;
+            t->jskel.resize(total);
+            size_t o = 0;
+            for (size_t k = 0; k < nj; ++k) {
+                const jwalk::Rec& r = recs[k];
+                const uint32_t i = ji[k];
+                if (r.verdict != jwalk::kInPlace) continue;
+                auto it = t->jin.find(dev_bytes[i]);
+                if (it != t->jin.end()) {  // the same address twice: one record serves both (another length: copied back)
+                    in_place[i] = it->second.len == lens[i];
+                    continue;
+                }
+                JpegInPlace& J = t->jin[dev_bytes[i]];
+                std::memcpy(t->jskel.data() + o, pin + o_jskel + (size_t)jwalk::kSlot * k, r.skel_len);
+                J.skel = t->jskel.data() + o;
+                J.skel_len = r.skel_len;
+                J.len = lens[i];
+                J.ent_off = r.ent_off;
+                J.eoi_off = r.eoi_off;
+                o += r.skel_len;
+                in_place[i] = 1;
+            }
+        }
+        size_t n_in = 0;
+        for (uint32_t i : ji) n_in += in_place[i] ? 1 : 0;
+        jpeg_device_count(0, n_in);
+        jpeg_device_count(1, nj - n_in);
         // PNG files stay where they are (the upload stage walks and gathers them on
-        // the GPU); any other item comes back to host memory for its host-side parse
+        // the GPU), and so do the JPEG files taken in place; any other item comes
+        // back to host memory for its host-side parse
         for (uint32_t i = 0; i < n; ++i) {
             const uint8_t* hd = t->heads.data() + 64 * (size_t)i;
-            if (!dev_bytes[i] || guess_format(hd, std::min<size_t>(lens[i], 64)) == Sniffed::Png) {
+            if (!dev_bytes[i] || in_place[i] || guess_format(hd, std::min<size_t>(lens[i], 64)) == Sniffed::Png) {
                 t->sniff[i] = dev_bytes[i] ? hd : nullptr;
                 continue;
             }

@@ -186,6 +186,10 @@ hipError_t launch_jsync_bases_decode(const jsync::Scan* scans, int nimg, const i
                                      const jsync::LaneRec* recs, jsync::LaneBase* bases, void* chunk_scratch,
                                      int* status, hipStream_t s);
 size_t jsync_chunk_scratch_bytes(long long lanes);
+// The marker walk over n JPEG files in device memory (ik_jpeg_walk.hip; the walk is
+// ik_jpeg_walk.h): skel takes jwalk::kSlot bytes per file, recs a jwalk::Rec each
+hipError_t launch_jpeg_walk(const uint64_t* files, const uint64_t* lens, int n, uint8_t* skel, void* recs,
+                            hipStream_t s);
 struct JpegScanArgs {
     const uint8_t* data;          // the scan's entropy-coded bytes (stuffed, with RST markers)
     long long size;

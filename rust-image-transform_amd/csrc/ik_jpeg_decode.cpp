@@ -30,6 +30,7 @@
 #include "../../include/imagekit_hip.h"
 #include "ik_png.h"
 #include "ik_runtime.h"
+#include "ik_jpeg_walk.h"
 
 namespace ik {
 namespace {
@@ -184,6 +185,11 @@ struct Decoder {
     const uint8_t* js_data = nullptr;
     size_t js_len = 0;
     long long js_nivl = 0;  // restart intervals the frame must have
+    // a file decoded where it lies in device memory: b..end is its skeleton (the
+    // segments up to the first SOS header), the scan is [ent_off, eoi_off) of the
+    // file on the device, and nothing here can be decoded on the host -- whatever the
+    // self-synchronising decoder does not take sets need_host (the file is copied back)
+    const JpegInPlace* skel = nullptr;
     jsync::Scan js_scan{};  // geometry (device pointers filled at launch)
 
     void ensure_coef() {
@@ -433,9 +439,12 @@ struct Decoder {
         // the scan's end: the last FF D9 of the file (trailing bytes after EOI are
         // ignored, as the parser ignores them), else the file's end
         const uint8_t* e = end;
-        for (const uint8_t* q = end - 2; q >= data && q >= end - 4096; --q)
-            if (q[0] == 0xFF && q[1] == 0xD9) { e = q; break; }
-        if ((size_t)(e - data) < kJsyncMinBytes) return false;
+        if (!skel)
+            for (const uint8_t* q = end - 2; q >= data && q >= end - 4096; --q)
+                if (q[0] == 0xFF && q[1] == 0xD9) { e = q; break; }
+        // (a file in device memory: the walk made the same search, jwalk::walk_file)
+        const size_t len = skel ? (size_t)(skel->eoi_off - skel->ent_off) : (size_t)(e - data);
+        if (len < kJsyncMinBytes) return false;
         a.bpm = bpm;
         a.mcux = mcux;
         a.single = single ? 1 : 0;
@@ -446,8 +455,8 @@ struct Decoder {
         a.W = jsync::kWarmBits;
         js_scan = a;
         js_nivl = restart ? (total_mcu + restart - 1) / restart : 1;
-        js_data = data;
-        js_len = (size_t)(e - data);
+        js_data = skel ? nullptr : data;
+        js_len = len;
         js = true;
         deferred = true;
         next = e;
@@ -519,7 +528,7 @@ struct Decoder {
             need_host = true;
             return IK_OK;
         }
-        if (try_gpu && progressive && !prog_host && prog_enabled()) {
+        if (try_gpu && progressive && !skel && !prog_host && prog_enabled()) {
             scanned = true;
             if (restart > 0 && defer_prog(order, kind, Ss, Se, Al, se, next)) return IK_OK;
             if (!prog.empty()) {  // a later scan the GPU cannot take: all scans on the host
@@ -532,6 +541,10 @@ struct Decoder {
         scanned = true;
         if (try_gpu && first_scan && kind == 0 && ns == (int)comps.size() && defer_jsync(order, se, next))
             return IK_OK;
+        if (skel) {  // the scan's bytes are not on the host
+            need_host = true;
+            return IK_OK;
+        }
         ensure_coef();
         for (auto& c : comps) c.pred = 0;
         eobrun = 0;
@@ -696,8 +709,23 @@ inline size_t up256(size_t x) { return (x + 255) / 256 * 256; }
 
 // process-wide: JPEG streams whose entropy decoding ran on the GPU / on the host
 std::atomic<unsigned long long> g_jpeg_gpu_streams{0}, g_jpeg_host_streams{0};
+// process-wide: JPEG files of device-resident batches taken in place / copied back
+// before parsing / taken in place and copied back later (ik_jpeg_device_counters)
+std::atomic<unsigned long long> g_jpeg_dev[3] = {{0}, {0}, {0}};
+std::atomic<int> g_jpeg_device{-1};  // ik_set_jpeg_device; -1: IK_JPEG_DEVICE, read per batch
 
 }  // namespace
+
+void jpeg_device_count(int which, unsigned long long n) { g_jpeg_dev[which] += n; }
+static std::atomic<float> g_jpeg_walk_ms{0.f};
+void jpeg_device_walk_ms(float ms) { g_jpeg_walk_ms.store(ms); }
+
+bool jpeg_device_inplace() {
+    const int m = g_jpeg_device.load();
+    if (m >= 0) return m == IK_JPEG_DEVICE_INPLACE;
+    const char* e = getenv("IK_JPEG_DEVICE");
+    return !(e && !strcmp(e, "copy"));
+}
 
 // ---- the upload stage's JPEG areas (JpegUpload) ------------------------------------
 struct JpegArea {
@@ -876,6 +904,10 @@ static void jsync_batch(std::vector<std::unique_ptr<Decoder>>& ds, const std::ve
             auto it = up->dev.find(files[idx[k]]);
             if (it != up->dev.end()) on_dev[k] = it->second + (ds[idx[k]]->js_data - files[idx[k]]);
         }
+    // a file of a device-resident batch: the caller's memory (no byte past the scan
+    // is the decoder's to read: the unstuffing kernels' scan_byte stops at scan_len)
+    for (int k = 0; k < m; ++k)
+        if (ds[idx[k]]->skel) on_dev[k] = files[idx[k]] + ds[idx[k]]->skel->ent_off;
     size_t o = 0;
     auto take = [&](size_t bytes) { const size_t r = o; o += up256(bytes); return r; };
     const size_t o_img = take(sizeof(JsImageDev) * m);
@@ -1001,7 +1033,7 @@ static void jsync_batch(std::vector<std::unique_ptr<Decoder>>& ds, const std::ve
     if (st_total && !hdata) { fail_all("memory"); return; }
     if (st_total)
         parallel_for(m, 0, [&](int k) {
-            if (!in_place[k]) std::memcpy(hdata + st_off[k], ds[idx[k]]->js_data, ds[idx[k]]->js_len);
+            if (!in_place[k] && !on_dev[k]) std::memcpy(hdata + st_off[k], ds[idx[k]]->js_data, ds[idx[k]]->js_len);
         });
     const double tm_tables = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     double tm_upwait = -1;  // (IK_TIMING: how long the upload stage's DMA still had to run)
@@ -1041,6 +1073,17 @@ static void jsync_batch(std::vector<std::unique_ptr<Decoder>>& ds, const std::ve
         for (int k = 0; k < m; ++k) {
             const Decoder& d = *ds[idx[k]];
             Lay& L = lay[k];
+            // An image that drops out here still has a Scan the per-image kernels
+            // (k_jsync_settle, k_jsync_seg2: a workgroup / a thread per image of the
+            // batch) load: one with no lanes -- its tables, and an interval table whose
+            // first entry, the lane count of zero intervals, is 0.  (Left zeroed, its
+            // null table pointers were read on the device whenever such an image
+            // shared a batch with one that decodes.)
+            scans[k] = d.js_scan;
+            scans[k].nivl = 0;
+            scans[k].lane0 = L.lane0;
+            scans[k].ivl_lane = reinterpret_cast<const int*>(dev + o_ivlane) + L.ivl0;
+            scans[k].tabs = reinterpret_cast<const JpegHuffTables*>(dev + L.tab);
             if (hst[k] || (long long)tot[2 * k + 1] + 1 != d.js_nivl) continue;  // stray marker / wrong restart count
             const long long* iv = hivl + L.ivl0;
             int* il = ivl_lane.data() + L.ivl0;
@@ -1325,12 +1368,26 @@ int decode_jpeg_batch(const uint8_t* const* bytes, const size_t* lens, int n, ik
     };
     static const bool timing = getenv("IK_TIMING") != nullptr;
     const auto tp0 = std::chrono::steady_clock::now();
+    // files decoded where they lie in device memory (bytes[i] is a device address):
+    // the parser reads the skeleton the marker walk brought back
+    std::vector<const JpegInPlace*> inpl(n, nullptr);
+    if (up && up->inplace)
+        for (int i = 0; i < n; ++i) {
+            auto it = up->inplace->find(bytes[i]);
+            if (it != up->inplace->end()) inpl[i] = &it->second;
+        }
     parallel_for(n, 0, [&](int i) {
         ds[i].reset(new Decoder());
-        ds[i]->b = bytes[i];
-        ds[i]->end = bytes[i] + lens[i];
-        ds[i]->try_gpu = true;
-        st[i] = ds[i]->parse();
+        Decoder& d = *ds[i];
+        d.b = inpl[i] ? inpl[i]->skel : bytes[i];
+        d.end = inpl[i] ? inpl[i]->skel + inpl[i]->skel_len : bytes[i] + lens[i];
+        d.skel = inpl[i];
+        d.try_gpu = true;
+        st[i] = d.parse();
+        if (inpl[i] && (st[i] || !d.js)) {  // not for the GPU after all: the host parser judges the whole file
+            st[i] = IK_OK;
+            d.need_host = true;
+        }
         note(i);
     });
     if (timing)
@@ -1350,9 +1407,25 @@ int decode_jpeg_batch(const uint8_t* const* bytes, const size_t* lens, int n, ik
     // image, the rest (and anything the GPU found inconsistent) with host entropy decoding
     const int nh = (int)host_idx.size();
     host_idx.insert(host_idx.end(), prog_idx.begin(), prog_idx.end());
+    // a file taken in place that the host decoder must take: it is copied back now,
+    // and only it
+    std::vector<std::vector<uint8_t>> back(n);
+    for (int k = 0; k < nh; ++k) {
+        const int i = host_idx[k];
+        if (!inpl[i]) continue;
+        back[i].resize(lens[i]);
+        const hipError_t e = hipMemcpy(back[i].data(), bytes[i], lens[i], hipMemcpyDeviceToHost);
+        if (e != hipSuccess) {
+            st[i] = hip_fail(e, "jpeg copy back");
+            note(i);
+            back[i].clear();
+        }
+        jpeg_device_count(2, 1);
+    }
     parallel_for((int)host_idx.size(), 0, [&](int k) {
         const int i = host_idx[k];
-        st[i] = decode_jpeg_impl(bytes[i], lens[i], &outs[i], k >= nh);
+        if (inpl[i] && back[i].empty()) return;  // (the copy failed)
+        st[i] = decode_jpeg_impl(inpl[i] ? back[i].data() : bytes[i], lens[i], &outs[i], k >= nh);
         note(i);
     });
     int first = IK_OK;
@@ -1382,6 +1455,38 @@ int ik_set_jpeg_reconstruction(int mode) {
 }
 
 int ik_get_jpeg_reconstruction(void) { return ik::jpeg_recon_mode(); }
+
+int ik_jpeg_device_counters(unsigned long long* out) {
+    if (!out) return ik::fail(IK_ERR_INVALID, "null pointer");
+    for (int k = 0; k < 3; ++k) out[k] = ik::g_jpeg_dev[k].load();
+    return IK_OK;
+}
+
+double ik_jpeg_device_walk_ms(void) { return (double)ik::g_jpeg_walk_ms.load(); }
+
+int ik_set_jpeg_device(int where) {
+    if (where < -1 || where > IK_JPEG_DEVICE_INPLACE) return ik::fail(IK_ERR_INVALID, "bad JPEG device mode %d", where);
+    ik::g_jpeg_device.store(where);
+    return IK_OK;
+}
+
+int ik_get_jpeg_device(void) { return ik::jpeg_device_inplace() ? IK_JPEG_DEVICE_INPLACE : IK_JPEG_DEVICE_COPY; }
+
+int ik_jpeg_walk_host(const uint8_t* bytes, size_t len, uint8_t* skeleton, size_t cap, ik_jpeg_walk_info* info) {
+    if (!skeleton || !info || (!bytes && len)) return ik::fail(IK_ERR_INVALID, "null pointer");
+    if (cap < IK_JPEG_SKELETON_BYTES) return ik::fail(IK_ERR_INVALID, "the skeleton buffer holds %zu bytes, not %d", cap, IK_JPEG_SKELETON_BYTES);
+    static_assert(IK_JPEG_SKELETON_BYTES == ik::jwalk::kSlot, "skeleton slot");
+    ik::jwalk::Rec r;
+    ik::jwalk::HostOps ops;
+    ik::jwalk::walk_file(bytes, len, skeleton, r, ops);
+    info->verdict = (int)r.verdict;
+    info->reason = (int)r.reason;
+    info->sof_marker = (int)r.sof;
+    info->skeleton_len = r.skel_len;
+    info->entropy_offset = r.ent_off;
+    info->eoi_offset = r.eoi_off;
+    return IK_OK;
+}
 
 int ik_jpeg_counters(unsigned long long* out) {
     if (!out) return ik::fail(IK_ERR_INVALID, "null pointer");

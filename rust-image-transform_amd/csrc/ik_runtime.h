@@ -363,12 +363,28 @@ int decode_jpeg_device(const uint8_t* b, size_t n, ik_image** out);
 // DMAs' end on the upload thread's stream.  Dropping the JpegUpload (after the
 // batch's decode returned) frees the area for the next batch.
 struct JpegArea;
+// A JPEG file of a device-resident batch that is decoded where it lies
+// (ik_transform_batch_submit_device; the marker walk, ik_jpeg_walk.h): what came
+// back to the host of it.  The file itself stays in the caller's device memory.
+struct JpegInPlace {
+    const uint8_t* skel = nullptr;  // its skeleton: SOI and the segments the parser reads, host memory
+    uint32_t skel_len = 0;
+    size_t len = 0;                 // the file's length
+    uint64_t ent_off = 0, eoi_off = 0;  // the first scan's bytes: [ent_off, eoi_off) of the file
+};
+typedef std::unordered_map<const uint8_t*, JpegInPlace> JpegInPlaceMap;  // by the file's device address
 struct JpegUpload {
     int n = 0;
     std::unordered_map<const uint8_t*, const uint8_t*> dev;  // host file -> its device copy
     hipEvent_t ev = nullptr;
     std::shared_ptr<JpegArea> area;
+    const JpegInPlaceMap* inplace = nullptr;  // device-resident batches: the files taken in place
 };
+// ik_jpeg_device_counters: 0 taken in place, 1 copied back before parsing, 2 copied back later
+void jpeg_device_count(int which, unsigned long long n);
+// IK_JPEG_DEVICE / ik_set_jpeg_device: baseline JPEG bodies in device memory are decoded in place
+bool jpeg_device_inplace();
+void jpeg_device_walk_ms(float ms);  // the last k_jpeg_walk launch's device time (ik_jpeg_device_walk_ms)
 int jpeg_upload_begin(const uint8_t* const* b, const size_t* lens, int n, JpegUpload& up);
 void jpeg_shutdown();  // ik_shutdown: the JPEG upload areas
 // n streams at once: baseline scans entropy-decoded together by the self-
