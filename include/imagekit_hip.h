@@ -259,6 +259,32 @@ double ik_jpeg_device_walk_ms(void);
 typedef enum { IK_JPEG_DEVICE_COPY = 0, IK_JPEG_DEVICE_INPLACE = 1 } ik_jpeg_device;
 int ik_set_jpeg_device(int where);
 int ik_get_jpeg_device(void);
+
+/* Where a progressive JPEG (SOF2, 8-bit) without restart markers is entropy-decoded.
+ * IK_JPEG_PROG_FREE_HOST, the default: on a host core, scan by scan.
+ * IK_JPEG_PROG_FREE_GPU: on the GPU, when no scan of the file has a restart interval in
+ * force and its entropy-coded bytes, over all scans, come to 4 KiB or more -- the DC and
+ * AC first scans through the self-synchronising decoder's launches, together with the
+ * batch's baseline files; DC refinement one bit per block; AC refinement, which does not
+ * synchronise by itself, as one serial chain per component: one GPU lane per chain, which
+ * takes about 1.5 s for a 2000 x 2000 file and about 6 s for a 4096 x 4096 one, in one
+ * launch, where a host core decodes the whole file in 67 ms -- the switch is for
+ * measurement, not for production.  A file whose first scans overlap, or that refines a
+ * band before coding it, stays on the host, which applies scans in file order.  The
+ * pixels are the same either way; a file the GPU finds inconsistent goes to the host
+ * decoder, which reports the reference's error.  Files in device memory are copied back at submit as before.
+ * -1 returns to the environment, IK_JPEG_PROG_FREE=host|gpu, read per file.
+ * IK_JPEG_PROG=0 keeps every progressive scan on the host and wins over this switch.
+ * ik_jpeg_counters counts a file decoded this way as GPU-decoded. */
+typedef enum { IK_JPEG_PROG_FREE_HOST = 0, IK_JPEG_PROG_FREE_GPU = 1 } ik_jpeg_prog_free;
+int ik_set_jpeg_prog_free(int where);
+int ik_get_jpeg_prog_free(void);
+/* Device milliseconds (HIP events) of the last batch that decoded such files on the GPU:
+ * out[0] the self-synchronising launches (shared with the batch's baseline files), out[1]
+ * the DC refinement launches, out[2] the AC refinement chains.  A development aid
+ * (tools/jpeg_prog_bench.py): the three values are process-wide, and decoding threads that
+ * run such batches at the same time overwrite each other's. */
+int ik_jpeg_prog_free_ms(double *out);
 /* The marker walk behind in-place decoding, run on host bytes (no GPU needed; the
  * same code as the kernel's).  skeleton (cap >= IK_JPEG_SKELETON_BYTES) receives SOI
  * and, verbatim and in order, the DQT, DHT, SOFn, DRI, APP0 and APP14 segments and

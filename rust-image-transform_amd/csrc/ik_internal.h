@@ -186,6 +186,14 @@ hipError_t launch_jsync_bases_decode(const jsync::Scan* scans, int nimg, const i
                                      const jsync::LaneRec* recs, jsync::LaneBase* bases, void* chunk_scratch,
                                      int* status, hipStream_t s);
 size_t jsync_chunk_scratch_bytes(long long lanes);
+// Progressive files without restart markers, after their Ah = 0 scans went through
+// the launches above (a jsync::Scan per scan): one DC refinement scan of each of n
+// images (list: their scans' indices; an image's DC refinements go in file order,
+// launch by launch), and every (image, component)'s AC refinement scans in one
+// launch (chains: (first, count) into list, file order); status[scan] |= 16 on a bad code
+hipError_t launch_jprog_dc_refine(const jsync::Scan* scans, const int* list, int n, long long max_blocks, hipStream_t s);
+hipError_t launch_jprog_ac_chain(const jsync::Scan* scans, const int2* chains, int nchains, const int* list, int* status,
+                                 hipStream_t s);
 // The marker walk over n JPEG files in device memory (ik_jpeg_walk.hip; the walk is
 // ik_jpeg_walk.h): skel takes jwalk::kSlot bytes per file, recs a jwalk::Rec each
 hipError_t launch_jpeg_walk(const uint64_t* files, const uint64_t* lens, int n, uint8_t* skel, void* recs,

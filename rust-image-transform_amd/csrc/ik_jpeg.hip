@@ -695,6 +695,14 @@ __device__ int decode_sym(GpuBits& br, const JpegHuffTables& T, int t) {
     return T.vals[t][T.valptr[t][len] + c - T.mincode[t][len]];
 }
 
+// jsync::ac_refine_block's reader over a ring of stuffed bytes
+struct RingReader {
+    GpuBits& br;
+    const JpegHuffTables& T;
+    __device__ int sym(int t) { return decode_sym(br, T, t); }
+    __device__ int get(int n) { return br.get(n); }
+};
+
 }  // namespace
 
 __device__ __forceinline__ void load_tables(const JpegHuffTables* g, JpegHuffTables& T, uint8_t* s_zz) {
@@ -724,7 +732,7 @@ __device__ void prog_interval(const JpegScanArgs& a, const JpegHuffTables& T, co
     int pred[4] = {0, 0, 0, 0};
     int eobrun = 0;
     const int kind = a.kind, Ss = a.Ss, Se = a.Se, Al = a.Al;
-    const int p1 = 1 << Al, m1 = -p1;
+    const int p1 = 1 << Al;
     const long long m0 = (long long)seg * a.restart;
     const int nm = (int)min((long long)a.restart, a.total_mcu - m0);
     const int row_len = a.single ? a.single_bw : a.mcux;
@@ -762,44 +770,10 @@ __device__ void prog_interval(const JpegScanArgs& a, const JpegHuffTables& T, co
                                 break;
                             }
                         }
-                    } else {  // AC refine
-                        int k = Ss;
-                        if (eobrun == 0) {
-                            for (; k <= Se; ++k) {
-                                const int rs = decode_sym(br, T, 4 + a.ta[ci]);
-                                if (rs < 0) { atomicOr(a.err, 2); return; }
-                                int r = rs >> 4, val = 0;
-                                const int sz = rs & 15;
-                                if (sz) {
-                                    if (sz != 1) { atomicOr(a.err, 8); return; }
-                                    val = br.get(1) ? p1 : m1;
-                                } else if (r != 15) {
-                                    eobrun = (1 << r) + (r ? br.get(r) : 0);
-                                    break;  // the rest of the band: the EOB-run pass below
-                                }
-                                // skip r zero-history coefficients, refining the nonzero ones passed
-                                do {
-                                    int16_t* co = blk + s_zz[k];
-                                    if (*co != 0) {
-                                        if (br.get(1) && (*co & p1) == 0) *co = (int16_t)(*co >= 0 ? *co + p1 : *co + m1);
-                                    } else if (--r < 0) {
-                                        break;
-                                    }
-                                    ++k;
-                                } while (k <= Se);
-                                if (val) {
-                                    if (k > Se) { atomicOr(a.err, 4); return; }
-                                    blk[s_zz[k]] = (int16_t)val;
-                                }
-                            }
-                        }
-                        if (eobrun > 0) {
-                            for (; k <= Se; ++k) {
-                                int16_t* co = blk + s_zz[k];
-                                if (*co != 0 && br.get(1) && (*co & p1) == 0) *co = (int16_t)(*co >= 0 ? *co + p1 : *co + m1);
-                            }
-                            --eobrun;
-                        }
+                    } else {  // AC refine (ac_refine_block: shared with k_jprog_ac_chain)
+                        RingReader rd{br, T};
+                        const int bad = jsync::ac_refine_block(rd, s_zz, a.ta[ci], blk, Ss, Se, Al, eobrun);
+                        if (bad) { atomicOr(a.err, bad); return; }
                     }
                 }
         }

@@ -151,6 +151,23 @@ bool prog_enabled() {
     return on;
 }
 
+}  // namespace
+
+std::atomic<int> g_jpeg_prog_free{-1};  // ik_set_jpeg_prog_free; -1: IK_JPEG_PROG_FREE, read per file
+
+// Progressive files without restart markers: IK_JPEG_PROG_FREE=gpu / ik_set_jpeg_prog_free
+// sends their scans to the GPU (the Ah = 0 scans through the self-synchronising
+// decoder, DC refinement a bit per block, AC refinement a serial chain per
+// component); the default keeps them on the host entropy decoder.
+bool jpeg_prog_free_gpu() {
+    const int m = g_jpeg_prog_free.load();
+    if (m >= 0) return m == IK_JPEG_PROG_FREE_GPU;
+    const char* e = getenv("IK_JPEG_PROG_FREE");
+    return e && !strcmp(e, "gpu");
+}
+
+namespace {
+
 struct Decoder {
     const uint8_t* b;
     const uint8_t* end;
@@ -191,6 +208,19 @@ struct Decoder {
     // self-synchronising decoder does not take sets need_host (the file is copied back)
     const JpegInPlace* skel = nullptr;
     jsync::Scan js_scan{};  // geometry (device pointers filled at launch)
+    // a progressive file without restart markers for the GPU (jpeg_prog_free_gpu):
+    // every scan recorded, in file order, with the Huffman tables as they stand at
+    // its SOS; pf once the whole file is recorded and large enough (finish)
+    struct FreeScan {
+        jsync::Scan geom;
+        JpegHuffTables tabs;
+        const uint8_t* data;  // entropy-coded bytes, up to the marker that ends the scan
+        size_t len;
+        int comp;             // the (first) component
+    };
+    std::vector<FreeScan> pf_scans;
+    bool pf = false;
+    uint64_t pf_first[4] = {};  // per component: the coefficients (zigzag index) an Ah = 0 scan has coded
 
     void ensure_coef() {
         if (coef.empty()) coef.assign(nblocks * 64, 0);
@@ -416,9 +446,10 @@ struct Decoder {
     // inside them, and counts the restart markers against the frame's intervals;
     // either mismatch sends the image to the host decoder, which reports png's --
     // zune-jpeg's -- error).
-    bool defer_jsync(const std::vector<int>& order, const uint8_t* data, const uint8_t*& next) {
+    // the self-synchronising decoder's geometry of a scan over the components `order`
+    bool scan_geom(const std::vector<int>& order, jsync::Scan& a, long long& total_mcu) const {
         const bool single = order.size() == 1;
-        jsync::Scan a{};
+        a = jsync::Scan{};
         int bpm = 0;
         for (size_t i = 0; i < order.size(); ++i) {
             const Component& c = comps[order[i]];
@@ -435,7 +466,86 @@ struct Decoder {
         }
         const Component& c0 = comps[order[0]];
         const int single_bw = (c0.dw + 7) / 8, single_bh = (c0.dh + 7) / 8;
-        const long long total_mcu = single ? (long long)single_bw * single_bh : (long long)mcux * mcuy;
+        total_mcu = single ? (long long)single_bw * single_bh : (long long)mcux * mcuy;
+        a.bpm = bpm;
+        a.mcux = mcux;
+        a.single = single ? 1 : 0;
+        a.single_bw = single_bw;
+        a.total_blocks = total_mcu * bpm;
+        a.ivl_blocks = a.total_blocks;
+        a.L = jsync::kLaneBits;
+        a.W = jsync::kWarmBits;
+        return true;
+    }
+
+    // Record a scan of a progressive file without restart markers: its bytes run to
+    // the first marker (fill bytes before it dropped, as the host reader feeds zeros
+    // from a marker's first FF on).  False: a scan the GPU path does not take (more
+    // blocks per MCU than a lane state holds, or an RSTn inside it).
+    bool defer_free(const std::vector<int>& order, int kind, int Ss, int Se, int Al, const uint8_t* data,
+                    const uint8_t*& next) {
+        // The GPU runs an image's Ah = 0 scans together and its refinements after them,
+        // the host decoder every scan in file order.  The two agree when no coefficient
+        // is coded by two first scans and every refinement follows the first scan of
+        // its whole band (T.81 G.1.1.1.1 asks for as much); any other file is the host's.
+        const uint64_t band = (Se == 63 ? ~0ull : (1ull << (Se + 1)) - 1) & ~((1ull << Ss) - 1);
+        const bool first = kind == jsync::kDcFirst || kind == jsync::kAcFirst;
+        for (int c : order)
+            if (first ? (pf_first[c] & band) != 0 : (pf_first[c] & band) != band) return false;
+        if (first)
+            for (int c : order) pf_first[c] |= band;
+        pf_scans.emplace_back();
+        FreeScan& fs = pf_scans.back();
+        long long total_mcu = 0;
+        bool good = scan_geom(order, fs.geom, total_mcu);
+        const uint8_t* q = data;
+        bool at_marker = false;
+        while (good && q + 1 < end) {
+            if (q[0] != 0xFF) {
+                const void* f = std::memchr(q, 0xFF, (size_t)(end - 1 - q));
+                if (!f) break;
+                q = static_cast<const uint8_t*>(f);
+            }
+            const uint8_t m = q[1];
+            if (m == 0x00) { q += 2; continue; }
+            if (m == 0xFF) { ++q; continue; }
+            at_marker = true;
+            if (m >= 0xD0 && m <= 0xD7) good = false;
+            break;
+        }
+        if (!good || (size_t)(end - data) > 0xffffffffu) {
+            pf_scans.pop_back();
+            return false;
+        }
+        const uint8_t* e = at_marker ? q : end;
+        if (at_marker)
+            while (e > data && e[-1] == 0xFF) --e;
+        fs.geom.kind = kind;
+        fs.geom.Ss = Ss;
+        fs.geom.Se = Se;
+        fs.geom.Al = Al;
+        fs.data = data;
+        fs.len = (size_t)(e - data);
+        fs.comp = order[0];
+        tables(fs.tabs);
+        next = at_marker ? q : end;
+        return true;
+    }
+
+    // after parse(): a recorded restart-free progressive file goes to the GPU when its
+    // entropy-coded bytes, over all scans, reach the baseline path's threshold
+    void finish() {
+        if (pf_scans.empty() || need_host) return;
+        size_t total = 0;
+        for (const FreeScan& f : pf_scans) total += f.len;
+        if (total >= kJsyncMinBytes) pf = true;
+        else need_host = true;
+    }
+
+    bool defer_jsync(const std::vector<int>& order, const uint8_t* data, const uint8_t*& next) {
+        jsync::Scan a{};
+        long long total_mcu = 0;
+        if (!scan_geom(order, a, total_mcu)) return false;
         // the scan's end: the last FF D9 of the file (trailing bytes after EOI are
         // ignored, as the parser ignores them), else the file's end
         const uint8_t* e = end;
@@ -445,14 +555,7 @@ struct Decoder {
         // (a file in device memory: the walk made the same search, jwalk::walk_file)
         const size_t len = skel ? (size_t)(skel->eoi_off - skel->ent_off) : (size_t)(e - data);
         if (len < kJsyncMinBytes) return false;
-        a.bpm = bpm;
-        a.mcux = mcux;
-        a.single = single ? 1 : 0;
-        a.single_bw = single_bw;
-        a.total_blocks = total_mcu * bpm;
-        a.ivl_blocks = restart ? (long long)restart * bpm : a.total_blocks;
-        a.L = jsync::kLaneBits;
-        a.W = jsync::kWarmBits;
+        if (restart) a.ivl_blocks = (long long)restart * a.bpm;
         js_scan = a;
         js_nivl = restart ? (total_mcu + restart - 1) / restart : 1;
         js_data = skel ? nullptr : data;
@@ -530,6 +633,16 @@ struct Decoder {
         }
         if (try_gpu && progressive && !skel && !prog_host && prog_enabled()) {
             scanned = true;
+            // no restart interval in force at any scan: the file is recorded for the
+            // GPU where the switch says so; a scan that cannot be, or a restart
+            // interval after recorded scans, sends every scan to the host
+            if (!pf_scans.empty() || (restart == 0 && prog.empty() && jpeg_prog_free_gpu())) {
+                if (restart == 0 && defer_free(order, kind, Ss, Se, Al, se, next)) return IK_OK;
+                if (!pf_scans.empty()) {
+                    need_host = true;
+                    return IK_OK;
+                }
+            }
             if (restart > 0 && defer_prog(order, kind, Ss, Se, Al, se, next)) return IK_OK;
             if (!prog.empty()) {  // a later scan the GPU cannot take: all scans on the host
                 need_host = true;
@@ -713,6 +826,9 @@ std::atomic<unsigned long long> g_jpeg_gpu_streams{0}, g_jpeg_host_streams{0};
 // before parsing / taken in place and copied back later (ik_jpeg_device_counters)
 std::atomic<unsigned long long> g_jpeg_dev[3] = {{0}, {0}, {0}};
 std::atomic<int> g_jpeg_device{-1};  // ik_set_jpeg_device; -1: IK_JPEG_DEVICE, read per batch
+// ik_jpeg_prog_free_ms: the last batch with restart-free progressive files -- device ms of
+// the self-synchronising launches, the DC refinement launches, the AC refinement chains
+std::atomic<float> g_prog_free_ms[3] = {{0.f}, {0.f}, {0.f}};
 
 }  // namespace
 
@@ -889,80 +1005,123 @@ static void jsync_batch(std::vector<std::unique_ptr<Decoder>>& ds, const std::ve
     const auto t0 = std::chrono::steady_clock::now();
     constexpr int kChunkBytes = 4096;
     // ---- layout ----
-    struct Lay {
-        size_t scan, out, ivl, qt, tab, coef, pl;
+    // An item is one scan of one image: a baseline image has one, a progressive file
+    // without restart markers (Decoder::pf) one per scan, in file order.  Each has
+    // its own unstuffed words, table slot, interval table (progressive: one interval),
+    // chunks and -- the Ah = 0 kinds -- lane range; the coefficients, planes and
+    // quantisation tables are the image's.
+    struct Item {
+        int k;                 // the image (index into idx)
+        const Decoder::FreeScan* fs;  // null: the baseline scan
+        const uint8_t* data;
+        size_t len;
+        long long nivl;
+        int kind;
+        size_t scan, out, tab;
         long long lanes_max, lane0;
         int chunk0, nchunks, ivl0;
+    };
+    struct ImgLay {
+        size_t qt, coef, pl;
+        int item0, nitems;
         JpegGeom g;
     };
-    std::vector<Lay> lay(m);
+    std::vector<Item> items;
+    std::vector<ImgLay> lay(m);
+    for (int k = 0; k < m; ++k) {
+        const Decoder& d = *ds[idx[k]];
+        lay[k].item0 = (int)items.size();
+        if (d.pf) {
+            for (const auto& fs : d.pf_scans) {
+                Item it{};
+                it.k = k; it.fs = &fs; it.data = fs.data; it.len = fs.len; it.nivl = 1; it.kind = fs.geom.kind;
+                items.push_back(it);
+            }
+        } else {
+            Item it{};
+            it.k = k; it.fs = nullptr; it.data = d.js_data; it.len = d.js_len; it.nivl = d.js_nivl; it.kind = kBaseline;
+            items.push_back(it);
+        }
+        lay[k].nitems = (int)items.size() - lay[k].item0;
+    }
+    const int ni = (int)items.size();
+    auto has_lanes = [](int kind) { return kind == kBaseline || kind == kDcFirst || kind == kAcFirst; };
     // scans the upload stage already put on the device (JpegUpload) are read where
     // they lie: no scratch copy is laid out for them
-    std::vector<const uint8_t*> on_dev(m, nullptr);
+    std::vector<const uint8_t*> on_dev(ni, nullptr);
     if (up && up->n)
-        for (int k = 0; k < m; ++k) {
-            auto it = up->dev.find(files[idx[k]]);
-            if (it != up->dev.end()) on_dev[k] = it->second + (ds[idx[k]]->js_data - files[idx[k]]);
+        for (int t = 0; t < ni; ++t) {
+            const int i = idx[items[t].k];
+            if (ds[i]->skel) continue;
+            auto it = up->dev.find(files[i]);
+            if (it != up->dev.end()) on_dev[t] = it->second + (items[t].data - files[i]);
         }
     // a file of a device-resident batch: the caller's memory (no byte past the scan
     // is the decoder's to read: the unstuffing kernels' scan_byte stops at scan_len)
-    for (int k = 0; k < m; ++k)
-        if (ds[idx[k]]->skel) on_dev[k] = files[idx[k]] + ds[idx[k]]->skel->ent_off;
+    for (int t = 0; t < ni; ++t) {
+        const int i = idx[items[t].k];
+        if (ds[i]->skel) on_dev[t] = files[i] + ds[i]->skel->ent_off;
+    }
     size_t o = 0;
     auto take = [&](size_t bytes) { const size_t r = o; o += up256(bytes); return r; };
-    const size_t o_img = take(sizeof(JsImageDev) * m);
+    const size_t o_img = take(sizeof(JsImageDev) * ni);
     int nchunks = 0, nivl_total = 0;
     long long lanes_max = 0;
     // lane length: 1,024 bits, longer for large batches (up to 4,096) while the batch
     // still has ~kJsyncLanes lanes -- a longer lane costs the sync pass less warm-up
     // per bit and the fix rounds about as many rounds (ik_jpeg_model.cpp on the
-    // bench's 4096^2 frames: sync + fix work 2.8x the scan at 1,024, 1.7x at 4,096)
+    // bench's 4096^2 frames: sync + fix work 2.8x the scan at 1,024, 1.7x at 4,096).
+    // The bits are those of every scan that takes lanes: the baseline scans and the
+    // progressive first scans.
     long long batch_bits = 0;
-    for (int k = 0; k < m; ++k) batch_bits += 8ll * (long long)ds[idx[k]]->js_len;
+    for (const Item& it : items)
+        if (has_lanes(it.kind)) batch_bits += 8ll * (long long)it.len;
     const int lane_bits = (int)std::min<long long>(4 * kLaneBits,
                                                    std::max<long long>(1, batch_bits / kJsyncLanes / kLaneBits) * kLaneBits);
-    for (int k = 0; k < m; ++k) {
-        const Decoder& d = *ds[idx[k]];
-        Lay& L = lay[k];
+    for (Item& L : items) {
         L.chunk0 = nchunks;
-        L.nchunks = (int)((d.js_len + kChunkBytes - 1) / kChunkBytes);
+        L.nchunks = (int)((L.len + kChunkBytes - 1) / kChunkBytes);
         nchunks += L.nchunks;
         L.ivl0 = nivl_total;
-        nivl_total += (int)d.js_nivl + 1;
+        nivl_total += (int)L.nivl + 1;
         L.lane0 = lanes_max;
-        L.lanes_max = ((long long)(8 * d.js_len) / lane_bits + d.js_nivl + 1 + 255) & ~255ll;
+        L.lanes_max = has_lanes(L.kind) ? ((long long)(8 * L.len) / lane_bits + L.nivl + 1 + 255) & ~255ll : 0;
         lanes_max += L.lanes_max;
     }
     const size_t o_chunks = take(sizeof(int2) * nchunks);
-    for (int k = 0; k < m; ++k) lay[k].tab = take(sizeof(JpegHuffTables));
+    for (Item& L : items) L.tab = take(sizeof(JpegHuffTables));
     for (int k = 0; k < m; ++k) lay[k].qt = take(512);
     const size_t small_end = o;  // [images | chunks | tables | qt]: one upload
-    const size_t o_status = take(sizeof(int) * m), o_totals = take(sizeof(uint32_t) * 2 * m);
+    const size_t o_status = take(sizeof(int) * ni), o_totals = take(sizeof(uint32_t) * 2 * ni);
     const size_t o_ivl = take(sizeof(long long) * nivl_total);  // contiguous: one read-back
     const size_t small2_end = o;  // [status | totals | ivl]: one read-back
     const size_t o_counts = take(sizeof(uint2) * nchunks);
-    const size_t o_scans = take(sizeof(Scan) * m);
+    const size_t o_scans = take(sizeof(Scan) * ni);
     const size_t o_ivlane = take(sizeof(int) * nivl_total);
     const size_t o_wgs = take(sizeof(int2) * (size_t)(lanes_max / 256));
-    const size_t tab2_bytes = o - o_scans;  // [scans | ivl_lane | wgs]: the second upload
+    const size_t o_rlist = take(sizeof(int) * ni);       // the refinement scans: DC by launch, then AC by chain
+    const size_t o_chains = take(sizeof(int2) * 4 * m);  // (image, component) chains of AC refinement scans
+    const size_t tab2_bytes = o - o_scans;  // [scans | ivl_lane | wgs | refinement lists]: the second upload
     const size_t o_changed = take(256);
     const size_t o_recs = take(sizeof(LaneRec) * (size_t)lanes_max);
     const size_t o_bases = take(sizeof(LaneBase) * (size_t)lanes_max);
     const size_t o_cs = take(jsync_chunk_scratch_bytes(lanes_max));
     const size_t o_items = take(sizeof(JpegReconItem) * m);  // the reconstruction launches' image table
+    for (int t = 0; t < ni; ++t) {
+        Item& L = items[t];
+        L.scan = on_dev[t] ? 0 : take(L.len + 64);
+        L.out = take(L.len + 4 * kPadWords + 8);
+    }
     for (int k = 0; k < m; ++k) {
         const Decoder& d = *ds[idx[k]];
-        Lay& L = lay[k];
-        L.scan = on_dev[k] ? 0 : take(d.js_len + 64);
-        L.out = take(d.js_len + 4 * kPadWords + 8);
-        const size_t pb = make_geom(d, L.g);
-        L.coef = take(d.nblocks * 64 * sizeof(int16_t));
-        L.pl = take(pb);
+        const size_t pb = make_geom(d, lay[k].g);
+        lay[k].coef = take(d.nblocks * 64 * sizeof(int16_t));
+        lay[k].pl = take(pb);
     }
     hipStream_t s = thread_stream();
     uint8_t* dev = scratch_slot(1, o);
     const size_t pin_bytes = std::max(std::max(small_end, sizeof(JpegReconItem) * m + 256),
-                                      std::max(small2_end - o_status, tab2_bytes)) + up256(sizeof(int) * m) + 256;
+                                      std::max(small2_end - o_status, tab2_bytes)) + up256(sizeof(int) * ni) + 256;
     uint8_t* hp = dev ? pinned_slot(1, pin_bytes) : nullptr;
     auto fail_all = [&](const char* why) {
         (void)why;
@@ -994,46 +1153,46 @@ static void jsync_batch(std::vector<std::unique_ptr<Decoder>>& ds, const std::ve
     {
         JsImageDev* I = reinterpret_cast<JsImageDev*>(hp + o_img);
         int2* ch = reinterpret_cast<int2*>(hp + o_chunks);
-        for (int k = 0; k < m; ++k) {
-            const Decoder& d = *ds[idx[k]];
-            const Lay& L = lay[k];
-            JsImageDev& J = I[k];
+        for (int t = 0; t < ni; ++t) {
+            const Item& L = items[t];
+            JsImageDev& J = I[t];
             J = JsImageDev{};
             J.scan = dev + L.scan;
-            J.scan_len = (long long)d.js_len;
+            J.scan_len = (long long)L.len;
             J.out = dev + L.out;
             J.ivl = reinterpret_cast<long long*>(dev + o_ivl) + L.ivl0;
-            J.ivl_cap = (int)d.js_nivl + 1;
+            J.ivl_cap = (int)L.nivl + 1;
             J.chunk0 = L.chunk0;
             J.nchunks = L.nchunks;
-            J.totals = reinterpret_cast<uint32_t*>(dev + o_totals) + 2 * k;
-            J.status = reinterpret_cast<int*>(dev + o_status) + k;
-            for (int c = 0; c < L.nchunks; ++c) ch[L.chunk0 + c] = make_int2(k, c);
+            J.totals = reinterpret_cast<uint32_t*>(dev + o_totals) + 2 * t;
+            J.status = reinterpret_cast<int*>(dev + o_status) + t;
+            for (int c = 0; c < L.nchunks; ++c) ch[L.chunk0 + c] = make_int2(t, c);
         }
-        parallel_for(m, 0, [&](int k) {
-            const Decoder& d = *ds[idx[k]];
-            d.tables(*reinterpret_cast<JpegHuffTables*>(hp + lay[k].tab));
-            qtables(d, reinterpret_cast<uint16_t*>(hp + lay[k].qt));
+        parallel_for(ni, 0, [&](int t) {
+            const Item& L = items[t];
+            JpegHuffTables* T = reinterpret_cast<JpegHuffTables*>(hp + L.tab);
+            if (L.fs) std::memcpy(T, &L.fs->tabs, sizeof(JpegHuffTables));  // as they stood at the scan's SOS
+            else ds[idx[L.k]]->tables(*T);
         });
+        parallel_for(m, 0, [&](int k) { qtables(*ds[idx[k]], reinterpret_cast<uint16_t*>(hp + lay[k].qt)); });
     }
     // the scan bytes: where the upload stage put them (JpegUpload), else DMAed in
     // place from page-locked memory, else through pinned staging
-    std::vector<char> in_place(m, 0);
-    std::vector<size_t> st_off(m, 0);
+    std::vector<char> in_place(ni, 0);
+    std::vector<size_t> st_off(ni, 0);
     size_t st_total = 0;
-    for (int k = 0; k < m; ++k) {
-        const Decoder& d = *ds[idx[k]];
-        if (on_dev[k]) continue;
-        in_place[k] = host_pinned(d.js_data, d.js_len) ? 1 : 0;
-        if (!in_place[k]) { st_off[k] = st_total; st_total += up256(d.js_len); }
+    for (int t = 0; t < ni; ++t) {
+        if (on_dev[t]) continue;
+        in_place[t] = host_pinned(items[t].data, items[t].len) ? 1 : 0;
+        if (!in_place[t]) { st_off[t] = st_total; st_total += up256(items[t].len); }
     }
-    for (int k = 0; k < m; ++k)
-        if (on_dev[k]) reinterpret_cast<JsImageDev*>(hp + o_img)[k].scan = on_dev[k];
+    for (int t = 0; t < ni; ++t)
+        if (on_dev[t]) reinterpret_cast<JsImageDev*>(hp + o_img)[t].scan = on_dev[t];
     uint8_t* hdata = st_total ? pinned_slot(2, st_total) : nullptr;
     if (st_total && !hdata) { fail_all("memory"); return; }
     if (st_total)
-        parallel_for(m, 0, [&](int k) {
-            if (!in_place[k] && !on_dev[k]) std::memcpy(hdata + st_off[k], ds[idx[k]]->js_data, ds[idx[k]]->js_len);
+        parallel_for(ni, 0, [&](int t) {
+            if (!in_place[t] && !on_dev[t]) std::memcpy(hdata + st_off[t], items[t].data, items[t].len);
         });
     const double tm_tables = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     double tm_upwait = -1;  // (IK_TIMING: how long the upload stage's DMA still had to run)
@@ -1043,17 +1202,19 @@ static void jsync_batch(std::vector<std::unique_ptr<Decoder>>& ds, const std::ve
         tm_upwait = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw).count();
     }
     hipError_t e = h2d(dev, 0, small_end);
-    for (int k = 0; k < m && e == hipSuccess; ++k) {
-        const Decoder& d = *ds[idx[k]];
-        if (on_dev[k]) continue;
-        e = hipMemcpyAsync(dev + lay[k].scan, in_place[k] ? d.js_data : hdata + st_off[k], d.js_len,
+    for (int t = 0; t < ni && e == hipSuccess; ++t) {
+        if (on_dev[t] || !items[t].len) continue;
+        e = hipMemcpyAsync(dev + items[t].scan, in_place[t] ? items[t].data : hdata + st_off[t], items[t].len,
                            hipMemcpyHostToDevice, s);
     }
     if (e == hipSuccess && up && up->n && up->ev) e = hipStreamWaitEvent(s, up->ev, 0);
     if (e == hipSuccess) e = hipMemsetAsync(dev + o_status, 0, small2_end - o_status, s);
+    // a progressive image's scans each store only what they code: its coefficients start at zero
+    for (int k = 0; k < m && e == hipSuccess; ++k)
+        if (ds[idx[k]]->pf) e = hipMemsetAsync(dev + lay[k].coef, 0, ds[idx[k]]->nblocks * 64 * sizeof(int16_t), s);
     // ---- 2. unstuffing; the interval tables back ----
     if (e == hipSuccess)
-        e = launch_jsync_unstuff(reinterpret_cast<JsImageDev*>(dev + o_img), m,
+        e = launch_jsync_unstuff(reinterpret_cast<JsImageDev*>(dev + o_img), ni,
                                  reinterpret_cast<const int2*>(dev + o_chunks), nchunks,
                                  reinterpret_cast<uint2*>(dev + o_counts), s);
     if (e == hipSuccess) e = d2h(0, dev + o_status, small2_end - o_status);
@@ -1061,10 +1222,10 @@ static void jsync_batch(std::vector<std::unique_ptr<Decoder>>& ds, const std::ve
     if (e != hipSuccess) { (void)hip_fail(e, "jpeg unstuff"); fail_all("device"); return; }
     const double t_unstuff = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     // ---- 3. lanes ----
-    std::vector<int> ok(m, 0), hstatus(m);
+    std::vector<int> ok(m, 0), hstatus(m, 0);
     std::vector<int> ivl_lane((size_t)nivl_total, 0);
     std::vector<int2> wgs;
-    std::vector<Scan> scans(m);
+    std::vector<Scan> scans(ni);
     long long lanes_used = 0;
     {
         const int* hst = reinterpret_cast<const int*>(hp);
@@ -1072,75 +1233,138 @@ static void jsync_batch(std::vector<std::unique_ptr<Decoder>>& ds, const std::ve
         const long long* hivl = reinterpret_cast<const long long*>(hp + (o_ivl - o_status));
         for (int k = 0; k < m; ++k) {
             const Decoder& d = *ds[idx[k]];
-            Lay& L = lay[k];
-            // An image that drops out here still has a Scan the per-image kernels
-            // (k_jsync_settle, k_jsync_seg2: a workgroup / a thread per image of the
-            // batch) load: one with no lanes -- its tables, and an interval table whose
+            const ImgLay& IL = lay[k];
+            // An image that drops out here still has Scans the per-scan kernels
+            // (k_jsync_settle, k_jsync_seg2: a workgroup / a thread per scan of the
+            // batch) load: ones with no lanes -- their tables, and an interval table whose
             // first entry, the lane count of zero intervals, is 0.  (Left zeroed, its
             // null table pointers were read on the device whenever such an image
             // shared a batch with one that decodes.)
-            scans[k] = d.js_scan;
-            scans[k].nivl = 0;
-            scans[k].lane0 = L.lane0;
-            scans[k].ivl_lane = reinterpret_cast<const int*>(dev + o_ivlane) + L.ivl0;
-            scans[k].tabs = reinterpret_cast<const JpegHuffTables*>(dev + L.tab);
-            if (hst[k] || (long long)tot[2 * k + 1] + 1 != d.js_nivl) continue;  // stray marker / wrong restart count
-            const long long* iv = hivl + L.ivl0;
-            int* il = ivl_lane.data() + L.ivl0;
             bool good = true;
-            il[0] = 0;
-            for (long long q = 0; q < d.js_nivl; ++q) {
-                const long long bits = iv[q + 1] - iv[q];
-                if (bits < 0) { good = false; break; }
-                il[q + 1] = il[q] + (int)std::max<long long>(1, (bits + lane_bits - 1) / lane_bits);
+            for (int t = IL.item0; t < IL.item0 + IL.nitems; ++t) {
+                const Item& L = items[t];
+                scans[t] = L.fs ? L.fs->geom : d.js_scan;
+                scans[t].nivl = 0;
+                scans[t].lane0 = L.lane0;
+                scans[t].ivl_lane = reinterpret_cast<const int*>(dev + o_ivlane) + L.ivl0;
+                scans[t].tabs = reinterpret_cast<const JpegHuffTables*>(dev + L.tab);
+                if (hst[t] || (long long)tot[2 * t + 1] + 1 != L.nivl) { good = false; continue; }  // stray marker / wrong restart count
+                if (!has_lanes(L.kind)) continue;  // (a refinement scan: no lanes, ivl_lane stays 0, 0)
+                const long long* iv = hivl + L.ivl0;
+                int* il = ivl_lane.data() + L.ivl0;
+                il[0] = 0;
+                for (long long q = 0; q < L.nivl; ++q) {
+                    const long long bits = iv[q + 1] - iv[q];
+                    if (bits < 0) { good = false; break; }
+                    il[q + 1] = il[q] + (int)std::max<long long>(1, (bits + lane_bits - 1) / lane_bits);
+                }
+                if (il[L.nivl] > L.lanes_max) good = false;
             }
-            if (!good || il[d.js_nivl] > L.lanes_max) continue;
+            if (!good) {
+                for (int t = IL.item0; t < IL.item0 + IL.nitems; ++t)
+                    for (long long q = 0; q <= items[t].nivl; ++q) ivl_lane[items[t].ivl0 + q] = 0;
+                continue;
+            }
             ok[k] = 1;
-            const int nl = il[d.js_nivl];
-            lanes_used += nl;
-            for (int w = 0; w < nl; w += 256) wgs.push_back(make_int2(k, w));
-            Scan& S = scans[k];
-            S = d.js_scan;
-            S.L = lane_bits;
-            S.words = reinterpret_cast<const uint32_t*>(dev + L.out);
-            S.ivl = reinterpret_cast<const long long*>(dev + o_ivl) + L.ivl0;
-            S.nivl = (int)d.js_nivl;
-            S.lane0 = L.lane0;
-            S.ivl_lane = reinterpret_cast<const int*>(dev + o_ivlane) + L.ivl0;
-            S.tabs = reinterpret_cast<const JpegHuffTables*>(dev + L.tab);
-            S.coef = reinterpret_cast<int16_t*>(dev + L.coef);
+            for (int t = IL.item0; t < IL.item0 + IL.nitems; ++t) {
+                const Item& L = items[t];
+                const int nl = ivl_lane[L.ivl0 + L.nivl];
+                lanes_used += nl;
+                for (int w = 0; w < nl; w += 256) wgs.push_back(make_int2(t, w));
+                Scan& S = scans[t];
+                S.L = lane_bits;
+                S.words = reinterpret_cast<const uint32_t*>(dev + L.out);
+                S.ivl = reinterpret_cast<const long long*>(dev + o_ivl) + L.ivl0;
+                S.nivl = (int)L.nivl;
+                S.coef = reinterpret_cast<int16_t*>(dev + IL.coef);
+            }
         }
     }
     for (int k = 0; k < m; ++k)
         if (!ok[k]) host_idx.push_back(idx[k]);
     const int nwg = (int)wgs.size();
     if (!nwg) return;
-    std::memcpy(hp, scans.data(), sizeof(Scan) * m);
+    // the refinement scans of the progressive images: launch r takes the r-th DC
+    // refinement scan of every image that has one; a chain per (image, component)
+    // takes that component's AC refinement scans in file order
+    std::vector<std::vector<int>> dc_rounds;
+    std::vector<int> rlist;
+    std::vector<int2> chains;
+    std::vector<long long> dc_blocks;
+    {
+        std::vector<std::vector<int>> ac(4);
+        for (int k = 0; k < m; ++k) {
+            if (!ok[k] || !ds[idx[k]]->pf) continue;
+            const ImgLay& IL = lay[k];
+            size_t r = 0;
+            for (auto& v : ac) v.clear();
+            for (int t = IL.item0; t < IL.item0 + IL.nitems; ++t) {
+                if (items[t].kind == kDcRefine) {
+                    if (dc_rounds.size() <= r) { dc_rounds.emplace_back(); dc_blocks.push_back(0); }
+                    dc_rounds[r].push_back(t);
+                    dc_blocks[r] = std::max(dc_blocks[r], scans[t].total_blocks);
+                    ++r;
+                } else if (items[t].kind == kAcRefine) {
+                    ac[items[t].fs->comp].push_back(t);
+                }
+            }
+            for (auto& v : ac)
+                if (!v.empty()) {
+                    chains.push_back(make_int2((int)rlist.size(), (int)v.size()));
+                    rlist.insert(rlist.end(), v.begin(), v.end());
+                }
+        }
+        // rlist: [DC launch 0 | DC launch 1 | ... | the chains' scans]
+        std::vector<int> all;
+        for (auto& v : dc_rounds) all.insert(all.end(), v.begin(), v.end());
+        for (int2& c : chains) c.x += (int)all.size();
+        all.insert(all.end(), rlist.begin(), rlist.end());
+        rlist.swap(all);
+    }
+    std::memcpy(hp, scans.data(), sizeof(Scan) * ni);
     std::memcpy(hp + (o_ivlane - o_scans), ivl_lane.data(), sizeof(int) * nivl_total);
     std::memcpy(hp + (o_wgs - o_scans), wgs.data(), sizeof(int2) * nwg);
+    if (!rlist.empty()) std::memcpy(hp + (o_rlist - o_scans), rlist.data(), sizeof(int) * rlist.size());
+    if (!chains.empty()) std::memcpy(hp + (o_chains - o_scans), chains.data(), sizeof(int2) * chains.size());
     const Scan* d_scans = reinterpret_cast<const Scan*>(dev + o_scans);
     const int2* d_wgs = reinterpret_cast<const int2*>(dev + o_wgs);
     LaneRec* d_recs = reinterpret_cast<LaneRec*>(dev + o_recs);
     int* d_status = reinterpret_cast<int*>(dev + o_status);
     int* d_changed = reinterpret_cast<int*>(dev + o_changed);
-    // ---- 4. sync, fix rounds, bases, decode ----
+    const int* d_rlist = reinterpret_cast<const int*>(dev + o_rlist);
+    // ---- 4. sync, fix rounds, bases, decode; then the refinement scans ----
     EvPair& ev = thread_events(2);
+    EvPair& ev2 = thread_events(3);
     e = h2d(dev + o_scans, 0, tab2_bytes);
     if (e == hipSuccess) ev_record(ev.a, s);
     if (e == hipSuccess) e = launch_jsync_sync(d_scans, d_wgs, nwg, d_recs, s);
     if (e == hipSuccess) e = hipMemsetAsync(d_changed, 0, sizeof(int), s);
-    if (e == hipSuccess) e = launch_jsync_fix(d_scans, m, d_wgs, nwg, d_recs, d_changed, s);
+    if (e == hipSuccess) e = launch_jsync_fix(d_scans, ni, d_wgs, nwg, d_recs, d_changed, s);
     if (e == hipSuccess)
-        e = launch_jsync_bases_decode(d_scans, m, d_wgs, nwg, d_recs, reinterpret_cast<LaneBase*>(dev + o_bases),
+        e = launch_jsync_bases_decode(d_scans, ni, d_wgs, nwg, d_recs, reinterpret_cast<LaneBase*>(dev + o_bases),
                                       dev + o_cs, d_status, s);
     if (e == hipSuccess) ev_record(ev.b, s);
-    int rounds = 0;  // the settle kernel's most rounds over the batch's images
-    if (e == hipSuccess) e = d2h(0, reinterpret_cast<const uint8_t*>(d_status), sizeof(int) * m);
-    if (e == hipSuccess) e = d2h(up256(sizeof(int) * m), reinterpret_cast<const uint8_t*>(d_changed), sizeof(int));
+    const bool refine = !rlist.empty();
+    if (refine) {
+        int at = 0;
+        for (size_t r = 0; r < dc_rounds.size() && e == hipSuccess; ++r) {
+            e = launch_jprog_dc_refine(d_scans, d_rlist + at, (int)dc_rounds[r].size(), dc_blocks[r], s);
+            at += (int)dc_rounds[r].size();
+        }
+        if (e == hipSuccess) ev_record(ev2.a, s);
+        if (e == hipSuccess)
+            e = launch_jprog_ac_chain(d_scans, reinterpret_cast<const int2*>(dev + o_chains), (int)chains.size(), d_rlist,
+                                      d_status, s);
+        if (e == hipSuccess) ev_record(ev2.b, s);
+    }
+    int rounds = 0;  // the settle kernel's most rounds over the batch's scans
+    if (e == hipSuccess) e = d2h(0, reinterpret_cast<const uint8_t*>(d_status), sizeof(int) * ni);
+    if (e == hipSuccess) e = d2h(up256(sizeof(int) * ni), reinterpret_cast<const uint8_t*>(d_changed), sizeof(int));
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e == hipSuccess) {
-        std::memcpy(hstatus.data(), hp, sizeof(int) * m);
-        std::memcpy(&rounds, hp + up256(sizeof(int) * m), sizeof(int));
+        const int* hs = reinterpret_cast<const int*>(hp);
+        for (int t = 0; t < ni; ++t) hstatus[items[t].k] |= hs[t];  // any scan's flag sends the image to the host
+        std::memcpy(&rounds, hp + up256(sizeof(int) * ni), sizeof(int));
     }
     if (e != hipSuccess) {
         if (e != hipSuccess) (void)hip_fail(e, "jpeg entropy decode");
@@ -1148,26 +1372,33 @@ static void jsync_batch(std::vector<std::unique_ptr<Decoder>>& ds, const std::ve
             if (ok[k]) host_idx.push_back(idx[k]);
         return;
     }
-#ifdef IK_JPEG_DUMP  // dev experiment: every image's unstuffed words, lane tables and coefficients
+    if (refine) {  // ik_jpeg_prog_free_ms: the last batch's phase A, DC refinement and chain launches
+        float dc_ms = 0.f;
+        if (!ev.b || !ev2.a || hipEventElapsedTime(&dc_ms, ev.b, ev2.a) != hipSuccess) dc_ms = 0.f;
+        g_prog_free_ms[0].store(ev_pair_ms(ev));
+        g_prog_free_ms[1].store(dc_ms);
+        g_prog_free_ms[2].store(ev_pair_ms(ev2));
+    }
+#ifdef IK_JPEG_DUMP  // dev experiment: every image's unstuffed words, lane tables and coefficients (its first scan's)
     if (e == hipSuccess) {
         std::lock_guard<std::mutex> lk(g_jdump_mu);
         g_jdump.assign(m, {});
         for (int k = 0; k < m; ++k) {
             if (!ok[k]) continue;
             const Decoder& d = *ds[idx[k]];
-            const Lay& L = lay[k];
-            const int nl = ivl_lane[L.ivl0 + d.js_nivl];
+            const Item& L = items[lay[k].item0];
+            const int nl = ivl_lane[L.ivl0 + L.nivl];
             auto get = [&](int what, const void* src, size_t bytes) {
                 g_jdump[k][what].resize(bytes);
                 (void)hipMemcpy(g_jdump[k][what].data(), src, bytes, hipMemcpyDeviceToHost);
             };
-            get(0, dev + L.out, d.js_len);
-            get(1, dev + o_ivl + sizeof(long long) * L.ivl0, sizeof(long long) * (d.js_nivl + 1));
+            get(0, dev + L.out, L.len);
+            get(1, dev + o_ivl + sizeof(long long) * L.ivl0, sizeof(long long) * (L.nivl + 1));
             get(2, dev + o_recs + sizeof(LaneRec) * L.lane0, sizeof(LaneRec) * nl);
             get(3, dev + o_bases + sizeof(LaneBase) * L.lane0, sizeof(LaneBase) * nl);
-            get(4, dev + L.coef, d.nblocks * 64 * sizeof(int16_t));
-            g_jdump[k][5].resize(sizeof(int) * (d.js_nivl + 1));
-            std::memcpy(g_jdump[k][5].data(), ivl_lane.data() + L.ivl0, sizeof(int) * (d.js_nivl + 1));
+            get(4, dev + lay[k].coef, d.nblocks * 64 * sizeof(int16_t));
+            g_jdump[k][5].resize(sizeof(int) * (L.nivl + 1));
+            std::memcpy(g_jdump[k][5].data(), ivl_lane.data() + L.ivl0, sizeof(int) * (L.nivl + 1));
             g_jdump[k][6].resize(sizeof(int) * 2);
             std::memcpy(g_jdump[k][6].data(), &hstatus[k], sizeof(int));
             std::memcpy(g_jdump[k][6].data() + sizeof(int), &rounds, sizeof(int));
@@ -1176,13 +1407,12 @@ static void jsync_batch(std::vector<std::unique_ptr<Decoder>>& ds, const std::ve
 #endif
     {  // ik_batch_last_timing: the decoding launches' time and algorithmic bytes
         double scan = 0, coef = 0;
+        for (const Item& L : items)
+            if (ok[L.k]) scan += (double)L.len;
         for (int k = 0; k < m; ++k)
-            if (ok[k]) {
-                scan += (double)ds[idx[k]]->js_len;
-                coef += (double)ds[idx[k]]->nblocks * 64 * sizeof(int16_t);
-            }
+            if (ok[k]) coef += (double)ds[idx[k]]->nblocks * 64 * sizeof(int16_t);
         const int d = current_device();
-        batch_timing_add(d, kBtJpegHuffMs, ev_pair_ms(ev));
+        batch_timing_add(d, kBtJpegHuffMs, ev_pair_ms(ev) + (refine ? g_prog_free_ms[1].load() + g_prog_free_ms[2].load() : 0.f));
         batch_timing_add(d, kBtJpegScanBytes, scan);
         batch_timing_add(d, kBtJpegCoefBytes, coef);
         batch_timing_add(d, kBtJpegImages, (double)(lanes_used ? std::count(ok.begin(), ok.end(), 1) : 0));
@@ -1190,7 +1420,7 @@ static void jsync_batch(std::vector<std::unique_ptr<Decoder>>& ds, const std::ve
     }
     // ---- 5. reconstruction: every image in three launches ----
     {
-        JpegReconItem* items = reinterpret_cast<JpegReconItem*>(hp);
+        JpegReconItem* ritems = reinterpret_cast<JpegReconItem*>(hp);
         int mi = 0, max_w = 0, max_h = 0;
         long long max_blocks = 0;
         bool any_fast = false, any_slow = false;
@@ -1208,7 +1438,7 @@ static void jsync_batch(std::vector<std::unique_ptr<Decoder>>& ds, const std::ve
             if (st[i]) continue;
             outs[i] = img;
             const bool fast = jpeg_zune_fast(g);
-            items[mi++] = JpegReconItem{g, img->d, img->pitch, fast ? 1 : 0, 0};
+            ritems[mi++] = JpegReconItem{g, img->d, img->pitch, fast ? 1 : 0, 0};
             max_blocks = std::max(max_blocks, g.nblocks);
             max_w = std::max(max_w, g.W);
             max_h = std::max(max_h, g.H);
@@ -1234,8 +1464,8 @@ static void jsync_batch(std::vector<std::unique_ptr<Decoder>>& ds, const std::ve
         g_jpeg_gpu_streams += 1;
     }
     if (timing)
-        fprintf(stderr, "[jsync] %d images, %lld lanes, %d fix rounds: layout %.2f, sync %.2f, tables %.2f, upload wait %.2f, "
-                "unstuff %.2f ms, total %.2f ms\n", m, lanes_used, rounds, tm_layout, tm_sync, tm_tables, tm_upwait, t_unstuff,
+        fprintf(stderr, "[jsync] %d images, %d scans, %lld lanes, %d fix rounds: layout %.2f, sync %.2f, tables %.2f, upload wait %.2f, "
+                "unstuff %.2f ms, total %.2f ms\n", m, ni, lanes_used, rounds, tm_layout, tm_sync, tm_tables, tm_upwait, t_unstuff,
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
 }
 
@@ -1258,8 +1488,9 @@ int decode_jpeg_impl(const uint8_t* bytes, size_t n, ik_image** out, bool try_gp
     d.try_gpu = try_gpu;
     int st = d.parse();
     if (st) return st;
+    d.finish();
     if (d.need_host) return decode_jpeg_impl(bytes, n, out, false);  // several scans: all on the host
-    if (d.js) {
+    if (d.js || d.pf) {
         int status = IK_OK;
         std::string msg;
         st = decode_jpeg_batch(&bytes, &n, 1, out, &status, &msg, nullptr);
@@ -1384,6 +1615,7 @@ int decode_jpeg_batch(const uint8_t* const* bytes, const size_t* lens, int n, ik
         d.skel = inpl[i];
         d.try_gpu = true;
         st[i] = d.parse();
+        if (!st[i]) d.finish();
         if (inpl[i] && (st[i] || !d.js)) {  // not for the GPU after all: the host parser judges the whole file
             st[i] = IK_OK;
             d.need_host = true;
@@ -1397,7 +1629,7 @@ int decode_jpeg_batch(const uint8_t* const* bytes, const size_t* lens, int n, ik
     for (int i = 0; i < n; ++i) {
         outs[i] = nullptr;
         if (st[i]) continue;
-        if (ds[i]->js && !ds[i]->need_host) js_idx.push_back(i);
+        if ((ds[i]->js || ds[i]->pf) && !ds[i]->need_host) js_idx.push_back(i);
         else if (!ds[i]->prog.empty() && !ds[i]->need_host) prog_idx.push_back(i);  // one by one, GPU
         else host_idx.push_back(i);
     }
@@ -1471,6 +1703,20 @@ int ik_set_jpeg_device(int where) {
 }
 
 int ik_get_jpeg_device(void) { return ik::jpeg_device_inplace() ? IK_JPEG_DEVICE_INPLACE : IK_JPEG_DEVICE_COPY; }
+
+int ik_set_jpeg_prog_free(int where) {
+    if (where < -1 || where > IK_JPEG_PROG_FREE_GPU) return ik::fail(IK_ERR_INVALID, "bad JPEG progressive mode %d", where);
+    ik::g_jpeg_prog_free.store(where);
+    return IK_OK;
+}
+
+int ik_get_jpeg_prog_free(void) { return ik::jpeg_prog_free_gpu() ? IK_JPEG_PROG_FREE_GPU : IK_JPEG_PROG_FREE_HOST; }
+
+int ik_jpeg_prog_free_ms(double* out) {
+    if (!out) return ik::fail(IK_ERR_INVALID, "null pointer");
+    for (int k = 0; k < 3; ++k) out[k] = (double)ik::g_prog_free_ms[k].load();
+    return IK_OK;
+}
 
 int ik_jpeg_walk_host(const uint8_t* bytes, size_t len, uint8_t* skeleton, size_t cap, ik_jpeg_walk_info* info) {
     if (!skeleton || !info || (!bytes && len)) return ik::fail(IK_ERR_INVALID, "null pointer");

@@ -1,5 +1,6 @@
 // ik_jpeg_sync.h -- self-synchronising parallel Huffman decoding of baseline JPEG
-// scans, shared by the GPU kernels (ik_jpeg.hip k_jsync_*) and their CPU model
+// scans and of the first (Ah = 0) scans of progressive ones, shared by the GPU
+// kernels (ik_jsync.hip k_jsync_*, k_jprog_*) and their CPU model
 // (ik_jpeg_model.cpp, CPU tests only).
 //
 // decode_image on a JPEG (reference src/transform.rs:31 -> image 0.25.8 ->
@@ -30,6 +31,20 @@
 //     block count come from its end padding and are cut.
 //  4. decode: every lane decodes its blocks again from its START with those
 //     bases and writes the coefficients.
+//
+// Progressive scans without restart markers (T.81 G.1.2) take the same passes
+// where they synchronise by themselves (Scan::kind):
+//   DC first   a unit is one block: a category symbol and its extra bits; the
+//              state, the DC sums and the bases are the baseline ones
+//   AC first   (one component) a unit is a block that ends on its own (EOB0, or k
+//              past Se), or an EOBn symbol with all the blocks its run covers; a
+//              state is taken only between units, where the EOB run is zero, and
+//              every block of a run belongs to the lane that decodes its symbol
+// Their decode pass stores only the coefficients the scan codes (another first scan
+// of the image writes other slots of the same block in the same launch).  DC
+// refinement is a bit per block (k_jprog_dc_refine); AC refinement reads what the
+// scans before it left and stays one serial chain per component (ac_refine_block,
+// k_jprog_ac_chain and k_jpeg_prog).
 #pragma once
 #include <stdint.h>
 
@@ -92,7 +107,15 @@ struct Scan {
     long long blk0[4];
     const JpegHuffTables* tabs;
     int16_t* coef;                    // [block][64] natural order
+    // ik_internal.h's numbering: 0 baseline, 1 DC first, 2 DC refine, 3 AC first, 4 AC refine
+    // (2 and 4 take no lanes); the band and the point transform of a progressive scan
+    int kind, Ss, Se, Al;
 };
+constexpr int kBaseline = 0, kDcFirst = 1, kDcRefine = 2, kAcFirst = 3, kAcRefine = 4;
+// blocks a lane counts at most (an AC-first lane of EOB runs counts up to 32,767
+// per symbol): 64 lanes of them still sum in an int (k_jsync_seg1), and more than
+// any lane of a real scan holds (4,096 bits / 15 bits per longest run = 8.9 M)
+constexpr int kMaxLaneBlocks = 1 << 24;
 // zero words a decoder may read past the data: one block of zero bits (16 + 11 + 63 * (16 + 10)),
 // plus the reader's three-word window
 constexpr int kPadWords = (16 + 11 + 63 * (16 + 10) + 31) / 32 + 4;
@@ -223,6 +246,93 @@ IK_HD bool block(Bits& br, const JpegHuffTables& T, const uint8_t* zz, int td, i
     return true;
 }
 
+// A DC-first block (T.81 G.1.2.1): the DC difference alone.  false on a bad code.
+IK_HD bool dc_first_block(Bits& br, const JpegHuffTables& T, int td, int* dcdiff) {
+    const int t = sym(br, T, td);
+    if (t < 0 || t > 11) return false;
+    *dcdiff = t ? extend(getbits(br, t), t) : 0;
+    return true;
+}
+
+// An AC-first unit (T.81 G.1.2.2): the band Ss..Se of one block, up to the end of
+// the band or an EOBn symbol; the levels << Al into blk when kStore.  Returns the
+// blocks the unit covers -- 1, or the EOB run's length, this block included -- or
+// 0 on a bad code (k + r > Se is one, as in the host decoder).
+template <bool kStore, typename Blk>
+IK_HD int ac_first_unit(Bits& br, const JpegHuffTables& T, const uint8_t* zz, int ta, int Ss, int Se, int Al, Blk blk) {
+    for (int k = Ss; k <= Se; ++k) {
+        const int rs = sym(br, T, 4 + ta);
+        if (rs < 0) return 0;
+        const int r = rs >> 4, sz = rs & 15;
+        if (sz) {
+            k += r;
+            if (k > Se) return 0;
+            const int val = extend(getbits(br, sz), sz);
+            if (kStore) blk[zz[k]] = (int16_t)(val * (1 << Al));
+        } else if (r == 15) {
+            k += 15;
+        } else {
+            return (1 << r) + getbits(br, r);
+        }
+    }
+    return 1;
+}
+
+// One block of an AC refinement scan (T.81 G.1.2.3; libjpeg jdphuff.c
+// decode_mcu_AC_refine), over any reader with sym(table) and get(bits): the
+// coefficients the scans before left are read and corrected in place, eobrun
+// carries the EOB run from block to block.  Returns 0, or 2 a bad code, 8 a
+// refinement size other than 1, 4 a run past the band.
+template <typename Reader>
+IK_HD int ac_refine_block(Reader& rd, const uint8_t* zz, int ta, int16_t* blk, int Ss, int Se, int Al, int& eobrun) {
+    const int p1 = 1 << Al, m1 = -p1;
+    int k = Ss;
+    if (eobrun == 0) {
+        for (; k <= Se; ++k) {
+            const int rs = rd.sym(4 + ta);
+            if (rs < 0) return 2;
+            int r = rs >> 4, val = 0;
+            const int sz = rs & 15;
+            if (sz) {
+                if (sz != 1) return 8;
+                val = rd.get(1) ? p1 : m1;
+            } else if (r != 15) {
+                eobrun = (1 << r) + (r ? rd.get(r) : 0);
+                break;  // the rest of the band: the EOB-run pass below
+            }
+            // skip r zero-history coefficients, refining the nonzero ones passed
+            do {
+                int16_t* co = blk + zz[k];
+                if (*co != 0) {
+                    if (rd.get(1) && (*co & p1) == 0) *co = (int16_t)(*co >= 0 ? *co + p1 : *co + m1);
+                } else if (--r < 0) {
+                    break;
+                }
+                ++k;
+            } while (k <= Se);
+            if (val) {
+                if (k > Se) return 4;
+                blk[zz[k]] = (int16_t)val;
+            }
+        }
+    }
+    if (eobrun > 0) {
+        for (; k <= Se; ++k) {
+            int16_t* co = blk + zz[k];
+            if (*co != 0 && rd.get(1) && (*co & p1) == 0) *co = (int16_t)(*co >= 0 ? *co + p1 : *co + m1);
+        }
+        --eobrun;
+    }
+    return 0;
+}
+// ac_refine_block's reader over unstuffed words
+struct WordReader {
+    Bits& br;
+    const JpegHuffTables& T;
+    IK_HD int sym(int t) { return jsync::sym(br, T, t); }
+    IK_HD int get(int n) { return getbits(br, n); }
+};
+
 // Unstuffing of the entropy-coded bytes b[0, n) of a scan (everything between the
 // SOS header and the marker that ends the scan), byte by byte from its neighbours
 // so that a GPU thread can decide any byte alone -- the same stream the host
@@ -264,8 +374,10 @@ IK_HD LaneGeom lane_geom(const Scan& S, int ivl, int q) {
 // >= g.lo becomes r.start, the blocks from there on are counted, and the state at
 // the first block start >= g.hi becomes r.exit.  A bad code ends the lane (r.err;
 // r.exit = 0, and r.start = 0 if it came before g.lo).
-IK_HD void run_lane(const Scan& S, const JpegHuffTables& T, const uint8_t* zz, const LaneGeom& g, uint64_t from,
-                    LaneRec& r) {
+// (kKind: the scan's kind, uniform over a workgroup -- run_lane branches on it once)
+template <int kKind>
+IK_HD void run_lane_kind(const Scan& S, const JpegHuffTables& T, const uint8_t* zz, const LaneGeom& g, uint64_t from,
+                         LaneRec& r) {
     r.start = r.exit = 0;
     r.nblk = 0;
     r.err = 0;
@@ -288,15 +400,24 @@ IK_HD void run_lane(const Scan& S, const JpegHuffTables& T, const uint8_t* zz, c
             break;
         }
         const int c = S.comp_of[j];
-        int diff;
-        if (!block<false>(br, T, zz, S.td[c], S.ta[c], &diff, (int16_t*)nullptr)) {
+        int diff = 0, nb = 1;  // the unit's DC difference and blocks
+        bool good;
+        if (kKind == kBaseline) {
+            good = block<false>(br, T, zz, S.td[c], S.ta[c], &diff, (int16_t*)nullptr);
+        } else if (kKind == kDcFirst) {
+            good = dc_first_block(br, T, S.td[c], &diff);
+        } else {
+            nb = ac_first_unit<false>(br, T, zz, S.ta[c], S.Ss, S.Se, S.Al, (int16_t*)nullptr);
+            good = nb > 0 && (!counting || nb <= kMaxLaneBlocks - r.nblk);  // (a count past the cap: bad data)
+        }
+        if (!good) {
             r.err = 1 + r.nblk;
             if (counting) ++r.nblk;  // the block started in the range (a padding block at an interval end)
             break;
         }
         ++r.work;
         if (counting) {
-            ++r.nblk;
+            r.nblk += nb;
             const int d = diff;
             dc0 += c == 0 ? d : 0;
             dc1 += c == 1 ? d : 0;
@@ -309,6 +430,14 @@ IK_HD void run_lane(const Scan& S, const JpegHuffTables& T, const uint8_t* zz, c
     r.dc[1] = dc1;
     r.dc[2] = dc2;
     r.dc[3] = dc3;
+}
+IK_HD void run_lane(const Scan& S, const JpegHuffTables& T, const uint8_t* zz, const LaneGeom& g, uint64_t from,
+                    LaneRec& r) {
+    // (the baseline kind first: with the progressive kinds tested ahead of it
+    // k_jsync_sync took 69 VGPRs, a wave per SIMD fewer; so it takes 64, and none spills)
+    if (S.kind == kBaseline) run_lane_kind<kBaseline>(S, T, zz, g, from, r);
+    else if (S.kind == kAcFirst) run_lane_kind<kAcFirst>(S, T, zz, g, from, r);
+    else run_lane_kind<kDcFirst>(S, T, zz, g, from, r);
 }
 
 // the sync pass's starting state for lane q: the interval start for q = 0, else a
@@ -327,6 +456,43 @@ IK_HD long long block_index(const Scan& S, long long b) {
     if (S.single) return S.blk0[c] + (mcu / S.single_bw) * S.bw[c] + (mcu % S.single_bw);
     const long long my = mcu / S.mcux, mx = mcu - my * S.mcux;
     return S.blk0[c] + (my * S.v[c] + S.by_of[j]) * S.bw[c] + mx * S.h[c] + S.bx_of[j];
+}
+
+// The decode pass of a lane of a progressive first scan: its B.count blocks from
+// the state (br, j), only the coefficients the scan codes, each stored straight to
+// coef (the image's [block][64]).  false on a bad code.
+template <int kKind, typename Coef>
+IK_HD bool decode_lane_prog(const Scan& S, const JpegHuffTables& T, const uint8_t* zz, Bits& br, int j, const LaneBase& B,
+                            Coef coef) {
+    if (kKind == kDcFirst) {
+        int p0 = B.dc[0], p1 = B.dc[1], p2 = B.dc[2], p3 = B.dc[3];
+        for (int i = 0; i < B.count; ++i) {
+            const int c = S.comp_of[j];
+            int diff;
+            if (!dc_first_block(br, T, S.td[c], &diff)) return false;
+            p0 += c == 0 ? diff : 0;
+            p1 += c == 1 ? diff : 0;
+            p2 += c == 2 ? diff : 0;
+            p3 += c == 3 ? diff : 0;
+            const int pred = c == 0 ? p0 : c == 1 ? p1 : c == 2 ? p2 : p3;
+            coef[block_index(S, B.block + i) * 64] = (int16_t)(pred * (1 << S.Al));
+            j = j + 1 == S.bpm ? 0 : j + 1;
+        }
+        return true;
+    }
+    const int ta = S.ta[0];
+    for (long long i = 0; i < B.count;) {  // (a run cut at the lane's count covers padding)
+        const int nb = ac_first_unit<true>(br, T, zz, ta, S.Ss, S.Se, S.Al, coef + block_index(S, B.block + i) * 64);
+        if (!nb) return false;
+        i += nb;
+    }
+    return true;
+}
+
+// DC refinement (T.81 G.1.2.1): bit i of the scan belongs to its i-th block; bits
+// at or past nbits read as zero, as the host reader feeds zeros at a marker
+IK_HD int dc_refine_bit(const IK_GLOBAL uint32_t* words, long long nbits, long long i) {
+    return i < nbits ? (int)((words[i >> 5] >> (31 - (int)(i & 31))) & 1u) : 0;
 }
 
 }  // namespace jsync

@@ -20,7 +20,16 @@
 //                    between chunks per image, then per lane), the padding's blocks
 //                    cut, inconsistent lanes and bad codes flagged
 //   k_jsync_decode   a thread per lane: its blocks from START, coefficients out
-//                    (each block staged in LDS and stored whole)
+//                    (each block staged in LDS and stored whole; a progressive first
+//                    scan stores only the coefficients it codes, straight to memory)
+//
+// Progressive files without restart markers share those launches for their Ah = 0
+// scans (one Scan each: jsync::Scan::kind), then
+//   k_jprog_dc_refine  a thread per block of a DC refinement scan: its bit
+//   k_jprog_ac_chain   a wave per (image, component): the component's AC refinement
+//                      scans in file order, lane 0 decoding each as one interval
+#include <algorithm>
+
 #include "ik_internal.h"
 #include "ik_jpeg_sync.h"
 
@@ -485,6 +494,14 @@ __global__ __launch_bounds__(kLanesPerWG) void k_jsync_decode(const Scan* scans,
     Bits br;
     br.init(S.words, st_bit(st), g.e);
     int j = st_j(st);
+    if (S.kind != kBaseline) {  // (uniform over the workgroup: its lanes are one scan's)
+        typedef __attribute__((address_space(1))) int16_t gi16;
+        gi16* const coef = (gi16*)S.coef;
+        const bool good = S.kind == kDcFirst ? decode_lane_prog<kDcFirst>(S, L.T, L.zz, br, j, B, coef)
+                                             : decode_lane_prog<kAcFirst>(S, L.T, L.zz, br, j, B, coef);
+        if (!good) atomicOr(status + w.x, 8);
+        return;
+    }
     int pred[4];
     for (int c = 0; c < 4; ++c) pred[c] = B.dc[c];
     typedef __attribute__((address_space(3))) int16_t lds_i16;
@@ -514,7 +531,75 @@ __global__ __launch_bounds__(kLanesPerWG) void k_jsync_decode(const Scan* scans,
     }
 }
 
+// ---- progressive refinement scans ----------------------------------------------------
+// A DC refinement scan: bit i of the unstuffed scan is block i's (scan order, the
+// decode pass's block_index), a set bit ORs 1 << Al into coefficient 0.  list: the
+// scans of this launch (one per image: an image's DC refinements are ordered among
+// themselves by the launches); a scan whose image dropped out has no interval.
+__global__ __launch_bounds__(256) void k_jprog_dc_refine(const Scan* scans, const int* list) {
+    __shared__ Scan S;
+    load_scan(scans + list[blockIdx.y], S);
+    __syncthreads();
+    if (S.nivl != 1) return;
+    const long long nbits = S.ivl[1];
+    const int p1 = 1 << S.Al;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < S.total_blocks; i += (long long)gridDim.x * 256)
+        if (dc_refine_bit(S.words, nbits, i)) {
+            int16_t* c = S.coef + block_index(S, i) * 64;
+            *c = (int16_t)(*c | p1);
+        }
+}
+
+// The AC refinement scans of one component of one image, in file order: chains[x] =
+// (first, count) into list, the scans' indices.  AC refinement reads what the scans
+// before it left in every coefficient and does not synchronise by itself, so each
+// scan is one interval decoded by lane 0 (ac_refine_block, k_jpeg_prog's rules);
+// the wave loads the scan and its tables, as they stood at its SOS, together.
+// A bad code, or a scan that ends before its blocks do, flags the scan (status 16).
+__global__ __launch_bounds__(64) void k_jprog_ac_chain(const Scan* scans, const int2* chains, const int* list, int* status) {
+    __shared__ JsLds L;
+    __shared__ Scan S;
+    const int2 ch = chains[blockIdx.x];
+    for (int n = 0; n < ch.y; ++n) {
+        const int it = list[ch.x + n];
+        __syncthreads();
+        load_scan(scans + it, S);
+        load_tables(scans[it].tabs, L);
+        __syncthreads();
+        if (S.nivl != 1) return;  // the image dropped out
+        int bad = 0;
+        if (threadIdx.x == 0) {
+            const uint64_t nbits = (uint64_t)S.ivl[1];
+            Bits br;
+            br.init(S.words, 0, nbits);
+            WordReader rd{br, L.T};
+            int eobrun = 0;
+            const int ta = S.ta[0], Ss = S.Ss, Se = S.Se, Al = S.Al;
+            for (long long b = 0; b < S.total_blocks && !bad; ++b) {
+                if (br.pos > nbits) bad = 1;  // (a block reads at most kPadWords past the data)
+                else bad = ac_refine_block(rd, L.zz, ta, S.coef + block_index(S, b) * 64, Ss, Se, Al, eobrun);
+            }
+            if (bad) atomicOr(status + it, 16);
+        }
+        if (__shfl(bad, 0, 64)) return;
+    }
+}
+
 // ---- launchers ------------------------------------------------------------------------
+hipError_t launch_jprog_dc_refine(const Scan* scans, const int* list, int n, long long max_blocks, hipStream_t s) {
+    if (n <= 0 || max_blocks <= 0) return hipSuccess;
+    const long long gx = std::min<long long>((max_blocks + 255) / 256, 1024);
+    hipLaunchKernelGGL(k_jprog_dc_refine, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, s, scans, list);
+    return hipGetLastError();
+}
+
+hipError_t launch_jprog_ac_chain(const Scan* scans, const int2* chains, int nchains, const int* list, int* status,
+                                 hipStream_t s) {
+    if (nchains <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_jprog_ac_chain, dim3(nchains), dim3(64), 0, s, scans, chains, list, status);
+    return hipGetLastError();
+}
+
 hipError_t launch_jsync_unstuff(JsImageDev* imgs, int nimg, const int2* chunks, int nchunks, uint2* counts,
                                 hipStream_t s) {
     if (nimg <= 0 || nchunks <= 0) return hipSuccess;

@@ -384,6 +384,10 @@ struct JpegUpload {
 void jpeg_device_count(int which, unsigned long long n);
 // IK_JPEG_DEVICE / ik_set_jpeg_device: baseline JPEG bodies in device memory are decoded in place
 bool jpeg_device_inplace();
+// IK_JPEG_PROG_FREE / ik_set_jpeg_prog_free: progressive files without restart markers are
+// entropy-decoded on the GPU (off by default: the host decoder takes them; IK_JPEG_PROG=0
+// keeps every progressive scan on the host whatever this says)
+bool jpeg_prog_free_gpu();
 void jpeg_device_walk_ms(float ms);  // the last k_jpeg_walk launch's device time (ik_jpeg_device_walk_ms)
 int jpeg_upload_begin(const uint8_t* const* b, const size_t* lens, int n, JpegUpload& up);
 void jpeg_shutdown();  // ik_shutdown: the JPEG upload areas

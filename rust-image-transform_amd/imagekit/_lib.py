@@ -95,6 +95,9 @@ SIGNATURES = [
     ("ik_jpeg_device_walk_ms", ctypes.c_double, []),
     ("ik_set_jpeg_device", ctypes.c_int, [ctypes.c_int]),
     ("ik_get_jpeg_device", ctypes.c_int, []),
+    ("ik_set_jpeg_prog_free", ctypes.c_int, [ctypes.c_int]),
+    ("ik_get_jpeg_prog_free", ctypes.c_int, []),
+    ("ik_jpeg_prog_free_ms", ctypes.c_int, [ctypes.POINTER(ctypes.c_double)]),
     ("ik_jpeg_walk_host", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     ("ik_get_resize_mode", ctypes.c_int, []),
     ("ik_resize_kernel_name", ctypes.c_char_p, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int]),
