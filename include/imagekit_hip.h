@@ -473,6 +473,20 @@ int ik_resize_batch_device(const uint8_t *dev_src, uint32_t W, uint32_t H, uint3
  * dev_yuv receives the Y (w*h), U and V ((w+1)/2 * (h+1)/2) planes back to back */
 int ik_webp_yuv420_device(const uint8_t *dev_src, uint32_t w, uint32_t h, uint32_t C,
                           size_t pitch, uint8_t *dev_yuv, void *hip_stream);
+/* the AVIF colour conversion (to_rgba8 + ravif's 8-bit BT.601 full-range YCbCr 4:4:4)
+ * on the device, for n images of w x h pixels with C channels: image i is read at
+ * dev_src + i*img_stride (rows pitch apart) and written at dev_planes +
+ * i*plane_img_stride as four planes of w*h bytes each, back to back: Y, U, V, A
+ * (A = 255 where the source has no alpha).  dev_transparent receives n ints: the call
+ * zeroes them, and flag i is 1 when any alpha of image i is below 255 (the AVIF file
+ * then carries an alpha plane).  Nothing past 4*w*h bytes of an image's planes is
+ * written.  Enqueued on hip_stream (NULL: the calling thread's stream) without waiting.
+ * IK_ERR_INVALID, with nothing written: a null pointer, a zero size, C outside 1..4,
+ * n == 0, h or n above 65535, pitch < w*C, or, when n > 1, img_stride < h*pitch or
+ * plane_img_stride < 4*w*h. */
+int ik_avif_yuv444_device(const uint8_t *dev_src, uint32_t w, uint32_t h, uint32_t C, size_t pitch,
+                          size_t img_stride, uint32_t n, uint8_t *dev_planes, size_t plane_img_stride,
+                          int *dev_transparent, void *hip_stream);
 /* libwebp's method-4 segment analysis on the GPU -- the first stage of
  * encode_image's WebP coder (src/transform.rs:129-137 -> libwebp VP8EncAnalyze +
  * VP8SetSegmentParams), exact: the same segment map and segment header libwebp

@@ -17,11 +17,17 @@
  *     webp 0.3.1 -> libwebp WebPEncodeRGB (Cargo.lock:2811, 1168).
  *   - libwebp's RGB -> YUV420 import (picture_csp_enc.c ImportYUVAFromRGBA),
  *     restated so the GPU colour-convert kernel can be checked plane by plane.
+ *   - ravif 0.11.20's RGB -> YCbCr 4:4:4 (image AvifEncoder, src/transform.rs:138-146),
+ *     restated from the published crate so the AVIF front-end kernel can be checked
+ *     the same way.
  *
  * Parity pinning (see DESIGN.md "Oracle"):
  *   - dimension policy: pinned by the reference's own tests/transform.rs KATs;
  *   - WebP YUV planes and WebP bytes: pinned against the system libwebp 1.2.2
  *     (a proxy for libwebp-sys 0.9.6's vendored copy);
+ *   - AVIF YUV planes: "parity unpinned" against ravif (no crate source here);
+ *     cross-checked against a float64 evaluation over every colour
+ *     (tests/test_oracle_avif.py);
  *   - resize pixel values and JPEG bytes: "parity unpinned" against the real
  *     image crate (no Rust toolchain, no crate sources here); cross-checked by an
  *     independent numpy restatement (tests/oracle_np.py).
@@ -70,6 +76,14 @@ void iko_to_rgba8(const uint8_t *src, uint32_t npix, uint32_t C, uint8_t *dst);
 /* libwebp ImportYUVAFromRGBA (no alpha, no dithering, non-iterative) on RGB8. */
 void iko_webp_rgb_to_yuv420(const uint8_t *rgb, int width, int height, int stride,
                             uint8_t *y, int y_stride, uint8_t *u, uint8_t *v, int uv_stride);
+
+/* image 0.25.8 AvifEncoder's colour conversion (avif_yuv.c): to_rgba8, then ravif
+ * 0.11.20's 8-bit BT.601 full-range YCbCr in f32, restated from the published
+ * crate.  y, u, v, a receive npix bytes each; *transparent = 1 when any alpha
+ * differs from 255.  chroma_fma != 0: the two chroma lines are one fused
+ * multiply-add each (the crate's mul_add); 0: a rounded multiply, then a rounded add. */
+void iko_avif_yuv444(const uint8_t *src, uint32_t npix, uint32_t C, int chroma_fma,
+                     uint8_t *y, uint8_t *u, uint8_t *v, uint8_t *a, int *transparent);
 
 /* image 0.25.8 JpegEncoder::new_with_quality(q).write_image(rgb, w, h, Rgb8).
  * Returns the byte count written to *out (malloc'd; free with iko_free), or -1. */

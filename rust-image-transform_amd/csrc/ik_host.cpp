@@ -2533,6 +2533,22 @@ int ik_webp_yuv420_device(const uint8_t* dev_src, uint32_t w, uint32_t h, uint32
     return IK_OK;
 }
 
+int ik_avif_yuv444_device(const uint8_t* dev_src, uint32_t w, uint32_t h, uint32_t C, size_t pitch,
+                          size_t img_stride, uint32_t n, uint8_t* dev_planes, size_t plane_img_stride,
+                          int* dev_transparent, void* hip_stream) {
+    IK_API_ENTER();
+    if (!dev_src || !dev_planes || !dev_transparent) return fail(IK_ERR_INVALID, "null device pointer");
+    if (!w || !h || C < 1 || C > 4 || !n || w > INT32_MAX || h > 65535 || n > 65535)
+        return fail(IK_ERR_INVALID, "bad geometry");
+    if (pitch < (size_t)w * C) return fail(IK_ERR_INVALID, "pitch too small");
+    if (n > 1 && (img_stride < pitch * h || plane_img_stride < 4 * (size_t)w * h))
+        return fail(IK_ERR_INVALID, "image stride too small");
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : thread_stream();
+    IK_HIP(launch_avif_yuv444(dev_src, (int)w, (int)h, (int)C, pitch, img_stride, dev_planes, plane_img_stride,
+                              dev_transparent, (int)n, s));
+    return IK_OK;
+}
+
 int ik_jpeg_coeffs_device(const uint8_t* dev_src, uint32_t w, uint32_t h, uint32_t C, size_t pitch,
                           int quality, int16_t* dev_coef, void* hip_stream) {
     IK_API_ENTER();

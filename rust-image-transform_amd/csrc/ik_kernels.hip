@@ -830,8 +830,13 @@ hipError_t launch_webp_yuv420(const uint8_t* src, int w, int h, int C, size_t pi
 // ---------------------------------------------------------------------------
 // AVIF front end (image 0.25.8 AvifEncoder: to_rgba8 -> ravif RGB->YCbCr): BT.601
 // full-range 4:4:4 planes plus the alpha plane; transparent[z] becomes 1 when any
-// alpha of image z is < 255 (ravif then codes an alpha plane; the caller zeroes
-// the flags).  One lane per pixel, grid.z = image of the batch.
+// alpha of image z is < 255 (ravif then codes an alpha plane; launch_avif_yuv444
+// zeroes the flags).  One lane per pixel, grid.z = image of the batch.
+// Op order (ravif 0.11.20, all f32): the Y sum left to right, each product and sum
+// rounded; each chroma line one fused multiply-add (the crate's mul_add), written as
+// a builtin so that -ffp-contract=off does not split it; round half up (equal to
+// f32::round on every colour), then saturate.  oracle/avif_yuv.c restates it and
+// tests/test_gpu_avif_front.py compares every colour.
 __global__ __launch_bounds__(kThreads) void k_avif_yuv444(const uint8_t* __restrict__ src, int w, int h, int C,
                                                           size_t pitch, size_t img_stride,
                                                           uint8_t* __restrict__ planes, size_t plane_img_stride,
@@ -844,8 +849,8 @@ __global__ __launch_bounds__(kThreads) void k_avif_yuv444(const uint8_t* __restr
     if (C >= 3) { r = p[0]; g = p[1]; b = p[2]; if (C == 4) al = p[3]; }
     else { r = g = b = p[0]; if (C == 2) al = p[1]; }
     const float Y = 0.299f * r + 0.587f * g + 0.114f * b;
-    const float U = (b - Y) * (0.5f / 0.886f) + 128.0f;
-    const float V = (r - Y) * (0.5f / 0.701f) + 128.0f;
+    const float U = __builtin_fmaf(b - Y, 0.5f / 0.886f, 128.0f);
+    const float V = __builtin_fmaf(r - Y, 0.5f / 0.701f, 128.0f);
     auto q8 = [](float v) -> uint8_t { v = floorf(v + 0.5f); return (uint8_t)(v < 0.f ? 0.f : (v > 255.f ? 255.f : v)); };
     const size_t n = (size_t)w * h, i = (size_t)y * w + x;
     planes[i] = q8(Y);

@@ -96,6 +96,26 @@ class Oracle:
         self.lib.iko_to_rgb8(_p(img), w * h, c, _p(out))
         return out
 
+    def to_rgba8(self, img: np.ndarray) -> np.ndarray:
+        img = np.ascontiguousarray(img)
+        h, w, c = img.shape
+        out = np.zeros((h, w, 4), np.uint8)
+        self.lib.iko_to_rgba8(_p(img), w * h, c, _p(out))
+        return out
+
+    def avif_yuv444(self, img: np.ndarray, chroma_fma: bool = True):
+        """ravif 0.11.20's planes for an (h, w, C) image (oracle/avif_yuv.c): Y, U, V, A
+        as (h, w) arrays and the transparent flag.  chroma_fma: fused chroma (the crate as
+        published) or a rounded multiply then a rounded add."""
+        img = np.ascontiguousarray(img)
+        h, w, c = img.shape
+        y, u, v, a = (np.zeros((h, w), np.uint8) for _ in range(4))
+        flag = ctypes.c_int(-1)
+        self.lib.iko_avif_yuv444.restype = None
+        self.lib.iko_avif_yuv444(_p(img), ctypes.c_uint32(w * h), ctypes.c_uint32(c), ctypes.c_int(bool(chroma_fma)),
+                                 _p(y), _p(u), _p(v), _p(a), ctypes.byref(flag))
+        return y, u, v, a, flag.value
+
     def webp_yuv420(self, rgb: np.ndarray):
         rgb = np.ascontiguousarray(rgb)
         h, w, _ = rgb.shape

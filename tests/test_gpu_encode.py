@@ -9,7 +9,9 @@ says which coder wrote its scan -- k_jpeg_huff_enc, or the host coder for a stre
 past the GPU coder's buffer (ik_jpeg_enc_counters) -- and that it is the one the
 plain Python coder (tests/oracle_jpeg_huff.py) predicts.  AVIF: rav1e (the reference's AV1 encoder)
 is absent, the build codes AV1 with libavif/aom: parity unpinned, checked as a
-decoded-PSNR bound (Pillow/dav1d), dimensions, alpha handling and q-monotone size."""
+decoded-PSNR bound (Pillow/dav1d), dimensions, alpha handling and q-monotone size.
+The AVIF front end itself (k_avif_yuv444: the Y, U, V, A planes and the transparent
+flag) is compared with the oracle value for value in tests/test_gpu_avif_front.py."""
 import ctypes
 import io
 
