@@ -31,6 +31,7 @@
 #include "ik_png.h"
 #include "ik_runtime.h"
 #include "ik_jpeg_walk.h"
+#include "ik_jsync_plan.h"
 
 namespace ik {
 namespace {
@@ -39,45 +40,6 @@ const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18,
                              12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
                              35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
                              58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-struct HuffTable {
-    bool present = false;
-    // canonical decode: maxcode[l], valptr[l], mincode[l]; plus a 9-bit lookahead
-    int maxcode[18] = {}, valptr[17] = {}, mincode[17] = {};
-    uint8_t vals[256] = {};
-    uint8_t look_len[512] = {}, look_val[512] = {};
-};
-
-bool build_huff(const uint8_t* bits, const uint8_t* vals, int nvals, HuffTable& t) {
-    t = HuffTable();
-    std::memcpy(t.vals, vals, nvals);
-    int code = 0, k = 0;
-    for (int l = 1; l <= 16; ++l) {
-        t.valptr[l] = k;
-        t.mincode[l] = code;
-        code += bits[l - 1];
-        k += bits[l - 1];
-        t.maxcode[l] = bits[l - 1] ? code - 1 : -1;
-        if (code > (1 << l)) return false;
-        code <<= 1;
-    }
-    t.maxcode[17] = 0x7fffffff;
-    // lookahead for codes up to 9 bits
-    code = 0;
-    k = 0;
-    for (int l = 1; l <= 9; ++l) {
-        for (int i = 0; i < bits[l - 1]; ++i, ++k, ++code) {
-            const int shift = 9 - l;
-            for (int f = 0; f < (1 << shift); ++f) {
-                t.look_len[(code << shift) | f] = (uint8_t)l;
-                t.look_val[(code << shift) | f] = vals[k];
-            }
-        }
-        code <<= 1;
-    }
-    t.present = true;
-    return true;
-}
 
 struct BitReader {
     const uint8_t* p;
@@ -138,8 +100,7 @@ const char* const kFmtErr = "Format error decoding Jpeg";
 // Baseline scans go to the self-synchronising GPU decoder (ik_jsync.hip) from this
 // size up; smaller ones are faster on the host entropy decoder.
 constexpr size_t kJsyncMinBytes = 4 << 10;
-// lanes a batch's self-synchronising decoding aims for (about what the chip holds at once)
-constexpr long long kJsyncLanes = 512 << 10;
+static_assert(jwalk::kMinScan == kJsyncMinBytes, "the marker walk keeps the same scans on the host decoder");
 
 // Progressive scans with restart intervals on the GPU (k_jpeg_prog);
 // IK_JPEG_PROG=0 keeps them on the host entropy decoder.
@@ -448,34 +409,12 @@ struct Decoder {
     // zune-jpeg's -- error).
     // the self-synchronising decoder's geometry of a scan over the components `order`
     bool scan_geom(const std::vector<int>& order, jsync::Scan& a, long long& total_mcu) const {
-        const bool single = order.size() == 1;
-        a = jsync::Scan{};
-        int bpm = 0;
-        for (size_t i = 0; i < order.size(); ++i) {
-            const Component& c = comps[order[i]];
-            const int nb = single ? 1 : c.h * c.v;
-            for (int k = 0; k < nb; ++k) {
-                if (bpm >= jsync::kMaxBPM) return false;
-                a.comp_of[bpm] = (int)i;
-                a.bx_of[bpm] = single ? 0 : k % c.h;
-                a.by_of[bpm] = single ? 0 : k / c.h;
-                ++bpm;
-            }
-            a.h[i] = c.h; a.v[i] = c.v; a.bw[i] = c.bw; a.td[i] = c.td; a.ta[i] = c.ta;
-            a.blk0[i] = (long long)c.blk0;
+        jsync::CompGeom cg[4];
+        for (size_t i = 0; i < comps.size(); ++i) {
+            const Component& c = comps[i];
+            cg[i] = jsync::CompGeom{c.h, c.v, c.bw, c.dw, c.dh, c.td, c.ta, (long long)c.blk0};
         }
-        const Component& c0 = comps[order[0]];
-        const int single_bw = (c0.dw + 7) / 8, single_bh = (c0.dh + 7) / 8;
-        total_mcu = single ? (long long)single_bw * single_bh : (long long)mcux * mcuy;
-        a.bpm = bpm;
-        a.mcux = mcux;
-        a.single = single ? 1 : 0;
-        a.single_bw = single_bw;
-        a.total_blocks = total_mcu * bpm;
-        a.ivl_blocks = a.total_blocks;
-        a.L = jsync::kLaneBits;
-        a.W = jsync::kWarmBits;
-        return true;
+        return jsync::scan_geom(cg, order.data(), (int)order.size(), mcux, mcuy, a, total_mcu);
     }
 
     // Record a scan of a progressive file without restart markers: its bytes run to
@@ -566,31 +505,7 @@ struct Decoder {
         return true;
     }
 
-    void tables(JpegHuffTables& t) const {
-        std::memset(&t, 0, sizeof(t));
-        for (int k = 0; k < 8; ++k) {
-            const HuffTable& h = k < 4 ? dc[k] : ac[k - 4];
-            for (int i = 0; i < 512; ++i) t.look[k][i] = (uint16_t)(h.look_len[i] << 8 | h.look_val[i]);
-            std::memcpy(t.maxcode[k], h.maxcode, sizeof(h.maxcode));
-            std::memcpy(t.valptr[k], h.valptr, sizeof(h.valptr));
-            std::memcpy(t.mincode[k], h.mincode, sizeof(h.mincode));
-            std::memcpy(t.vals[k], h.vals, sizeof(h.vals));
-            int carry = 0;
-            for (int l = 1; l <= 16; ++l) {
-                if (h.maxcode[l] >= 0) carry = (h.maxcode[l] + 1) << (16 - l);
-                t.lj[k][l] = carry;
-            }
-            if (k < 4) continue;
-            for (int i = 0; i < 512; ++i) {  // run/size code and its magnitude bits in one lookup
-                const int L = h.look_len[i], rs = h.look_val[i], r = rs >> 4, sz = rs & 15;
-                if (!L || !sz || L + sz > 9) continue;
-                const int v = (i >> (9 - L - sz)) & ((1 << sz) - 1);
-                const int val = v < (1 << (sz - 1)) ? v - (1 << sz) + 1 : v;
-                if (val < -128 || val > 127) continue;
-                t.fast_ac[k - 4][i] = (int16_t)(val * 256 + r * 16 + L + sz);
-            }
-        }
-    }
+    void tables(JpegHuffTables& t) const { pack_tables(dc, ac, t); }
 
     int scan(const uint8_t* s, const uint8_t* se, const uint8_t*& next) {
         if (!have_frame) return fail(IK_ERR_TRANSFORM, "%s: SOS before SOF", kFmtErr);
@@ -818,7 +733,7 @@ void qtables(const Decoder& d, uint16_t q[256]) {
     for (int i = 0; i < (int)d.comps.size(); ++i) std::memcpy(&q[i * 64], d.qt[d.comps[i].tq], 64 * sizeof(uint16_t));
 }
 
-inline size_t up256(size_t x) { return (x + 255) / 256 * 256; }
+using jsync::up256;
 
 // process-wide: JPEG streams whose entropy decoding ran on the GPU / on the host
 std::atomic<unsigned long long> g_jpeg_gpu_streams{0}, g_jpeg_host_streams{0};
@@ -985,255 +900,209 @@ std::vector<std::array<std::vector<uint8_t>, 7>> g_jdump;  // per image of the l
 
 // The baseline scans of a batch (ds[idx[k]]->js), all through the self-synchronising
 // GPU decoder at once (ik_jsync.hip; algorithm ik_jpeg_sync.h):
-//   1. upload: every scan's bytes (DMAed in place when page-locked, else staged),
+//   1. layout: every scan's and image's share of one scratch block, one pinned block
+//   2. upload: every scan's bytes (DMAed in place when page-locked, else staged),
 //      Huffman and quantisation tables, the unstuffing chunk table -- one small copy
-//   2. unstuffing on the GPU, then the interval tables come back (a few KB)
-//   3. lanes: per image, each interval cut into pieces of lane_bits (host)
-//   4. the sync pass, the fix rounds (one over all lanes, then the settle kernel's
-//      per image until no lane changes), bases, the decode pass -- no host round trip
-//   5. reconstruction of every image (IDCT, upsampling, colour)
+//   3. unstuffing on the GPU, then the interval tables come back (a few KB)
+//   4. lanes: per image, each interval cut into pieces of lane_bits (host); the
+//      refinement scans of the progressive images put into launches and chains
+//   5. the sync pass, the fix rounds (one over all lanes, then the settle kernel's
+//      per image until no lane changes), bases, the decode pass, the refinement
+//      scans -- no host round trip
+//   6. counters
+//   7. reconstruction of every image (IDCT, upsampling, colour)
 // An image the GPU finds inconsistent (a stray marker, a restart count that does
 // not match the frame, lanes that never synchronise, a bad code) goes to host_idx:
 // the host decoder decides and reports the reference's errors.
-static void jsync_batch(std::vector<std::unique_ptr<Decoder>>& ds, const std::vector<int>& idx, ik_image** outs,
-                        std::vector<int>& st, std::vector<int>& host_idx, const uint8_t* const* files,
-                        const JpegUpload* up) {
-    using namespace jsync;
+// The host's decisions -- scratch layout, lane rules, refinement schedule -- are
+// ik_jsync_plan.h's; the steps below add the device pointers, copy and launch.
+struct JsyncBatch {
+    std::vector<std::unique_ptr<Decoder>>& ds;
+    const std::vector<int>& idx;
+    ik_image** outs;
+    std::vector<int>& st;
+    std::vector<int>& host_idx;
+    const uint8_t* const* files;
+    const JpegUpload* up;
     const int m = (int)idx.size();
-    if (!m) return;
-    static const bool timing = getenv("IK_TIMING") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    constexpr int kChunkBytes = 4096;
-    // ---- layout ----
+    JsyncBatch(std::vector<std::unique_ptr<Decoder>>& ds_, const std::vector<int>& idx_, ik_image** outs_, std::vector<int>& st_,
+               std::vector<int>& host_idx_, const uint8_t* const* files_, const JpegUpload* up_)
+        : ds(ds_), idx(idx_), outs(outs_), st(st_), host_idx(host_idx_), files(files_), up(up_) {}
     // An item is one scan of one image: a baseline image has one, a progressive file
-    // without restart markers (Decoder::pf) one per scan, in file order.  Each has
-    // its own unstuffed words, table slot, interval table (progressive: one interval),
-    // chunks and -- the Ah = 0 kinds -- lane range; the coefficients, planes and
-    // quantisation tables are the image's.
+    // without restart markers (Decoder::pf) one per scan, in file order.
     struct Item {
-        int k;                 // the image (index into idx)
+        int k;                        // the image (index into idx)
         const Decoder::FreeScan* fs;  // null: the baseline scan
         const uint8_t* data;
-        size_t len;
-        long long nivl;
-        int kind;
-        size_t scan, out, tab;
-        long long lanes_max, lane0;
-        int chunk0, nchunks, ivl0;
-    };
-    struct ImgLay {
-        size_t qt, coef, pl;
-        int item0, nitems;
-        JpegGeom g;
+        const uint8_t* on_dev;        // the scan where it already lies on the device, or null
     };
     std::vector<Item> items;
-    std::vector<ImgLay> lay(m);
-    for (int k = 0; k < m; ++k) {
-        const Decoder& d = *ds[idx[k]];
-        lay[k].item0 = (int)items.size();
-        if (d.pf) {
-            for (const auto& fs : d.pf_scans) {
-                Item it{};
-                it.k = k; it.fs = &fs; it.data = fs.data; it.len = fs.len; it.nivl = 1; it.kind = fs.geom.kind;
-                items.push_back(it);
-            }
-        } else {
-            Item it{};
-            it.k = k; it.fs = nullptr; it.data = d.js_data; it.len = d.js_len; it.nivl = d.js_nivl; it.kind = kBaseline;
-            items.push_back(it);
-        }
-        lay[k].nitems = (int)items.size() - lay[k].item0;
+    std::vector<jsync::ScanIn> sin;
+    std::vector<JpegGeom> geom;
+    jsync::BatchLayout B;
+    int ni = 0;
+    hipStream_t s = nullptr;
+    uint8_t *dev = nullptr, *hp = nullptr, *hp_dev = nullptr;
+    hipError_t e = hipSuccess;
+    std::vector<int> ok, hstatus, ivl_lane;
+    std::vector<int2> wgs;
+    std::vector<jsync::Scan> scans;
+    jsync::RefinePlan R;
+    long long lanes_used = 0;
+    int rounds = 0;  // the settle kernel's most rounds over the batch's scans
+    EvPair *ev = nullptr, *ev2 = nullptr;
+    const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    double tm_layout = 0, tm_sync = 0, tm_tables = 0, tm_upwait = -1, t_unstuff = 0;
+    const bool timing = [] { static const bool on = getenv("IK_TIMING") != nullptr; return on; }();
+
+    double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+    const Decoder& dec(int k) const { return *ds[idx[k]]; }
+    template <class T> T* at(const jsync::Region& r) const { return reinterpret_cast<T*>(dev + r.off); }
+    void to_host(bool only_ok) {
+        for (int k = 0; k < m; ++k)
+            if (!only_ok || ok[k]) host_idx.push_back(idx[k]);
     }
-    const int ni = (int)items.size();
-    auto has_lanes = [](int kind) { return kind == kBaseline || kind == kDcFirst || kind == kAcFirst; };
-    // scans the upload stage already put on the device (JpegUpload) are read where
-    // they lie: no scratch copy is laid out for them
-    std::vector<const uint8_t*> on_dev(ni, nullptr);
-    if (up && up->n)
-        for (int t = 0; t < ni; ++t) {
-            const int i = idx[items[t].k];
-            if (ds[i]->skel) continue;
-            auto it = up->dev.find(files[i]);
-            if (it != up->dev.end()) on_dev[t] = it->second + (items[t].data - files[i]);
-        }
-    // a file of a device-resident batch: the caller's memory (no byte past the scan
-    // is the decoder's to read: the unstuffing kernels' scan_byte stops at scan_len)
-    for (int t = 0; t < ni; ++t) {
-        const int i = idx[items[t].k];
-        if (ds[i]->skel) on_dev[t] = files[i] + ds[i]->skel->ent_off;
-    }
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t r = o; o += up256(bytes); return r; };
-    const size_t o_img = take(sizeof(JsImageDev) * ni);
-    int nchunks = 0, nivl_total = 0;
-    long long lanes_max = 0;
-    // lane length: 1,024 bits, longer for large batches (up to 4,096) while the batch
-    // still has ~kJsyncLanes lanes -- a longer lane costs the sync pass less warm-up
-    // per bit and the fix rounds about as many rounds (ik_jpeg_model.cpp on the
-    // bench's 4096^2 frames: sync + fix work 2.8x the scan at 1,024, 1.7x at 4,096).
-    // The bits are those of every scan that takes lanes: the baseline scans and the
-    // progressive first scans.
-    long long batch_bits = 0;
-    for (const Item& it : items)
-        if (has_lanes(it.kind)) batch_bits += 8ll * (long long)it.len;
-    const int lane_bits = (int)std::min<long long>(4 * kLaneBits,
-                                                   std::max<long long>(1, batch_bits / kJsyncLanes / kLaneBits) * kLaneBits);
-    for (Item& L : items) {
-        L.chunk0 = nchunks;
-        L.nchunks = (int)((L.len + kChunkBytes - 1) / kChunkBytes);
-        nchunks += L.nchunks;
-        L.ivl0 = nivl_total;
-        nivl_total += (int)L.nivl + 1;
-        L.lane0 = lanes_max;
-        L.lanes_max = has_lanes(L.kind) ? ((long long)(8 * L.len) / lane_bits + L.nivl + 1 + 255) & ~255ll : 0;
-        lanes_max += L.lanes_max;
-    }
-    const size_t o_chunks = take(sizeof(int2) * nchunks);
-    for (Item& L : items) L.tab = take(sizeof(JpegHuffTables));
-    for (int k = 0; k < m; ++k) lay[k].qt = take(512);
-    const size_t small_end = o;  // [images | chunks | tables | qt]: one upload
-    const size_t o_status = take(sizeof(int) * ni), o_totals = take(sizeof(uint32_t) * 2 * ni);
-    const size_t o_ivl = take(sizeof(long long) * nivl_total);  // contiguous: one read-back
-    const size_t small2_end = o;  // [status | totals | ivl]: one read-back
-    const size_t o_counts = take(sizeof(uint2) * nchunks);
-    const size_t o_scans = take(sizeof(Scan) * ni);
-    const size_t o_ivlane = take(sizeof(int) * nivl_total);
-    const size_t o_wgs = take(sizeof(int2) * (size_t)(lanes_max / 256));
-    const size_t o_rlist = take(sizeof(int) * ni);       // the refinement scans: DC by launch, then AC by chain
-    const size_t o_chains = take(sizeof(int2) * 4 * m);  // (image, component) chains of AC refinement scans
-    const size_t tab2_bytes = o - o_scans;  // [scans | ivl_lane | wgs | refinement lists]: the second upload
-    const size_t o_changed = take(256);
-    const size_t o_recs = take(sizeof(LaneRec) * (size_t)lanes_max);
-    const size_t o_bases = take(sizeof(LaneBase) * (size_t)lanes_max);
-    const size_t o_cs = take(jsync_chunk_scratch_bytes(lanes_max));
-    const size_t o_items = take(sizeof(JpegReconItem) * m);  // the reconstruction launches' image table
-    for (int t = 0; t < ni; ++t) {
-        Item& L = items[t];
-        L.scan = on_dev[t] ? 0 : take(L.len + 64);
-        L.out = take(L.len + 4 * kPadWords + 8);
-    }
-    for (int k = 0; k < m; ++k) {
-        const Decoder& d = *ds[idx[k]];
-        const size_t pb = make_geom(d, lay[k].g);
-        lay[k].coef = take(d.nblocks * 64 * sizeof(int16_t));
-        lay[k].pl = take(pb);
-    }
-    hipStream_t s = thread_stream();
-    uint8_t* dev = scratch_slot(1, o);
-    const size_t pin_bytes = std::max(std::max(small_end, sizeof(JpegReconItem) * m + 256),
-                                      std::max(small2_end - o_status, tab2_bytes)) + up256(sizeof(int) * ni) + 256;
-    uint8_t* hp = dev ? pinned_slot(1, pin_bytes) : nullptr;
-    auto fail_all = [&](const char* why) {
-        (void)why;
-        for (int k = 0; k < m; ++k) host_idx.push_back(idx[k]);
-    };
-    if (!dev || !hp) { fail_all("memory"); return; }
-    const double tm_layout = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    (void)hipStreamSynchronize(s);  // the pinned block is free
     // Small transfers between hp and the device go through a copy kernel on this
     // stream that reads or writes the pinned block directly (ik_png_decode.cpp Xfer):
     // SDMA copies queue behind the next batch's scan upload on the same engine --
     // ~12 ms per transfer with configs[2]'s 683 MB batches in flight.
-    uint8_t* hp_dev = nullptr;
-    if (hipHostGetDevicePointer((void**)&hp_dev, hp, 0) != hipSuccess) hp_dev = nullptr;
-    auto h2d = [&](uint8_t* d, size_t off, size_t n) -> hipError_t {  // hp[off, off + n) -> d
+    hipError_t h2d(uint8_t* d, size_t off, size_t n) {  // hp[off, off + n) -> d
         if (!n) return hipSuccess;
         if (!hp_dev) return hipMemcpyAsync(d, hp + off, n, hipMemcpyHostToDevice, s);
-        return launch_copy_words(reinterpret_cast<const uint32_t*>(hp_dev + off), reinterpret_cast<uint32_t*>(d),
-                                 (n + 3) / 4, s);
-    };
-    auto d2h = [&](size_t off, const uint8_t* d, size_t n) -> hipError_t {  // d -> hp[off, off + n)
+        return launch_copy_words(reinterpret_cast<const uint32_t*>(hp_dev + off), reinterpret_cast<uint32_t*>(d), (n + 3) / 4, s);
+    }
+    hipError_t d2h(size_t off, const uint8_t* d, size_t n) {  // d -> hp[off, off + n)
         if (!n) return hipSuccess;
         if (!hp_dev) return hipMemcpyAsync(hp + off, d, n, hipMemcpyDeviceToHost, s);
-        return launch_copy_words(reinterpret_cast<const uint32_t*>(d), reinterpret_cast<uint32_t*>(hp_dev + off),
-                                 (n + 3) / 4, s);
-    };
-    const double tm_sync = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    // ---- 1. upload ----
-    {
-        JsImageDev* I = reinterpret_cast<JsImageDev*>(hp + o_img);
-        int2* ch = reinterpret_cast<int2*>(hp + o_chunks);
+        return launch_copy_words(reinterpret_cast<const uint32_t*>(d), reinterpret_cast<uint32_t*>(hp_dev + off), (n + 3) / 4, s);
+    }
+
+    // 1. the items, their layout, the scratch and the pinned block
+    bool layout() {
+        std::vector<jsync::ImageIn> imgs(m);
+        geom.resize(m);
+        for (int k = 0; k < m; ++k) {
+            const int i = idx[k];
+            const Decoder& d = *ds[i];
+            auto add = [&](const Decoder::FreeScan* fs, const uint8_t* data, size_t len, long long nivl, const jsync::Scan& g, int comp) {
+                // a scan the upload stage already put on the device (JpegUpload) is read
+                // where it lies, and so is a file of a device-resident batch: the caller's
+                // memory (no byte past the scan is the decoder's to read: the unstuffing
+                // kernels' scan_byte stops at scan_len)
+                const uint8_t* on_dev = nullptr;
+                if (d.skel) on_dev = files[i] + d.skel->ent_off;
+                else if (up && up->n) {
+                    auto it = up->dev.find(files[i]);
+                    if (it != up->dev.end()) on_dev = it->second + (data - files[i]);
+                }
+                items.push_back(Item{k, fs, data, on_dev});
+                sin.push_back(jsync::ScanIn{len, nivl, g.kind, k, comp, on_dev != nullptr, g.total_blocks});
+            };
+            if (d.pf)
+                for (const auto& fs : d.pf_scans) add(&fs, fs.data, fs.len, 1, fs.geom, fs.comp);
+            else add(nullptr, d.js_data, d.js_len, d.js_nivl, d.js_scan, 0);
+            imgs[k].nblocks = d.nblocks;
+            imgs[k].plane_bytes = make_geom(d, geom[k]);
+        }
+        ni = (int)items.size();
+        B = jsync::plan_layout(sin.data(), ni, imgs.data(), m, jsync::DevSizes{sizeof(JsImageDev), sizeof(JpegReconItem), jsync_chunk_scratch_bytes});
+        s = thread_stream();
+        dev = scratch_slot(1, B.total);
+        hp = dev ? pinned_slot(1, B.pin_bytes) : nullptr;
+        if (!dev || !hp) { to_host(false); return false; }
+        tm_layout = ms();
+        (void)hipStreamSynchronize(s);  // the pinned block is free
+        if (hipHostGetDevicePointer((void**)&hp_dev, hp, 0) != hipSuccess) hp_dev = nullptr;
+        tm_sync = ms();
+        return true;
+    }
+
+    // 2. one small upload (scan records, chunk table, Huffman and quantisation tables),
+    // the scan bytes, and the zeroing; false: no staging memory
+    bool upload() {
+        JsImageDev* I = reinterpret_cast<JsImageDev*>(hp + B.img.off);
+        int2* ch = reinterpret_cast<int2*>(hp + B.chunks.off);
         for (int t = 0; t < ni; ++t) {
-            const Item& L = items[t];
+            const jsync::ScanLay& L = B.scans[t];
             JsImageDev& J = I[t];
             J = JsImageDev{};
-            J.scan = dev + L.scan;
-            J.scan_len = (long long)L.len;
-            J.out = dev + L.out;
-            J.ivl = reinterpret_cast<long long*>(dev + o_ivl) + L.ivl0;
-            J.ivl_cap = (int)L.nivl + 1;
+            J.scan = items[t].on_dev ? items[t].on_dev : dev + L.scan.off;
+            J.scan_len = (long long)sin[t].len;
+            J.out = dev + L.out.off;
+            J.ivl = at<long long>(B.ivl) + L.ivl0;
+            J.ivl_cap = (int)sin[t].nivl + 1;
             J.chunk0 = L.chunk0;
             J.nchunks = L.nchunks;
-            J.totals = reinterpret_cast<uint32_t*>(dev + o_totals) + 2 * t;
-            J.status = reinterpret_cast<int*>(dev + o_status) + t;
+            J.totals = at<uint32_t>(B.totals) + 2 * t;
+            J.status = at<int>(B.status) + t;
             for (int c = 0; c < L.nchunks; ++c) ch[L.chunk0 + c] = make_int2(t, c);
         }
         parallel_for(ni, 0, [&](int t) {
-            const Item& L = items[t];
-            JpegHuffTables* T = reinterpret_cast<JpegHuffTables*>(hp + L.tab);
-            if (L.fs) std::memcpy(T, &L.fs->tabs, sizeof(JpegHuffTables));  // as they stood at the scan's SOS
-            else ds[idx[L.k]]->tables(*T);
+            JpegHuffTables* T = reinterpret_cast<JpegHuffTables*>(hp + B.scans[t].tab.off);
+            if (items[t].fs) std::memcpy(T, &items[t].fs->tabs, sizeof(JpegHuffTables));  // as they stood at the scan's SOS
+            else dec(items[t].k).tables(*T);
         });
-        parallel_for(m, 0, [&](int k) { qtables(*ds[idx[k]], reinterpret_cast<uint16_t*>(hp + lay[k].qt)); });
+        parallel_for(m, 0, [&](int k) { qtables(dec(k), reinterpret_cast<uint16_t*>(hp + B.images[k].qt.off)); });
+        // the scan bytes: where the upload stage put them (JpegUpload), else DMAed in
+        // place from page-locked memory, else through pinned staging
+        std::vector<char> in_place(ni, 0);
+        std::vector<size_t> st_off(ni, 0);
+        size_t st_total = 0;
+        for (int t = 0; t < ni; ++t) {
+            if (items[t].on_dev) continue;
+            in_place[t] = host_pinned(items[t].data, sin[t].len) ? 1 : 0;
+            if (!in_place[t]) { st_off[t] = st_total; st_total += up256(sin[t].len); }
+        }
+        uint8_t* hdata = st_total ? pinned_slot(2, st_total) : nullptr;
+        if (st_total && !hdata) { to_host(false); return false; }
+        if (st_total)
+            parallel_for(ni, 0, [&](int t) {
+                if (!in_place[t] && !items[t].on_dev) std::memcpy(hdata + st_off[t], items[t].data, sin[t].len);
+            });
+        tm_tables = ms();
+        const bool wait_up = up && up->n && up->ev;
+        if (timing && wait_up) {  // (IK_TIMING: how long the upload stage's DMA still had to run)
+            const double tw = ms();
+            if (hipEventQuery(up->ev) != hipSuccess) (void)hipEventSynchronize(up->ev);
+            tm_upwait = ms() - tw;
+        }
+        e = h2d(dev, 0, B.upload1.bytes);
+        for (int t = 0; t < ni && e == hipSuccess; ++t) {
+            if (items[t].on_dev || !sin[t].len) continue;
+            e = hipMemcpyAsync(dev + B.scans[t].scan.off, in_place[t] ? items[t].data : hdata + st_off[t], sin[t].len,
+                               hipMemcpyHostToDevice, s);
+        }
+        if (e == hipSuccess && wait_up) e = hipStreamWaitEvent(s, up->ev, 0);
+        if (e == hipSuccess) e = hipMemsetAsync(dev + B.readback.off, 0, B.readback.bytes, s);
+        // a progressive image's scans each store only what they code: its coefficients start at zero
+        for (int k = 0; k < m && e == hipSuccess; ++k)
+            if (dec(k).pf) e = hipMemsetAsync(dev + B.images[k].coef.off, 0, B.images[k].coef.bytes, s);
+        return true;
     }
-    // the scan bytes: where the upload stage put them (JpegUpload), else DMAed in
-    // place from page-locked memory, else through pinned staging
-    std::vector<char> in_place(ni, 0);
-    std::vector<size_t> st_off(ni, 0);
-    size_t st_total = 0;
-    for (int t = 0; t < ni; ++t) {
-        if (on_dev[t]) continue;
-        in_place[t] = host_pinned(items[t].data, items[t].len) ? 1 : 0;
-        if (!in_place[t]) { st_off[t] = st_total; st_total += up256(items[t].len); }
+
+    // 3. unstuffing; status, totals and the interval tables back; false: the device failed
+    bool unstuff() {
+        if (e == hipSuccess)
+            e = launch_jsync_unstuff(at<JsImageDev>(B.img), ni, at<const int2>(B.chunks), B.nchunks, at<uint2>(B.counts), s);
+        if (e == hipSuccess) e = d2h(0, dev + B.readback.off, B.readback.bytes);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { (void)hip_fail(e, "jpeg unstuff"); to_host(false); return false; }
+        t_unstuff = ms();
+        return true;
     }
-    for (int t = 0; t < ni; ++t)
-        if (on_dev[t]) reinterpret_cast<JsImageDev*>(hp + o_img)[t].scan = on_dev[t];
-    uint8_t* hdata = st_total ? pinned_slot(2, st_total) : nullptr;
-    if (st_total && !hdata) { fail_all("memory"); return; }
-    if (st_total)
-        parallel_for(ni, 0, [&](int t) {
-            if (!in_place[t] && !on_dev[t]) std::memcpy(hdata + st_off[t], items[t].data, items[t].len);
-        });
-    const double tm_tables = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    double tm_upwait = -1;  // (IK_TIMING: how long the upload stage's DMA still had to run)
-    if (timing && up && up->n && up->ev) {
-        const auto tw = std::chrono::steady_clock::now();
-        if (hipEventQuery(up->ev) != hipSuccess) (void)hipEventSynchronize(up->ev);
-        tm_upwait = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw).count();
-    }
-    hipError_t e = h2d(dev, 0, small_end);
-    for (int t = 0; t < ni && e == hipSuccess; ++t) {
-        if (on_dev[t] || !items[t].len) continue;
-        e = hipMemcpyAsync(dev + items[t].scan, in_place[t] ? items[t].data : hdata + st_off[t], items[t].len,
-                           hipMemcpyHostToDevice, s);
-    }
-    if (e == hipSuccess && up && up->n && up->ev) e = hipStreamWaitEvent(s, up->ev, 0);
-    if (e == hipSuccess) e = hipMemsetAsync(dev + o_status, 0, small2_end - o_status, s);
-    // a progressive image's scans each store only what they code: its coefficients start at zero
-    for (int k = 0; k < m && e == hipSuccess; ++k)
-        if (ds[idx[k]]->pf) e = hipMemsetAsync(dev + lay[k].coef, 0, ds[idx[k]]->nblocks * 64 * sizeof(int16_t), s);
-    // ---- 2. unstuffing; the interval tables back ----
-    if (e == hipSuccess)
-        e = launch_jsync_unstuff(reinterpret_cast<JsImageDev*>(dev + o_img), ni,
-                                 reinterpret_cast<const int2*>(dev + o_chunks), nchunks,
-                                 reinterpret_cast<uint2*>(dev + o_counts), s);
-    if (e == hipSuccess) e = d2h(0, dev + o_status, small2_end - o_status);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { (void)hip_fail(e, "jpeg unstuff"); fail_all("device"); return; }
-    const double t_unstuff = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    // ---- 3. lanes ----
-    std::vector<int> ok(m, 0), hstatus(m, 0);
-    std::vector<int> ivl_lane((size_t)nivl_total, 0);
-    std::vector<int2> wgs;
-    std::vector<Scan> scans(ni);
-    long long lanes_used = 0;
-    {
-        const int* hst = reinterpret_cast<const int*>(hp);
-        const uint32_t* tot = reinterpret_cast<const uint32_t*>(hp + (o_totals - o_status));
-        const long long* hivl = reinterpret_cast<const long long*>(hp + (o_ivl - o_status));
+
+    // 4. per image, each interval cut into lanes; the images that drop out go to the
+    // host; the refinement schedule; all of it into the pinned block.  False: no lanes
+    bool lanes() {
+        ok.assign(m, 0);
+        hstatus.assign(m, 0);
+        ivl_lane.assign((size_t)B.nivl_total, 0);
+        scans.resize(ni);
+        const int* hst = reinterpret_cast<const int*>(hp + B.in_readback(B.status));
+        const uint32_t* tot = reinterpret_cast<const uint32_t*>(hp + B.in_readback(B.totals));
+        const long long* hivl = reinterpret_cast<const long long*>(hp + B.in_readback(B.ivl));
         for (int k = 0; k < m; ++k) {
-            const Decoder& d = *ds[idx[k]];
-            const ImgLay& IL = lay[k];
+            const jsync::ImageLay& IL = B.images[k];
             // An image that drops out here still has Scans the per-scan kernels
             // (k_jsync_settle, k_jsync_seg2: a workgroup / a thread per scan of the
             // batch) load: ones with no lanes -- their tables, and an interval table whose
@@ -1242,184 +1111,151 @@ static void jsync_batch(std::vector<std::unique_ptr<Decoder>>& ds, const std::ve
             // shared a batch with one that decodes.)
             bool good = true;
             for (int t = IL.item0; t < IL.item0 + IL.nitems; ++t) {
-                const Item& L = items[t];
-                scans[t] = L.fs ? L.fs->geom : d.js_scan;
+                const jsync::ScanLay& L = B.scans[t];
+                scans[t] = items[t].fs ? items[t].fs->geom : dec(k).js_scan;
                 scans[t].nivl = 0;
                 scans[t].lane0 = L.lane0;
-                scans[t].ivl_lane = reinterpret_cast<const int*>(dev + o_ivlane) + L.ivl0;
-                scans[t].tabs = reinterpret_cast<const JpegHuffTables*>(dev + L.tab);
-                if (hst[t] || (long long)tot[2 * t + 1] + 1 != L.nivl) { good = false; continue; }  // stray marker / wrong restart count
-                if (!has_lanes(L.kind)) continue;  // (a refinement scan: no lanes, ivl_lane stays 0, 0)
-                const long long* iv = hivl + L.ivl0;
-                int* il = ivl_lane.data() + L.ivl0;
-                il[0] = 0;
-                for (long long q = 0; q < L.nivl; ++q) {
-                    const long long bits = iv[q + 1] - iv[q];
-                    if (bits < 0) { good = false; break; }
-                    il[q + 1] = il[q] + (int)std::max<long long>(1, (bits + lane_bits - 1) / lane_bits);
-                }
-                if (il[L.nivl] > L.lanes_max) good = false;
+                scans[t].ivl_lane = at<const int>(B.ivl_lane) + L.ivl0;
+                scans[t].tabs = reinterpret_cast<const JpegHuffTables*>(dev + L.tab.off);
+                if (hst[t] || (long long)tot[2 * t + 1] + 1 != sin[t].nivl) { good = false; continue; }  // stray marker / wrong restart count
+                if (!jsync::has_lanes(sin[t].kind)) continue;  // (a refinement scan: no lanes, ivl_lane stays 0, 0)
+                if (!jsync::split_lanes(hivl + L.ivl0, sin[t].nivl, B.lane_bits, L.lanes_max, ivl_lane.data() + L.ivl0)) good = false;
             }
             if (!good) {
                 for (int t = IL.item0; t < IL.item0 + IL.nitems; ++t)
-                    for (long long q = 0; q <= items[t].nivl; ++q) ivl_lane[items[t].ivl0 + q] = 0;
+                    for (long long q = 0; q <= sin[t].nivl; ++q) ivl_lane[B.scans[t].ivl0 + q] = 0;
                 continue;
             }
             ok[k] = 1;
             for (int t = IL.item0; t < IL.item0 + IL.nitems; ++t) {
-                const Item& L = items[t];
-                const int nl = ivl_lane[L.ivl0 + L.nivl];
+                const jsync::ScanLay& L = B.scans[t];
+                const int nl = ivl_lane[L.ivl0 + sin[t].nivl];
                 lanes_used += nl;
                 for (int w = 0; w < nl; w += 256) wgs.push_back(make_int2(t, w));
-                Scan& S = scans[t];
-                S.L = lane_bits;
-                S.words = reinterpret_cast<const uint32_t*>(dev + L.out);
-                S.ivl = reinterpret_cast<const long long*>(dev + o_ivl) + L.ivl0;
-                S.nivl = (int)L.nivl;
-                S.coef = reinterpret_cast<int16_t*>(dev + IL.coef);
+                jsync::Scan& S = scans[t];
+                S.L = B.lane_bits;
+                S.words = reinterpret_cast<const uint32_t*>(dev + L.out.off);
+                S.ivl = at<const long long>(B.ivl) + L.ivl0;
+                S.nivl = (int)sin[t].nivl;
+                S.coef = at<int16_t>(IL.coef);
             }
         }
+        for (int k = 0; k < m; ++k)
+            if (!ok[k]) host_idx.push_back(idx[k]);
+        if (wgs.empty()) return false;
+        R = jsync::plan_refinement(sin.data(), ni, ok.data());
+        static_assert(sizeof(jsync::Chain) == sizeof(int2), "k_jprog_ac_chain reads the chains as int2");
+        auto put = [&](const jsync::Region& r, const void* src, size_t bytes) {
+            if (bytes) std::memcpy(hp + B.in_upload2(r), src, bytes);
+        };
+        put(B.scan_tab, scans.data(), sizeof(jsync::Scan) * ni);
+        put(B.ivl_lane, ivl_lane.data(), sizeof(int) * B.nivl_total);
+        put(B.wgs, wgs.data(), sizeof(int2) * wgs.size());
+        put(B.rlist, R.rlist.data(), sizeof(int) * R.rlist.size());
+        put(B.chains, R.chains.data(), sizeof(jsync::Chain) * R.chains.size());
+        return true;
     }
-    for (int k = 0; k < m; ++k)
-        if (!ok[k]) host_idx.push_back(idx[k]);
-    const int nwg = (int)wgs.size();
-    if (!nwg) return;
-    // the refinement scans of the progressive images: launch r takes the r-th DC
-    // refinement scan of every image that has one; a chain per (image, component)
-    // takes that component's AC refinement scans in file order
-    std::vector<std::vector<int>> dc_rounds;
-    std::vector<int> rlist;
-    std::vector<int2> chains;
-    std::vector<long long> dc_blocks;
-    {
-        std::vector<std::vector<int>> ac(4);
-        for (int k = 0; k < m; ++k) {
-            if (!ok[k] || !ds[idx[k]]->pf) continue;
-            const ImgLay& IL = lay[k];
-            size_t r = 0;
-            for (auto& v : ac) v.clear();
-            for (int t = IL.item0; t < IL.item0 + IL.nitems; ++t) {
-                if (items[t].kind == kDcRefine) {
-                    if (dc_rounds.size() <= r) { dc_rounds.emplace_back(); dc_blocks.push_back(0); }
-                    dc_rounds[r].push_back(t);
-                    dc_blocks[r] = std::max(dc_blocks[r], scans[t].total_blocks);
-                    ++r;
-                } else if (items[t].kind == kAcRefine) {
-                    ac[items[t].fs->comp].push_back(t);
-                }
-            }
-            for (auto& v : ac)
-                if (!v.empty()) {
-                    chains.push_back(make_int2((int)rlist.size(), (int)v.size()));
-                    rlist.insert(rlist.end(), v.begin(), v.end());
-                }
-        }
-        // rlist: [DC launch 0 | DC launch 1 | ... | the chains' scans]
-        std::vector<int> all;
-        for (auto& v : dc_rounds) all.insert(all.end(), v.begin(), v.end());
-        for (int2& c : chains) c.x += (int)all.size();
-        all.insert(all.end(), rlist.begin(), rlist.end());
-        rlist.swap(all);
-    }
-    std::memcpy(hp, scans.data(), sizeof(Scan) * ni);
-    std::memcpy(hp + (o_ivlane - o_scans), ivl_lane.data(), sizeof(int) * nivl_total);
-    std::memcpy(hp + (o_wgs - o_scans), wgs.data(), sizeof(int2) * nwg);
-    if (!rlist.empty()) std::memcpy(hp + (o_rlist - o_scans), rlist.data(), sizeof(int) * rlist.size());
-    if (!chains.empty()) std::memcpy(hp + (o_chains - o_scans), chains.data(), sizeof(int2) * chains.size());
-    const Scan* d_scans = reinterpret_cast<const Scan*>(dev + o_scans);
-    const int2* d_wgs = reinterpret_cast<const int2*>(dev + o_wgs);
-    LaneRec* d_recs = reinterpret_cast<LaneRec*>(dev + o_recs);
-    int* d_status = reinterpret_cast<int*>(dev + o_status);
-    int* d_changed = reinterpret_cast<int*>(dev + o_changed);
-    const int* d_rlist = reinterpret_cast<const int*>(dev + o_rlist);
-    // ---- 4. sync, fix rounds, bases, decode; then the refinement scans ----
-    EvPair& ev = thread_events(2);
-    EvPair& ev2 = thread_events(3);
-    e = h2d(dev + o_scans, 0, tab2_bytes);
-    if (e == hipSuccess) ev_record(ev.a, s);
-    if (e == hipSuccess) e = launch_jsync_sync(d_scans, d_wgs, nwg, d_recs, s);
-    if (e == hipSuccess) e = hipMemsetAsync(d_changed, 0, sizeof(int), s);
-    if (e == hipSuccess) e = launch_jsync_fix(d_scans, ni, d_wgs, nwg, d_recs, d_changed, s);
-    if (e == hipSuccess)
-        e = launch_jsync_bases_decode(d_scans, ni, d_wgs, nwg, d_recs, reinterpret_cast<LaneBase*>(dev + o_bases),
-                                      dev + o_cs, d_status, s);
-    if (e == hipSuccess) ev_record(ev.b, s);
-    const bool refine = !rlist.empty();
-    if (refine) {
-        int at = 0;
-        for (size_t r = 0; r < dc_rounds.size() && e == hipSuccess; ++r) {
-            e = launch_jprog_dc_refine(d_scans, d_rlist + at, (int)dc_rounds[r].size(), dc_blocks[r], s);
-            at += (int)dc_rounds[r].size();
-        }
-        if (e == hipSuccess) ev_record(ev2.a, s);
+
+    // 5. sync, fix rounds, bases, decode; then the refinement scans; status and the
+    // settle kernel's rounds back.  False: the device failed
+    bool launch() {
+        const jsync::Scan* d_scans = at<const jsync::Scan>(B.scan_tab);
+        const int2* d_wgs = at<const int2>(B.wgs);
+        const int nwg = (int)wgs.size();
+        jsync::LaneRec* d_recs = at<jsync::LaneRec>(B.recs);
+        int* d_status = at<int>(B.status);
+        int* d_changed = at<int>(B.changed);
+        const int* d_rlist = at<const int>(B.rlist);
+        ev = &thread_events(2);
+        ev2 = &thread_events(3);
+        e = h2d(dev + B.upload2.off, 0, B.upload2.bytes);
+        if (e == hipSuccess) ev_record(ev->a, s);
+        if (e == hipSuccess) e = launch_jsync_sync(d_scans, d_wgs, nwg, d_recs, s);
+        if (e == hipSuccess) e = hipMemsetAsync(d_changed, 0, sizeof(int), s);
+        if (e == hipSuccess) e = launch_jsync_fix(d_scans, ni, d_wgs, nwg, d_recs, d_changed, s);
         if (e == hipSuccess)
-            e = launch_jprog_ac_chain(d_scans, reinterpret_cast<const int2*>(dev + o_chains), (int)chains.size(), d_rlist,
-                                      d_status, s);
-        if (e == hipSuccess) ev_record(ev2.b, s);
-    }
-    int rounds = 0;  // the settle kernel's most rounds over the batch's scans
-    if (e == hipSuccess) e = d2h(0, reinterpret_cast<const uint8_t*>(d_status), sizeof(int) * ni);
-    if (e == hipSuccess) e = d2h(up256(sizeof(int) * ni), reinterpret_cast<const uint8_t*>(d_changed), sizeof(int));
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess) {
+            e = launch_jsync_bases_decode(d_scans, ni, d_wgs, nwg, d_recs, at<jsync::LaneBase>(B.bases), dev + B.cs.off, d_status, s);
+        if (e == hipSuccess) ev_record(ev->b, s);
+        const bool refine = !R.rlist.empty();
+        if (refine) {
+            int at_scan = 0;
+            for (size_t r = 0; r < R.dc_sizes.size() && e == hipSuccess; ++r) {
+                e = launch_jprog_dc_refine(d_scans, d_rlist + at_scan, R.dc_sizes[r], R.dc_blocks[r], s);
+                at_scan += R.dc_sizes[r];
+            }
+            if (e == hipSuccess) ev_record(ev2->a, s);
+            if (e == hipSuccess)
+                e = launch_jprog_ac_chain(d_scans, at<const int2>(B.chains), (int)R.chains.size(), d_rlist, d_status, s);
+            if (e == hipSuccess) ev_record(ev2->b, s);
+        }
+        if (e == hipSuccess) e = d2h(0, reinterpret_cast<const uint8_t*>(d_status), sizeof(int) * ni);
+        if (e == hipSuccess) e = d2h(B.pin_changed, reinterpret_cast<const uint8_t*>(d_changed), sizeof(int));
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            (void)hip_fail(e, "jpeg entropy decode");
+            to_host(true);
+            return false;
+        }
         const int* hs = reinterpret_cast<const int*>(hp);
         for (int t = 0; t < ni; ++t) hstatus[items[t].k] |= hs[t];  // any scan's flag sends the image to the host
-        std::memcpy(&rounds, hp + up256(sizeof(int) * ni), sizeof(int));
+        std::memcpy(&rounds, hp + B.pin_changed, sizeof(int));
+        if (refine) {  // ik_jpeg_prog_free_ms: the last batch's phase A, DC refinement and chain launches
+            float dc_ms = 0.f;
+            if (!ev->b || !ev2->a || hipEventElapsedTime(&dc_ms, ev->b, ev2->a) != hipSuccess) dc_ms = 0.f;
+            g_prog_free_ms[0].store(ev_pair_ms(*ev));
+            g_prog_free_ms[1].store(dc_ms);
+            g_prog_free_ms[2].store(ev_pair_ms(*ev2));
+        }
+        return true;
     }
-    if (e != hipSuccess) {
-        if (e != hipSuccess) (void)hip_fail(e, "jpeg entropy decode");
-        for (int k = 0; k < m; ++k)
-            if (ok[k]) host_idx.push_back(idx[k]);
-        return;
-    }
-    if (refine) {  // ik_jpeg_prog_free_ms: the last batch's phase A, DC refinement and chain launches
-        float dc_ms = 0.f;
-        if (!ev.b || !ev2.a || hipEventElapsedTime(&dc_ms, ev.b, ev2.a) != hipSuccess) dc_ms = 0.f;
-        g_prog_free_ms[0].store(ev_pair_ms(ev));
-        g_prog_free_ms[1].store(dc_ms);
-        g_prog_free_ms[2].store(ev_pair_ms(ev2));
-    }
+
 #ifdef IK_JPEG_DUMP  // dev experiment: every image's unstuffed words, lane tables and coefficients (its first scan's)
-    if (e == hipSuccess) {
+    void dump() {
         std::lock_guard<std::mutex> lk(g_jdump_mu);
         g_jdump.assign(m, {});
         for (int k = 0; k < m; ++k) {
             if (!ok[k]) continue;
-            const Decoder& d = *ds[idx[k]];
-            const Item& L = items[lay[k].item0];
-            const int nl = ivl_lane[L.ivl0 + L.nivl];
+            const int t = B.images[k].item0;
+            const jsync::ScanLay& L = B.scans[t];
+            const long long nivl = sin[t].nivl;
+            const int nl = ivl_lane[L.ivl0 + nivl];
             auto get = [&](int what, const void* src, size_t bytes) {
                 g_jdump[k][what].resize(bytes);
                 (void)hipMemcpy(g_jdump[k][what].data(), src, bytes, hipMemcpyDeviceToHost);
             };
-            get(0, dev + L.out, L.len);
-            get(1, dev + o_ivl + sizeof(long long) * L.ivl0, sizeof(long long) * (L.nivl + 1));
-            get(2, dev + o_recs + sizeof(LaneRec) * L.lane0, sizeof(LaneRec) * nl);
-            get(3, dev + o_bases + sizeof(LaneBase) * L.lane0, sizeof(LaneBase) * nl);
-            get(4, dev + lay[k].coef, d.nblocks * 64 * sizeof(int16_t));
-            g_jdump[k][5].resize(sizeof(int) * (L.nivl + 1));
-            std::memcpy(g_jdump[k][5].data(), ivl_lane.data() + L.ivl0, sizeof(int) * (L.nivl + 1));
+            get(0, dev + L.out.off, sin[t].len);
+            get(1, at<long long>(B.ivl) + L.ivl0, sizeof(long long) * (nivl + 1));
+            get(2, at<jsync::LaneRec>(B.recs) + L.lane0, sizeof(jsync::LaneRec) * nl);
+            get(3, at<jsync::LaneBase>(B.bases) + L.lane0, sizeof(jsync::LaneBase) * nl);
+            get(4, dev + B.images[k].coef.off, B.images[k].coef.bytes);
+            g_jdump[k][5].resize(sizeof(int) * (nivl + 1));
+            std::memcpy(g_jdump[k][5].data(), ivl_lane.data() + L.ivl0, sizeof(int) * (nivl + 1));
             g_jdump[k][6].resize(sizeof(int) * 2);
             std::memcpy(g_jdump[k][6].data(), &hstatus[k], sizeof(int));
             std::memcpy(g_jdump[k][6].data() + sizeof(int), &rounds, sizeof(int));
         }
     }
 #endif
-    {  // ik_batch_last_timing: the decoding launches' time and algorithmic bytes
+
+    // 6. ik_batch_last_timing: the decoding launches' time and algorithmic bytes
+    void counters() {
         double scan = 0, coef = 0;
-        for (const Item& L : items)
-            if (ok[L.k]) scan += (double)L.len;
+        for (int t = 0; t < ni; ++t)
+            if (ok[items[t].k]) scan += (double)sin[t].len;
         for (int k = 0; k < m; ++k)
-            if (ok[k]) coef += (double)ds[idx[k]]->nblocks * 64 * sizeof(int16_t);
+            if (ok[k]) coef += (double)B.images[k].coef.bytes;
         const int d = current_device();
-        batch_timing_add(d, kBtJpegHuffMs, ev_pair_ms(ev) + (refine ? g_prog_free_ms[1].load() + g_prog_free_ms[2].load() : 0.f));
+        const bool refine = !R.rlist.empty();
+        batch_timing_add(d, kBtJpegHuffMs, ev_pair_ms(*ev) + (refine ? g_prog_free_ms[1].load() + g_prog_free_ms[2].load() : 0.f));
         batch_timing_add(d, kBtJpegScanBytes, scan);
         batch_timing_add(d, kBtJpegCoefBytes, coef);
         batch_timing_add(d, kBtJpegImages, (double)(lanes_used ? std::count(ok.begin(), ok.end(), 1) : 0));
         batch_timing_add(d, kBtJpegLanes, (double)lanes_used);
     }
-    // ---- 5. reconstruction: every image in three launches ----
-    {
+
+    // 7. reconstruction, every image in three launches; then each image is counted,
+    // or -- the device failed -- handed to the host decoder
+    void reconstruct() {
         JpegReconItem* ritems = reinterpret_cast<JpegReconItem*>(hp);
         int mi = 0, max_w = 0, max_h = 0;
         long long max_blocks = 0;
@@ -1429,10 +1265,10 @@ static void jsync_batch(std::vector<std::unique_ptr<Decoder>>& ds, const std::ve
             const int i = idx[k];
             if (hstatus[k]) { host_idx.push_back(i); continue; }
             const Decoder& d = *ds[i];
-            JpegGeom g = lay[k].g;
-            g.qt = reinterpret_cast<const uint16_t*>(dev + lay[k].qt);
-            g.coef = reinterpret_cast<const int16_t*>(dev + lay[k].coef);
-            g.planes = dev + lay[k].pl;
+            JpegGeom g = geom[k];
+            g.qt = at<const uint16_t>(B.images[k].qt);
+            g.coef = at<const int16_t>(B.images[k].coef);
+            g.planes = dev + B.images[k].pl.off;
             ik_image* img = nullptr;
             st[i] = alloc_image((uint32_t)d.width, (uint32_t)d.height, d.comps.size() == 1 ? 1u : 3u, &img);
             if (st[i]) continue;
@@ -1445,34 +1281,45 @@ static void jsync_batch(std::vector<std::unique_ptr<Decoder>>& ds, const std::ve
             any_fast = any_fast || fast;
             any_slow = any_slow || !fast;
         }
-        const JpegReconItem* d_items = reinterpret_cast<const JpegReconItem*>(dev + o_items);
-        e = h2d(dev + o_items, 0, sizeof(JpegReconItem) * mi);
-        if (e == hipSuccess) e = launch_jpeg_reconstruct_batch(d_items, mi, max_blocks, max_w, max_h, any_fast, any_slow, true, s);
+        e = h2d(dev + B.items.off, 0, sizeof(JpegReconItem) * mi);
+        if (e == hipSuccess)
+            e = launch_jpeg_reconstruct_batch(at<const JpegReconItem>(B.items), mi, max_blocks, max_w, max_h, any_fast, any_slow, true, s);
         if (e != hipSuccess) (void)hip_fail(e, "jpeg reconstruct");
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    for (int k = 0; k < m; ++k) {
-        const int i = idx[k];
-        if (!ok[k] || hstatus[k] || !outs[i]) continue;
-        if (e != hipSuccess) {  // the device failed: the host decoder takes them
-            ik_image_free(outs[i]);
-            outs[i] = nullptr;
-            st[i] = IK_OK;
-            host_idx.push_back(i);
-            continue;
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        for (int k = 0; k < m; ++k) {
+            const int i = idx[k];
+            if (!ok[k] || hstatus[k] || !outs[i]) continue;
+            if (e != hipSuccess) {  // the device failed: the host decoder takes them
+                ik_image_free(outs[i]);
+                outs[i] = nullptr;
+                st[i] = IK_OK;
+                host_idx.push_back(i);
+                continue;
+            }
+            g_jpeg_gpu_streams += 1;
         }
-        g_jpeg_gpu_streams += 1;
+        if (timing)
+            fprintf(stderr, "[jsync] %d images, %d scans, %lld lanes, %d fix rounds: layout %.2f, sync %.2f, tables %.2f, upload wait %.2f, "
+                    "unstuff %.2f ms, total %.2f ms\n", m, ni, lanes_used, rounds, tm_layout, tm_sync, tm_tables, tm_upwait, t_unstuff, ms());
     }
-    if (timing)
-        fprintf(stderr, "[jsync] %d images, %d scans, %lld lanes, %d fix rounds: layout %.2f, sync %.2f, tables %.2f, upload wait %.2f, "
-                "unstuff %.2f ms, total %.2f ms\n", m, ni, lanes_used, rounds, tm_layout, tm_sync, tm_tables, tm_upwait, t_unstuff,
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-}
+};
 
-}  // namespace
-int decode_jpeg_batch(const uint8_t* const* bytes, const size_t* lens, int n, ik_image** outs, int* status,
-                      std::string* msgs, const JpegUpload* up);
-namespace {
+static void jsync_batch(std::vector<std::unique_ptr<Decoder>>& ds, const std::vector<int>& idx, ik_image** outs,
+                        std::vector<int>& st, std::vector<int>& host_idx, const uint8_t* const* files,
+                        const JpegUpload* up) {
+    if (idx.empty()) return;
+    JsyncBatch J(ds, idx, outs, st, host_idx, files, up);
+    if (!J.layout()) return;   // no memory: every image to the host decoder
+    if (!J.upload()) return;   // (the same)
+    if (!J.unstuff()) return;  // the device failed: every image to the host decoder
+    if (!J.lanes()) return;    // no image left with lanes (those that dropped out are the host's)
+    if (!J.launch()) return;   // the device failed: the images that had lanes to the host decoder
+#ifdef IK_JPEG_DUMP
+    J.dump();
+#endif
+    J.counters();
+    J.reconstruct();
+}
 
 // try_gpu: baseline scans go through the self-synchronising GPU decoder (the batch
 // path with one image), progressive scans with restart intervals scan by scan

@@ -8,13 +8,19 @@
 // a plain serial decode of the same scan (interval by interval from its exact
 // start), so that the tests can check the parallel machinery on many streams
 // without a GPU and report how many lanes the warm-up synchronised.
+//
+// Shared with the product, not copied: the kernels' per-lane code (ik_jpeg_sync.h)
+// and the host's plan (ik_jsync_plan.h) -- Huffman table build and packing, scan
+// geometry, lane capacity and split, and, through ikm_jsync_plan, the lane length,
+// the scratch layout and the refinement schedule.  The model's own: the marker
+// parsers below (test scaffolding) and the serial reference decoders.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
-#include "ik_jpeg_sync.h"
+#include "ik_jsync_plan.h"
 
 using namespace ik;
 using namespace ik::jsync;
@@ -25,79 +31,40 @@ const uint8_t kZz[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11,
                          41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                          30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
-struct Huff {
-    bool present = false;
-    int maxcode[18] = {}, valptr[17] = {}, mincode[17] = {};
-    uint8_t vals[256] = {};
-    uint8_t look_len[512] = {}, look_val[512] = {};
-};
-
-bool build(const uint8_t* bits, const uint8_t* vals, int nvals, Huff& t) {
-    t = Huff();
-    std::memcpy(t.vals, vals, nvals);
-    int code = 0, k = 0;
-    for (int l = 1; l <= 16; ++l) {
-        t.valptr[l] = k;
-        t.mincode[l] = code;
-        code += bits[l - 1];
-        k += bits[l - 1];
-        t.maxcode[l] = bits[l - 1] ? code - 1 : -1;
-        if (code > (1 << l)) return false;
-        code <<= 1;
-    }
-    t.maxcode[17] = 0x7fffffff;
-    code = 0;
-    k = 0;
-    for (int l = 1; l <= 9; ++l) {
-        for (int i = 0; i < bits[l - 1]; ++i, ++k, ++code)
-            for (int f = 0; f < (1 << (9 - l)); ++f) {
-                t.look_len[(code << (9 - l)) | f] = (uint8_t)l;
-                t.look_val[(code << (9 - l)) | f] = vals[k];
-            }
-        code <<= 1;
-    }
-    t.present = true;
-    return true;
-}
-
-// the product's table layout (ik_jpeg_decode.cpp Decoder::tables)
-void tables(const Huff* dc, const Huff* ac, JpegHuffTables& t) {
-    std::memset(&t, 0, sizeof(t));
-    for (int k = 0; k < 8; ++k) {
-        const Huff& h = k < 4 ? dc[k] : ac[k - 4];
-        for (int i = 0; i < 512; ++i) t.look[k][i] = (uint16_t)(h.look_len[i] << 8 | h.look_val[i]);
-        std::memcpy(t.maxcode[k], h.maxcode, sizeof(h.maxcode));
-        std::memcpy(t.valptr[k], h.valptr, sizeof(h.valptr));
-        std::memcpy(t.mincode[k], h.mincode, sizeof(h.mincode));
-        std::memcpy(t.vals[k], h.vals, sizeof(h.vals));
-        int carry = 0;
-        for (int l = 1; l <= 16; ++l) {
-            if (h.maxcode[l] >= 0) carry = (h.maxcode[l] + 1) << (16 - l);
-            t.lj[k][l] = carry;
+// what both parsers below keep of a file: its tables as they stand and its frame
+struct Frame {
+    HuffTable dc[4], ac[4];
+    std::vector<CompGeom> comps;
+    int id[4] = {};
+    int W = 0, H = 0, hmax = 1, vmax = 1, mcux = 0, mcuy = 0;
+    long long nblocks = 0;
+    // s: the SOF payload, its sampling factors checked by the caller
+    void frame(const uint8_t* s) {
+        H = (int)s[1] << 8 | s[2];
+        W = (int)s[3] << 8 | s[4];
+        comps.assign(s[5], CompGeom{});
+        for (size_t i = 0; i < comps.size(); ++i) {
+            id[i] = s[6 + 3 * i];
+            comps[i].h = s[7 + 3 * i] >> 4;
+            comps[i].v = s[7 + 3 * i] & 15;
+            hmax = std::max(hmax, comps[i].h);
+            vmax = std::max(vmax, comps[i].v);
         }
-        if (k < 4) continue;
-        for (int i = 0; i < 512; ++i) {
-            const int L = h.look_len[i], rs = h.look_val[i], r = rs >> 4, sz = rs & 15;
-            if (!L || !sz || L + sz > 9) continue;
-            const int v = (i >> (9 - L - sz)) & ((1 << sz) - 1);
-            const int val = v < (1 << (sz - 1)) ? v - (1 << sz) + 1 : v;
-            if (val < -128 || val > 127) continue;
-            t.fast_ac[k - 4][i] = (int16_t)(val * 256 + r * 16 + L + sz);
+        mcux = (W + 8 * hmax - 1) / (8 * hmax);
+        mcuy = (H + 8 * vmax - 1) / (8 * vmax);
+        for (auto& c : comps) {
+            c.bw = mcux * c.h;
+            c.dw = (W * c.h + hmax - 1) / hmax;
+            c.dh = (H * c.v + vmax - 1) / vmax;
+            c.blk0 = nblocks;
+            nblocks += (long long)c.bw * mcuy * c.v;
         }
     }
-}
-
-struct Comp {
-    int id = 0, h = 1, v = 1, td = 0, ta = 0, bw = 0, bh = 0, dw = 0, dh = 0;
-    long long blk0 = 0;
 };
 
 // a baseline single-scan JPEG, parsed far enough for the entropy decoder
-struct Jpeg {
-    Huff dc[4], ac[4];
-    std::vector<Comp> comps;
-    int W = 0, H = 0, restart = 0, hmax = 1, vmax = 1, mcux = 0, mcuy = 0;
-    long long nblocks = 0;
+struct Jpeg : Frame {
+    int restart = 0;
     std::vector<int> order;
     const uint8_t* scan = nullptr;
     size_t scan_len = 0;
@@ -117,40 +84,21 @@ struct Jpeg {
                     const int tc = s[0] >> 4, th = s[0] & 15;
                     int total = 0;
                     for (int i = 0; i < 16; ++i) total += s[1 + i];
-                    if (!build(s + 1, s + 17, total, tc ? ac[th] : dc[th])) return false;
+                    if (!build_huff(s + 1, s + 17, total, tc ? ac[th] : dc[th])) return false;
                     s += 17 + total;
                 }
             } else if (m == 0xDD) {
                 restart = be16(p + 4);
             } else if (m == 0xC0 || m == 0xC1) {
-                H = be16(p + 5);
-                W = be16(p + 7);
-                const int nc = s[5];
-                comps.resize(nc);
-                for (int i = 0; i < nc; ++i) {
-                    comps[i].id = s[6 + 3 * i];
-                    comps[i].h = s[7 + 3 * i] >> 4;
-                    comps[i].v = s[7 + 3 * i] & 15;
-                    hmax = std::max(hmax, comps[i].h);
-                    vmax = std::max(vmax, comps[i].v);
-                }
-                mcux = (W + 8 * hmax - 1) / (8 * hmax);
-                mcuy = (H + 8 * vmax - 1) / (8 * vmax);
-                for (auto& c : comps) {
-                    c.bw = mcux * c.h;
-                    c.bh = mcuy * c.v;
-                    c.dw = (W * c.h + hmax - 1) / hmax;
-                    c.dh = (H * c.v + vmax - 1) / vmax;
-                    c.blk0 = nblocks;
-                    nblocks += (long long)c.bw * c.bh;
-                }
+                if (s[5] > 4) return false;
+                frame(s);
             } else if (m == 0xC2) {
                 return false;  // progressive: not this decoder's
             } else if (m == 0xDA) {
                 const int ns = s[0];
                 for (int i = 0; i < ns; ++i) {
                     for (int k = 0; k < (int)comps.size(); ++k)
-                        if (comps[k].id == s[1 + 2 * i]) {
+                        if (id[k] == s[1 + 2 * i]) {
                             comps[k].td = s[2 + 2 * i] >> 4;
                             comps[k].ta = s[2 + 2 * i] & 15;
                             order.push_back(k);
@@ -181,34 +129,12 @@ struct Model {
     long long total_mcu = 0;
 
     bool setup() {
-        tables(J.dc, J.ac, T);
-        const bool single = J.order.size() == 1;
-        int bpm = 0;
-        for (size_t i = 0; i < J.order.size(); ++i) {
-            const Comp& c = J.comps[J.order[i]];
-            const int nb = single ? 1 : c.h * c.v;
-            for (int k = 0; k < nb; ++k) {
-                if (bpm >= kMaxBPM) return false;
-                S.comp_of[bpm] = (int)i;
-                S.bx_of[bpm] = single ? 0 : k % c.h;
-                S.by_of[bpm] = single ? 0 : k / c.h;
-                ++bpm;
-            }
-            S.h[i] = c.h; S.v[i] = c.v; S.bw[i] = c.bw; S.td[i] = c.td; S.ta[i] = c.ta + 4;
-            S.td[i] = c.td;
-            S.blk0[i] = c.blk0;
-        }
-        // (S.ta holds the table index 4..7 in the combined table: see block())
-        for (size_t i = 0; i < J.order.size(); ++i) S.ta[i] = J.comps[J.order[i]].ta;
-        const Comp& c0 = J.comps[J.order[0]];
-        const int sbw = (c0.dw + 7) / 8, sbh = (c0.dh + 7) / 8;
-        total_mcu = single ? (long long)sbw * sbh : (long long)J.mcux * J.mcuy;
-        S.bpm = bpm;
-        S.mcux = J.mcux;
-        S.single = single;
-        S.single_bw = sbw;
-        S.total_blocks = total_mcu * bpm;
-        S.ivl_blocks = J.restart ? (long long)J.restart * bpm : S.total_blocks;
+        pack_tables(J.dc, J.ac, T);
+        const int L = S.L, W = S.W;  // (the caller's)
+        if (!scan_geom(J.comps.data(), J.order.data(), (int)J.order.size(), J.mcux, J.mcuy, S, total_mcu)) return false;
+        S.L = L;
+        S.W = W;
+        if (J.restart) S.ivl_blocks = (long long)J.restart * S.bpm;  // as defer_jsync
         // unstuff, byte by byte (the GPU's rule)
         std::vector<uint8_t> out;
         ivl.assign(1, 0);
@@ -227,11 +153,7 @@ struct Model {
         words.assign((out.size() + 3) / 4 + kPadWords, 0u);
         for (size_t i = 0; i < out.size(); ++i) words[i >> 2] |= (uint32_t)out[i] << (24 - 8 * (i & 3));
         ivl_lane.assign(ivl.size(), 0);
-        for (size_t k = 0; k + 1 < ivl.size(); ++k) {
-            const long long bits = ivl[k + 1] - ivl[k];
-            const int nl = bits > 0 ? (int)((bits + S.L - 1) / S.L) : 1;
-            ivl_lane[k + 1] = ivl_lane[k] + nl;
-        }
+        if (!split_lanes(ivl.data(), want_ivl, S.L, lane_capacity(kBaseline, n, want_ivl, S.L), ivl_lane.data())) return false;
         S.words = words.data();
         S.ivl = ivl.data();
         S.nivl = (int)ivl.size() - 1;
@@ -437,11 +359,7 @@ struct PScan {
     long long nbits = 0;
 };
 
-struct ProgFile {
-    Huff dc[4], ac[4];
-    std::vector<Comp> comps;
-    int W = 0, H = 0, hmax = 1, vmax = 1, mcux = 0, mcuy = 0;
-    long long nblocks = 0;
+struct ProgFile : Frame {
     std::vector<PScan> scans;
 
     // false: not a restart-free 8-bit SOF2 file whose scans pass the host parser's checks
@@ -449,7 +367,7 @@ struct ProgFile {
         if (n < 4 || b[0] != 0xFF || b[1] != 0xD8) return false;
         size_t p = 2;
         auto be16 = [&](size_t q) { return (int)b[q] << 8 | b[q + 1]; };
-        bool frame = false;
+        bool have_frame = false;
         int restart = 0;
         while (p + 4 <= n) {
             if (b[p] != 0xFF) { ++p; continue; }
@@ -468,48 +386,32 @@ struct ProgFile {
                     int total = 0;
                     for (int i = 0; i < 16; ++i) total += s[1 + i];
                     if (total > 256 || s + 17 + total > se) return false;
-                    if (!build(s + 1, s + 17, total, tc ? ac[th] : dc[th])) return false;
+                    if (!build_huff(s + 1, s + 17, total, tc ? ac[th] : dc[th])) return false;
                     s += 17 + total;
                 }
             } else if (m == 0xDD) {
                 restart = be16(p + 4);
             } else if (m == 0xC2) {
-                if (frame || s[0] != 8) return false;
-                H = be16(p + 5);
-                W = be16(p + 7);
+                if (have_frame || s[0] != 8) return false;
                 const int nc = s[5];
-                if (!W || !H || (nc != 1 && nc != 3 && nc != 4)) return false;
-                comps.resize(nc);
+                if (!be16(p + 5) || !be16(p + 7) || (nc != 1 && nc != 3 && nc != 4)) return false;
                 for (int i = 0; i < nc; ++i) {
-                    comps[i].id = s[6 + 3 * i];
-                    comps[i].h = s[7 + 3 * i] >> 4;
-                    comps[i].v = s[7 + 3 * i] & 15;
-                    if (comps[i].h < 1 || comps[i].h > 4 || comps[i].v < 1 || comps[i].v > 4) return false;
-                    hmax = std::max(hmax, comps[i].h);
-                    vmax = std::max(vmax, comps[i].v);
+                    const int h = s[7 + 3 * i] >> 4, v = s[7 + 3 * i] & 15;
+                    if (h < 1 || h > 4 || v < 1 || v > 4) return false;
                 }
-                mcux = (W + 8 * hmax - 1) / (8 * hmax);
-                mcuy = (H + 8 * vmax - 1) / (8 * vmax);
-                for (auto& c : comps) {
-                    c.bw = mcux * c.h;
-                    c.bh = mcuy * c.v;
-                    c.dw = (W * c.h + hmax - 1) / hmax;
-                    c.dh = (H * c.v + vmax - 1) / vmax;
-                    c.blk0 = nblocks;
-                    nblocks += (long long)c.bw * c.bh;
-                }
-                frame = true;
+                frame(s);
+                have_frame = true;
             } else if (m >= 0xC0 && m <= 0xCF && m != 0xC8 && m != 0xCC) {
                 return false;  // any other frame type
             } else if (m == 0xDA) {
-                if (!frame || restart) return false;
+                if (!have_frame || restart) return false;
                 PScan sc;
                 const int ns = s[0];
                 if (ns < 1 || ns > (int)comps.size() || se - s < 1 + 2 * ns + 3) return false;
                 for (int i = 0; i < ns; ++i) {
                     int k = -1;
                     for (int j = 0; j < (int)comps.size(); ++j)
-                        if (comps[j].id == s[1 + 2 * i]) k = j;
+                        if (id[j] == s[1 + 2 * i]) k = j;
                     if (k < 0) return false;
                     sc.td[i] = s[2 + 2 * i] >> 4;
                     sc.ta[i] = s[2 + 2 * i] & 15;
@@ -532,7 +434,7 @@ struct ProgFile {
                     if (sc.kind == kDcFirst && !dc[sc.td[i]].present) return false;
                     if (sc.kind >= kAcFirst && !ac[sc.ta[i]].present) return false;
                 }
-                tables(dc, ac, sc.T);
+                pack_tables(dc, ac, sc.T);
                 // the scan ends at the first marker (an RSTn is a stray one here)
                 size_t q = (size_t)(se - b);
                 while (q + 1 < n && !(b[q] == 0xFF && b[q + 1] != 0x00 && b[q + 1] != 0xFF)) ++q;
@@ -549,38 +451,17 @@ struct ProgFile {
             }
             p += 2 + len;
         }
-        return frame && !scans.empty();
+        return have_frame && !scans.empty();
     }
 };
 
-// the lane scheme's view of scan sc (geometry as ik_jpeg_decode.cpp defer_jsync)
+// the lane scheme's view of scan sc (as ik_jpeg_decode.cpp defer_free records it)
 bool prog_scan_geom(const ProgFile& F, PScan& sc, int L, int W, Scan& S, std::vector<long long>& ivl,
                     std::vector<int>& ivl_lane) {
-    S = Scan{};
-    const bool single = sc.order.size() == 1;
-    int bpm = 0;
-    for (size_t i = 0; i < sc.order.size(); ++i) {
-        const Comp& c = F.comps[sc.order[i]];
-        const int nb = single ? 1 : c.h * c.v;
-        for (int k = 0; k < nb; ++k) {
-            if (bpm >= kMaxBPM) return false;
-            S.comp_of[bpm] = (int)i;
-            S.bx_of[bpm] = single ? 0 : k % c.h;
-            S.by_of[bpm] = single ? 0 : k / c.h;
-            ++bpm;
-        }
-        S.h[i] = c.h; S.v[i] = c.v; S.bw[i] = c.bw; S.td[i] = sc.td[i]; S.ta[i] = sc.ta[i];
-        S.blk0[i] = c.blk0;
-    }
-    const Comp& c0 = F.comps[sc.order[0]];
-    const int sbw = (c0.dw + 7) / 8, sbh = (c0.dh + 7) / 8;
-    const long long total_mcu = single ? (long long)sbw * sbh : (long long)F.mcux * F.mcuy;
-    S.bpm = bpm;
-    S.mcux = F.mcux;
-    S.single = single;
-    S.single_bw = sbw;
-    S.total_blocks = total_mcu * bpm;
-    S.ivl_blocks = S.total_blocks;
+    std::vector<CompGeom> cg = F.comps;  // with the table ids of this scan's SOS
+    for (size_t i = 0; i < sc.order.size(); ++i) { cg[sc.order[i]].td = sc.td[i]; cg[sc.order[i]].ta = sc.ta[i]; }
+    long long total_mcu = 0;
+    if (!scan_geom(cg.data(), sc.order.data(), (int)sc.order.size(), F.mcux, F.mcuy, S, total_mcu)) return false;
     S.L = L;
     S.W = W;
     S.kind = sc.kind; S.Ss = sc.Ss; S.Se = sc.Se; S.Al = sc.Al;
@@ -595,7 +476,8 @@ bool prog_scan_geom(const ProgFile& F, PScan& sc, int L, int W, Scan& S, std::ve
     sc.words.assign((out.size() + 3) / 4 + kPadWords, 0u);
     for (size_t i = 0; i < out.size(); ++i) sc.words[i >> 2] |= (uint32_t)out[i] << (24 - 8 * (i & 3));
     ivl.assign({0, sc.nbits});
-    ivl_lane.assign({0, sc.nbits > 0 ? (int)((sc.nbits + L - 1) / L) : 1});
+    ivl_lane.assign(2, 0);
+    if (!split_lanes(ivl.data(), 1, L, lane_capacity(kDcFirst, sc.len, 1, L), ivl_lane.data())) return false;
     S.words = sc.words.data();
     S.ivl = ivl.data();
     S.nivl = 1;
@@ -705,6 +587,52 @@ int ikm_jprog_decode(const uint8_t* jpeg, size_t n, int lane_bits, int warm_bits
     const std::vector<int16_t>& outv = serial_only ? ser : par;
     if (coef_out && (serial_only ? sok : ok)) std::memcpy(coef_out, outv.data(), std::min(coef_cap, outv.size()) * sizeof(int16_t));
     return (serial_only ? sok : ok && sok) ? 0 : 1;
+}
+
+// The host plan of a batch (ik_jsync_plan.h), from lengths alone.  Per scan, in file order image by
+// image: len, nivl, kind, image, comp, on_dev, blocks (total_blocks); per image: img_blocks,
+// plane_bytes, img_ok (the images the refinement schedule takes).  ivl_bits (may be null): every
+// scan's nivl + 1 interval start bits, at the scan's ivl0 as in the batch's interval table.  The
+// device-only records' sizes are stand-ins (a scan record 64, a reconstruction item 256, the bases
+// pass's scratch 64 per 64 lanes); no layout rule depends on them.  Out, regions as (offset, bytes held):
+//  head[10]         lane_bits, total, pin_bytes, pin_changed, nchunks, nivl_total, lanes_max, DC launches, chains, rlist entries
+//  regions[19][2]   BatchLayout's regions in its order, img to items, then the groups upload1, readback, upload2
+//  per_scan[ni][11] scan (0, 0: none), out, tab, capacity, lane0, ivl0, chunk0, nchunks;  per_image[m][6] qt, coef, pl
+//  ivl_lane[nivl_total], split_ok[ni] (1, 0 refused, -1 a scan without lanes): split_lanes
+//  rlist[ni], dc_sizes[ni], dc_blocks[ni], chains[4 m][2]: the refinement schedule
+int ikm_jsync_plan(int ni, const long long* len, const long long* nivl, const int* kind, const int* image, const int* comp,
+                   const int* on_dev, const long long* blocks, int m, const long long* img_blocks, const long long* plane_bytes,
+                   const int* img_ok, const long long* ivl_bits, long long* head, long long* regions, long long* per_scan,
+                   long long* per_image, int* ivl_lane, int* split_ok, int* rlist, int* dc_sizes, long long* dc_blocks,
+                   int* chains) {
+    std::vector<ScanIn> sc(ni);
+    std::vector<ImageIn> im(m);
+    for (int t = 0; t < ni; ++t)
+        sc[t] = ScanIn{(size_t)len[t], nivl[t], kind[t], image[t], comp[t], on_dev[t] != 0, blocks[t]};
+    for (int k = 0; k < m; ++k) im[k] = ImageIn{(size_t)img_blocks[k], (size_t)plane_bytes[k]};
+    const BatchLayout B = plan_layout(sc.data(), ni, im.data(), m, DevSizes{64, 256, [](long long lanes) { return (size_t)((lanes + 63) / 64) * 64; }});
+    const RefinePlan R = plan_refinement(sc.data(), ni, img_ok);
+    const long long h[10] = {B.lane_bits, (long long)B.total, (long long)B.pin_bytes, (long long)B.pin_changed, B.nchunks,
+                             B.nivl_total, B.lanes_max, (long long)R.dc_sizes.size(), (long long)R.chains.size(), (long long)R.rlist.size()};
+    std::memcpy(head, h, sizeof(h));
+    auto put = [](long long*& o, const Region& r) { *o++ = (long long)r.off; *o++ = (long long)(r.end() - r.off); };
+    for (const Region* r : {&B.img, &B.chunks, &B.status, &B.totals, &B.ivl, &B.counts, &B.scan_tab, &B.ivl_lane, &B.wgs, &B.rlist,
+                            &B.chains, &B.changed, &B.recs, &B.bases, &B.cs, &B.items, &B.upload1, &B.readback, &B.upload2})
+        put(regions, *r);
+    for (int t = 0; t < ni; ++t) {
+        const ScanLay& L = B.scans[t];
+        put(per_scan, L.scan); put(per_scan, L.out); put(per_scan, L.tab);
+        for (long long v : {L.lanes_max, L.lane0, (long long)L.ivl0, (long long)L.chunk0, (long long)L.nchunks}) *per_scan++ = v;
+        split_ok[t] = -1;
+        if (ivl_bits && has_lanes(kind[t]))
+            split_ok[t] = split_lanes(ivl_bits + L.ivl0, nivl[t], B.lane_bits, L.lanes_max, ivl_lane + L.ivl0) ? 1 : 0;
+    }
+    for (const ImageLay& I : B.images) { put(per_image, I.qt); put(per_image, I.coef); put(per_image, I.pl); }
+    std::copy(R.rlist.begin(), R.rlist.end(), rlist);
+    std::copy(R.dc_sizes.begin(), R.dc_sizes.end(), dc_sizes);
+    std::copy(R.dc_blocks.begin(), R.dc_blocks.end(), dc_blocks);
+    for (const Chain& c : R.chains) { *chains++ = c.first; *chains++ = c.count; }
+    return 0;
 }
 
 }  // extern "C"
