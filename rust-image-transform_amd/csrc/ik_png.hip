@@ -1943,105 +1943,229 @@ hipError_t launch_copy_words(const uint32_t* src, uint32_t* dst, size_t n, hipSt
 // The upload stage DMAs whole PNG files into the raw area; this pass assembles
 // each file's zlib stream from its IDAT payloads (and the zero padding after it)
 // and computes the CRC-32 png checks on every chunk, so the host neither copies
-// nor checksums the compressed bytes.  One 256-thread workgroup per piece of
-// <= 64 KiB; thread t copies and checksums bytes [256 t, 256 t + 256) of the
-// piece (dword stores once the destination is aligned, the source words
-// realigned with v_alignbyte), then the workgroup joins the 256 partial CRCs in
-// a tree (ik_crc.h: crc(A || B) = crc(A) x^(8 |B|) + crc(B)).
+// nor checksums the compressed bytes.
+//
+// Thread mapping.  A workgroup of 512 threads (eight waves) takes one piece of
+// <= 64 KiB at a time and strides over the plan's pieces (at most kGatherGrid
+// workgroups), so its tables are built once for many pieces.  A piece is
+// handled in the 16-byte granules of its SOURCE, counted back from the granule
+// of its last byte: thread t takes granules k = t, t + 512, t + 1024, ... (k =
+// 0: the last one), in address order, the next row's load in flight while the
+// current one is stored and checksummed.  One wave instruction so loads one
+// contiguous, 16-byte-aligned 1 KiB span (the "tile") as global_load_dwordx4.
+// Only granules holding a byte of the piece are ever loaded.
+//
+// Copy.  Source and destination have independent byte alignments.  With s =
+// (src - dst) & 15, the aligned destination granule whose first byte is source
+// byte s of granule k is bytes s..15 of granule k and 0..s-1 of granule k - 1:
+// lane l gets granule k - 1 from lane l - 1 by a DPP wave shift (a wave's first
+// lane loads it: one granule per 1 KiB, never one outside the piece) and
+// v_alignbyte funnels the eight words.  A wave's store instruction so covers one
+// contiguous aligned span with global_store_dwordx4; the (at most two) granules
+// that the piece's [dst, dst + len) covers only in part are stored byte by byte,
+// so pieces sharing a destination granule never write each other's bytes.  With
+// s != 0 there is one more destination granule than source granules (k = the
+// granule count: its low half is before the piece and masked).
+//
+// CRC without a transpose.  A thread's granules are not consecutive bytes, but
+// the CRC register is linear (ik_crc.h): with r(g) the register after granule g
+// from a zero register, a thread keeps S <- S x^(8 * 8192) + r(g) over its rows
+// (the row operator as four table lookups, like a slicing step), and the piece's
+// register is the sum over threads of S_t x^(8 * 16 t): thread t's last granule
+// is t granules before the end.  w_t = x^(128 t) is a per-thread register, so
+// the join is one multiplication per thread and an XOR reduction (__shfl_xor,
+// then eight words of LDS), once per piece.  Bytes of the first and last
+// granule outside the piece count as zeros: leading zeros leave a zero register
+// alone, and the register's preset enters as pre[h] = ~0 x^(-8 h) in front of
+// the first granule (h = src & 15); the u zero bytes after the last byte are
+// divided out at the end (unpad[u] = x^(-8 u)).  The per-piece results are the
+// same finished CRC and length k_png_crc_check has always joined.
+//
+// LDS: 4 KiB slicing-by-4 tables + 4 KiB row-operator tables + 64 B of partial
+// sums = 8,256 B = 7 units of 1,280 B for eight waves (0.875 units per wave; the
+// previous kernel held 5 units for four waves).  There is no staging tile: a
+// tile of 64 B per lane would alone be 4 KiB per wave.
+constexpr int kGatherThreads = 512;
+constexpr uint32_t kGatherRow = 16u * kGatherThreads;  // bytes between a thread's successive granules
+constexpr int kGatherGrid = 1024;                      // workgroups at most (four per CU of 2,048 threads)
+
 struct CrcOps {
     uint32_t x2n[32];    // x^(2^k) mod P
-    uint32_t level[8];   // x^(8 * 256 * 2^k): the join operator of full subtrees at tree level k
+    uint32_t gran[9];    // x^(8 * 16 * 2^b): w_t is their product over the set bits of t
+    uint32_t row;        // x^(8 * kGatherRow)
+    uint32_t pre[16];    // ~0 * x^(-8 h): the preset, h bytes before the piece's first byte
+    uint32_t unpad[16];  // x^(-8 u): takes u appended zero bytes back
     uint32_t piece;      // x^(8 * kPngGatherPiece): the join operator of a full piece
     uint32_t crc_idat;   // finished CRC of the chunk type "IDAT" (the first 4 bytes a chunk CRC covers)
 };
 
-__global__ __launch_bounds__(256) void k_png_gather(uintptr_t raw, uint8_t* __restrict__ stream,
-                                                    const PngGatherPiece* __restrict__ pieces,
-                                                    uint32_t* __restrict__ piece_crc, CrcOps ops) {
-    __shared__ uint32_t t[1024];
-    __shared__ uint32_t s_crc[256], s_len[256];
-    const int tid = (int)threadIdx.x;
-    t[tid] = crc::table_entry((uint32_t)tid);
+// a * b modulo P in 32 fixed steps (crc::multmodp without its data-dependent exit)
+__device__ __forceinline__ uint32_t crc_mul(uint32_t a, uint32_t b) {
+    uint32_t p = 0;
+#pragma unroll
+    for (int i = 31; i >= 0; --i) {
+        p ^= (uint32_t)((int32_t)(a << (31 - i)) >> 31) & b;
+        b = (b >> 1) ^ ((0u - (b & 1u)) & crc::kPoly);
+    }
+    return p;
+}
+
+typedef uint32_t gather_u4 __attribute__((ext_vector_type(4)));
+
+// the destination granule at `oa`: whole when [da, de) covers it, else its covered bytes
+__device__ __forceinline__ void gather_store(uintptr_t oa, gather_u4 v, uintptr_t da, uintptr_t de) {
+    if (oa >= da && oa + 16 <= de) {
+        *reinterpret_cast<IK_GLOBAL gather_u4*>(oa) = v;
+        return;
+    }
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+        if (oa + i >= da && oa + i < de) *reinterpret_cast<IK_GLOBAL uint8_t*>(oa + i) = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
+}
+
+__global__ __launch_bounds__(kGatherThreads) void k_png_gather(uintptr_t raw, uint8_t* __restrict__ stream,
+                                                               const PngGatherPiece* __restrict__ pieces, int npieces,
+                                                               uint32_t* __restrict__ piece_crc, CrcOps ops) {
+    typedef gather_u4 u4;
+    __shared__ uint32_t s_t[1024];  // slicing-by-4 (crc::step_word)
+    __shared__ uint32_t s_k[1024];  // the row operator: s_k[256 q + i] = (i << 8 q) * x^(8 * kGatherRow)
+    __shared__ uint32_t s_part[2][kGatherThreads / 64];
+    static_assert(sizeof(s_t) + sizeof(s_k) + sizeof(s_part) <= 7 * 1280 && 7 * 4 < 5 * (kGatherThreads / 64),
+                  "k_png_gather's LDS: 7 units per 8 waves, under the 5 units per 4 waves it had");
+    static_assert(kGatherRow == 8192 && kGatherThreads == 512, "CrcOps::row and ::gran are made for this geometry");
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    // ---- once per workgroup: the tables and this thread's weight ----
+    if (tid < 256) s_t[tid] = crc::table_entry(tid);
     __syncthreads();
 #pragma unroll
     for (int sl = 1; sl < 4; ++sl) {
-        const uint32_t prev = t[256 * (sl - 1) + tid];
-        t[256 * sl + tid] = (prev >> 8) ^ t[prev & 255u];
+        if (tid < 256) {
+            const uint32_t prev = s_t[256 * (sl - 1) + tid];
+            s_t[256 * sl + tid] = (prev >> 8) ^ s_t[prev & 255u];
+        }
         __syncthreads();
     }
-    const PngGatherPiece P = pieces[blockIdx.x];
-    const uint32_t b0 = 256u * (uint32_t)tid;
-    const uint32_t len = P.len > b0 ? (P.len - b0 < 256u ? P.len - b0 : 256u) : 0u;
-    uint32_t c = ~0u;
-    IK_GLOBAL uint8_t* dp = (IK_GLOBAL uint8_t*)(stream + P.dst + b0);
-    if (len && P.src == kPngNoSrc) {
-        for (uint32_t i = 0; i < len; ++i) dp[i] = 0;
-    } else if (len) {
-        const IK_GLOBAL uint8_t* sp = (const IK_GLOBAL uint8_t*)(raw + (uintptr_t)(P.src + b0));
-        uint32_t i = 0;
-        const uint32_t mis = (uint32_t)((uintptr_t)dp & 3u);
-        const uint32_t pre = mis ? (4u - mis < len ? 4u - mis : len) : 0u;
-        for (; i < pre; ++i) {
-            const uint32_t b = sp[i];
-            dp[i] = (uint8_t)b;
-            c = crc::step_byte(c, b, t);
-        }
-        const uint32_t nw = (len - i) >> 2;
-        if (nw) {
-            const uintptr_t sa = (uintptr_t)(sp + i);
-            const uint32_t sh = (uint32_t)(sa & 3u);
-            const IK_GLOBAL uint32_t* ws = reinterpret_cast<const IK_GLOBAL uint32_t*>(sa - sh);
-            IK_GLOBAL uint32_t* wd = reinterpret_cast<IK_GLOBAL uint32_t*>(dp + i);
-            uint32_t lo = ws[0];
-            uint32_t k = 0;
-            // eight words at a time: the loads are independent of the CRC chain
-            for (; k + 8 <= nw; k += 8) {
-                uint32_t in[9];
-                in[0] = lo;
-#pragma unroll
-                for (int u = 1; u <= 8; ++u) in[u] = sh ? ws[k + u] : (u < 8 ? ws[k + u] : 0u);
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const uint32_t v = sh ? __builtin_amdgcn_alignbyte(in[u + 1], in[u], sh) : in[u];
-                    wd[k + u] = v;
-                    c = crc::step_word(c, v, t);
-                }
-                lo = sh ? in[8] : (k + 8 < nw ? ws[k + 8] : 0u);
-            }
-            for (; k < nw; ++k) {
-                const uint32_t hi = sh ? ws[k + 1] : 0u;
-                const uint32_t v = sh ? __builtin_amdgcn_alignbyte(hi, lo, sh) : lo;
-                wd[k] = v;
-                c = crc::step_word(c, v, t);
-                lo = sh ? hi : (k + 1 < nw ? ws[k + 1] : 0u);
-            }
-            i += 4u * nw;
-        }
-        for (; i < len; ++i) {
-            const uint32_t b = sp[i];
-            dp[i] = (uint8_t)b;
-            c = crc::step_byte(c, b, t);
-        }
+    {
+        // q = 3, 2 by multiplication; (i << 8 (q - 2)) = (i << 8 q) x^16: two zero-byte steps
+        const uint32_t q = 3u - (tid >> 8), i = tid & 255u;
+        uint32_t v = crc_mul(ops.row, i << (8 * q));
+        s_k[256 * q + i] = v;
+        v = (v >> 8) ^ s_t[v & 255u];
+        v = (v >> 8) ^ s_t[v & 255u];
+        s_k[256 * (q - 2) + i] = v;
     }
-    s_crc[tid] = ~c;  // finished CRC of this thread's bytes (0 for none)
-    s_len[tid] = len;
-    __syncthreads();
+    uint32_t wgt = crc::kOne;  // x^(8 * 16 * tid)
 #pragma unroll 1
-    for (int k = 0; k < 8; ++k) {
-        const int stride = 1 << k;
-        if ((tid & (2 * stride - 1)) == 0) {
-            const uint32_t rl = s_len[tid + stride];
-            if (rl) {
-                const uint32_t op = rl == (256u << k) ? ops.level[k] : crc::x8n(rl, ops.x2n);
-                s_crc[tid] = crc::combine_op(s_crc[tid], s_crc[tid + stride], op);
-                s_len[tid] += rl;
+    for (int b = 0; b < 9; ++b)
+        if ((tid >> b) & 1u) wgt = crc_mul(ops.gran[b], wgt);
+    __syncthreads();
+
+    uint32_t joins = 0;
+    for (int p = (int)blockIdx.x; p < npieces; p += (int)gridDim.x) {
+        const PngGatherPiece P = pieces[p];
+        const uint32_t len = P.len;
+        const uintptr_t da = (uintptr_t)stream + (uintptr_t)P.dst, de = da + len;
+        if (len == 0 || P.src == kPngNoSrc) {
+            if (len) {
+                const uintptr_t d0 = da & ~(uintptr_t)15;
+                const uint32_t n = (uint32_t)((((de - 1) & ~(uintptr_t)15) - d0) >> 4) + 1u;
+                for (uint32_t k = tid; k < n; k += kGatherThreads) gather_store(d0 + 16u * (uintptr_t)k, u4{0, 0, 0, 0}, da, de);
             }
+            if (tid == 0) {
+                piece_crc[2 * (size_t)p] = 0;
+                piece_crc[2 * (size_t)p + 1] = len;
+            }
+            continue;
         }
+        const uintptr_t sa = raw + (uintptr_t)P.src;
+        const uintptr_t s_first = sa & ~(uintptr_t)15, s_last = (sa + len - 1) & ~(uintptr_t)15;
+        const uint32_t h = (uint32_t)(sa & 15u);                    // bytes of the first granule before the piece
+        const uint32_t u = 15u - (uint32_t)((sa + len - 1) & 15u);  // bytes of the last granule after it
+        const uint32_t ngran = (uint32_t)((s_last - s_first) >> 4) + 1u;
+        const uint32_t s = (uint32_t)((sa - da) & 15u);
+        const uint32_t nk = ngran + (s ? 1u : 0u);  // destination granules
+        const uintptr_t o_last = s_last + s + da - sa;  // (16-byte aligned) destination granule of k = 0
+        const uint32_t pre = ops.pre[h];
+        const int rows = (int)((nk + kGatherThreads - 1) / kGatherThreads);
+
+        auto load = [&](uint32_t k) -> u4 {  // granule k of the piece (zeros outside it)
+            return k < ngran ? *reinterpret_cast<const IK_GLOBAL u4*>(s_last - 16u * (uintptr_t)k) : u4{0, 0, 0, 0};
+        };
+        auto load_edge = [&](uint32_t k) -> u4 {  // granule k - 1 for a wave's first lane
+            return (s && lane == 0 && k >= 1u) ? load(k - 1u) : u4{0, 0, 0, 0};
+        };
+        uint32_t S = 0;
+        uint32_t k = tid + kGatherThreads * (uint32_t)(rows - 1);
+        u4 cur = load(k), edge = load_edge(k);
+        for (int j = rows - 1; j >= 0; --j, k -= kGatherThreads) {
+            u4 nxt{0, 0, 0, 0}, nedge{0, 0, 0, 0};
+            if (j > 0) {
+                nxt = load(k - kGatherThreads);
+                nedge = load_edge(k - kGatherThreads);
+            }
+            if (k - lane < nk) {  // (wave-uniform: the wave has a granule in this row)
+                // ---- copy ----
+                u4 out = cur;
+                if (s) {
+                    uint32_t w[8] = {cur.x, cur.y, cur.z, cur.w, 0, 0, 0, 0};
+                    // granule k - 1 from lane - 1 (wave_shr:1; lane 0 keeps its own load)
+                    w[4] = (uint32_t)__builtin_amdgcn_update_dpp((int)edge.x, (int)cur.x, 0x138, 0xF, 0xF, false);
+                    w[5] = (uint32_t)__builtin_amdgcn_update_dpp((int)edge.y, (int)cur.y, 0x138, 0xF, 0xF, false);
+                    w[6] = (uint32_t)__builtin_amdgcn_update_dpp((int)edge.z, (int)cur.z, 0x138, 0xF, 0xF, false);
+                    w[7] = (uint32_t)__builtin_amdgcn_update_dpp((int)edge.w, (int)cur.w, 0x138, 0xF, 0xF, false);
+                    uint32_t v[5];
+                    switch (s >> 2) {
+                        case 0: v[0] = w[0], v[1] = w[1], v[2] = w[2], v[3] = w[3], v[4] = w[4]; break;
+                        case 1: v[0] = w[1], v[1] = w[2], v[2] = w[3], v[3] = w[4], v[4] = w[5]; break;
+                        case 2: v[0] = w[2], v[1] = w[3], v[2] = w[4], v[3] = w[5], v[4] = w[6]; break;
+                        default: v[0] = w[3], v[1] = w[4], v[2] = w[5], v[3] = w[6], v[4] = w[7]; break;
+                    }
+                    const uint32_t r = s & 3u;
+                    out.x = __builtin_amdgcn_alignbyte(v[1], v[0], r);
+                    out.y = __builtin_amdgcn_alignbyte(v[2], v[1], r);
+                    out.z = __builtin_amdgcn_alignbyte(v[3], v[2], r);
+                    out.w = __builtin_amdgcn_alignbyte(v[4], v[3], r);
+                }
+                if (k < nk) gather_store(o_last - 16u * (uintptr_t)k, out, da, de);
+                // ---- CRC ----
+                u4 g = cur;
+                if (k == 0 || k + 1u == ngran) {  // the piece's last / first granule: outside bytes count as zeros
+                    const uint32_t lo = k + 1u == ngran ? h : 0u, hi = k == 0 ? 16u - u : 16u;
+                    uint32_t m[4];
+#pragma unroll
+                    for (uint32_t i = 0; i < 4; ++i) {
+                        const uint32_t a = lo > 4 * i ? (lo >= 4 * i + 4 ? 0u : ~0u << (8 * (lo - 4 * i))) : ~0u;
+                        const uint32_t b = hi < 4 * i + 4 ? (hi <= 4 * i ? 0u : ~0u >> (8 * (4 * i + 4 - hi))) : ~0u;
+                        m[i] = a & b;
+                    }
+                    g.x &= m[0], g.y &= m[1], g.z &= m[2], g.w &= m[3];
+                }
+                uint32_t c = k + 1u == ngran ? pre : 0u;
+                c = crc::step_word(c, g.x, s_t);
+                c = crc::step_word(c, g.y, s_t);
+                c = crc::step_word(c, g.z, s_t);
+                c = crc::step_word(c, g.w, s_t);
+                S = s_k[S & 255u] ^ s_k[256 + ((S >> 8) & 255u)] ^ s_k[512 + ((S >> 16) & 255u)] ^ s_k[768 + (S >> 24)] ^ c;
+            }
+            cur = nxt;
+            edge = nedge;
+        }
+        // ---- join: the sum of S_t x^(128 t), without the u zero bytes after the end ----
+        uint32_t x = crc_mul(wgt, S);
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) x ^= (uint32_t)__shfl_xor((int)x, m);
+        uint32_t* part = s_part[joins & 1u];  // (two sets: one barrier per piece)
+        ++joins;
+        if (lane == 0) part[wave] = x;
         __syncthreads();
-    }
-    if (tid == 0) {
-        piece_crc[2 * blockIdx.x] = s_crc[0];
-        piece_crc[2 * blockIdx.x + 1] = s_len[0];
+        if (tid == 0) {
+            uint32_t t = 0;
+#pragma unroll
+            for (int i = 0; i < kGatherThreads / 64; ++i) t ^= part[i];
+            piece_crc[2 * (size_t)p] = ~crc_mul(ops.unpad[u], t);
+            piece_crc[2 * (size_t)p + 1] = len;
+        }
     }
 }
 
@@ -2067,7 +2191,13 @@ static CrcOps crc_ops() {
     static const CrcOps o = [] {
         CrcOps r{};
         crc::x2n_table(r.x2n);
-        for (int k = 0; k < 8; ++k) r.level[k] = crc::x8n((uint64_t)256 << k, r.x2n);
+        for (int b = 0; b < 9; ++b) r.gran[b] = crc::x8n((uint64_t)16 << b, r.x2n);
+        r.row = crc::x8n(kGatherRow, r.x2n);
+        // x has order 2^32 - 1 modulo P, so x^(-8 n) = x^(8 (2^32 - 1 - n))
+        for (uint32_t n = 0; n < 16; ++n) {
+            r.unpad[n] = crc::x8n(0xFFFFFFFFull - n, r.x2n);
+            r.pre[n] = crc::multmodp(r.unpad[n], 0xFFFFFFFFu);
+        }
         r.piece = crc::x8n(kPngGatherPiece, r.x2n);
         uint32_t t[1024];
         for (uint32_t i = 0; i < 256; ++i) t[i] = crc::table_entry(i);
@@ -2084,8 +2214,8 @@ static CrcOps crc_ops() {
 hipError_t launch_png_gather(uintptr_t raw, uint8_t* stream, const PngGatherPiece* pieces, int npieces,
                              uint32_t* piece_crc, hipStream_t s) {
     if (npieces <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_png_gather, dim3((unsigned)npieces), dim3(256), 0, s, raw, stream, pieces, piece_crc,
-                       crc_ops());
+    hipLaunchKernelGGL(k_png_gather, dim3((unsigned)std::min(npieces, kGatherGrid)), dim3(kGatherThreads), 0, s, raw,
+                       stream, pieces, npieces, piece_crc, crc_ops());
     return hipGetLastError();
 }
 

@@ -14,7 +14,7 @@
 
 namespace ik {
 
-constexpr uint32_t kPngGatherPiece = 65536;  // bytes per piece (one 256-thread workgroup, 256 B per thread)
+constexpr uint32_t kPngGatherPiece = 65536;  // bytes per piece (a 512-thread workgroup's unit of work: 8 rows of 8 KiB)
 constexpr uint32_t kPngNoChunk = 0xFFFFFFFFu;
 constexpr uint64_t kPngNoSrc = ~0ull;
 

@@ -375,9 +375,11 @@ int ikm_inflate_wave(const uint8_t* z, size_t zlen, size_t chunk_bytes, uint8_t*
 }
 
 // The upload gather pass (ik_png.hip k_png_gather + k_png_crc_check) on the host:
-// the same plan (ik_png_gather.h), the same per-thread split (256 B per thread,
-// bytes until the destination is word aligned, then words), the same tree join of
-// the 256 partial CRCs and the same chunk check.  file: a whole PNG file as
+// the same plan (ik_png_gather.h), the same per-piece CRC and length pairs and the
+// same chunk check.  A piece's CRC is joined here from 256 runs of 256 B (bytes
+// until the destination is word aligned, then words) in a tree; the kernel sums
+// its threads' interleaved granules instead -- both are crc32 of the piece's
+// bytes, which tests/test_png_gather_model.py holds against zlib.  file: a whole PNG file as
 // uploaded at raw offset `raw_off` (the destination alignment follows z_off).
 // Writes the assembled zlib stream + `tail` zero bytes to stream[z_off ..];
 // bad[k] = 1 for each IDAT chunk whose CRC does not match; returns the number of
