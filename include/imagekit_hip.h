@@ -324,6 +324,21 @@ int ik_get_resize_mode(void);
  * "k_resize_fused", or "k_vert_naive" (the two-pass fallback); NULL on bad
  * arguments or without a device. */
 const char *ik_resize_kernel_name(uint32_t W, uint32_t H, uint32_t C, uint32_t nw, uint32_t nh, int filter);
+/* The variant a launch of n images of this geometry takes under the current
+ * modes, for tests: out[0..] = slots (A), rows (R), flush (F), weights_in_lds,
+ * NS (column strips), NB (bands of the fused plan), per_A, per_R, NBp (bands of
+ * the periodic plan; per_A = 0: the geometry is not periodic), Tx, Ty,
+ * max_strip_cols, kernel family (0 "k_vert_naive", 1 "k_resize_fused",
+ * 2 "k_resize_periodic", for rows W * C bytes apart).  Computed from the geometry
+ * alone: needs no device.  The device path caches plans by geometry and fused band
+ * height, not by n, while the periodic bands depend on n: where two launch sizes
+ * share a band height but not a periodic one (outputs of thousands of rows), a
+ * launch may reuse the plan first built, and NBp here is then that of n alone.
+ * Fills at most cap values; returns how many there are
+ * (IK_RESIZE_PLAN_INFO_LEN), or a negative value on bad arguments. */
+#define IK_RESIZE_PLAN_INFO_LEN 13
+int ik_resize_plan_info(uint32_t W, uint32_t H, uint32_t C, uint32_t nw, uint32_t nh, int filter, uint32_t n,
+                        int32_t *out, int cap);
 
 /* JPEG reconstruction behind decode_image (src/transform.rs:31 -> image 0.25.8
  * -> zune-jpeg 0.4.21, Cargo.lock:3106).  IK_JPEG_RECON_ZUNE (default): zune-jpeg's

@@ -2521,6 +2521,18 @@ const char* ik_resize_kernel_name(uint32_t W, uint32_t H, uint32_t C, uint32_t n
     return plan ? resize_kernel_name(*plan, (size_t)W * C) : nullptr;
 }
 
+int ik_resize_plan_info(uint32_t W, uint32_t H, uint32_t C, uint32_t nw, uint32_t nh, int filter, uint32_t n,
+                        int32_t* out, int cap) {
+    if (C < 1 || C > 4 || !W || !H || !nw || !nh || !n || filter < 0 || filter > 4 || !out || cap < 0) return -1;
+    ResizeTables t;
+    build_resize_tables((int)W, (int)H, (int)C, (int)nw, (int)nh, filter, (int)n, t);
+    const int32_t v[IK_RESIZE_PLAN_INFO_LEN] = {
+        t.slots, t.rows, t.flush, t.weights_in_lds ? 1 : 0, t.NS, t.NB, t.per_A, t.per_R, t.NBp, t.Tx, t.Ty,
+        t.max_strip_cols, resize_family_of(t, (size_t)W * C)};
+    for (int i = 0; i < IK_RESIZE_PLAN_INFO_LEN && i < cap; ++i) out[i] = v[i];
+    return IK_RESIZE_PLAN_INFO_LEN;
+}
+
 int ik_webp_yuv420_device(const uint8_t* dev_src, uint32_t w, uint32_t h, uint32_t C, size_t pitch,
                           uint8_t* dev_yuv, void* hip_stream) {
     IK_API_ENTER();

@@ -10,6 +10,7 @@
 
 #include "../../include/imagekit_hip.h"
 #include "ik_jpeg_sync.h"
+#include "ik_resize_plan.h"
 
 namespace ik {
 
@@ -17,13 +18,7 @@ namespace ik {
 // sequence, bit-exact) or IK_RESIZE_FMA (fused multiply-add, within 1 LSB)
 int resize_mode();
 
-constexpr int kThreads = 256;            // workgroup size (4 wave64s)
-constexpr int kBytesPerLane = 8;         // vertical pass: bytes of a source row per lane
-constexpr int kStripBytes = kBytesPerLane * kThreads;  // 2048 source bytes per strip
-constexpr int kRowWords = kStripBytes + kStripBytes / 8;  // LDS f32 row, +4 words per 32
-constexpr int kMaxFlushRows = 4;         // vertical rows staged in LDS per horizontal pass (plan: 2..4)
-constexpr int kMaxStripCols = 512;       // output columns per strip (LDS offset/count tables)
-constexpr int kMaxStripWeights = 4096;   // horizontal weights per strip kept in LDS (16 KB: an RGB Lanczos3 8x strip's 85 x 48)
+// kThreads, kStripBytes, kRowWords, ... and the host half of a resize plan: ik_resize_plan.h
 
 // Everything the resize kernels read.  Weight tables follow image 0.25.8
 // sample.rs (see ik_plan.cpp); tables live in one device allocation per plan.
@@ -59,6 +54,7 @@ struct ResizeArgs {
     int per_base, NBp;
     int max_strip_cols;      // max output columns of a strip (LDS table size)
     int max_strip_weights;   // max nox*Tx of a strip (LDS weights size when in LDS)
+    int lds_pad;             // zeroed LDS words after the column offsets (ik_resize_plan.h)
     float* tmp;        // naive path only: f32 vertical intermediate [n][nh][row_bytes]
     // fused path, images anywhere in memory: per-image base pointers (device
     // arrays, [n]); null = src + img * src_img_stride / dst + img * dst_img_stride
@@ -83,8 +79,8 @@ struct ResizePlan {
 // ---- launchers (ik_kernels.hip) ----
 // The fused kernel addresses one source image through a buffer descriptor with
 // 32-bit num_records and row offsets: images over INT32_MAX bytes take the naive
-// two-pass path (whose caller must then pass naive_tmp).
-inline bool resize_fused_fits(size_t src_pitch, size_t H) { return src_pitch * H <= 0x7FFFFFFFull; }
+// two-pass path (whose caller must then pass naive_tmp): resize_fused_fits
+// (ik_resize_plan.h).
 // 16-bit images: the two-pass path over u16 samples (tmp: nh * W * C floats), and
 // the u16 -> u8 rescale of to_rgb8 / to_rgba8
 hipError_t launch_resize16(const ResizePlan& plan, const uint8_t* src, size_t src_pitch, uint8_t* dst,
@@ -97,12 +93,10 @@ hipError_t launch_resize(const ResizePlan& plan, const uint8_t* src, size_t src_
                          const uint64_t* src_tab = nullptr, const uint64_t* dst_tab = nullptr);
 // dynamic LDS bytes of the fused kernel
 size_t resize_lds_bytes(const ResizeArgs& a, bool wl, int flush);
-// k_resize_periodic (ik_kernels.hip): whether (A accumulators, R rows per step) has
-// an instance; its band plan aims at kPerTargetWG workgroups, bands >= kPerMinBand rows
-bool periodic_instance(int A, int R);
 // the kernel launch_resize picks for this plan (ik_resize_kernel_name)
 const char* resize_kernel_name(const ResizePlan& plan, size_t src_pitch);
-constexpr int kPerTargetWG = 4096, kPerMinBand = 32;
+// the same choice as a ResizeFamily index, from a host-only plan (ik_resize_plan_info)
+int resize_family_of(const ResizeTables& t, size_t src_pitch);
 hipError_t launch_webp_yuv420(const uint8_t* src, int w, int h, int C, size_t pitch,
                               size_t img_stride, uint8_t* yuv /* Y, U, V planes per image */,
                               size_t yuv_img_stride, int n, const uint16_t* gamma_to_lin,
@@ -243,10 +237,7 @@ inline size_t jpeg_enc_cap(int w, int h) {  // stuffed-stream capacity per image
 }
 
 // ---- plans (ik_plan.cpp) ----
-// sample.rs weights for one axis; returns the tap count T (row stride of w).
-int axis_weights(int in, int out, int filter, std::vector<int>& left, std::vector<int>& cnt,
-                 std::vector<float>& w);
-int required_slots(const std::vector<int>& left, const std::vector<int>& cnt);
+// axis_weights, required_slots and the tables themselves: ik_resize_plan.h
 ResizePlan* get_resize_plan(int device, int W, int H, int C, int nw, int nh, int filter, int n);
 
 }  // namespace ik

@@ -93,8 +93,10 @@ __device__ __forceinline__ void row_put(float* __restrict__ row, const RowPut& r
 // sequential sums, one C-byte store.  Taps run over the plan's Tx (a multiple of
 // 4; zero weights past the column's own count), kHTaps at a time so their LDS
 // reads are in flight together.  A zero-weight tap past the strip reads finite
-// data (the next LDS row or the tables after the rows; the rows are zeroed at the
-// start) and adds +-0, which leaves the sum bit-identical.
+// data (the next LDS row or the tables after the rows: the rows, the unused tails
+// of the tables and the plan's lds_pad words after them are zeroed at the start,
+// so no such read leaves the launch's LDS or meets a word nobody wrote) and adds
+// +-0, which leaves the sum bit-identical.
 // out(r, ox, c) = round(sum_k tmp[r][(lx[ox]+k)*C + c] * wx[ox][k]), sequential k.
 template <int C, bool FMA, int kHTaps = 2>
 __device__ __forceinline__ void horizontal_rows_c(const ResizeArgs& a, const float* __restrict__ lds,
@@ -244,7 +246,10 @@ __global__ __launch_bounds__(kThreads, FusedOcc<A>::value) void k_resize_fused(R
     if (WL) {
         const float* __restrict__ gw = a.wx + (size_t)ox0 * a.Tx;
         for (int t = threadIdx.x; t < nox * a.Tx; t += kThreads) s_w[t] = gw[t];
+        for (int t = nox * a.Tx + threadIdx.x; t < a.max_strip_weights; t += kThreads) s_w[t] = 0.0f;
     }
+    // what a narrower strip leaves unused, and the pad: zero-weight taps read them
+    for (int t = nox + threadIdx.x; t < a.max_strip_cols + a.lds_pad; t += kThreads) s_off[t] = 0;
     const float* __restrict__ hw = WL ? s_w : a.wx + (size_t)ox0 * a.Tx;
 
     // Source rows through a buffer descriptor over this image: per-lane byte
@@ -415,7 +420,10 @@ __global__ __launch_bounds__(kThreads) void k_resize_periodic(ResizeArgs a) {
     if (WL) {
         const float* __restrict__ gw = a.wx + (size_t)ox0 * a.Tx;
         for (int t = threadIdx.x; t < nox * a.Tx; t += kThreads) s_w[t] = gw[t];
+        for (int t = nox * a.Tx + threadIdx.x; t < a.max_strip_weights; t += kThreads) s_w[t] = 0.0f;
     }
+    // what a narrower strip leaves unused, and the pad: zero-weight taps read them
+    for (int t = nox + threadIdx.x; t < a.max_strip_cols + a.lds_pad; t += kThreads) s_off[t] = 0;
     const float* __restrict__ hw = WL ? s_w : a.wx + (size_t)ox0 * a.Tx;
 
     const int mybyte = sb + kBytesPerLane * (int)threadIdx.x;
@@ -619,14 +627,7 @@ hipError_t launch_u16_to_u8(const uint8_t* src, size_t sp, uint8_t* dst, size_t 
     return hipGetLastError();
 }
 
-#define IK_PERIODIC_INSTANCES(X) X(2, 2) X(2, 4) X(2, 8) X(4, 2) X(4, 4) X(4, 8) X(6, 2) X(6, 4) X(6, 8)
-
-bool periodic_instance(int A, int R) {
-#define IK_PER_HAS(A_, R_) if (A == A_ && R == R_) return true;
-    IK_PERIODIC_INSTANCES(IK_PER_HAS)
-#undef IK_PER_HAS
-    return false;
-}
+// IK_PERIODIC_INSTANCES / periodic_instance: ik_resize_plan.h
 
 // IK_RESIZE_PERIODIC=0: periodic geometries on k_resize_fused too (A/B, tests)
 static bool periodic_enabled() {
@@ -635,16 +636,18 @@ static bool periodic_enabled() {
 }
 
 const char* resize_kernel_name(const ResizePlan& plan, size_t src_pitch) {
-    if (!(plan.slots > 0 && resize_fused_fits(src_pitch, (size_t)plan.H))) return "k_vert_naive";
-    if (plan.per_A && resize_mode() != IK_RESIZE_FMA && plan.flush == 3 && periodic_enabled() &&
-        periodic_instance(plan.per_A, plan.per_R))
-        return "k_resize_periodic";
-    return "k_resize_fused";
+    static const char* const names[] = {"k_vert_naive", "k_resize_fused", "k_resize_periodic"};
+    return names[resize_family(plan.slots, plan.per_A, plan.per_R, plan.flush, src_pitch, (size_t)plan.H,
+                               resize_mode() == IK_RESIZE_FMA, periodic_enabled())];
+}
+
+int resize_family_of(const ResizeTables& t, size_t src_pitch) {
+    return resize_family(t.slots, t.per_A, t.per_R, t.flush, src_pitch, (size_t)t.H, resize_mode() == IK_RESIZE_FMA,
+                         periodic_enabled());
 }
 
 size_t resize_lds_bytes(const ResizeArgs& a, bool wl, int flush) {
-    return sizeof(float) * ((size_t)flush * kRowWords + (wl ? (size_t)a.max_strip_weights : 0) +
-                            (size_t)a.max_strip_cols);
+    return sizeof(float) * resize_lds_words(flush, wl, a.max_strip_weights, a.max_strip_cols, a.lds_pad);
 }
 
 // Instances that fit the register file without spilling (ik_plan.cpp picks A, R);

@@ -101,6 +101,7 @@ SIGNATURES = [
     ("ik_jpeg_walk_host", ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     ("ik_get_resize_mode", ctypes.c_int, []),
     ("ik_resize_kernel_name", ctypes.c_char_p, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int]),
+    ("ik_resize_plan_info", ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int]),
     ("ik_set_jpeg_reconstruction", ctypes.c_int, [ctypes.c_int]),
     ("ik_get_jpeg_reconstruction", ctypes.c_int, []),
     ("ik_pipeline_submit", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32]),
