@@ -79,6 +79,27 @@ void ik_schedule_plan(const uint64_t *costs, uint32_t n, uint32_t ndev, const ui
  * with min_batch = IK_MIN_DEVICE_BATCH (64). */
 uint32_t ik_schedule_split(const uint64_t *costs, uint32_t n, uint32_t ndev, const uint64_t *outstanding,
                            uint32_t min_batch, uint32_t *part_lo, uint32_t *part_dev);
+/* ik_transform_batch's post-stage routing on its own (no device work): for m decoded
+ * requests -- ok[k] (decoded), the image's W, H, C, pitch, device and depth (bytes per
+ * sample), the requested w / h (negative = None), fmt and quality -- under a WebP encoder
+ * setting (IK_WEBP_*) and a mixed mode (IK_WEBP_MIXED_*): the size each request is coded
+ * at (nw, nh; 0 when its resize target cannot be computed), the same-geometry resize
+ * group (one launch) and the coder group inside it (one group call) it belongs to, or
+ * -1, and its route.  Groups are numbered in launch order.  info[4]: whether the batch
+ * makes a mixed exact call, the fewest requests that call takes, the resize group count,
+ * the coder group count.  The rules: csrc/ik_post_plan.h. */
+typedef enum {
+    IK_POST_NONE = 0,             /* the decode failed                                        */
+    IK_POST_SINGLE = 1,           /* per-image resize and / or encoder front end              */
+    IK_POST_WEBP_MIXED = 2,       /* kept for the batch's one mixed exact WebP call           */
+    IK_POST_WEBP_FRONT_GROUP = 3, /* group colour launch, libwebp codes the planes            */
+    IK_POST_WEBP_EXACT_GROUP = 4, /* group call of the exact GPU WebP coder                   */
+    IK_POST_JPEG_GROUP = 5        /* group call of the GPU JPEG coder                         */
+} ik_post_route;
+int ik_post_plan(uint32_t m, const int *ok, const uint32_t *W, const uint32_t *H, const uint32_t *C,
+                 const uint64_t *pitch, const int *device, const uint32_t *depth, const int64_t *w, const int64_t *h,
+                 const int *fmt, const int *quality, int webp_encoder, int mixed_mode, uint32_t *nw, uint32_t *nh,
+                 int *resize_group, int *coder_group, int *route, uint32_t *info);
 /* Orderly teardown: waits for every submitted batch, ends
  * the library's stage threads and worker pools (each releases its HIP streams
  * and arenas), then frees the pooled images, upload areas, resize plans and

@@ -372,7 +372,7 @@ bool host_pinned(const void* p, size_t n) {
 // staging buffer with stream-ordered async copies on the thread's stream.  (A
 // synchronous hipMemcpy* from pageable memory is issued on the null stream, and
 // a non-blocking stream is not ordered after its DMA.)
-static uint8_t* staging(size_t bytes) { return pinned_slot(0, bytes); }
+static uint8_t* staging(size_t bytes) { return pinned_slot(kPinnedStaging, bytes); }
 
 int copy_h2d_2d(uint8_t* dst, size_t dpitch, const uint8_t* src, size_t spitch, size_t width,
                 size_t height, hipStream_t s) {
@@ -427,7 +427,7 @@ uint8_t* scratch_slot(int slot, size_t bytes) {
     return a.p;
 }
 
-uint8_t* scratch(size_t bytes) { return scratch_slot(0, bytes); }
+uint8_t* scratch(size_t bytes) { return scratch_slot(kScratchDefault, bytes); }
 
 size_t pitch_for(uint32_t w, uint32_t c) { return ((size_t)w * c + 255) & ~size_t(255); }
 
@@ -489,14 +489,6 @@ int alloc_image(uint32_t w, uint32_t h, uint32_t c, ik_image** out, uint32_t dep
     return IK_OK;
 }
 
-void webp_gamma_tables(uint16_t g2l[256], int l2g[33]) {
-    // libwebp picture_csp_enc.c InitGammaTables: kGamma 0.80, kGammaFix 12, kGammaTabFix 7
-    const double scale = (double)(1 << 7) / ((1 << 12) - 1);
-    const double norm = 1. / 255.;
-    for (int v = 0; v <= 255; ++v) g2l[v] = (uint16_t)(pow(norm * v, 0.80) * ((1 << 12) - 1) + .5);
-    for (int v = 0; v <= 32; ++v) l2g[v] = (int)(255. * pow(scale * v, 1. / 0.80) + .5);
-}
-
 namespace {
 std::atomic<int> g_resize_mode{-1};  // -1 = not yet read from IK_RESIZE_MODE
 }  // namespace
@@ -511,199 +503,6 @@ int resize_mode() {
         m = g_resize_mode.load();
     }
     return m;
-}
-
-namespace {
-std::mutex g_consts_mu;
-std::map<int, DeviceConsts*> g_consts;
-std::atomic<unsigned long long> g_jpeg_enc_gpu{0}, g_jpeg_enc_host{0};
-}  // namespace
-
-void jpeg_enc_count(bool gpu_coded) { (gpu_coded ? g_jpeg_enc_gpu : g_jpeg_enc_host) += 1; }
-
-const DeviceConsts* device_consts(int device) {
-    std::mutex& mu = g_consts_mu;
-    std::map<int, DeviceConsts*>& m = g_consts;
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = m.find(device);
-    if (it != m.end()) return it->second;
-    uint16_t g2l[256];
-    int l2g[33];
-    webp_gamma_tables(g2l, l2g);
-    uint32_t hf[4 * 256];
-    jpeg_huff_u32(hf);
-    auto* dc = new DeviceConsts();
-    (void)hipSetDevice(device);
-    if (hipMalloc(&dc->gamma_to_lin, sizeof(g2l)) != hipSuccess ||
-        hipMalloc(&dc->lin_to_gamma, sizeof(l2g)) != hipSuccess ||
-        hipMalloc(&dc->jpeg_huff, sizeof(hf)) != hipSuccess ||
-        hipMemcpy(dc->gamma_to_lin, g2l, sizeof(g2l), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dc->lin_to_gamma, l2g, sizeof(l2g), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dc->jpeg_huff, hf, sizeof(hf), hipMemcpyHostToDevice) != hipSuccess ||
-        hipDeviceSynchronize() != hipSuccess) {  // order before non-blocking streams
-        delete dc;
-        return nullptr;
-    }
-    m[device] = dc;
-    return dc;
-}
-
-// Run the device front end of encode_image and hand its output to the host
-// entropy stage.  WebP: to_rgb8 + RGB->YUV420 on the GPU, libwebp VP8 coding of
-// those planes on the host.  JPEG: to_rgb8 + YCbCr + FDCT + quantise on the GPU,
-// baseline Huffman coding on the host.  AVIF: to_rgba8 + YCbCr 4:4:4 on the GPU,
-// AV1 coding by libavif/aom on the host.
-int encode_device_front(const uint8_t* dev, uint32_t w, uint32_t h, uint32_t c, size_t pitch, int fmt, int quality,
-                        EncodePrep& p, std::vector<uint8_t>& out) {
-    const int q = clamp_quality(quality);
-    p.fmt = fmt;
-    p.q = q;
-    p.w = w;
-    p.h = h;
-    p.done = true;  // unless a host coder is left to run (encode_host_back)
-    hipStream_t s = thread_stream();
-    if (!s) return fail(IK_ERR_DEVICE, "cannot create HIP stream");
-    if (fmt == IK_FORMAT_WEBP) {
-        if (w > 16383 || h > 16383) return fail(IK_ERR_TRANSFORM, "WebP dimensions %ux%u exceed 16383", w, h);
-        const DeviceConsts* dc = device_consts(current_device());
-        if (!dc) return fail(IK_ERR_DEVICE, "cannot upload WebP tables");
-        const size_t bytes = yuv420_bytes(w, h);
-        if (default_webp_encoder() == IK_WEBP_EXACT) {  // (read once: a concurrent switch cannot mix paths)
-            uint8_t* dyuv = scratch(bytes);
-            if (!dyuv) return fail(IK_ERR_DEVICE, "cannot allocate device scratch");
-            hipError_t e = launch_webp_yuv420(dev, (int)w, (int)h, (int)c, pitch, 0, dyuv, 0, 1,
-                                              dc->gamma_to_lin, dc->lin_to_gamma, s);
-            if (e != hipSuccess) return hip_fail(e, "webp yuv420");
-            std::vector<std::vector<uint8_t>> files;
-            if (int rc = webp_encode_exact(dyuv, 0, 1, (int)w, (int)h, q, files)) return rc;
-            out.swap(files[0]);
-            return IK_OK;
-        }
-        // the colour kernel writes the planes straight into pinned host memory: no
-        // copy-engine transfer, which would queue behind another batch's stream upload
-        uint8_t* hp = pinned_slot(4, bytes);
-        void* dhp = nullptr;
-        if (!hp || hipHostGetDevicePointer(&dhp, hp, 0) != hipSuccess || !dhp)
-            return fail(IK_ERR_NOMEM, "cannot map pinned WebP planes");
-        hipError_t e = launch_webp_yuv420(dev, (int)w, (int)h, (int)c, pitch, 0, reinterpret_cast<uint8_t*>(dhp), 0, 1,
-                                          dc->gamma_to_lin, dc->lin_to_gamma, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return hip_fail(e, "webp yuv420");
-        p.planes.assign(hp, hp + bytes);
-        p.done = false;  // libwebp's VP8 coding of the planes: encode_host_back
-        return IK_OK;
-    }
-    if (fmt == IK_FORMAT_JPEG) {
-        if (w > 65535 || h > 65535) return fail(IK_ERR_TRANSFORM, "JPEG dimensions %ux%u exceed 65535", w, h);
-        uint8_t qt[128];
-        jpeg_quant_tables(q, qt);
-        const size_t nmcu = (size_t)((w + 7) / 8) * ((h + 7) / 8);
-        const size_t cbytes = nmcu * 3 * 64 * sizeof(int16_t);
-        const DeviceConsts* dc = device_consts(current_device());
-        if (!dc) return fail(IK_ERR_DEVICE, "cannot upload JPEG tables");
-        // [qtables 256][coefficients][Huffman work: words + staging][stuffed stream][length]
-        const size_t cap = jpeg_enc_cap((int)w, (int)h);
-        const size_t c_off = 256, w_off = c_off + (cbytes + 255) / 256 * 256;
-        const size_t o_off = w_off + 2 * cap, l_off = o_off + cap;
-        uint8_t* dq = scratch(l_off + 256);
-        if (!dq) return fail(IK_ERR_DEVICE, "cannot allocate device scratch");
-        int16_t* dcoef = (int16_t*)(dq + c_off);
-        int rc = copy_h2d_2d(dq, 128, qt, 128, 128, 1, s);
-        if (rc) return rc;
-        hipError_t e = launch_jpeg_coeffs(dev, (int)w, (int)h, (int)c, pitch, 0, dq, dcoef, 0, 1, s);
-        if (e != hipSuccess) return hip_fail(e, "jpeg coefficients");
-        JpegEncArgs a{};
-        a.coef = dcoef;
-        a.coef_img_stride = 0;
-        a.nmcu = (int)nmcu;
-        a.huff = dc->jpeg_huff;
-        a.work = dq + w_off;
-        a.work_img_bytes = 2 * cap;
-        a.words_bytes = cap;
-        a.out = dq + o_off;
-        a.out_img_stride = cap;
-        a.out_cap = cap;
-        a.out_len = reinterpret_cast<uint32_t*>(dq + l_off);
-        e = launch_jpeg_huff_enc(a, 1, s);
-        if (e != hipSuccess) return hip_fail(e, "jpeg huffman");
-        uint32_t len = 0;
-        rc = copy_d2h_2d(reinterpret_cast<uint8_t*>(&len), 4, dq + l_off, 4, 4, 1, s);
-        if (rc) return rc;
-        if (len == 0xffffffffu) {  // does not fit the GPU coder's buffer: host coder
-            std::vector<int16_t> coef(nmcu * 3 * 64);
-            rc = copy_d2h_2d((uint8_t*)coef.data(), cbytes, (const uint8_t*)dcoef, cbytes, cbytes, 1, s);
-            if (rc) return rc;
-            jpeg_write(coef.data(), (int)w, (int)h, qt, out);
-            jpeg_enc_count(false);
-            return IK_OK;
-        }
-        jpeg_enc_count(true);
-        jpeg_header((int)w, (int)h, qt, out);
-        const size_t hdr = out.size();
-        out.resize(hdr + len + 2);
-        if (len) rc = copy_d2h_2d(out.data() + hdr, len, dq + o_off, len, len, 1, s);
-        if (rc) return rc;
-        out[hdr + len] = 0xFF;
-        out[hdr + len + 1] = 0xD9;
-        return IK_OK;
-    }
-    if (fmt == IK_FORMAT_AVIF) {
-        // image 0.25.8 AvifEncoder::new_with_speed_quality(out, 4, q) (src/transform.rs:140-145)
-        const size_t n = (size_t)w * h;
-        uint8_t* dp = scratch(4 * n + 256);
-        if (!dp) return fail(IK_ERR_DEVICE, "cannot allocate device scratch");
-        int* dflag = reinterpret_cast<int*>(dp + 4 * n + 128 - ((4 * n) & 127));
-        hipError_t e = launch_avif_yuv444(dev, (int)w, (int)h, (int)c, pitch, 0, dp, 0, dflag, 1, s);
-        if (e != hipSuccess) return hip_fail(e, "avif yuv444");
-        p.planes.resize(4 * n);
-        int transparent = 0;
-        int rc = copy_d2h_2d(p.planes.data(), 4 * n, dp, 4 * n, 4 * n, 1, s);
-        if (!rc) rc = copy_d2h_2d(reinterpret_cast<uint8_t*>(&transparent), 4, reinterpret_cast<const uint8_t*>(dflag), 4, 4, 1, s);
-        if (rc) return rc;
-        p.transparent = transparent != 0;
-        p.done = false;  // AV1 coding by libavif: encode_host_back
-        return IK_OK;
-    }
-    return fail(IK_ERR_INVALID, "unknown ImageFormat %d", fmt);
-}
-
-int encode_host_back(EncodePrep& p, std::vector<uint8_t>& out) {
-    if (p.done) return IK_OK;
-    p.done = true;
-    if (p.fmt == IK_FORMAT_WEBP) {
-        const size_t uvw = (p.w + 1) / 2, uvh = (p.h + 1) / 2;
-        const uint8_t* Y = p.plane_data();
-        return webp_encode_yuv420(Y, Y + (size_t)p.w * p.h, Y + (size_t)p.w * p.h + uvw * uvh, (int)p.w, (int)p.h,
-                                  (float)p.q, out);
-    }
-    if (p.fmt == IK_FORMAT_AVIF) return avif_encode_yuv444(p.plane_data(), p.transparent, (int)p.w, (int)p.h, p.q, 4, out);
-    return fail(IK_ERR_INVALID, "unknown ImageFormat %d", p.fmt);
-}
-
-int encode_device_image(const uint8_t* dev, uint32_t w, uint32_t h, uint32_t c, size_t pitch, int fmt, int quality,
-                        std::vector<uint8_t>& out) {
-    EncodePrep p;
-    const int rc = encode_device_front(dev, w, h, c, pitch, fmt, quality, p, out);
-    return rc ? rc : encode_host_back(p, out);
-}
-
-// the front half of ik_encode on a handle (u16 images are rescaled to u8 first,
-// as to_rgb8 / to_rgba8 do)
-int encode_image_front(const ik_image* img, int fmt, int quality, EncodePrep& p, std::vector<uint8_t>& out) {
-    if (!img) return fail(IK_ERR_INVALID, "null pointer");
-    if (img->w == 0 || img->h == 0) return fail(IK_ERR_TRANSFORM, "cannot encode an empty image");
-    DeviceGuard g(img->device);
-    if (img->depth != 2) return encode_device_front(img->d, img->w, img->h, img->c, img->pitch, fmt, quality, p, out);
-    ik_image* u8 = nullptr;
-    int st = alloc_image(img->w, img->h, img->c, &u8);
-    if (st) return st;
-    hipError_t e = launch_u16_to_u8(img->d, img->pitch, u8->d, u8->pitch, (int)(img->w * img->c), (int)img->h,
-                                    thread_stream());
-    st = e == hipSuccess ? encode_device_front(u8->d, u8->w, u8->h, u8->c, u8->pitch, fmt, quality, p, out)
-                         : hip_fail(e, "u16 -> u8");
-    if (e == hipSuccess && !st) (void)hipStreamSynchronize(thread_stream());  // u8 is read before it is freed
-    ik_image_free(u8);
-    return st;
 }
 
 }  // namespace ik
@@ -844,6 +643,36 @@ void ik_schedule_plan(const uint64_t* costs, uint32_t n, uint32_t ndev, const ui
                       uint32_t* assign) {
     if (!costs || !assign || !ndev) return;
     sched_plan(costs, n, ndev, outstanding, assign);
+}
+
+int ik_post_plan(uint32_t m, const int* ok, const uint32_t* W, const uint32_t* H, const uint32_t* C,
+                 const uint64_t* pitch, const int* device, const uint32_t* depth, const int64_t* w, const int64_t* h,
+                 const int* fmt, const int* quality, int webp_encoder, int mixed_mode, uint32_t* nw, uint32_t* nh,
+                 int* resize_group, int* coder_group, int* route, uint32_t* info) {
+    if (!ok || !W || !H || !C || !pitch || !device || !depth || !w || !h || !fmt || !quality || !nw || !nh ||
+        !resize_group || !coder_group || !route || !info)
+        return fail(IK_ERR_INVALID, "null pointer");
+    std::vector<PostRequest> rq(m);
+    for (uint32_t k = 0; k < m; ++k) {
+        rq[k].ok = ok[k] != 0;
+        rq[k].W = W[k]; rq[k].H = H[k]; rq[k].C = C[k];
+        rq[k].pitch = (size_t)pitch[k]; rq[k].device = device[k]; rq[k].depth = depth[k];
+        rq[k].w = w[k]; rq[k].h = h[k]; rq[k].fmt = fmt[k]; rq[k].quality = quality[k];
+    }
+    const PostPlan P = post_plan(rq.data(), m, webp_encoder, mixed_mode);
+    for (uint32_t k = 0; k < m; ++k) {
+        const PostPlan::Req& q = P.req[k];
+        nw[k] = q.sized ? q.nw : 0;
+        nh[k] = q.sized ? q.nh : 0;
+        resize_group[k] = q.rgroup;
+        coder_group[k] = q.cgroup;
+        route[k] = (int)q.route;
+    }
+    info[0] = P.mixed;
+    info[1] = (uint32_t)P.mixed_min;
+    info[2] = (uint32_t)P.rgroups.size();
+    info[3] = (uint32_t)P.cgroups.size();
+    return IK_OK;
 }
 
 uint32_t ik_schedule_split(const uint64_t* costs, uint32_t n, uint32_t ndev, const uint64_t* outstanding,
@@ -997,358 +826,19 @@ int ik_resize_exact(const ik_image* img, uint32_t nw, uint32_t nh, int filter, i
     return IK_OK;
 }
 
-static uint32_t f32_as_u32(float v) {
-    if (!(v > 0.0f)) return 0;
-    if (v >= 4294967296.0f) return 0xFFFFFFFFu;
-    return (uint32_t)v;
-}
-
 }  // extern "C"
 
 namespace ik {
 
 // The output size of src/transform.rs:62-90 + DynamicImage::resize for a w x h
-// image and the request's (w, h) options (-1 = None; not both None)
+// image and the request's (w, h) options (-1 = None; not both None): the
+// arithmetic is resize_target_dims (ik_post_plan.h), shared with the post plan
 int resize_target(uint32_t W, uint32_t H, int64_t w, int64_t h, uint32_t* onw, uint32_t* onh) {
-    if (w > 0xFFFFFFFFll || h > 0xFFFFFFFFll) return fail(IK_ERR_INVALID, "dimension exceeds u32");
-    uint32_t tw, th;
-    if (w >= 0) tw = (uint32_t)w;
-    else tw = f32_as_u32(roundf((float)W * ((float)(uint32_t)h / (float)H)));
-    if (h >= 0) th = (uint32_t)h;
-    else th = f32_as_u32(roundf((float)H * ((float)(uint32_t)w / (float)W)));
-    if (tw < 1) tw = 1;
-    if (th < 1) th = 1;
-    uint32_t nw = tw, nh = th;
-    if (!(tw == W && th == H)) {
-        const double wr = (double)tw / (double)W, hr = (double)th / (double)H;
-        const double r = wr < hr ? wr : hr;
-        double fw = std::round((double)W * r), fh = std::round((double)H * r);
-        unsigned long long rw = fw < 1 ? 1 : (unsigned long long)fw;
-        unsigned long long rh = fh < 1 ? 1 : (unsigned long long)fh;
-        if (rw > 0xFFFFFFFFull || rh > 0xFFFFFFFFull) return fail(IK_ERR_INVALID, "dimension overflow");
-        nw = (uint32_t)rw; nh = (uint32_t)rh;
+    switch (resize_target_dims(W, H, w, h, onw, onh)) {
+        case 0: return IK_OK;
+        case 1: return fail(IK_ERR_INVALID, "dimension exceeds u32");
+        default: return fail(IK_ERR_INVALID, "dimension overflow");
     }
-    *onw = nw;
-    *onh = nh;
-    return IK_OK;
-}
-
-// encode_image's device front end for n same-geometry 8-bit images going to WebP
-// through libwebp: ONE colour-conversion launch over per-image base pointers,
-// writing every image's YUV420 planes straight into pinned host memory; prep[i]
-// gets the planes for encode_host_back.  Returns IK_ERR_UNSUPPORTED (nothing
-// done) when the per-image path applies instead (the GPU VP8 encoder, > 16383).
-// Page-locked blocks shared by the requests of a batched colour launch: a pool of
-// free blocks (process-wide); a block goes back when its last holder drops it.
-// Best fit (the smallest free block that holds the request, at most twice its
-// size, so a small group does not take the block a large one needs), and at most
-// kPinnedPoolBytes kept: a block returned past that goes back to the runtime.
-namespace {
-constexpr size_t kPinnedPoolBytes = size_t(2) << 30;
-std::mutex g_pblk_mu;
-std::multimap<size_t, uint8_t*> g_pblk_free;  // capacity -> block
-size_t g_pblk_held = 0;
-}  // namespace
-static std::shared_ptr<uint8_t> pinned_block(size_t bytes) {
-    uint8_t* p = nullptr;
-    size_t cap = 0;
-    {
-        std::lock_guard<std::mutex> lk(g_pblk_mu);
-        auto it = g_pblk_free.lower_bound(bytes);
-        if (it != g_pblk_free.end() && it->first <= 2 * bytes) {
-            cap = it->first;
-            p = it->second;
-            g_pblk_held -= cap;
-            g_pblk_free.erase(it);
-        }
-    }
-    if (!p) {
-        cap = bytes;
-        if (hipHostMalloc((void**)&p, cap, hipHostMallocDefault) != hipSuccess) return nullptr;
-    }
-    return std::shared_ptr<uint8_t>(p, [cap](uint8_t* q) {
-        {
-            std::lock_guard<std::mutex> lk(g_pblk_mu);
-            if (g_pblk_held + cap <= kPinnedPoolBytes) {
-                g_pblk_free.emplace(cap, q);
-                g_pblk_held += cap;
-                return;
-            }
-        }
-        (void)hipHostFree(q);
-    });
-}
-
-// The exact coder for a same-geometry group (IK_WEBP_EXACT): one batched colour launch
-// into device memory, then the whole group through webp_encode_exact -- the files
-// are final, no host coder runs.
-static int webp_exact_group(const std::vector<ik_image*>& imgs, int quality, std::vector<std::vector<uint8_t>*>& outs) {
-    const size_t n = imgs.size();
-    const ik_image* i0 = imgs[0];
-    DeviceGuard g(i0->device);
-    const DeviceConsts* dc = device_consts(current_device());
-    if (!dc) return fail(IK_ERR_DEVICE, "cannot upload WebP tables");
-    const uint32_t w = i0->w, h = i0->h;
-    const size_t bytes = yuv420_bytes(w, h);
-    const size_t stride = (bytes + 255) & ~size_t(255);
-    hipStream_t s = thread_stream();
-    uint8_t* dyuv = scratch(stride * n + 16 * n + 256);
-    if (!dyuv) return fail(IK_ERR_DEVICE, "cannot allocate device scratch");
-    std::vector<uint64_t> htab(n);
-    for (size_t i = 0; i < n; ++i) htab[i] = (uint64_t)(uintptr_t)imgs[i]->d;
-    uint64_t* dtab = reinterpret_cast<uint64_t*>(dyuv + stride * n);
-    hipError_t e = hipMemcpyAsync(dtab, htab.data(), 8 * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = launch_webp_yuv420(nullptr, (int)w, (int)h, (int)i0->c, i0->pitch, 0, dyuv, stride, (int)n,
-                               dc->gamma_to_lin, dc->lin_to_gamma, s, dtab);
-    if (e != hipSuccess) return hip_fail(e, "webp yuv420 (exact group)");
-    std::vector<std::vector<uint8_t>> files;
-    const int q = clamp_quality(quality);
-    if (int rc = webp_encode_exact(dyuv, stride, (int)n, (int)w, (int)h, q, files)) return rc;
-    for (size_t i = 0; i < n; ++i) outs[i]->swap(files[i]);
-    return IK_OK;
-}
-
-// The exact coder for a batch's WebP requests of mixed sizes and qualities
-// (IK_WEBP_MIXED_GPU): one colour launch over a table of the images into device
-// memory, then all of them through one webp_encode_exact_mixed call -- the files are
-// final, no host coder runs.  8-bit images of at most 16383 x 16383 on one device.
-static int webp_exact_mixed_group(const std::vector<ik_image*>& imgs, const std::vector<int>& quality,
-                                  std::vector<std::vector<uint8_t>*>& outs) {
-    const size_t n = imgs.size();
-    DeviceGuard g(imgs[0]->device);
-    const DeviceConsts* dc = device_consts(current_device());
-    if (!dc) return fail(IK_ERR_DEVICE, "cannot upload WebP tables");
-    hipStream_t s = thread_stream();
-    if (!s) return fail(IK_ERR_DEVICE, "cannot create HIP stream");
-    std::vector<size_t> at(n);
-    size_t total = 0;
-    int max_w = 0, max_h = 0;
-    for (size_t i = 0; i < n; ++i) {
-        const size_t w = imgs[i]->w, h = imgs[i]->h;
-        at[i] = total;
-        total += (yuv420_bytes(w, h) + 255) & ~size_t(255);
-        max_w = std::max(max_w, (int)w);
-        max_h = std::max(max_h, (int)h);
-    }
-    uint8_t* dyuv = scratch_slot(kScratchMixedPlanes, total + sizeof(WebpYuvItem) * n);
-    WebpYuvItem* htab = reinterpret_cast<WebpYuvItem*>(pinned_slot(kPinnedMixedTab, sizeof(WebpYuvItem) * n));
-    if (!dyuv || !htab) return fail(IK_ERR_DEVICE, "cannot allocate the mixed WebP planes");
-    (void)hipStreamSynchronize(s);  // nothing pending reads the pinned table
-    std::vector<ExactItem> items(n);
-    for (size_t i = 0; i < n; ++i) {
-        htab[i] = WebpYuvItem{imgs[i]->d, dyuv + at[i], imgs[i]->pitch, (int32_t)imgs[i]->w, (int32_t)imgs[i]->h,
-                              (int32_t)imgs[i]->c, 0};
-        items[i] = ExactItem{dyuv + at[i], (int)imgs[i]->w, (int)imgs[i]->h, clamp_quality(quality[i])};
-    }
-    WebpYuvItem* dtab = reinterpret_cast<WebpYuvItem*>(dyuv + total);
-    hipError_t e = hipMemcpyAsync(dtab, htab, sizeof(WebpYuvItem) * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = launch_webp_yuv420_items(dtab, (int)n, max_w, max_h, dc->gamma_to_lin, dc->lin_to_gamma, s);
-    if (e != hipSuccess) return hip_fail(e, "webp yuv420 (mixed group)");
-    std::vector<std::vector<uint8_t>> files;
-    if (int rc = webp_encode_exact_mixed(items.data(), (int)n, files)) return rc;
-    for (size_t i = 0; i < n; ++i) outs[i]->swap(files[i]);
-    return IK_OK;
-}
-
-int webp_front_group(const std::vector<ik_image*>& imgs, int quality, std::vector<EncodePrep*>& prep) {
-    const size_t n = imgs.size();
-    if (!n) return IK_OK;
-    const ik_image* i0 = imgs[0];
-    if (i0->w > 16383 || i0->h > 16383 || i0->depth != 1)  // (the caller chose the libwebp coder)
-        return IK_ERR_UNSUPPORTED;
-    DeviceGuard g(i0->device);
-    const DeviceConsts* dc = device_consts(current_device());
-    if (!dc) return fail(IK_ERR_DEVICE, "cannot upload WebP tables");
-    const uint32_t w = i0->w, h = i0->h;
-    const size_t bytes = yuv420_bytes(w, h);
-    const size_t stride = (bytes + 255) & ~size_t(255);
-    std::shared_ptr<uint8_t> blk = pinned_block(stride * n + 16 * n + 256);
-    uint8_t* hp = blk.get();
-    void* dhp = nullptr;
-    if (!hp || hipHostGetDevicePointer(&dhp, hp, 0) != hipSuccess || !dhp)
-        return fail(IK_ERR_NOMEM, "cannot map pinned WebP planes");
-    uint64_t* dtab = reinterpret_cast<uint64_t*>(scratch_slot(3, sizeof(uint64_t) * n));
-    if (!dtab) return fail(IK_ERR_DEVICE, "cannot allocate device scratch");
-    hipStream_t s = thread_stream();
-    (void)hipStreamSynchronize(s);  // nothing pending reads the pinned area
-    uint64_t* htab = reinterpret_cast<uint64_t*>(hp + stride * n);
-    for (size_t i = 0; i < n; ++i) htab[i] = (uint64_t)(uintptr_t)imgs[i]->d;
-    hipError_t e = launch_copy_words(reinterpret_cast<const uint32_t*>(reinterpret_cast<uint8_t*>(dhp) + stride * n),
-                                     reinterpret_cast<uint32_t*>(dtab), 2 * n, s);
-    if (e == hipSuccess)
-        e = launch_webp_yuv420(nullptr, (int)w, (int)h, (int)i0->c, i0->pitch, 0, reinterpret_cast<uint8_t*>(dhp), stride,
-                               (int)n, dc->gamma_to_lin, dc->lin_to_gamma, s, dtab);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(e, "webp yuv420 (batched)");
-    const int q = clamp_quality(quality);
-    for (size_t i = 0; i < n; ++i) {
-        EncodePrep& p = *prep[i];
-        p.fmt = IK_FORMAT_WEBP;
-        p.q = q;
-        p.w = w;
-        p.h = h;
-        p.pin_block = blk;
-        p.pin_planes = hp + stride * i;
-        p.done = false;
-    }
-    return IK_OK;
-}
-
-// imageops::resize over n 8-bit images of one geometry (same W, H, C, pitch) in
-// ONE fused launch: the kernel reads each image's base pointer from a table, so
-// the images may sit anywhere.  Same arithmetic as ik_resize_exact, per image.
-// Returns IK_ERR_UNSUPPORTED (nothing allocated) when the geometry needs the
-// two-kernel fallback; the caller then resizes image by image.
-// encode_image's JPEG branch for a group of same-size 8-bit images (one quality),
-// batched: one coefficient launch (to_rgb8 + YCbCr + FDCT + quantise) and one
-// Huffman launch over all of them, writing the stuffed streams and their lengths
-// straight into pinned host memory -- instead of a launch pair and two blocking
-// copies per image, which serialised 256 small launches per configs[2] batch.
-// Images whose stream does not fit the GPU coder's buffer are coded by the
-// single-image path (its host fallback).  out[i] gets the finished JPEG bytes.
-int jpeg_front_group(const std::vector<ik_image*>& imgs, int quality, std::vector<std::vector<uint8_t>*>& out) {
-    const size_t n = imgs.size();
-    if (!n) return IK_OK;
-    const ik_image* i0 = imgs[0];
-    if (i0->w > 65535 || i0->h > 65535 || i0->depth != 1) return IK_ERR_UNSUPPORTED;
-    DeviceGuard g(i0->device);
-    const DeviceConsts* dc = device_consts(current_device());
-    if (!dc) return fail(IK_ERR_DEVICE, "cannot upload JPEG tables");
-    const int q = clamp_quality(quality);
-    const uint32_t w = i0->w, h = i0->h;
-    uint8_t qt[128];
-    jpeg_quant_tables(q, qt);
-    std::vector<uint8_t> hdr;
-    jpeg_header((int)w, (int)h, qt, hdr);
-    const size_t nmcu = (size_t)((w + 7) / 8) * ((h + 7) / 8);
-    const size_t cimg = ((nmcu * 3 * 64 * sizeof(int16_t)) + 255) & ~size_t(255);  // coefficients per image
-    const size_t cap = jpeg_enc_cap((int)w, (int)h);
-    hipStream_t s = thread_stream();
-    // sub-batches bound the device and pinned memory (2 cap + coefficients per image)
-    constexpr size_t kSub = 64;
-    for (size_t b0 = 0; b0 < n; b0 += kSub) {
-        const size_t m = std::min(kSub, n - b0);
-        // device: [qt 256][src table][coefficients][Huffman work]; pinned: [streams][lengths][qt + table staging]
-        const size_t o_tab = 256, o_coef = o_tab + ((sizeof(uint64_t) * m + 255) & ~size_t(255));
-        const size_t o_work = o_coef + cimg * m;
-        uint8_t* dv = scratch_slot(4, o_work + 2 * cap * m);
-        const size_t p_len = cap * m, p_stage = p_len + ((sizeof(uint32_t) * m + 255) & ~size_t(255));
-        uint8_t* hp = pinned_slot(5, p_stage + 256 + sizeof(uint64_t) * m);
-        void* dhp = nullptr;
-        if (!dv || !hp || hipHostGetDevicePointer(&dhp, hp, 0) != hipSuccess || !dhp)
-            return fail(IK_ERR_NOMEM, "cannot allocate the batched JPEG encoder's buffers");
-        uint8_t* dh = reinterpret_cast<uint8_t*>(dhp);
-        (void)hipStreamSynchronize(s);  // nothing pending reads the pinned area
-        std::memcpy(hp + p_stage, qt, 128);
-        uint64_t* htab = reinterpret_cast<uint64_t*>(hp + p_stage + 256);
-        for (size_t i = 0; i < m; ++i) htab[i] = (uint64_t)(uintptr_t)imgs[b0 + i]->d;
-        EvPair& ev = thread_events(1);
-        hipError_t e = launch_copy_words(reinterpret_cast<const uint32_t*>(dh + p_stage), reinterpret_cast<uint32_t*>(dv),
-                                         32, s);
-        if (e == hipSuccess) ev_record(ev.a, s);
-        if (e == hipSuccess)
-            e = launch_copy_words(reinterpret_cast<const uint32_t*>(dh + p_stage + 256),
-                                  reinterpret_cast<uint32_t*>(dv + o_tab), 2 * m, s);
-        if (e == hipSuccess)
-            e = launch_jpeg_coeffs(nullptr, (int)w, (int)h, (int)i0->c, i0->pitch, 0, dv,
-                                   reinterpret_cast<int16_t*>(dv + o_coef), cimg / sizeof(int16_t), (int)m, s,
-                                   reinterpret_cast<const uint64_t*>(dv + o_tab));
-        if (e == hipSuccess) {
-            JpegEncArgs a{};
-            a.coef = reinterpret_cast<const int16_t*>(dv + o_coef);
-            a.coef_img_stride = cimg / sizeof(int16_t);
-            a.nmcu = (int)nmcu;
-            a.huff = dc->jpeg_huff;
-            a.work = dv + o_work;
-            a.work_img_bytes = 2 * cap;
-            a.words_bytes = cap;
-            a.out = dh;
-            a.out_img_stride = cap;
-            a.out_cap = cap;
-            a.out_len = reinterpret_cast<uint32_t*>(dh + p_len);
-            e = launch_jpeg_huff_enc(a, (int)m, s);
-        }
-        if (e == hipSuccess) ev_record(ev.b, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return hip_fail(e, "jpeg encode (batched)");
-        batch_timing_add(current_device(), kBtJpegEncMs, ev_pair_ms(ev));
-        batch_timing_add(current_device(), kBtJpegEncImages, (double)m);
-        const uint32_t* lens = reinterpret_cast<const uint32_t*>(hp + p_len);
-        for (size_t i = 0; i < m; ++i) {
-            std::vector<uint8_t>& o = *out[b0 + i];
-            if (lens[i] == 0xffffffffu) {  // past the GPU coder's buffer: the single-image path (host coder, counted there)
-                EncodePrep pp;
-                if (int rc = encode_device_front(imgs[b0 + i]->d, w, h, i0->c, i0->pitch, IK_FORMAT_JPEG, q, pp, o))
-                    return rc;
-                continue;
-            }
-            jpeg_enc_count(true);
-            o.assign(hdr.begin(), hdr.end());
-            o.insert(o.end(), hp + cap * i, hp + cap * i + lens[i]);
-            o.push_back(0xFF);
-            o.push_back(0xD9);
-        }
-    }
-    return IK_OK;
-}
-
-int resize_group(const std::vector<ik_image*>& src, uint32_t nw, uint32_t nh, int filter, std::vector<ik_image*>& out) {
-    const size_t n = src.size();
-    out.assign(n, nullptr);
-    if (!n) return IK_OK;
-    const ik_image* s0 = src[0];
-    DeviceGuard g(s0->device);
-    ResizePlan* plan = get_resize_plan(current_device(), (int)s0->w, (int)s0->h, (int)s0->c, (int)nw, (int)nh, filter,
-                                       (int)n);
-    if (!plan) return fail(IK_ERR_DEVICE, "cannot build resize plan");
-    if (plan->slots == 0 || !resize_fused_fits(s0->pitch, s0->h) || (s0->pitch & 7)) return IK_ERR_UNSUPPORTED;
-    std::vector<uint64_t> tab(2 * n);
-    for (size_t i = 0; i < n; ++i) {
-        const int st = alloc_image(nw, nh, s0->c, &out[i]);
-        if (st) {
-            for (ik_image*& o : out) { ik_image_free(o); o = nullptr; }
-            return st;
-        }
-        tab[i] = (uint64_t)(uintptr_t)src[i]->d;
-        tab[n + i] = (uint64_t)(uintptr_t)out[i]->d;
-    }
-    hipStream_t s = thread_stream();
-    uint64_t* dtab = reinterpret_cast<uint64_t*>(scratch_slot(3, sizeof(uint64_t) * 2 * n));
-    // the pointer table goes up through a copy kernel reading pinned memory (a
-    // copy-engine transfer would queue behind another batch's stream upload)
-    uint8_t* ht = pinned_slot(5, 16 * n);
-    void* dht = nullptr;
-    int rc = IK_OK;
-    if (!dtab) rc = fail(IK_ERR_DEVICE, "cannot allocate device scratch");
-    else if (!ht || hipHostGetDevicePointer(&dht, ht, 0) != hipSuccess || !dht)
-        rc = fail(IK_ERR_NOMEM, "cannot map pinned resize table");
-    if (!rc) {
-        (void)hipStreamSynchronize(s);  // the previous table is read
-        std::memcpy(ht, tab.data(), 16 * n);
-        const hipError_t e = launch_copy_words(reinterpret_cast<const uint32_t*>(dht), reinterpret_cast<uint32_t*>(dtab),
-                                               4 * n, s);
-        if (e != hipSuccess) rc = hip_fail(e, "resize table upload");
-    }
-    if (!rc) {
-        EvPair& ev = thread_events(0);
-        ev_record(ev.a, s);
-        hipError_t e = launch_resize(*plan, nullptr, s0->pitch, 0, nullptr, out[0]->pitch, 0, (int)n, nullptr, s, dtab,
-                                     dtab + n);
-        if (e == hipSuccess) ev_record(ev.b, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) rc = hip_fail(e, "resize (batched)");
-        if (!rc) {
-            const int d = current_device();
-            batch_timing_add(d, kBtResizeMs, ev_pair_ms(ev));
-            batch_timing_add(d, kBtResizeBytes, (double)n * s0->c * ((double)s0->w * s0->h + (double)nw * nh));
-            batch_timing_add(d, kBtResizeImages, (double)n);
-        }
-    }
-    if (rc)
-        for (ik_image*& o : out) { ik_image_free(o); o = nullptr; }
-    return rc;
 }
 
 }  // namespace ik
@@ -1719,90 +1209,49 @@ static void transform_post_phase(const int64_t* w, const int64_t* h, const int* 
     hp.bytes_out.assign(m, std::vector<uint8_t>());
     std::vector<EncodePrep>& prep = hp.prep;
     std::vector<std::vector<uint8_t>>& bytes_out = hp.bytes_out;
-    // requests whose decoded images share a geometry and an output size resize in
-    // one launch (resize_group); the rest, image by image below
-    std::vector<ik_image*> rsz(m, nullptr);
-    std::vector<char> fronted(m, 0);  // encode front end already run (batched WebP colour conversion)
-    // IK_WEBP_MIXED_GPU (read once for the batch): the WebP requests that no uniform exact
-    // group takes keep their resized image (kept[k]) and are coded together below, when
-    // the batch can hold kAutoMixedMin of them at all; at IK_WEBP_MIXED_HOST nothing is kept
-    std::vector<ik_image*> kept(m, nullptr);
-    bool mixed = false;
-    size_t mixed_min = kAutoMixedMin;  // (EXACT: any two, as its uniform groups)
-    if (webp_mixed_mode() == IK_WEBP_MIXED_GPU && default_webp_encoder() != IK_WEBP_LIBWEBP) {
-        if (default_webp_encoder() == IK_WEBP_EXACT) mixed_min = 2;
-        size_t cand = 0;
-        for (uint32_t k = 0; k < m; ++k)
-            cand += !ds[k] && imgs[k] && imgs[k]->depth == 1 && fmt[idx[k]] == IK_FORMAT_WEBP;
-        mixed = cand >= mixed_min;
-    }
-    {
-        std::map<std::tuple<uint32_t, uint32_t, uint32_t, size_t, int, uint32_t, uint32_t>, std::vector<uint32_t>> groups;
-        for (uint32_t k = 0; k < m; ++k) {
-            const uint32_t i = idx[k];
-            if (ds[k] || !imgs[k] || imgs[k]->depth != 1 || (w[i] < 0 && h[i] < 0)) continue;
-            uint32_t nw, nh;
-            if (resize_target(imgs[k]->w, imgs[k]->h, w[i], h[i], &nw, &nh)) continue;
-            if (nw == imgs[k]->w && nh == imgs[k]->h) continue;
-            groups[std::make_tuple(imgs[k]->w, imgs[k]->h, imgs[k]->c, imgs[k]->pitch, imgs[k]->device, nw, nh)]
-                .push_back(k);
+    // which launch resizes each request and which coder writes its file: ik_post_plan.h
+    // (the encoder setting and the mixed mode are read once for the batch)
+    std::vector<PostRequest> rq(m);
+    for (uint32_t k = 0; k < m; ++k) {
+        const uint32_t i = idx[k];
+        const ik_image* im = imgs[k];
+        rq[k].ok = !ds[k] && im;
+        if (rq[k].ok) {
+            rq[k].W = im->w; rq[k].H = im->h; rq[k].C = im->c;
+            rq[k].pitch = im->pitch; rq[k].device = im->device; rq[k].depth = im->depth;
         }
-        const auto t0 = std::chrono::steady_clock::now();
-        for (auto& kv : groups) {
-            if (kv.second.size() < 2) continue;
-            std::vector<ik_image*> src, out;
-            for (uint32_t k : kv.second) src.push_back(imgs[k]);
-            if (resize_group(src, std::get<5>(kv.first), std::get<6>(kv.first), filter, out) != IK_OK) continue;
-            for (size_t j = 0; j < out.size(); ++j) rsz[kv.second[j]] = out[j];
-            // the group's WebP requests of one quality: one colour-conversion launch;
-            // its JPEG requests of one quality: one coefficient + one Huffman launch
-            std::map<int, std::vector<uint32_t>> byq, jbyq;
-            for (uint32_t k : kv.second) {
-                if (fmt[idx[k]] == IK_FORMAT_WEBP) byq[quality[idx[k]]].push_back(k);
-                if (fmt[idx[k]] == IK_FORMAT_JPEG) jbyq[quality[idx[k]]].push_back(k);
-            }
-            const int webp_enc = default_webp_encoder();  // read once for the batch's groups (AUTO: exact)
-            for (auto& qv : byq) {
-                if (qv.second.size() < 2) continue;
-                std::vector<ik_image*> im;
-                std::vector<EncodePrep*> pp;
-                for (uint32_t k : qv.second) { im.push_back(rsz[k]); pp.push_back(&prep[k]); }
-                // AUTO: the GPU coder from kAutoExactMinGroup frames of one geometry on (its
-                // chain of macroblock steps costs about the same for 2 frames as for 64; a
-                // mixed-size stream's small groups code faster on the host threads:
-                // configs[3]'s loadtest 2,106 vs 1,224 requests/s)
-                const bool exact = webp_enc == IK_WEBP_EXACT ||
-                                   (webp_enc == IK_WEBP_AUTO && qv.second.size() >= kAutoExactMinGroup);
-                if (exact && im[0]->depth == 1 && im[0]->w <= 16383 && im[0]->h <= 16383) {
-                    std::vector<std::vector<uint8_t>*> oo;
-                    for (uint32_t k : qv.second) oo.push_back(&bytes_out[k]);
-                    if (webp_exact_group(im, qv.first, oo) == IK_OK)
-                        for (uint32_t k : qv.second) {
-                            fronted[k] = 1;
-                            prep[k].fmt = IK_FORMAT_WEBP;
-                            prep[k].done = true;  // the files are final: no host coder
-                        }
-                    continue;
-                }
-                if (mixed) continue;  // with the batch's other WebP requests, below
-                if (webp_front_group(im, qv.first, pp) == IK_OK)
-                    for (uint32_t k : qv.second) fronted[k] = 1;
-            }
-            for (auto& qv : jbyq) {
-                if (qv.second.size() < 2) continue;
-                std::vector<ik_image*> im;
-                std::vector<std::vector<uint8_t>*> oo;
-                for (uint32_t k : qv.second) { im.push_back(rsz[k]); oo.push_back(&bytes_out[k]); }
-                if (jpeg_front_group(im, qv.first, oo) == IK_OK)
-                    for (uint32_t k : qv.second) {
-                        fronted[k] = 1;
-                        prep[k].fmt = IK_FORMAT_JPEG;
-                        prep[k].done = true;  // the bytes are final: no host coder
-                    }
+        rq[k].w = w[i]; rq[k].h = h[i]; rq[k].fmt = fmt[i]; rq[k].quality = quality[i];
+    }
+    const PostPlan plan = post_plan(rq.data(), m, default_webp_encoder(), webp_mixed_mode());
+    std::vector<ik_image*> rsz(m, nullptr);   // resized by its group's launch
+    std::vector<char> fronted(m, 0);          // encode front end already run by its group's call
+    std::vector<ik_image*> kept(m, nullptr);  // resized image kept for the mixed exact call
+    const auto tg0 = std::chrono::steady_clock::now();
+    for (const PostPlan::ResizeGroup& G : plan.rgroups) {
+        std::vector<ik_image*> src, out;
+        for (uint32_t k : G.members) src.push_back(imgs[k]);
+        if (resize_group(src, G.nw, G.nh, filter, out) != IK_OK) continue;  // its members: image by image below
+        for (size_t j = 0; j < out.size(); ++j) rsz[G.members[j]] = out[j];
+        for (uint32_t c = G.cg_lo; c < G.cg_hi; ++c) {
+            const PostPlan::CoderGroup& cg = plan.cgroups[c];
+            std::vector<ik_image*> im;
+            std::vector<EncodePrep*> pp;
+            std::vector<std::vector<uint8_t>*> oo;
+            for (uint32_t k : cg.members) { im.push_back(rsz[k]); pp.push_back(&prep[k]); oo.push_back(&bytes_out[k]); }
+            const bool planes = cg.route == PostRoute::WebpFrontGroup;  // libwebp codes them in the host stage
+            const int rc = planes                                      ? webp_front_group(im, cg.quality, pp)
+                           : cg.route == PostRoute::WebpExactGroup ? webp_exact_group(im, cg.quality, oo)
+                                                                       : jpeg_front_group(im, cg.quality, oo);
+            if (rc != IK_OK) continue;  // its members: image by image below (Req::solo)
+            for (uint32_t k : cg.members) {
+                fronted[k] = 1;
+                if (planes) continue;
+                prep[k].fmt = rq[k].fmt;
+                prep[k].done = true;  // the files are final: no host coder
             }
         }
-        t_resize += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
+    t_resize += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tg0).count();
     parallel_for((int)m, threads, [&](int k) {
         const uint32_t i = idx[k];
         if (ds[k]) { st[i] = ds[k]; errs[i] = dm[k]; return; }
@@ -1810,8 +1259,7 @@ static void transform_post_phase(const int64_t* w, const int64_t* h, const int* 
         const auto t0 = std::chrono::steady_clock::now();
         int r = rs ? IK_OK : ik_resize(imgs[k], w[i], h[i], filter, &rs);
         const auto t1 = std::chrono::steady_clock::now();
-        if (!r && !fronted[k] && mixed && fmt[i] == IK_FORMAT_WEBP && rs->depth == 1 && rs->w && rs->h &&
-            rs->w <= 16383 && rs->h <= 16383) {
+        if (!r && !fronted[k] && plan.req[k].solo == PostRoute::WebpMixed) {
             (void)hipStreamSynchronize(thread_stream());  // this thread's resize is done: another's stream reads it
             kept[k] = rs;
         } else if (!r && !fronted[k]) r = encode_image_front(rs, fmt[i], quality[i], prep[k], bytes_out[k]);
@@ -1826,36 +1274,34 @@ static void transform_post_phase(const int64_t* w, const int64_t* h, const int* 
         if (imgs[k] != kept[k]) ik_image_free(imgs[k]);
         imgs[k] = nullptr;
     });
-    if (mixed) {
-        // one colour launch and one mixed exact call for the kept requests; fewer than
-        // the minimum of them (the uniform groups took the rest), or a failed call: the
-        // existing front end, image by image
-        std::vector<uint32_t> ks;
-        for (uint32_t k = 0; k < m; ++k)
-            if (kept[k]) ks.push_back(k);
-        bool coded = false;
-        if (ks.size() >= mixed_min) {
-            std::vector<ik_image*> im;
-            std::vector<int> qs;
-            std::vector<std::vector<uint8_t>*> oo;
-            for (uint32_t k : ks) { im.push_back(kept[k]); qs.push_back(quality[idx[k]]); oo.push_back(&bytes_out[k]); }
-            const auto t0 = std::chrono::steady_clock::now();
-            coded = webp_exact_mixed_group(im, qs, oo) == IK_OK;
-            t_front += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        }
-        parallel_for((int)ks.size(), threads, [&](int j) {
-            const uint32_t k = ks[(size_t)j], i = idx[k];
-            if (coded) {
-                prep[k].fmt = IK_FORMAT_WEBP;
-                prep[k].done = true;  // the files are final: no host coder
-            } else if (int r = encode_image_front(kept[k], fmt[i], quality[i], prep[k], bytes_out[k])) {
-                errs[i] = last_error_str();
-                st[i] = r;
-                prep[k].done = true;
-            }
-            ik_image_free(kept[k]);
-        });
+    // one colour launch and one mixed exact call for the kept requests; fewer than the
+    // minimum of them (the uniform groups took the rest), or a failed call: the existing
+    // front end, image by image
+    std::vector<uint32_t> ks;
+    for (uint32_t k = 0; k < m; ++k)
+        if (kept[k]) ks.push_back(k);
+    bool coded = false;
+    if (ks.size() >= plan.mixed_min) {
+        std::vector<ik_image*> im;
+        std::vector<int> qs;
+        std::vector<std::vector<uint8_t>*> oo;
+        for (uint32_t k : ks) { im.push_back(kept[k]); qs.push_back(quality[idx[k]]); oo.push_back(&bytes_out[k]); }
+        const auto t0 = std::chrono::steady_clock::now();
+        coded = webp_exact_mixed_group(im, qs, oo) == IK_OK;
+        t_front += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
+    parallel_for((int)ks.size(), threads, [&](int j) {
+        const uint32_t k = ks[(size_t)j], i = idx[k];
+        if (coded) {
+            prep[k].fmt = IK_FORMAT_WEBP;
+            prep[k].done = true;  // the files are final: no host coder
+        } else if (int r = encode_image_front(kept[k], fmt[i], quality[i], prep[k], bytes_out[k])) {
+            errs[i] = last_error_str();
+            st[i] = r;
+            prep[k].done = true;
+        }
+        ik_image_free(kept[k]);
+    });
     batch_timing_commit(current_device(), true);
     gate_pin(kGatePost, false);
     std::vector<ik_image*>().swap(hp.imgs);
@@ -2112,21 +1558,7 @@ static void memory_shutdown() {
             kv.second->held = 0;
         }
     }
-    {
-        std::lock_guard<std::mutex> lk(g_pblk_mu);
-        for (auto& b : g_pblk_free) (void)hipHostFree(b.second);
-        g_pblk_free.clear();
-        g_pblk_held = 0;
-    }
-    std::lock_guard<std::mutex> lk(g_consts_mu);
-    for (auto& kv : g_consts) {
-        (void)hipSetDevice(kv.first);
-        (void)hipFree(kv.second->gamma_to_lin);
-        (void)hipFree(kv.second->lin_to_gamma);
-        (void)hipFree(kv.second->jpeg_huff);
-        delete kv.second;
-    }
-    g_consts.clear();
+    encode_shutdown();
 }
 
 // ik_shutdown: wait for every submitted batch, end the stage threads and the
@@ -2306,7 +1738,7 @@ int ik_transform_batch_submit_device(const uint8_t* const* dev_bytes, const size
         const size_t o_files = (64 * (size_t)n + 255) & ~size_t(255);
         const size_t o_jrecs = o_files + 2 * sizeof(uint64_t) * n;
         const size_t o_jskel = (o_jrecs + sizeof(jwalk::Rec) * n + 255) & ~size_t(255);
-        uint8_t* pin = pinned_slot(7, o_jskel + (size_t)jwalk::kSlot * n);
+        uint8_t* pin = pinned_slot(kPinnedDeviceHeads, o_jskel + (size_t)jwalk::kSlot * n);
         void* dp = nullptr;
         if (!pin || hipHostGetDevicePointer(&dp, pin, 0) != hipSuccess || !dp)
             return fail(IK_ERR_NOMEM, "cannot allocate pinned memory for the input headers");
@@ -2335,7 +1767,7 @@ int ik_transform_batch_submit_device(const uint8_t* const* dev_bytes, const size
                 files[nj + k] = lens[ji[k]];
             }
             uint8_t* dpin = reinterpret_cast<uint8_t*>(dp);
-            EvPair& ev = thread_events(0);
+            EvPair& ev = thread_events(kEvJpegWalk);
             ev_record(ev.a, s);
             IK_HIP(launch_jpeg_walk(df, df + nj, (int)nj, dpin + o_jskel, dpin + o_jrecs, s));
             ev_record(ev.b, s);
@@ -2587,25 +2019,15 @@ int ik_jpeg_huffman_device(const int16_t* dev_coef, size_t coef_img_stride, uint
     if (!dc) return fail(IK_ERR_DEVICE, "cannot upload JPEG tables");
     hipStream_t s = thread_stream();
     if (!s) return fail(IK_ERR_DEVICE, "cannot create HIP stream");
-    const size_t nmcu = (size_t)((w + 7) / 8) * ((h + 7) / 8);
-    if (n > 1 && coef_img_stride < nmcu * 3 * 64) return fail(IK_ERR_INVALID, "coefficient stride too small");
+    const JpegEncGeom jg = jpeg_enc_geom(w, h);
+    if (n > 1 && coef_img_stride < jg.nmcu * 3 * 64) return fail(IK_ERR_INVALID, "coefficient stride too small");
     // [Huffman work: words + staging][stuffed streams][lengths], as encode_device_front lays them out
-    const size_t cap = jpeg_enc_cap((int)w, (int)h);
-    const size_t o_off = 2 * cap * n, l_off = o_off + cap * n;
+    const size_t cap = jg.cap;
+    const size_t o_off = jg.work_bytes * n, l_off = o_off + cap * n;
     uint8_t* dw = scratch(l_off + sizeof(uint32_t) * n);
     if (!dw) return fail(IK_ERR_DEVICE, "cannot allocate device scratch");
-    JpegEncArgs a{};
-    a.coef = dev_coef;
-    a.coef_img_stride = coef_img_stride;
-    a.nmcu = (int)nmcu;
-    a.huff = dc->jpeg_huff;
-    a.work = dw;
-    a.work_img_bytes = 2 * cap;
-    a.words_bytes = cap;
-    a.out = dw + o_off;
-    a.out_img_stride = cap;
-    a.out_cap = cap;
-    a.out_len = reinterpret_cast<uint32_t*>(dw + l_off);
+    const JpegEncArgs a = jg.args(dev_coef, coef_img_stride, dc->jpeg_huff, dw, dw + o_off,
+                                  reinterpret_cast<uint32_t*>(dw + l_off));
     // the caller's bytes go up first, so whatever the kernel leaves alone comes back as it was
     if (int rc = copy_h2d_2d(dw + o_off, cap * n, host_out, cap * n, cap * n, 1, s)) return rc;
     const hipError_t e = launch_jpeg_huff_enc(a, (int)n, s);
@@ -2617,13 +2039,6 @@ int ik_jpeg_huffman_device(const int16_t* dev_coef, size_t coef_img_stride, uint
                              4 * (size_t)n, 1, s))
         return rc;
     return copy_d2h_2d(host_out, cap * n, dw + o_off, cap * n, cap * n, 1, s);
-}
-
-int ik_jpeg_enc_counters(unsigned long long* out) {
-    if (!out) return fail(IK_ERR_INVALID, "null pointer");
-    out[0] = g_jpeg_enc_gpu.load();
-    out[1] = g_jpeg_enc_host.load();
-    return IK_OK;
 }
 
 int ik_dev_alloc(size_t bytes, void** dev_ptr) {

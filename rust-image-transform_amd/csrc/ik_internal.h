@@ -235,6 +235,34 @@ hipError_t launch_jpeg_huff_enc(const JpegEncArgs& a, int n, hipStream_t s);
 inline size_t jpeg_enc_cap(int w, int h) {  // stuffed-stream capacity per image
     return ((size_t)3 * w * h + 4096 + 15) & ~(size_t)15;
 }
+// What the two encoder launches need of a w x h image, and the Huffman launch's
+// arguments over a caller's buffers (the callers' layouts differ: pointers, no layout)
+struct JpegEncGeom {
+    size_t nmcu;        // 8 x 8 blocks per component
+    size_t coef_bytes;  // the int16 coefficients of one image
+    size_t cap;         // stuffed-stream capacity per image
+    size_t work_bytes;  // Huffman work per image: cap of bit words, cap of staging
+    JpegEncArgs args(const int16_t* coef, size_t coef_img_stride, const uint32_t* huff, uint8_t* work, uint8_t* out,
+                     uint32_t* out_len) const {
+        JpegEncArgs a{};
+        a.coef = coef;
+        a.coef_img_stride = coef_img_stride;
+        a.nmcu = (int)nmcu;
+        a.huff = huff;
+        a.work = work;
+        a.work_img_bytes = work_bytes;
+        a.words_bytes = cap;
+        a.out = out;
+        a.out_img_stride = cap;
+        a.out_cap = cap;
+        a.out_len = out_len;
+        return a;
+    }
+};
+inline JpegEncGeom jpeg_enc_geom(uint32_t w, uint32_t h) {
+    const size_t nmcu = (size_t)((w + 7) / 8) * ((h + 7) / 8), cap = jpeg_enc_cap((int)w, (int)h);
+    return JpegEncGeom{nmcu, nmcu * 3 * 64 * sizeof(int16_t), cap, 2 * cap};
+}
 
 // ---- plans (ik_plan.cpp) ----
 // axis_weights, required_slots and the tables themselves: ik_resize_plan.h

@@ -108,8 +108,8 @@ struct ik_pipeline {
     uint8_t qt[128];
     float* d_tmp = nullptr;      // naive resize path only
     int webp_enc = IK_WEBP_LIBWEBP;  // IK_WEBP_EXACT: the exact GPU coder in the collect stage
-    uint8_t* d_jwork = nullptr;      // JPEG: k_jpeg_huff_enc work (2 * jcap per image)
-    size_t jcap = 0;
+    uint8_t* d_jwork = nullptr;      // JPEG: k_jpeg_huff_enc work (jgeom.work_bytes per image)
+    ik::JpegEncGeom jgeom{};         // JPEG: block count, coefficient bytes, stream capacity
     std::vector<uint8_t> jpeg_hdr;   // SOI .. SOS for this geometry and quality
     // Two slots: the device stage of batch k+1 (enqueued by submit) runs while
     // the host entropy stage of batch k (collect) works from its slot.  The
@@ -118,7 +118,7 @@ struct ik_pipeline {
     // slot's planes while the resize of batch k+1 runs.
     struct Slot {
         uint8_t* h_stage = nullptr;       // pinned planes / coefficients
-        uint8_t* h_jpeg = nullptr;        // pinned entropy-coded JPEG segments (k_jpeg_huff_enc), jcap apart
+        uint8_t* h_jpeg = nullptr;        // pinned entropy-coded JPEG segments (k_jpeg_huff_enc), jgeom.cap apart
         uint32_t* h_jlen = nullptr;       // their lengths
         int* d_aflag = nullptr;           // AVIF: per image, 1 when any alpha < 255 (k_avif_yuv444)
         int* h_aflag = nullptr;           // their pinned copies
@@ -183,18 +183,9 @@ int enqueue(ik_pipeline* p, ik_pipeline::Slot& s, const uint8_t* dev_src, size_t
     {
         IK_HIP(hipEventRecord(s.ev[5], p->stream));
         if (copy_out && p->fmt == IK_FORMAT_JPEG) {  // Huffman coding on the GPU, straight into pinned memory
-            JpegEncArgs ja{};
-            ja.coef = reinterpret_cast<const int16_t*>(s.d_stage);
-            ja.coef_img_stride = p->stage_bytes / sizeof(int16_t);
-            ja.nmcu = (int)(((p->nw + 7) / 8) * ((p->nh + 7) / 8));
-            ja.huff = device_consts(p->device)->jpeg_huff;
-            ja.work = p->d_jwork;
-            ja.work_img_bytes = 2 * p->jcap;
-            ja.words_bytes = p->jcap;
-            ja.out = s.h_jpeg;
-            ja.out_img_stride = p->jcap;
-            ja.out_cap = p->jcap;
-            ja.out_len = s.h_jlen;
+            const JpegEncArgs ja = p->jgeom.args(reinterpret_cast<const int16_t*>(s.d_stage),
+                                                 p->stage_bytes / sizeof(int16_t), device_consts(p->device)->jpeg_huff,
+                                                 p->d_jwork, s.h_jpeg, s.h_jlen);
             IK_HIP(launch_jpeg_huff_enc(ja, (int)n, p->stream));
         }
         IK_HIP(hipEventRecord(s.ev[3], p->stream));
@@ -254,13 +245,7 @@ int host_stage(ik_pipeline* p, const ik_pipeline::Slot& s, uint8_t* out, size_t 
                 errs[i] = buf;
             }
         } else if (s.h_jlen[i] != 0xffffffffu) {  // GPU-coded segment: header + bytes + EOI
-            const uint32_t len = s.h_jlen[i];
-            std::vector<uint8_t>& o = p->outs[i];
-            o.resize(p->jpeg_hdr.size() + len + 2);
-            std::memcpy(o.data(), p->jpeg_hdr.data(), p->jpeg_hdr.size());
-            std::memcpy(o.data() + p->jpeg_hdr.size(), s.h_jpeg + p->jcap * (size_t)i, len);
-            o[o.size() - 2] = 0xFF;
-            o[o.size() - 1] = 0xD9;
+            jpeg_file(p->jpeg_hdr, s.h_jpeg + p->jgeom.cap * (size_t)i, s.h_jlen[i], p->outs[i]);
             jpeg_enc_count(true);
         } else {  // did not fit the GPU coder's buffer: coefficients back, host coder
             std::vector<int16_t> coef(p->stage_bytes / sizeof(int16_t));
@@ -310,10 +295,8 @@ int ik_pipeline_create(uint32_t W, uint32_t H, uint32_t C, uint32_t nw, uint32_t
         return rc;
     }
     *out = p;
-    // EXACT, or AUTO with batches of kAutoExactMinGroup frames (the rule of a batch's
-    // same-geometry groups)
-    const int enc = default_webp_encoder();
-    if (fmt == IK_FORMAT_WEBP && (enc == IK_WEBP_EXACT || (enc == IK_WEBP_AUTO && max_batch >= kAutoExactMinGroup)))
+    // the rule of a batch's same-geometry groups, over max_batch frames (ik_post_plan.h)
+    if (fmt == IK_FORMAT_WEBP && webp_takes_exact(default_webp_encoder(), max_batch))
         return ik_pipeline_set_webp_encoder(p, IK_WEBP_EXACT);
     return IK_OK;
 }
@@ -344,13 +327,13 @@ int pipeline_create(uint32_t W, uint32_t H, uint32_t C, uint32_t nw, uint32_t nh
             IK_HIP(hipHostMalloc(&sl.h_aflag, sizeof(int) * max_batch, hipHostMallocDefault));
         }
     } else {
-        p->stage_bytes = (size_t)((nw + 7) / 8) * ((nh + 7) / 8) * 3 * 64 * sizeof(int16_t);
+        p->jgeom = jpeg_enc_geom(nw, nh);
+        p->stage_bytes = p->jgeom.coef_bytes;
         jpeg_quant_tables(p->quality, p->qt);
         jpeg_header((int)nw, (int)nh, p->qt, p->jpeg_hdr);
-        p->jcap = jpeg_enc_cap((int)nw, (int)nh);
-        IK_HIP(hipMalloc(&p->d_jwork, 2 * p->jcap * max_batch));
+        IK_HIP(hipMalloc(&p->d_jwork, p->jgeom.work_bytes * max_batch));
         for (auto& sl : p->slot) {
-            IK_HIP(hipHostMalloc(&sl.h_jpeg, p->jcap * max_batch, hipHostMallocDefault));
+            IK_HIP(hipHostMalloc(&sl.h_jpeg, p->jgeom.cap * max_batch, hipHostMallocDefault));
             IK_HIP(hipHostMalloc(&sl.h_jlen, sizeof(uint32_t) * max_batch, hipHostMallocDefault));
         }
         if (!device_consts(p->device)) return fail(IK_ERR_DEVICE, "cannot upload JPEG tables");

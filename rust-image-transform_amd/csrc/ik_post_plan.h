@@ -1,0 +1,210 @@
+// ik_post_plan.h -- the post stage's routing of a batch (ik_transform_batch): which
+// launch resizes each request and which coder writes its file.  Policy only, in sizes
+// and counts: plain C++17, no HIP, nothing read from the process (the caller passes the
+// WebP encoder setting and the mixed mode, each read once per batch).  The product's
+// executor (ik_host.cpp transform_post_phase) walks the plan; ik_post_plan exports it
+// for tests/test_post_plan.py.
+//
+// The rules:
+//   resize groups   requests whose decoded images share (W, H, C, pitch, device) and
+//                   whose targets (nw, nh) agree resize in one launch (resize_group),
+//                   when there are at least 2 of them.  Emitted in ascending key order,
+//                   members in request order.
+//   coder groups    inside a resize group, its WebP and its JPEG requests of one quality
+//                   (at least 2) are coded by one group call.  WebP groups first, then
+//                   JPEG, each in ascending quality.
+//   the exact rule  a WebP group goes to the exact GPU coder under IK_WEBP_EXACT, or
+//                   under IK_WEBP_AUTO from kAutoExactMinGroup (32) frames on
+//                   (webp_takes_exact); the rest to libwebp behind one colour launch.
+//   the mixed call  under IK_WEBP_MIXED_GPU (and an encoder other than LIBWEBP) a batch
+//                   with at least mixed_min 8-bit WebP requests -- kAutoMixedMin (32); 2
+//                   under EXACT -- keeps every WebP request that no exact group takes
+//                   for one mixed exact call.
+//
+// Kept as they are, odd as they look:
+//   - a request that needs no resize (w = h = None, or a target equal to its size)
+//     joins no group, so 32 of them never reach the uniform exact call: WebpMixed or Single
+//   - a WebP group with an output dimension above 16383 is routed Single: the per-image
+//     front end reports "WebP dimensions ... exceed 16383" for each of its requests
+//   - 16-bit images are never grouped and are never mixed candidates
+//   - the candidate count behind `mixed` includes requests an exact group then takes, so
+//     `mixed` can hold with fewer than mixed_min requests left for the mixed call: the
+//     executor counts the survivors again
+#pragma once
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <map>
+#include <tuple>
+#include <vector>
+
+#include "../../include/imagekit_hip.h"
+
+namespace ik {
+
+// IK_WEBP_AUTO: smallest same-geometry group of a batch, and smallest max_batch of a
+// pipeline (ik_pipeline.cpp), that the exact GPU coder takes
+constexpr size_t kAutoExactMinGroup = 32;
+// IK_WEBP_MIXED_GPU: fewest WebP requests of a batch that one mixed exact call takes
+// (provisional: the uniform rule's figure, until the two are measured against each
+// other -- profiles/webp_mixed_notes.md)
+constexpr size_t kAutoMixedMin = 32;
+constexpr uint32_t kWebpMaxDim = 16383;
+
+// whether a group, or a pipeline, of `count` same-geometry frames takes the exact GPU
+// coder under `encoder` (its chain of macroblock steps costs about the same for 2 frames
+// as for 64; a mixed-size stream's small groups code faster on the host threads:
+// configs[3]'s loadtest 2,106 vs 1,224 requests/s)
+inline bool webp_takes_exact(int encoder, size_t count) {
+    return encoder == IK_WEBP_EXACT || (encoder == IK_WEBP_AUTO && count >= kAutoExactMinGroup);
+}
+
+// The output size of src/transform.rs:62-90 + DynamicImage::resize for a W x H image
+// and the request's (w, h) options (negative = None; not both None).  0, or which limit
+// the request broke: 1 a dimension above u32, 2 the fitted size above u32
+inline uint32_t f32_as_u32(float v) {
+    if (!(v > 0.0f)) return 0;
+    if (v >= 4294967296.0f) return 0xFFFFFFFFu;
+    return (uint32_t)v;
+}
+inline int resize_target_dims(uint32_t W, uint32_t H, int64_t w, int64_t h, uint32_t* onw, uint32_t* onh) {
+    if (w > 0xFFFFFFFFll || h > 0xFFFFFFFFll) return 1;
+    uint32_t tw, th;
+    if (w >= 0) tw = (uint32_t)w;
+    else tw = f32_as_u32(roundf((float)W * ((float)(uint32_t)h / (float)H)));
+    if (h >= 0) th = (uint32_t)h;
+    else th = f32_as_u32(roundf((float)H * ((float)(uint32_t)w / (float)W)));
+    if (tw < 1) tw = 1;
+    if (th < 1) th = 1;
+    uint32_t nw = tw, nh = th;
+    if (!(tw == W && th == H)) {
+        const double wr = (double)tw / (double)W, hr = (double)th / (double)H;
+        const double r = wr < hr ? wr : hr;
+        double fw = std::round((double)W * r), fh = std::round((double)H * r);
+        unsigned long long rw = fw < 1 ? 1 : (unsigned long long)fw;
+        unsigned long long rh = fh < 1 ? 1 : (unsigned long long)fh;
+        if (rw > 0xFFFFFFFFull || rh > 0xFFFFFFFFull) return 2;
+        nw = (uint32_t)rw; nh = (uint32_t)rh;
+    }
+    *onw = nw;
+    *onh = nh;
+    return 0;
+}
+
+enum class PostRoute : int {  // (ik_post_route, as ik_post_plan reports it)
+    None = IK_POST_NONE,                       // the decode failed: its status is the request's
+    Single = IK_POST_SINGLE,                   // the per-image ik_resize and / or encode_image_front
+    WebpMixed = IK_POST_WEBP_MIXED,            // its resized image is kept for the batch's one mixed exact call
+    WebpFrontGroup = IK_POST_WEBP_FRONT_GROUP, // its coder group goes to webp_front_group (libwebp codes the planes)
+    WebpExactGroup = IK_POST_WEBP_EXACT_GROUP, // its coder group goes to webp_exact_group
+    JpegGroup = IK_POST_JPEG_GROUP,            // its coder group goes to jpeg_front_group
+};
+
+struct PostRequest {
+    bool ok = false;  // decode status 0 and a non-null image
+    uint32_t W = 0, H = 0, C = 0;
+    size_t pitch = 0;
+    int device = 0;
+    uint32_t depth = 1;
+    int64_t w = -1, h = -1;  // negative: None
+    int fmt = 0, quality = 0;
+};
+
+struct PostPlan {
+    struct Req {
+        bool sized = false;    // (nw, nh) is the size its encoder sees (false: the decode or resize_target failed)
+        uint32_t nw = 0, nh = 0;
+        int rgroup = -1, cgroup = -1;
+        PostRoute route = PostRoute::None;
+        // its route when no group call takes it (it is in no coder group, or its group's
+        // resize or coder call failed at run time): Single or WebpMixed
+        PostRoute solo = PostRoute::None;
+    };
+    struct ResizeGroup {
+        uint32_t nw = 0, nh = 0;
+        std::vector<uint32_t> members;  // request order
+        uint32_t cg_lo = 0, cg_hi = 0;  // its coder groups: cgroups[cg_lo, cg_hi)
+    };
+    struct CoderGroup {
+        PostRoute route = PostRoute::None;
+        int quality = 0;
+        int rgroup = -1;
+        std::vector<uint32_t> members;
+    };
+    bool mixed = false;
+    size_t mixed_min = kAutoMixedMin;
+    std::vector<Req> req;
+    std::vector<ResizeGroup> rgroups;
+    std::vector<CoderGroup> cgroups;
+};
+
+inline PostPlan post_plan(const PostRequest* rq, uint32_t m, int webp_encoder, int mixed_mode) {
+    PostPlan P;
+    P.req.resize(m);
+    if (webp_encoder == IK_WEBP_EXACT) P.mixed_min = 2;  // any two, as EXACT's uniform groups
+    if (mixed_mode == IK_WEBP_MIXED_GPU && webp_encoder != IK_WEBP_LIBWEBP) {
+        size_t cand = 0;  // (counted before the exact groups take theirs: see above)
+        for (uint32_t k = 0; k < m; ++k) cand += rq[k].ok && rq[k].depth == 1 && rq[k].fmt == IK_FORMAT_WEBP;
+        P.mixed = cand >= P.mixed_min;
+    }
+    std::map<std::tuple<uint32_t, uint32_t, uint32_t, size_t, int, uint32_t, uint32_t>, std::vector<uint32_t>> groups;
+    for (uint32_t k = 0; k < m; ++k) {
+        const PostRequest& r = rq[k];
+        PostPlan::Req& q = P.req[k];
+        if (!r.ok) continue;
+        q.route = q.solo = PostRoute::Single;
+        if (r.w < 0 && r.h < 0) {  // no resize asked for
+            q.sized = true;
+            q.nw = r.W;
+            q.nh = r.H;
+        } else {
+            q.sized = resize_target_dims(r.W, r.H, r.w, r.h, &q.nw, &q.nh) == 0;
+        }
+        if (!q.sized) continue;  // Single: ik_resize reports it
+        if (P.mixed && r.fmt == IK_FORMAT_WEBP && r.depth == 1 && q.nw >= 1 && q.nh >= 1 && q.nw <= kWebpMaxDim &&
+            q.nh <= kWebpMaxDim)
+            q.route = q.solo = PostRoute::WebpMixed;
+        if (r.depth == 1 && !(q.nw == r.W && q.nh == r.H))  // (never a request that needs no resize)
+            groups[std::make_tuple(r.W, r.H, r.C, r.pitch, r.device, q.nw, q.nh)].push_back(k);
+    }
+    for (auto& kv : groups) {
+        if (kv.second.size() < 2) continue;
+        const int g = (int)P.rgroups.size();
+        PostPlan::ResizeGroup G;
+        G.nw = std::get<5>(kv.first);
+        G.nh = std::get<6>(kv.first);
+        G.cg_lo = (uint32_t)P.cgroups.size();
+        std::map<int, std::vector<uint32_t>> byq, jbyq;
+        for (uint32_t k : kv.second) {
+            P.req[k].rgroup = g;
+            if (rq[k].fmt == IK_FORMAT_WEBP) byq[rq[k].quality].push_back(k);
+            if (rq[k].fmt == IK_FORMAT_JPEG) jbyq[rq[k].quality].push_back(k);
+        }
+        auto emit = [&](PostRoute route, int quality, std::vector<uint32_t>& members) {
+            for (uint32_t k : members) {
+                P.req[k].cgroup = (int)P.cgroups.size();
+                P.req[k].route = route;
+            }
+            PostPlan::CoderGroup cg;
+            cg.route = route;
+            cg.quality = quality;
+            cg.rgroup = g;
+            cg.members.swap(members);
+            P.cgroups.push_back(std::move(cg));
+        };
+        for (auto& qv : byq) {
+            if (qv.second.size() < 2) continue;
+            if (G.nw > kWebpMaxDim || G.nh > kWebpMaxDim) continue;  // Single, for the per-image error
+            if (webp_takes_exact(webp_encoder, qv.second.size())) emit(PostRoute::WebpExactGroup, qv.first, qv.second);
+            else if (!P.mixed) emit(PostRoute::WebpFrontGroup, qv.first, qv.second);
+        }
+        for (auto& qv : jbyq)
+            if (qv.second.size() >= 2) emit(PostRoute::JpegGroup, qv.first, qv.second);
+        G.cg_hi = (uint32_t)P.cgroups.size();
+        G.members.swap(kv.second);
+        P.rgroups.push_back(std::move(G));
+    }
+    return P;
+}
+
+}  // namespace ik

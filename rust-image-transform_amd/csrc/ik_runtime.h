@@ -13,6 +13,7 @@
 #include <unordered_map>
 
 #include "ik_internal.h"
+#include "ik_post_plan.h"
 
 struct ik_image {
     uint32_t w = 0, h = 0, c = 0;  // c interleaved channels
@@ -112,6 +113,12 @@ struct EvPair {
 };
 EvPair& thread_events(int which);  // which < 4
 float ev_pair_ms(const EvPair& e);
+// Who owns which pair (2 and 3: the JPEG and WebP decoders').  kEvResize times
+// resize_group's launch and, on a submitting caller's thread, the JPEG marker walk
+// (ik_transform_batch_submit_device): each reads its pair right after the stream
+// synchronisation that follows its launch, so neither finds the other's events
+// pending.  kEvJpegGroup times jpeg_front_group's launches.
+constexpr int kEvResize = 0, kEvJpegWalk = kEvResize, kEvJpegGroup = 1;
 
 // A scope in which batch_timing_add records (the decode and post stages of a
 // batch set it on their thread); work outside one -- a single-image ik_decode, a
@@ -198,6 +205,26 @@ uint8_t* scratch(size_t bytes);  // per-thread device scratch, valid until the n
 // batch decode, slot 2: PNG batch decode); valid until the next call with that slot
 uint8_t* scratch_slot(int slot, size_t bytes);
 uint8_t* pinned_slot(int slot, size_t bytes);  // per-thread grow-only pinned host arenas (slots 0..11)
+// Who owns which arena.  Device slots 1, 2, 5 and pinned slots 1, 2, 3, 6 are the JPEG and
+// PNG decoders' (ik_jpeg_decode.cpp, ik_png_decode.cpp).
+// scratch(): the single-image calls' work area, valid until the thread's next scratch()
+constexpr int kScratchDefault = 0;
+// copy_h2d_2d / copy_d2h_2d's staging; each copy synchronises the stream before it returns
+constexpr int kPinnedStaging = 0;
+// a group launch's table of image base pointers, webp_front_group's and resize_group's:
+// both run on one thread and synchronise the stream after the launch that reads the table
+constexpr int kScratchPtrTable = 3;
+// jpeg_front_group's device work area: quantisation tables, source table, coefficients, Huffman work
+constexpr int kScratchJpegGroup = 4;
+// encode_device_front's WebP planes, written by the colour kernel; the stream is
+// synchronised before the planes are copied out
+constexpr int kPinnedWebpPlanes = 4;
+// jpeg_front_group's streams, lengths and table staging, and resize_group's pointer-table
+// staging: both run on one thread and synchronise the stream before they write the area
+constexpr int kPinnedGroupStage = 5;
+// ik_transform_batch_submit_device's file heads and JPEG marker-walk records (the caller's
+// thread; synchronised before they are read)
+constexpr int kPinnedDeviceHeads = 7;
 // the exact WebP coder's arenas: its device work area; its constants in, its records out
 constexpr int kScratchExact = 8, kPinnedExactIn = 8, kPinnedExactOut = 9;
 // the mixed exact call's: same-geometry planes gathered a common stride apart; a batch's
@@ -237,13 +264,8 @@ void jpeg_enc_count(bool gpu_coded);
 // otherwise (ik_webp_gpu.cpp)
 constexpr int kDefaultWebpEncoder = IK_WEBP_AUTO;
 int default_webp_encoder();
-// IK_WEBP_AUTO: smallest same-geometry group (ik_host.cpp), and smallest max_batch of a
-// pipeline (ik_pipeline.cpp), that the exact GPU coder takes
-constexpr size_t kAutoExactMinGroup = 32;
-// IK_WEBP_MIXED_GPU: fewest WebP requests outside those groups that one mixed exact call
-// takes (provisional: the uniform rule's figure, until the two are measured against each
-// other -- profiles/webp_mixed_notes.md)
-constexpr size_t kAutoMixedMin = 32;
+// IK_WEBP_AUTO's and IK_WEBP_MIXED_GPU's thresholds (kAutoExactMinGroup, kAutoMixedMin)
+// and the rule that applies them (webp_takes_exact): ik_post_plan.h
 // encode_image's quality range, and the bytes of a w x h image's YUV420 planes
 inline int clamp_quality(int q) { return q < 1 ? 1 : (q > 100 ? 100 : q); }
 inline size_t yuv420_bytes(size_t w, size_t h) { return w * h + 2 * ((w + 1) / 2) * ((h + 1) / 2); }
@@ -421,9 +443,26 @@ int encode_device_front(const uint8_t* dev, uint32_t w, uint32_t h, uint32_t c, 
                         EncodePrep& p, std::vector<uint8_t>& out);
 int encode_image_front(const ik_image* img, int fmt, int quality, EncodePrep& p, std::vector<uint8_t>& out);
 int encode_host_back(EncodePrep& p, std::vector<uint8_t>& out);
+// A finished JPEG file in out: hdr (SOI .. SOS), len entropy-coded bytes, EOI.  The
+// bytes are copied from `stream`, or, when it is null, left for the caller to fill
+// (a copy from device memory); returns where they lie in out
+uint8_t* jpeg_file(const std::vector<uint8_t>& hdr, const uint8_t* stream, uint32_t len, std::vector<uint8_t>& out);
+// The post stage's group calls (ik_encode.cpp), each over n same-geometry 8-bit images
+// on one device; a return other than IK_OK leaves every image to the per-image path.
+// webp_exact_group: the exact coder's files (outs[i]) for one quality.
+// webp_exact_mixed_group: the same over images of any sizes and qualities.
+// webp_front_group: the YUV420 planes libwebp codes, in pinned memory (prep[i]).
+// jpeg_front_group: the finished JPEG files (out[i]).
+int webp_exact_group(const std::vector<ik_image*>& imgs, int quality, std::vector<std::vector<uint8_t>*>& outs);
+int webp_exact_mixed_group(const std::vector<ik_image*>& imgs, const std::vector<int>& quality,
+                           std::vector<std::vector<uint8_t>*>& outs);
+int webp_front_group(const std::vector<ik_image*>& imgs, int quality, std::vector<EncodePrep*>& prep);
+int jpeg_front_group(const std::vector<ik_image*>& imgs, int quality, std::vector<std::vector<uint8_t>*>& out);
+void encode_shutdown();  // ik_shutdown: their pinned blocks, the per-device constant tables
 
-// resize_image's output size (src/transform.rs:62-90 + DynamicImage::resize) and
-// a one-launch resize of same-geometry 8-bit images (ik_host.cpp)
+// resize_image's output size (src/transform.rs:62-90 + DynamicImage::resize; its
+// arithmetic: ik_post_plan.h) and a one-launch resize of same-geometry 8-bit images
+// (ik_encode.cpp)
 int resize_target(uint32_t W, uint32_t H, int64_t w, int64_t h, uint32_t* nw, uint32_t* nh);
 int resize_group(const std::vector<ik_image*>& src, uint32_t nw, uint32_t nh, int filter, std::vector<ik_image*>& out);
 
