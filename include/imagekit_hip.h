@@ -100,6 +100,32 @@ int ik_post_plan(uint32_t m, const int *ok, const uint32_t *W, const uint32_t *H
                  const uint64_t *pitch, const int *device, const uint32_t *depth, const int64_t *w, const int64_t *h,
                  const int *fmt, const int *quality, int webp_encoder, int mixed_mode, uint32_t *nw, uint32_t *nh,
                  int *resize_group, int *coder_group, int *route, uint32_t *info);
+/* How a request's (w, h) becomes pixels (the reference's query parser declares
+ * fit=cover|contain, src/transform/params.rs:37-64).  With (tw, th) the request's target
+ * -- a missing side computed in f32 with round, each side at least 1:
+ *   IK_FIT_CONTAIN  DynamicImage::resize: the largest size of the image's aspect inside
+ *                   tw x th (resize_image, src/transform.rs:62-90; ik_resize)
+ *   IK_FIT_COVER    DynamicImage::resize_to_fill: the smallest size of the image's aspect
+ *                   that covers tw x th -- resize_dimensions(fill), f64 ratio max(tw/W,
+ *                   th/H), round, at least 1 -- resampled as ik_resize_exact does and
+ *                   cropped to tw x th, centred ((iw - tw) / 2 or (ih - th) / 2, integer
+ *                   division) along the axis that overflows.  With one of w / h None there
+ *                   is nothing to crop: IK_FIT_CONTAIN.  (image 0.25.8 as recalled; parity
+ *                   unpinned)
+ *   IK_FIT_EXACT    DynamicImage::resize_exact: tw x th, the aspect not kept
+ * Only the kept columns and rows are computed: a cover launch reads the source columns
+ * and rows its window needs and writes nw x nh pixels. */
+typedef enum { IK_FIT_CONTAIN = 0, IK_FIT_COVER = 1, IK_FIT_EXACT = 2 } ik_fit;
+/* ik_post_plan with a fit mode per request (fit NULL: every request IK_FIT_CONTAIN, which
+ * is ik_post_plan).  Resize groups share the whole window, so an exact and a cover request
+ * of one output size are different groups.  window (may be NULL): six values per request,
+ * iw, ih, x0, y0, nw, nh -- it is coded at columns [x0, x0 + nw), rows [y0, y0 + nh) of its
+ * image resampled to iw x ih; zeros when that cannot be computed. */
+int ik_post_plan_fit(uint32_t m, const int *ok, const uint32_t *W, const uint32_t *H, const uint32_t *C,
+                     const uint64_t *pitch, const int *device, const uint32_t *depth, const int64_t *w,
+                     const int64_t *h, const int *fit, const int *fmt, const int *quality, int webp_encoder,
+                     int mixed_mode, uint32_t *nw, uint32_t *nh, int *resize_group, int *coder_group, int *route,
+                     uint32_t *info, uint32_t *window);
 /* Orderly teardown: waits for every submitted batch, ends
  * the library's stage threads and worker pools (each releases its HIP streams
  * and arenas), then frees the pooled images, upload areas, resize plans and
@@ -331,6 +357,12 @@ int ik_jpeg_walk_host(const uint8_t *bytes, size_t len, uint8_t *skeleton, size_
  * the Rust shim drops its by-value argument).  filter: IK_FILTER_* (Lanczos3 in
  * the reference). */
 int ik_resize(ik_image *img, int64_t w, int64_t h, int filter, ik_image **out);
+/* The window a W x H image's request (w, h; negative = None, not both) computes under
+ * `fit` (ik_fit): out[6] = iw, ih, x0, y0, nw, nh.  Needs no device.  IK_OK, or
+ * IK_ERR_INVALID: a dimension, or the fitted / covering size, above u32 (as ik_resize). */
+int ik_fit_target(uint32_t W, uint32_t H, int64_t w, int64_t h, int fit, uint32_t *out);
+/* ik_resize under a fit mode (ik_fit); IK_FIT_CONTAIN is ik_resize.  8- and 16-bit images. */
+int ik_resize_fit(ik_image *img, int64_t w, int64_t h, int fit, int filter, ik_image **out);
 
 /* Resampler arithmetic.  IK_RESIZE_EXACT (default): image 0.25.8's f32 sequence,
  * separately rounded multiply and add per tap -- bit-exact.  IK_RESIZE_FMA: one
@@ -360,6 +392,10 @@ const char *ik_resize_kernel_name(uint32_t W, uint32_t H, uint32_t C, uint32_t n
 #define IK_RESIZE_PLAN_INFO_LEN 13
 int ik_resize_plan_info(uint32_t W, uint32_t H, uint32_t C, uint32_t nw, uint32_t nh, int filter, uint32_t n,
                         int32_t *out, int cap);
+/* The same values for the launch that computes columns [x0, x0 + nw) and rows
+ * [y0, y0 + nh) of the image resampled to iw x ih (ik_resize_window). */
+int ik_resize_plan_info_window(uint32_t W, uint32_t H, uint32_t C, uint32_t iw, uint32_t ih, uint32_t x0, uint32_t y0,
+                               uint32_t nw, uint32_t nh, int filter, uint32_t n, int32_t *out, int cap);
 
 /* JPEG reconstruction behind decode_image (src/transform.rs:31 -> image 0.25.8
  * -> zune-jpeg 0.4.21, Cargo.lock:3106).  IK_JPEG_RECON_ZUNE (default): zune-jpeg's
@@ -374,6 +410,13 @@ int ik_get_jpeg_reconstruction(void);
 
 /* imageops::resize to exact dimensions (the resampler under resize_image) */
 int ik_resize_exact(const ik_image *img, uint32_t nw, uint32_t nh, int filter, ik_image **out);
+/* Columns [x0, x0 + nw) and rows [y0, y0 + nh) of ik_resize_exact(img, iw, ih): the same
+ * pixels as resizing and then cropping, computed from the window's own weight-table rows
+ * and the source columns and rows they read (the primitive under IK_FIT_COVER).  iw x ih
+ * equal to the image's size copies the window, as ik_resize_exact copies the image.  A
+ * window that is empty or not inside iw x ih: IK_ERR_INVALID. */
+int ik_resize_window(const ik_image *img, uint32_t iw, uint32_t ih, uint32_t x0, uint32_t y0, uint32_t nw,
+                     uint32_t nh, int filter, ik_image **out);
 
 /* encode_image (src/transform.rs:113-150): quality clamped to [1,100].
  * *out is allocated by the library; release with ik_buf_free. */
@@ -407,6 +450,9 @@ int ik_get_webp_encoder(void);
 /* decode -> resize_image -> encode_image in one call (handler src/lib.rs:175-191) */
 int ik_transform(const uint8_t *bytes, size_t len, int64_t w, int64_t h, int fmt, int quality,
                  int filter, uint8_t **out, size_t *out_len);
+/* ik_transform under a fit mode (ik_fit; IK_FIT_CONTAIN is ik_transform) */
+int ik_transform_fit(const uint8_t *bytes, size_t len, int64_t w, int64_t h, int fit, int fmt, int quality,
+                     int filter, uint8_t **out, size_t *out_len);
 
 /* ik_transform over n requests at once (the /img handler under load, loadtest C4
  * mix): decode_image (one set of GPU launches for the batch's PNG streams, one set
@@ -440,6 +486,15 @@ int ik_transform_batch_submit(const uint8_t *const *bytes, const size_t *lens, u
                               const int64_t *h, const int *fmt, const int *quality, int filter, int threads,
                               uint8_t **outs, size_t *out_lens, int *status, uint64_t *ticket);
 int ik_transform_batch_wait(uint64_t ticket);
+/* ik_transform_batch / ik_transform_batch_submit with a fit mode (ik_fit) per request;
+ * fit NULL, or all IK_FIT_CONTAIN, is the call without it.  Requests resize in one launch
+ * when their whole windows agree.  Wait with ik_transform_batch_wait. */
+int ik_transform_batch_fit(const uint8_t *const *bytes, const size_t *lens, uint32_t n, const int64_t *w,
+                           const int64_t *h, const int *fit, const int *fmt, const int *quality, int filter,
+                           int threads, uint8_t **outs, size_t *out_lens, int *status);
+int ik_transform_batch_submit_fit(const uint8_t *const *bytes, const size_t *lens, uint32_t n, const int64_t *w,
+                                  const int64_t *h, const int *fit, const int *fmt, const int *quality, int filter,
+                                  int threads, uint8_t **outs, size_t *out_lens, int *status, uint64_t *ticket);
 
 /* ik_transform_batch_submit over request bodies already in device memory (HBM)
  * of one device: dev_bytes[i] are device addresses (hipMalloc / ik_dev_alloc),
@@ -505,6 +560,14 @@ int ik_resize_batch_device(const uint8_t *dev_src, uint32_t W, uint32_t H, uint3
                            size_t src_pitch, size_t src_image_stride, uint32_t n, uint32_t nw,
                            uint32_t nh, int filter, uint8_t *dev_dst, size_t dst_pitch,
                            size_t dst_image_stride, void *hip_stream);
+/* ik_resize_batch_device over a window: image i's columns [x0, x0 + nw) and rows
+ * [y0, y0 + nh) of its resize to iw x ih, written as nw x nh pixels at dev_dst +
+ * i*dst_image_stride.  Nothing outside those nw*C bytes of nh rows is written, and no
+ * source byte is read past the image's last row. */
+int ik_resize_window_batch_device(const uint8_t *dev_src, uint32_t W, uint32_t H, uint32_t C, size_t src_pitch,
+                                  size_t src_image_stride, uint32_t n, uint32_t iw, uint32_t ih, uint32_t x0,
+                                  uint32_t y0, uint32_t nw, uint32_t nh, int filter, uint8_t *dev_dst,
+                                  size_t dst_pitch, size_t dst_image_stride, void *hip_stream);
 /* the WebP colour conversion (to_rgb8 + libwebp RGB->YUV420) on the device;
  * dev_yuv receives the Y (w*h), U and V ((w+1)/2 * (h+1)/2) planes back to back */
 int ik_webp_yuv420_device(const uint8_t *dev_src, uint32_t w, uint32_t h, uint32_t C,

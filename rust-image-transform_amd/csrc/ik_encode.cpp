@@ -459,17 +459,19 @@ int jpeg_front_group(const std::vector<ik_image*>& imgs, int quality, std::vecto
 
 // imageops::resize over n 8-bit images of one geometry (same W, H, C, pitch) in
 // ONE fused launch: the kernel reads each image's base pointer from a table, so
-// the images may sit anywhere.  Same arithmetic as ik_resize_exact, per image.
+// the images may sit anywhere.  Same arithmetic as ik_resize_window, per image.
 // Returns IK_ERR_UNSUPPORTED (nothing allocated) when the geometry needs the
 // two-kernel fallback; the caller then resizes image by image.
-int resize_group(const std::vector<ik_image*>& src, uint32_t nw, uint32_t nh, int filter, std::vector<ik_image*>& out) {
+int resize_group(const std::vector<ik_image*>& src, const FitWindow& win, int filter, std::vector<ik_image*>& out) {
     const size_t n = src.size();
+    const uint32_t nw = win.nw, nh = win.nh;
     out.assign(n, nullptr);
     if (!n) return IK_OK;
     const ik_image* s0 = src[0];
     DeviceGuard g(s0->device);
-    ResizePlan* plan = get_resize_plan(current_device(), (int)s0->w, (int)s0->h, (int)s0->c, (int)nw, (int)nh, filter,
-                                       (int)n);
+    if (!resize_window_ok(win.iw, win.ih, win.x0, win.y0, win.nw, win.nh)) return IK_ERR_UNSUPPORTED;
+    ResizePlan* plan = get_resize_plan_window(current_device(), (int)s0->w, (int)s0->h, (int)s0->c, (int)win.iw,
+                                              (int)win.ih, (int)win.x0, (int)win.y0, (int)nw, (int)nh, filter, (int)n);
     if (!plan) return fail(IK_ERR_DEVICE, "cannot build resize plan");
     if (plan->slots == 0 || !resize_fused_fits(s0->pitch, s0->h) || (s0->pitch & 7)) return IK_ERR_UNSUPPORTED;
     std::vector<uint64_t> tab(2 * n);

@@ -649,6 +649,15 @@ int ik_post_plan(uint32_t m, const int* ok, const uint32_t* W, const uint32_t* H
                  const uint64_t* pitch, const int* device, const uint32_t* depth, const int64_t* w, const int64_t* h,
                  const int* fmt, const int* quality, int webp_encoder, int mixed_mode, uint32_t* nw, uint32_t* nh,
                  int* resize_group, int* coder_group, int* route, uint32_t* info) {
+    return ik_post_plan_fit(m, ok, W, H, C, pitch, device, depth, w, h, nullptr, fmt, quality, webp_encoder, mixed_mode,
+                            nw, nh, resize_group, coder_group, route, info, nullptr);
+}
+
+int ik_post_plan_fit(uint32_t m, const int* ok, const uint32_t* W, const uint32_t* H, const uint32_t* C,
+                     const uint64_t* pitch, const int* device, const uint32_t* depth, const int64_t* w,
+                     const int64_t* h, const int* fit, const int* fmt, const int* quality, int webp_encoder,
+                     int mixed_mode, uint32_t* nw, uint32_t* nh, int* resize_group, int* coder_group, int* route,
+                     uint32_t* info, uint32_t* window) {
     if (!ok || !W || !H || !C || !pitch || !device || !depth || !w || !h || !fmt || !quality || !nw || !nh ||
         !resize_group || !coder_group || !route || !info)
         return fail(IK_ERR_INVALID, "null pointer");
@@ -658,6 +667,10 @@ int ik_post_plan(uint32_t m, const int* ok, const uint32_t* W, const uint32_t* H
         rq[k].W = W[k]; rq[k].H = H[k]; rq[k].C = C[k];
         rq[k].pitch = (size_t)pitch[k]; rq[k].device = device[k]; rq[k].depth = depth[k];
         rq[k].w = w[k]; rq[k].h = h[k]; rq[k].fmt = fmt[k]; rq[k].quality = quality[k];
+        if (fit) {
+            if (fit[k] < IK_FIT_CONTAIN || fit[k] > IK_FIT_EXACT) return fail(IK_ERR_INVALID, "unknown fit %d", fit[k]);
+            rq[k].fit = fit[k];
+        }
     }
     const PostPlan P = post_plan(rq.data(), m, webp_encoder, mixed_mode);
     for (uint32_t k = 0; k < m; ++k) {
@@ -667,6 +680,11 @@ int ik_post_plan(uint32_t m, const int* ok, const uint32_t* W, const uint32_t* H
         resize_group[k] = q.rgroup;
         coder_group[k] = q.cgroup;
         route[k] = (int)q.route;
+        if (window) {
+            const FitWindow f = q.sized ? q.win : FitWindow();
+            const uint32_t v[6] = {f.iw, f.ih, f.x0, f.y0, f.nw, f.nh};
+            std::copy(v, v + 6, window + 6 * (size_t)k);
+        }
     }
     info[0] = P.mixed;
     info[1] = (uint32_t)P.mixed_min;
@@ -780,9 +798,21 @@ void ik_buf_free(uint8_t* buf) { free(buf); }
 // imageops::resize(image, nw, nh, filter)
 int ik_resize_exact(const ik_image* img, uint32_t nw, uint32_t nh, int filter, ik_image** out) {
     IK_API_ENTER();
+    if (nw == 0 || nh == 0) return fail(IK_ERR_INVALID, "zero output dimension");
+    return ik_resize_window(img, nw, nh, 0, 0, nw, nh, filter, out);
+}
+
+// imageops::resize(image, iw, ih, filter) cropped to (x0, y0, nw, nh): only the window
+// is computed
+int ik_resize_window(const ik_image* img, uint32_t iw, uint32_t ih, uint32_t x0, uint32_t y0, uint32_t nw,
+                     uint32_t nh, int filter, ik_image** out) {
+    IK_API_ENTER();
     if (!img || !out) return fail(IK_ERR_INVALID, "null pointer");
     if (filter < 0 || filter > 4) return fail(IK_ERR_INVALID, "unknown filter %d", filter);
     if (nw == 0 || nh == 0) return fail(IK_ERR_INVALID, "zero output dimension");
+    if ((uint64_t)x0 + nw > iw || (uint64_t)y0 + nh > ih)
+        return fail(IK_ERR_INVALID, "window %ux%u at (%u, %u) outside %ux%u", nw, nh, x0, y0, iw, ih);
+    if (iw > 0x7FFFFFFFu || ih > 0x7FFFFFFFu) return fail(IK_ERR_INVALID, "dimension overflow");
     DeviceGuard g(img->device);
     ik_image* o = nullptr;
     int st = alloc_image(nw, nh, img->c, &o, img->depth);
@@ -796,8 +826,9 @@ int ik_resize_exact(const ik_image* img, uint32_t nw, uint32_t nh, int filter, i
         *out = o;
         return IK_OK;
     }
-    if (nw == img->w && nh == img->h) {  // copy instead of resampling
-        hipError_t e = hipMemcpy2DAsync(o->d, o->pitch, img->d, img->pitch, orow, nh, hipMemcpyDeviceToDevice, s);
+    if (iw == img->w && ih == img->h) {  // copy instead of resampling
+        const uint8_t* from = img->d + (size_t)y0 * img->pitch + (size_t)x0 * img->c * img->depth;
+        hipError_t e = hipMemcpy2DAsync(o->d, o->pitch, from, img->pitch, orow, nh, hipMemcpyDeviceToDevice, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) { ik_image_free(o); return hip_fail(e, "copy image"); }
         *out = o;
@@ -805,17 +836,17 @@ int ik_resize_exact(const ik_image* img, uint32_t nw, uint32_t nh, int filter, i
     }
     int rc;
     if (img->depth == 2) {  // 16-bit: the two-pass path over u16 samples
-        ResizePlan* plan = get_resize_plan(current_device(), (int)img->w, (int)img->h, (int)img->c, (int)nw, (int)nh,
-                                           filter, 1);
-        float* tmp = plan ? (float*)scratch(sizeof(float) * (size_t)nh * img->w * img->c) : nullptr;
+        ResizePlan* plan = get_resize_plan_window(current_device(), (int)img->w, (int)img->h, (int)img->c, (int)iw,
+                                                  (int)ih, (int)x0, (int)y0, (int)nw, (int)nh, filter, 1);
+        float* tmp = plan ? (float*)scratch(sizeof(float) * (size_t)nh * plan->args.tmp_span) : nullptr;
         if (!plan || !tmp) rc = fail(IK_ERR_DEVICE, "cannot set up the 16-bit resize");
         else {
             hipError_t e = launch_resize16(*plan, img->d, img->pitch, o->d, o->pitch, tmp, s);
             rc = e == hipSuccess ? IK_OK : hip_fail(e, "resize (16-bit)");
         }
     } else {
-        rc = ik_resize_batch_device(img->d, img->w, img->h, img->c, img->pitch, 0, 1, nw, nh, filter,
-                                    o->d, o->pitch, 0, s);
+        rc = ik_resize_window_batch_device(img->d, img->w, img->h, img->c, img->pitch, 0, 1, iw, ih, x0, y0, nw, nh,
+                                           filter, o->d, o->pitch, 0, s);
     }
     if (rc == IK_OK) {
         hipError_t e = hipStreamSynchronize(s);
@@ -850,12 +881,34 @@ extern "C" {
 // f64, round, max 1) -> imageops::resize.
 int ik_resize(ik_image* img, int64_t w, int64_t h, int filter, ik_image** out) {
     IK_API_ENTER();
+    return ik_resize_fit(img, w, h, IK_FIT_CONTAIN, filter, out);
+}
+
+int ik_fit_target(uint32_t W, uint32_t H, int64_t w, int64_t h, int fit, uint32_t* out) {
+    if (!out) return fail(IK_ERR_INVALID, "null pointer");
+    if (fit < IK_FIT_CONTAIN || fit > IK_FIT_EXACT) return fail(IK_ERR_INVALID, "unknown fit %d", fit);
+    if (w < 0 && h < 0) return fail(IK_ERR_INVALID, "no target: w and h are both None");
+    FitWindow f;
+    switch (fit_target(W, H, w, h, fit, &f)) {
+        case 0: break;
+        case 1: return fail(IK_ERR_INVALID, "dimension exceeds u32");
+        default: return fail(IK_ERR_INVALID, "dimension overflow");
+    }
+    out[0] = f.iw; out[1] = f.ih; out[2] = f.x0; out[3] = f.y0; out[4] = f.nw; out[5] = f.nh;
+    return IK_OK;
+}
+
+// resize_image under a fit mode: CONTAIN is src/transform.rs:62-90 as above; COVER is
+// DynamicImage::resize_to_fill and EXACT DynamicImage::resize_exact on the same target
+int ik_resize_fit(ik_image* img, int64_t w, int64_t h, int fit, int filter, ik_image** out) {
+    IK_API_ENTER();
     if (!img || !out) return fail(IK_ERR_INVALID, "null pointer");
+    if (fit < IK_FIT_CONTAIN || fit > IK_FIT_EXACT) return fail(IK_ERR_INVALID, "unknown fit %d", fit);
     if (w < 0 && h < 0) { *out = img; return IK_OK; }
-    uint32_t nw, nh;
-    const int st = resize_target(img->w, img->h, w, h, &nw, &nh);
+    uint32_t f[6];
+    const int st = ik_fit_target(img->w, img->h, w, h, fit, f);
     if (st) return st;
-    return ik_resize_exact(img, nw, nh, filter, out);
+    return ik_resize_window(img, f[0], f[1], f[2], f[3], f[4], f[5], filter, out);
 }
 
 int ik_encode(const ik_image* img, int fmt, int quality, uint8_t** out, size_t* out_len) {
@@ -1188,8 +1241,8 @@ static void transform_decode_phase(const uint8_t* const* bytes, const size_t* le
 // Device half, post stage: resize, the encoders' device front ends (under the
 // post gate, so a batch's resize runs beside the next batch's decode kernels);
 // request i's status / message land in st[i] / errs[i]
-static void transform_post_phase(const int64_t* w, const int64_t* h, const int* fmt, const int* quality, int filter,
-                                 int* st, std::string* errs, HostPhase& hp) {
+static void transform_post_phase(const int64_t* w, const int64_t* h, const int* fit, const int* fmt, const int* quality,
+                                 int filter, int* st, std::string* errs, HostPhase& hp) {
     const std::vector<uint32_t>& idx = hp.idx;
     const int threads = hp.threads;
     const uint32_t m = (uint32_t)idx.size();
@@ -1221,6 +1274,7 @@ static void transform_post_phase(const int64_t* w, const int64_t* h, const int* 
             rq[k].pitch = im->pitch; rq[k].device = im->device; rq[k].depth = im->depth;
         }
         rq[k].w = w[i]; rq[k].h = h[i]; rq[k].fmt = fmt[i]; rq[k].quality = quality[i];
+        if (fit) rq[k].fit = fit[i];  // (null: every request IK_FIT_CONTAIN)
     }
     const PostPlan plan = post_plan(rq.data(), m, default_webp_encoder(), webp_mixed_mode());
     std::vector<ik_image*> rsz(m, nullptr);   // resized by its group's launch
@@ -1230,7 +1284,7 @@ static void transform_post_phase(const int64_t* w, const int64_t* h, const int* 
     for (const PostPlan::ResizeGroup& G : plan.rgroups) {
         std::vector<ik_image*> src, out;
         for (uint32_t k : G.members) src.push_back(imgs[k]);
-        if (resize_group(src, G.nw, G.nh, filter, out) != IK_OK) continue;  // its members: image by image below
+        if (resize_group(src, G.win, filter, out) != IK_OK) continue;  // its members: image by image below
         for (size_t j = 0; j < out.size(); ++j) rsz[G.members[j]] = out[j];
         for (uint32_t c = G.cg_lo; c < G.cg_hi; ++c) {
             const PostPlan::CoderGroup& cg = plan.cgroups[c];
@@ -1257,7 +1311,7 @@ static void transform_post_phase(const int64_t* w, const int64_t* h, const int* 
         if (ds[k]) { st[i] = ds[k]; errs[i] = dm[k]; return; }
         ik_image* rs = rsz[k];
         const auto t0 = std::chrono::steady_clock::now();
-        int r = rs ? IK_OK : ik_resize(imgs[k], w[i], h[i], filter, &rs);
+        int r = rs ? IK_OK : ik_resize_fit(imgs[k], w[i], h[i], fit ? fit[i] : IK_FIT_CONTAIN, filter, &rs);
         const auto t1 = std::chrono::steady_clock::now();
         if (!r && !fronted[k] && plan.req[k].solo == PostRoute::WebpMixed) {
             (void)hipStreamSynchronize(thread_stream());  // this thread's resize is done: another's stream reads it
@@ -1395,6 +1449,7 @@ struct BatchPart {
     const size_t* lens = nullptr;
     const int64_t* w = nullptr;
     const int64_t* h = nullptr;
+    const int* fit = nullptr;  // null: every request IK_FIT_CONTAIN
     const int* fmt = nullptr;
     const int* quality = nullptr;
     int filter = 0;
@@ -1469,7 +1524,8 @@ private:
             if (stage == 2) {
                 // resize + the encoders' device front ends, beside the next batch's decode
                 Ticket& t = *p->t;
-                transform_post_phase(p->w, p->h, p->fmt, p->quality, p->filter, t.st.data(), t.errs.data(), p->hp);
+                transform_post_phase(p->w, p->h, p->fit, p->fmt, p->quality, p->filter, t.st.data(), t.errs.data(),
+                                     p->hp);
                 pool_->post([p] {
                     Ticket& tk = *p->t;
                     transform_host_phase(tk.outs, tk.out_lens, tk.st.data(), tk.errs.data(), p->hp);
@@ -1626,12 +1682,12 @@ namespace {
 // the stages read (Ticket::eff / sniff for device-resident inputs); phys >= 0:
 // the inputs live on that physical device, so the batch goes whole to it
 int submit_parts(const std::shared_ptr<Ticket>& t, const uint8_t* const* bytes, const uint8_t* const* sniff,
-                 int phys, const size_t* lens, uint32_t n, const int64_t* w, const int64_t* h, const int* fmt,
-                 const int* quality, int filter, int threads, uint64_t* ticket) {
+                 int phys, const size_t* lens, uint32_t n, const int64_t* w, const int64_t* h, const int* fit,
+                 const int* fmt, const int* quality, int filter, int threads, uint64_t* ticket) {
     auto make_part = [&](uint32_t lo, uint32_t hi) {
         auto p = std::make_shared<BatchPart>();
         p->t = t;
-        p->bytes = bytes; p->lens = lens; p->w = w; p->h = h; p->fmt = fmt; p->quality = quality;
+        p->bytes = bytes; p->lens = lens; p->w = w; p->h = h; p->fit = fit; p->fmt = fmt; p->quality = quality;
         p->sniff = sniff;
         p->filter = filter;
         p->hp.threads = threads;
@@ -1699,10 +1755,21 @@ int ik_transform_batch_submit(const uint8_t* const* bytes, const size_t* lens, u
                               const int64_t* h, const int* fmt, const int* quality, int filter, int threads,
                               uint8_t** outs, size_t* out_lens, int* status, uint64_t* ticket) {
     IK_API_ENTER();
+    return ik_transform_batch_submit_fit(bytes, lens, n, w, h, nullptr, fmt, quality, filter, threads, outs, out_lens,
+                                         status, ticket);
+}
+
+int ik_transform_batch_submit_fit(const uint8_t* const* bytes, const size_t* lens, uint32_t n, const int64_t* w,
+                                  const int64_t* h, const int* fit, const int* fmt, const int* quality, int filter,
+                                  int threads, uint8_t** outs, size_t* out_lens, int* status, uint64_t* ticket) {
+    IK_API_ENTER();
     if (!bytes || !lens || !w || !h || !fmt || !quality || !outs || !out_lens || !n || !ticket)
         return fail(IK_ERR_INVALID, "bad batch");
+    for (uint32_t i = 0; fit && i < n; ++i)
+        if (fit[i] < IK_FIT_CONTAIN || fit[i] > IK_FIT_EXACT)
+            return fail(IK_ERR_INVALID, "request %u: unknown fit %d", i, fit[i]);
     auto t = new_ticket(n, outs, out_lens, status);
-    return submit_parts(t, bytes, nullptr, -1, lens, n, w, h, fmt, quality, filter, threads, ticket);
+    return submit_parts(t, bytes, nullptr, -1, lens, n, w, h, fit, fmt, quality, filter, threads, ticket);
 }
 
 int ik_transform_batch_submit_device(const uint8_t* const* dev_bytes, const size_t* lens, uint32_t n,
@@ -1819,7 +1886,8 @@ int ik_transform_batch_submit_device(const uint8_t* const* dev_bytes, const size
     }
     // the batch runs where its inputs are: on a logical device of `phys`, or (single-
     // device mode) on the stages of `phys` whatever the calling thread's device is
-    return submit_parts(t, t->eff.data(), t->sniff.data(), phys, lens, n, w, h, fmt, quality, filter, threads, ticket);
+    return submit_parts(t, t->eff.data(), t->sniff.data(), phys, lens, n, w, h, nullptr, fmt, quality, filter, threads,
+                        ticket);
 }
 
 int ik_memory_stats(uint64_t* out, int n) {
@@ -1868,20 +1936,27 @@ int ik_transform_batch(const uint8_t* const* bytes, const size_t* lens, uint32_t
                        const int64_t* h, const int* fmt, const int* quality, int filter, int threads, uint8_t** outs,
                        size_t* out_lens, int* status) {
     IK_API_ENTER();
+    return ik_transform_batch_fit(bytes, lens, n, w, h, nullptr, fmt, quality, filter, threads, outs, out_lens, status);
+}
+
+int ik_transform_batch_fit(const uint8_t* const* bytes, const size_t* lens, uint32_t n, const int64_t* w,
+                           const int64_t* h, const int* fit, const int* fmt, const int* quality, int filter,
+                           int threads, uint8_t** outs, size_t* out_lens, int* status) {
+    IK_API_ENTER();
     uint64_t ticket = 0;
-    if (int rc = ik_transform_batch_submit(bytes, lens, n, w, h, fmt, quality, filter, threads, outs, out_lens, status,
-                                           &ticket))
+    if (int rc = ik_transform_batch_submit_fit(bytes, lens, n, w, h, fit, fmt, quality, filter, threads, outs, out_lens,
+                                               status, &ticket))
         return rc;
     return ik_transform_batch_wait(ticket);
 }
 
-static int transform_here(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fmt, int quality,
+static int transform_here(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int fmt, int quality,
                           int filter, uint8_t** out, size_t* out_len) {
     ik_image* img = nullptr;
     int st = decode_one(bytes, len, &img, nullptr);
     if (st) return st;
     ik_image* rs = nullptr;
-    st = ik_resize(img, w, h, filter, &rs);
+    st = ik_resize_fit(img, w, h, fit, filter, &rs);
     if (st) { ik_image_free(img); return st; }
     st = ik_encode(rs, fmt, quality, out, out_len);
     if (rs != img) ik_image_free(rs);
@@ -1892,7 +1967,13 @@ static int transform_here(const uint8_t* bytes, size_t len, int64_t w, int64_t h
 int ik_transform(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fmt, int quality,
                  int filter, uint8_t** out, size_t* out_len) {
     IK_API_ENTER();
-    if (!sched_multi()) return transform_here(bytes, len, w, h, fmt, quality, filter, out, out_len);
+    return ik_transform_fit(bytes, len, w, h, IK_FIT_CONTAIN, fmt, quality, filter, out, out_len);
+}
+
+int ik_transform_fit(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int fmt, int quality,
+                     int filter, uint8_t** out, size_t* out_len) {
+    IK_API_ENTER();
+    if (!sched_multi()) return transform_here(bytes, len, w, h, fit, fmt, quality, filter, out, out_len);
     // several devices: queue the request to the least-loaded device's workers
     const uint64_t cost = request_cost(bytes, len, w, h, fmt);
     const int ld = sched_acquire(cost);
@@ -1902,7 +1983,7 @@ int ik_transform(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fmt
     int st = IK_OK;
     std::string msg;
     sched_pool(ld).post([&] {
-        const int r = transform_here(bytes, len, w, h, fmt, quality, filter, out, out_len);
+        const int r = transform_here(bytes, len, w, h, fit, fmt, quality, filter, out, out_len);
         std::string m = r ? last_error_str() : std::string();
         std::lock_guard<std::mutex> lk(mu);
         st = r;
@@ -1924,8 +2005,19 @@ int ik_resize_batch_device(const uint8_t* dev_src, uint32_t W, uint32_t H, uint3
                            uint32_t nh, int filter, uint8_t* dev_dst, size_t dst_pitch,
                            size_t dst_image_stride, void* hip_stream) {
     IK_API_ENTER();
+    return ik_resize_window_batch_device(dev_src, W, H, C, src_pitch, src_image_stride, n, nw, nh, 0, 0, nw, nh, filter,
+                                         dev_dst, dst_pitch, dst_image_stride, hip_stream);
+}
+
+int ik_resize_window_batch_device(const uint8_t* dev_src, uint32_t W, uint32_t H, uint32_t C, size_t src_pitch,
+                                  size_t src_image_stride, uint32_t n, uint32_t iw, uint32_t ih, uint32_t x0,
+                                  uint32_t y0, uint32_t nw, uint32_t nh, int filter, uint8_t* dev_dst,
+                                  size_t dst_pitch, size_t dst_image_stride, void* hip_stream) {
+    IK_API_ENTER();
     if (!dev_src || !dev_dst) return fail(IK_ERR_INVALID, "null device pointer");
     if (C < 1 || C > 4 || !W || !H || !nw || !nh || !n) return fail(IK_ERR_INVALID, "bad geometry");
+    if (!resize_window_ok(iw, ih, x0, y0, nw, nh))
+        return fail(IK_ERR_INVALID, "window %ux%u at (%u, %u) outside %ux%u", nw, nh, x0, y0, iw, ih);
     if (filter < 0 || filter > 4) return fail(IK_ERR_INVALID, "unknown filter %d", filter);
     if (src_pitch < (size_t)W * C || dst_pitch < (size_t)nw * C) return fail(IK_ERR_INVALID, "pitch too small");
     if ((src_pitch & 7) || ((uintptr_t)dev_src & 7)) return fail(IK_ERR_INVALID, "source rows must be 8-byte aligned");
@@ -1934,11 +2026,12 @@ int ik_resize_batch_device(const uint8_t* dev_src, uint32_t W, uint32_t H, uint3
     if (n > 1 && (src_image_stride < src_pitch * H || dst_image_stride < dst_pitch * nh))
         return fail(IK_ERR_INVALID, "image stride too small");
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : thread_stream();
-    ResizePlan* plan = get_resize_plan(current_device(), (int)W, (int)H, (int)C, (int)nw, (int)nh, filter, (int)n);
+    ResizePlan* plan = get_resize_plan_window(current_device(), (int)W, (int)H, (int)C, (int)iw, (int)ih, (int)x0,
+                                              (int)y0, (int)nw, (int)nh, filter, (int)n);
     if (!plan) return fail(IK_ERR_DEVICE, "cannot build resize plan");
     float* tmp = nullptr;
     if (plan->slots == 0 || !resize_fused_fits(src_pitch, H)) {
-        tmp = (float*)scratch(sizeof(float) * (size_t)n * nh * W * C);
+        tmp = (float*)scratch(sizeof(float) * (size_t)n * nh * plan->args.tmp_span);
         if (!tmp) return fail(IK_ERR_DEVICE, "cannot allocate device scratch");
     }
     hipError_t e = launch_resize(*plan, dev_src, src_pitch, src_image_stride, dev_dst, dst_pitch,
@@ -1955,9 +2048,16 @@ const char* ik_resize_kernel_name(uint32_t W, uint32_t H, uint32_t C, uint32_t n
 
 int ik_resize_plan_info(uint32_t W, uint32_t H, uint32_t C, uint32_t nw, uint32_t nh, int filter, uint32_t n,
                         int32_t* out, int cap) {
+    return ik_resize_plan_info_window(W, H, C, nw, nh, 0, 0, nw, nh, filter, n, out, cap);
+}
+
+int ik_resize_plan_info_window(uint32_t W, uint32_t H, uint32_t C, uint32_t iw, uint32_t ih, uint32_t x0, uint32_t y0,
+                               uint32_t nw, uint32_t nh, int filter, uint32_t n, int32_t* out, int cap) {
     if (C < 1 || C > 4 || !W || !H || !nw || !nh || !n || filter < 0 || filter > 4 || !out || cap < 0) return -1;
+    if (!resize_window_ok(iw, ih, x0, y0, nw, nh)) return -1;
     ResizeTables t;
-    build_resize_tables((int)W, (int)H, (int)C, (int)nw, (int)nh, filter, (int)n, t);
+    build_resize_tables_window((int)W, (int)H, (int)C, (int)iw, (int)ih, (int)x0, (int)y0, (int)nw, (int)nh, filter,
+                               (int)n, t);
     const int32_t v[IK_RESIZE_PLAN_INFO_LEN] = {
         t.slots, t.rows, t.flush, t.weights_in_lds ? 1 : 0, t.NS, t.NB, t.per_A, t.per_R, t.NBp, t.Tx, t.Ty,
         t.max_strip_cols, resize_family_of(t, (size_t)W * C)};

@@ -55,16 +55,20 @@ struct ResizeArgs {
     int max_strip_cols;      // max output columns of a strip (LDS table size)
     int max_strip_weights;   // max nox*Tx of a strip (LDS weights size when in LDS)
     int lds_pad;             // zeroed LDS words after the column offsets (ik_resize_plan.h)
-    float* tmp;        // naive path only: f32 vertical intermediate [n][nh][row_bytes]
+    float* tmp;        // naive path only: f32 vertical intermediate [n][nh][tmp_span]
+    // naive path: the source samples per row its vertical pass covers, [tmp_col0,
+    // tmp_col0 + tmp_span): the columns the plan's outputs read (a whole resize: the row)
+    int tmp_col0, tmp_span;
     // fused path, images anywhere in memory: per-image base pointers (device
     // arrays, [n]); null = src + img * src_img_stride / dst + img * dst_img_stride
     const uint64_t* src_tab;
     const uint64_t* dst_tab;
 };
 
-// Host-side plan for one (W,H,C,nw,nh,filter,band height) geometry.
+// Host-side plan for one (W,H,C,window,filter,band height) geometry.
 struct ResizePlan {
     int W = 0, H = 0, C = 0, nw = 0, nh = 0, filter = 0;
+    int iw = 0, ih = 0, x0 = 0, y0 = 0;  // the window: ResizeTables (ik_resize_plan.h)
     int slots = 0;        // accumulator slots the fused kernel needs (0 = naive path)
     int rows = 0;         // prefetch depth: max source rows consumed per output row
     bool weights_in_lds = false;
@@ -81,7 +85,7 @@ struct ResizePlan {
 // 32-bit num_records and row offsets: images over INT32_MAX bytes take the naive
 // two-pass path (whose caller must then pass naive_tmp): resize_fused_fits
 // (ik_resize_plan.h).
-// 16-bit images: the two-pass path over u16 samples (tmp: nh * W * C floats), and
+// 16-bit images: the two-pass path over u16 samples (tmp: nh * plan.args.tmp_span floats), and
 // the u16 -> u8 rescale of to_rgb8 / to_rgba8
 hipError_t launch_resize16(const ResizePlan& plan, const uint8_t* src, size_t src_pitch, uint8_t* dst,
                            size_t dst_pitch, float* tmp, hipStream_t s);
@@ -267,5 +271,8 @@ inline JpegEncGeom jpeg_enc_geom(uint32_t w, uint32_t h) {
 // ---- plans (ik_plan.cpp) ----
 // axis_weights, required_slots and the tables themselves: ik_resize_plan.h
 ResizePlan* get_resize_plan(int device, int W, int H, int C, int nw, int nh, int filter, int n);
+// the plan of a window (x0, y0, nw, nh) of the source resampled to iw x ih
+ResizePlan* get_resize_plan_window(int device, int W, int H, int C, int iw, int ih, int x0, int y0, int nw, int nh,
+                                   int filter, int n);
 
 }  // namespace ik

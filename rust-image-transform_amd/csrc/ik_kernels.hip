@@ -521,13 +521,14 @@ __global__ __launch_bounds__(kThreads) void k_resize_periodic(ResizeArgs a) {
         }, std::make_integer_sequence<int, G>());
 }
 
-// Fallback vertical pass: one thread per (byte column, output row, image).
+// Fallback vertical pass: one thread per (byte column, output row, image), over the
+// byte columns [tmp_col0, tmp_col0 + tmp_span) that the plan's output columns read.
 __global__ __launch_bounds__(kThreads) void k_vert_naive(ResizeArgs a) {
     const int b = blockIdx.x * kThreads + threadIdx.x;
     const int r = blockIdx.y;
     const int img = blockIdx.z;
-    if (b >= a.row_bytes) return;
-    const uint8_t* __restrict__ src = a.src + (size_t)img * a.src_img_stride + b;
+    if (b >= a.tmp_span) return;
+    const uint8_t* __restrict__ src = a.src + (size_t)img * a.src_img_stride + a.tmp_col0 + b;
     const int l = a.ly[r], n = a.ny[r];
     const float* __restrict__ w = a.wy + (size_t)r * a.Ty;
     float t = 0.0f;
@@ -535,7 +536,7 @@ __global__ __launch_bounds__(kThreads) void k_vert_naive(ResizeArgs a) {
         const float prod = (float)src[(size_t)(l + k) * a.src_pitch] * w[k];
         t = t + prod;
     }
-    a.tmp[((size_t)img * a.nh + r) * a.row_bytes + b] = t;
+    a.tmp[((size_t)img * a.nh + r) * a.tmp_span + b] = t;
 }
 
 // Fallback horizontal pass: one thread per (output byte, output row, image).
@@ -545,10 +546,10 @@ __global__ __launch_bounds__(kThreads) void k_horz_naive(ResizeArgs a) {
     const int img = blockIdx.z;
     if (v >= a.nw * a.C) return;
     const int ox = v / a.C, c = v - ox * a.C;
-    const float* __restrict__ t = a.tmp + ((size_t)img * a.nh + r) * a.row_bytes;
+    const float* __restrict__ t = a.tmp + ((size_t)img * a.nh + r) * a.tmp_span;
     const int n = a.nx[ox];
     const float* __restrict__ w = a.wx + (size_t)ox * a.Tx;
-    int idx = a.lx[ox] * a.C + c;
+    int idx = a.lx[ox] * a.C + c - a.tmp_col0;
     float acc = 0.0f;
     for (int k = 0; k < n; ++k, idx += a.C) {
         const float prod = t[idx] * w[k];
@@ -560,20 +561,21 @@ __global__ __launch_bounds__(kThreads) void k_horz_naive(ResizeArgs a) {
 // ---- 16-bit images (Rgb16 / Rgba16 / L16 / La16 from 16-bit PNG) ----------------
 // image 0.25.8 resamples u16 samples with the same f32 sequence as u8 ones and
 // clamps to u16::MAX before FloatNearest; the two passes of the fallback path,
-// over samples instead of bytes (a.row_bytes counts samples here).
+// over samples instead of bytes (a.tmp_col0 / a.tmp_span count samples here).
 __global__ __launch_bounds__(kThreads) void k_vert_naive16(ResizeArgs a) {
     const int b = blockIdx.x * kThreads + threadIdx.x;
     const int r = blockIdx.y;
-    if (b >= a.row_bytes) return;
+    if (b >= a.tmp_span) return;
     const int l = a.ly[r], n = a.ny[r];
     const float* __restrict__ w = a.wy + (size_t)r * a.Ty;
     float t = 0.0f;
     for (int k = 0; k < n; ++k) {
-        const uint16_t v = *reinterpret_cast<const uint16_t*>(a.src + (size_t)(l + k) * a.src_pitch + 2 * (size_t)b);
+        const uint16_t v =
+            *reinterpret_cast<const uint16_t*>(a.src + (size_t)(l + k) * a.src_pitch + 2 * (size_t)(a.tmp_col0 + b));
         const float prod = (float)v * w[k];
         t = t + prod;
     }
-    a.tmp[(size_t)r * a.row_bytes + b] = t;
+    a.tmp[(size_t)r * a.tmp_span + b] = t;
 }
 
 __global__ __launch_bounds__(kThreads) void k_horz_naive16(ResizeArgs a) {
@@ -581,10 +583,10 @@ __global__ __launch_bounds__(kThreads) void k_horz_naive16(ResizeArgs a) {
     const int r = blockIdx.y;
     if (v >= a.nw * a.C) return;
     const int ox = v / a.C, c = v - ox * a.C;
-    const float* __restrict__ t = a.tmp + (size_t)r * a.row_bytes;
+    const float* __restrict__ t = a.tmp + (size_t)r * a.tmp_span;
     const int n = a.nx[ox];
     const float* __restrict__ w = a.wx + (size_t)ox * a.Tx;
-    int idx = a.lx[ox] * a.C + c;
+    int idx = a.lx[ox] * a.C + c - a.tmp_col0;
     float acc = 0.0f;
     for (int k = 0; k < n; ++k, idx += a.C) {
         const float prod = t[idx] * w[k];
@@ -601,7 +603,7 @@ hipError_t launch_resize16(const ResizePlan& plan, const uint8_t* src, size_t sr
     a.dst = dst; a.dst_pitch = dst_pitch; a.dst_img_stride = 0;
     a.src_tab = nullptr; a.dst_tab = nullptr;
     a.tmp = tmp;
-    dim3 g1((a.row_bytes + kThreads - 1) / kThreads, a.nh);
+    dim3 g1((a.tmp_span + kThreads - 1) / kThreads, a.nh);
     hipLaunchKernelGGL(k_vert_naive16, g1, dim3(kThreads), 0, s, a);
     dim3 g2((a.nw * a.C + kThreads - 1) / kThreads, a.nh);
     hipLaunchKernelGGL(k_horz_naive16, g2, dim3(kThreads), 0, s, a);
@@ -700,7 +702,7 @@ hipError_t launch_resize(const ResizePlan& plan, const uint8_t* src, size_t src_
         return hipErrorInvalidValue;
     }
     if (!naive_tmp) return hipErrorInvalidValue;
-    dim3 g1((a.row_bytes + kThreads - 1) / kThreads, a.nh, n);
+    dim3 g1((a.tmp_span + kThreads - 1) / kThreads, a.nh, n);
     hipLaunchKernelGGL(k_vert_naive, g1, dim3(kThreads), 0, s, a);
     dim3 g2((a.nw * a.C + kThreads - 1) / kThreads, a.nh, n);
     hipLaunchKernelGGL(k_horz_naive, g2, dim3(kThreads), 0, s, a);

@@ -4,6 +4,7 @@
 // a device in ik_resize_plan.h (shared with the CPU model, ik_resize_model.cpp);
 // this file caches plans and uploads their tables.
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <cstdio>
@@ -20,9 +21,13 @@ namespace ik {
 namespace {
 
 std::mutex g_plan_mu;
-std::map<std::tuple<int, int, int, int, int, int, int, int, int>, ResizePlan*> g_plans;
+// (device, W, H, C, iw, ih, x0, y0, nw, nh, filter, band height, flush): a crop of a
+// resize and the whole resize to the crop's size are different plans
+typedef std::array<int, 13> PlanKey;
+std::map<PlanKey, ResizePlan*> g_plans;
 // request -> plan (several requests can share one plan in g_plans)
-std::map<std::tuple<int, int, int, int, int, int, int, int>, ResizePlan*> g_front;
+typedef std::array<int, 12> FrontKey;
+std::map<FrontKey, ResizePlan*> g_front;
 
 template <typename T>
 size_t put(std::vector<char>& blob, const std::vector<T>& v) {
@@ -34,18 +39,24 @@ size_t put(std::vector<char>& blob, const std::vector<T>& v) {
 
 }  // namespace
 
-ResizePlan* build_resize_plan(int device, int W, int H, int C, int nw, int nh, int filter, int n);
+ResizePlan* build_resize_plan(int device, int W, int H, int C, int iw, int ih, int x0, int y0, int nw, int nh,
+                              int filter, int n);
 
 ResizePlan* get_resize_plan(int device, int W, int H, int C, int nw, int nh, int filter, int n) {
+    return get_resize_plan_window(device, W, H, C, nw, nh, 0, 0, nw, nh, filter, n);
+}
+
+ResizePlan* get_resize_plan_window(int device, int W, int H, int C, int iw, int ih, int x0, int y0, int nw, int nh,
+                                   int filter, int n) {
     // front cache on the request itself, so a repeated geometry costs a map
     // lookup, not a recomputation of the weights
-    const auto fkey = std::make_tuple(device, W, H, C, nw, nh, filter, n);
+    const FrontKey fkey = {device, W, H, C, iw, ih, x0, y0, nw, nh, filter, n};
     {
         std::lock_guard<std::mutex> lk(g_plan_mu);
         auto it = g_front.find(fkey);
         if (it != g_front.end()) return it->second;
     }
-    ResizePlan* p = build_resize_plan(device, W, H, C, nw, nh, filter, n);
+    ResizePlan* p = build_resize_plan(device, W, H, C, iw, ih, x0, y0, nw, nh, filter, n);
     if (p) {
         std::lock_guard<std::mutex> lk(g_plan_mu);
         g_front[fkey] = p;
@@ -53,10 +64,11 @@ ResizePlan* get_resize_plan(int device, int W, int H, int C, int nw, int nh, int
     return p;
 }
 
-ResizePlan* build_resize_plan(int device, int W, int H, int C, int nw, int nh, int filter, int n) {
+ResizePlan* build_resize_plan(int device, int W, int H, int C, int iw, int ih, int x0, int y0, int nw, int nh,
+                              int filter, int n) {
     ResizeTables t;
-    resize_plan_head(W, H, C, nw, nh, filter, n, t);
-    const auto key = std::make_tuple(device, W, H, C, nw, nh, filter, t.band_h, t.flush);
+    resize_plan_head_window(W, H, C, iw, ih, x0, y0, nw, nh, filter, n, t);
+    const PlanKey key = {device, W, H, C, iw, ih, x0, y0, nw, nh, filter, t.band_h, t.flush};
     std::lock_guard<std::mutex> lk(g_plan_mu);
     auto it = g_plans.find(key);
     if (it != g_plans.end()) return it->second;
@@ -76,6 +88,7 @@ ResizePlan* build_resize_plan(int device, int W, int H, int C, int nw, int nh, i
 
     auto* p = new ResizePlan();
     p->W = W; p->H = H; p->C = C; p->nw = nw; p->nh = nh; p->filter = filter;
+    p->iw = iw; p->ih = ih; p->x0 = x0; p->y0 = y0;
     p->slots = t.slots;
     p->rows = t.rows;
     p->weights_in_lds = t.weights_in_lds;
@@ -115,6 +128,8 @@ ResizePlan* build_resize_plan(int device, int W, int H, int C, int nw, int nh, i
     a.per_bands = (const int*)(d + o_pb);
     a.per_base = t.per_base;
     a.NBp = t.NBp;
+    a.tmp_col0 = t.col0;
+    a.tmp_span = t.col_span;
     g_plans[key] = p;
     return p;
 }

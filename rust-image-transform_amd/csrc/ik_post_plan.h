@@ -7,9 +7,10 @@
 //
 // The rules:
 //   resize groups   requests whose decoded images share (W, H, C, pitch, device) and
-//                   whose targets (nw, nh) agree resize in one launch (resize_group),
-//                   when there are at least 2 of them.  Emitted in ascending key order,
-//                   members in request order.
+//                   whose windows (iw, ih, x0, y0, nw, nh; fit_target) agree resize in one
+//                   launch (resize_group), when there are at least 2 of them: an exact and a
+//                   cover request of one output size are different groups.  Emitted in
+//                   ascending key order, members in request order.
 //   coder groups    inside a resize group, its WebP and its JPEG requests of one quality
 //                   (at least 2) are coded by one group call.  WebP groups first, then
 //                   JPEG, each in ascending quality.
@@ -67,27 +68,86 @@ inline uint32_t f32_as_u32(float v) {
     if (v >= 4294967296.0f) return 0xFFFFFFFFu;
     return (uint32_t)v;
 }
-inline int resize_target_dims(uint32_t W, uint32_t H, int64_t w, int64_t h, uint32_t* onw, uint32_t* onh) {
+// the request's target (tw, th): a missing side in f32 with round, each side max(1).
+// 1: a dimension above u32
+inline int request_target(uint32_t W, uint32_t H, int64_t w, int64_t h, uint32_t* otw, uint32_t* oth) {
     if (w > 0xFFFFFFFFll || h > 0xFFFFFFFFll) return 1;
     uint32_t tw, th;
     if (w >= 0) tw = (uint32_t)w;
     else tw = f32_as_u32(roundf((float)W * ((float)(uint32_t)h / (float)H)));
     if (h >= 0) th = (uint32_t)h;
     else th = f32_as_u32(roundf((float)H * ((float)(uint32_t)w / (float)W)));
-    if (tw < 1) tw = 1;
-    if (th < 1) th = 1;
+    *otw = tw < 1 ? 1 : tw;
+    *oth = th < 1 ? 1 : th;
+    return 0;
+}
+// image 0.25.8 resize_dimensions (f64 ratio, round, max 1): aspect fit, or fill.  2: a
+// side above u32
+inline int resize_dimensions(uint32_t W, uint32_t H, uint32_t tw, uint32_t th, bool fill, uint32_t* onw,
+                             uint32_t* onh) {
+    const double wr = (double)tw / (double)W, hr = (double)th / (double)H;
+    const double r = fill ? (wr > hr ? wr : hr) : (wr < hr ? wr : hr);
+    double fw = std::round((double)W * r), fh = std::round((double)H * r);
+    if (!(fw < 1.8e19) || !(fh < 1.8e19)) return 2;
+    unsigned long long rw = fw < 1 ? 1 : (unsigned long long)fw;
+    unsigned long long rh = fh < 1 ? 1 : (unsigned long long)fh;
+    if (rw > 0xFFFFFFFFull || rh > 0xFFFFFFFFull) return 2;
+    *onw = (uint32_t)rw;
+    *onh = (uint32_t)rh;
+    return 0;
+}
+inline int resize_target_dims(uint32_t W, uint32_t H, int64_t w, int64_t h, uint32_t* onw, uint32_t* onh) {
+    uint32_t tw, th;
+    if (request_target(W, H, w, h, &tw, &th)) return 1;
     uint32_t nw = tw, nh = th;
-    if (!(tw == W && th == H)) {
-        const double wr = (double)tw / (double)W, hr = (double)th / (double)H;
-        const double r = wr < hr ? wr : hr;
-        double fw = std::round((double)W * r), fh = std::round((double)H * r);
-        unsigned long long rw = fw < 1 ? 1 : (unsigned long long)fw;
-        unsigned long long rh = fh < 1 ? 1 : (unsigned long long)fh;
-        if (rw > 0xFFFFFFFFull || rh > 0xFFFFFFFFull) return 2;
-        nw = (uint32_t)rw; nh = (uint32_t)rh;
-    }
+    if (!(tw == W && th == H) && resize_dimensions(W, H, tw, th, false, &nw, &nh)) return 2;
     *onw = nw;
     *onh = nh;
+    return 0;
+}
+
+// What a request computes under a fit mode (ik_fit): columns [x0, x0 + nw) and rows
+// [y0, y0 + nh) of the image resampled to iw x ih.
+//   CONTAIN  DynamicImage::resize: the aspect-fitted size, whole
+//   EXACT    DynamicImage::resize_exact: the target, whole
+//   COVER    DynamicImage::resize_to_fill (image 0.25.8 as recalled):
+//            resize_dimensions(fill) -> resize_exact -> crop, centred along the axis
+//            that overflows the target; with one side None there is nothing to crop
+// (w, h as resize_target_dims: not both None.)  The same codes.
+struct FitWindow {
+    uint32_t iw = 0, ih = 0, x0 = 0, y0 = 0, nw = 0, nh = 0;
+    bool whole() const { return x0 == 0 && y0 == 0 && nw == iw && nh == ih; }
+    bool operator==(const FitWindow& o) const {
+        return iw == o.iw && ih == o.ih && x0 == o.x0 && y0 == o.y0 && nw == o.nw && nh == o.nh;
+    }
+};
+inline int fit_target(uint32_t W, uint32_t H, int64_t w, int64_t h, int fit, FitWindow* out) {
+    FitWindow f;
+    if (fit == IK_FIT_CONTAIN || (fit == IK_FIT_COVER && (w < 0 || h < 0))) {
+        if (int rc = resize_target_dims(W, H, w, h, &f.nw, &f.nh)) return rc;
+        f.iw = f.nw;
+        f.ih = f.nh;
+        *out = f;
+        return 0;
+    }
+    uint32_t tw, th;
+    if (request_target(W, H, w, h, &tw, &th)) return 1;
+    if (fit == IK_FIT_EXACT || W == 0 || H == 0) {  // (an empty image: ik_resize_exact's blank tw x th)
+        f.iw = f.nw = tw;
+        f.ih = f.nh = th;
+        *out = f;
+        return 0;
+    }
+    if (int rc = resize_dimensions(W, H, tw, th, true, &f.iw, &f.ih)) return rc;
+    uint32_t cx = 0, cy = 0;
+    if ((uint64_t)tw * f.ih > (uint64_t)f.iw * th) cy = f.ih > th ? (f.ih - th) / 2 : 0;
+    else cx = f.iw > tw ? (f.iw - tw) / 2 : 0;
+    // imageops::crop clamps the rectangle to what is left of the image
+    f.x0 = cx < f.iw ? cx : f.iw;
+    f.y0 = cy < f.ih ? cy : f.ih;
+    f.nw = tw < f.iw - f.x0 ? tw : f.iw - f.x0;
+    f.nh = th < f.ih - f.y0 ? th : f.ih - f.y0;
+    *out = f;
     return 0;
 }
 
@@ -108,12 +168,14 @@ struct PostRequest {
     uint32_t depth = 1;
     int64_t w = -1, h = -1;  // negative: None
     int fmt = 0, quality = 0;
+    int fit = IK_FIT_CONTAIN;
 };
 
 struct PostPlan {
     struct Req {
-        bool sized = false;    // (nw, nh) is the size its encoder sees (false: the decode or resize_target failed)
+        bool sized = false;    // (nw, nh) is the size its encoder sees (false: the decode or fit_target failed)
         uint32_t nw = 0, nh = 0;
+        FitWindow win;         // (sized) what it computes: win.nw x win.nh = nw x nh
         int rgroup = -1, cgroup = -1;
         PostRoute route = PostRoute::None;
         // its route when no group call takes it (it is in no coder group, or its group's
@@ -122,6 +184,7 @@ struct PostPlan {
     };
     struct ResizeGroup {
         uint32_t nw = 0, nh = 0;
+        FitWindow win;
         std::vector<uint32_t> members;  // request order
         uint32_t cg_lo = 0, cg_hi = 0;  // its coder groups: cgroups[cg_lo, cg_hi)
     };
@@ -147,7 +210,10 @@ inline PostPlan post_plan(const PostRequest* rq, uint32_t m, int webp_encoder, i
         for (uint32_t k = 0; k < m; ++k) cand += rq[k].ok && rq[k].depth == 1 && rq[k].fmt == IK_FORMAT_WEBP;
         P.mixed = cand >= P.mixed_min;
     }
-    std::map<std::tuple<uint32_t, uint32_t, uint32_t, size_t, int, uint32_t, uint32_t>, std::vector<uint32_t>> groups;
+    // (W, H, C, pitch, device), then the window: iw, ih, x0, y0 and with them (nw, nh)
+    typedef std::tuple<uint32_t, uint32_t, uint32_t, size_t, int, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t,
+                       uint32_t> GroupKey;
+    std::map<GroupKey, std::pair<FitWindow, std::vector<uint32_t>>> groups;
     for (uint32_t k = 0; k < m; ++k) {
         const PostRequest& r = rq[k];
         PostPlan::Req& q = P.req[k];
@@ -155,27 +221,37 @@ inline PostPlan post_plan(const PostRequest* rq, uint32_t m, int webp_encoder, i
         q.route = q.solo = PostRoute::Single;
         if (r.w < 0 && r.h < 0) {  // no resize asked for
             q.sized = true;
-            q.nw = r.W;
-            q.nh = r.H;
+            q.win.iw = q.win.nw = r.W;
+            q.win.ih = q.win.nh = r.H;
         } else {
-            q.sized = resize_target_dims(r.W, r.H, r.w, r.h, &q.nw, &q.nh) == 0;
+            q.sized = fit_target(r.W, r.H, r.w, r.h, r.fit, &q.win) == 0;
         }
+        q.nw = q.sized ? q.win.nw : 0;
+        q.nh = q.sized ? q.win.nh : 0;
         if (!q.sized) continue;  // Single: ik_resize reports it
         if (P.mixed && r.fmt == IK_FORMAT_WEBP && r.depth == 1 && q.nw >= 1 && q.nh >= 1 && q.nw <= kWebpMaxDim &&
             q.nh <= kWebpMaxDim)
             q.route = q.solo = PostRoute::WebpMixed;
-        if (r.depth == 1 && !(q.nw == r.W && q.nh == r.H))  // (never a request that needs no resize)
-            groups[std::make_tuple(r.W, r.H, r.C, r.pitch, r.device, q.nw, q.nh)].push_back(k);
+        // (never a request that needs no resampling: a whole copy or, under COVER, a crop of one)
+        if (r.depth == 1 && !(q.win.iw == r.W && q.win.ih == r.H)) {
+            // ordered by (nw, nh) first, as before the windows, then by the rest of the window
+            auto& slot = groups[GroupKey(r.W, r.H, r.C, r.pitch, r.device, q.nw, q.nh, q.win.iw, q.win.ih, q.win.x0,
+                                         q.win.y0)];
+            slot.first = q.win;
+            slot.second.push_back(k);
+        }
     }
-    for (auto& kv : groups) {
-        if (kv.second.size() < 2) continue;
+    for (auto& gv : groups) {
+        std::vector<uint32_t>& gm = gv.second.second;
+        if (gm.size() < 2) continue;
         const int g = (int)P.rgroups.size();
         PostPlan::ResizeGroup G;
-        G.nw = std::get<5>(kv.first);
-        G.nh = std::get<6>(kv.first);
+        G.win = gv.second.first;
+        G.nw = G.win.nw;
+        G.nh = G.win.nh;
         G.cg_lo = (uint32_t)P.cgroups.size();
         std::map<int, std::vector<uint32_t>> byq, jbyq;
-        for (uint32_t k : kv.second) {
+        for (uint32_t k : gm) {
             P.req[k].rgroup = g;
             if (rq[k].fmt == IK_FORMAT_WEBP) byq[rq[k].quality].push_back(k);
             if (rq[k].fmt == IK_FORMAT_JPEG) jbyq[rq[k].quality].push_back(k);
@@ -201,7 +277,7 @@ inline PostPlan post_plan(const PostRequest* rq, uint32_t m, int webp_encoder, i
         for (auto& qv : jbyq)
             if (qv.second.size() >= 2) emit(PostRoute::JpegGroup, qv.first, qv.second);
         G.cg_hi = (uint32_t)P.cgroups.size();
-        G.members.swap(kv.second);
+        G.members.swap(gm);
         P.rgroups.push_back(std::move(G));
     }
     return P;

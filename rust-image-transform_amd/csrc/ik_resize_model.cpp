@@ -23,22 +23,31 @@ using namespace ik;
 
 namespace {
 
+// a window (x0, y0, nw, nh) of the source resampled to iw x ih; whole: (nw, nh, 0, 0, nw, nh)
+struct Win {
+    int iw, ih, x0, y0, nw, nh;
+};
+
 struct Key {
-    int v[7];
+    int v[11];
     bool operator==(const Key& o) const { return std::memcmp(v, o.v, sizeof v) == 0; }
 };
-thread_local Key g_key = {{0, 0, 0, 0, 0, 0, 0}};
+thread_local Key g_key = {{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}};
 thread_local ResizeTables g_t;
 
-const ResizeTables* plan_for(int W, int H, int C, int nw, int nh, int filter, int n) {
-    if (C < 1 || C > 4 || W < 1 || H < 1 || nw < 1 || nh < 1 || n < 1 || filter < 0 || filter > 4) return nullptr;
-    const Key k = {{W, H, C, nw, nh, filter, n}};
+const ResizeTables* plan_for(int W, int H, int C, const Win& w, int filter, int n) {
+    if (C < 1 || C > 4 || W < 1 || H < 1 || n < 1 || filter < 0 || filter > 4) return nullptr;
+    if (!resize_window_ok(w.iw, w.ih, w.x0, w.y0, w.nw, w.nh)) return nullptr;
+    const Key k = {{W, H, C, w.iw, w.ih, w.x0, w.y0, w.nw, w.nh, filter, n}};
     if (!(k == g_key)) {
         g_t = ResizeTables();
-        build_resize_tables(W, H, C, nw, nh, filter, n, g_t);
+        build_resize_tables_window(W, H, C, w.iw, w.ih, w.x0, w.y0, w.nw, w.nh, filter, n, g_t);
         g_key = k;
     }
     return &g_t;
+}
+const ResizeTables* plan_for(int W, int H, int C, int nw, int nh, int filter, int n) {
+    return plan_for(W, H, C, Win{nw, nh, 0, 0, nw, nh}, filter, n);
 }
 
 inline int lds_idx(int i) { return i + ((i >> 5) << 2); }
@@ -250,15 +259,18 @@ struct Run {
         }
     }
 
-    // k_vert_naive / k_horz_naive: each output's own taps only
+    // k_vert_naive / k_horz_naive: each output's own taps only, the vertical pass over
+    // the byte columns [col0, col0 + col_span) of the plan
     void naive() {
-        const int rbts = t.W * t.C;
-        std::vector<float> tmp((size_t)t.nh * rbts);
+        const int rbts = t.col_span, c0 = t.col0;
+        std::vector<float> tmp((size_t)t.nh * rbts, std::numeric_limits<float>::quiet_NaN());
         for (int r = 0; r < t.nh; ++r)
             for (int b = 0; b < rbts; ++b) {
                 float v = 0.0f;
                 for (int k = 0; k < t.cy[r]; ++k) {
-                    const float prod = (float)src[(size_t)(t.ly[r] + k) * pitch + b] * t.wy[(size_t)r * t.Ty + k];
+                    const size_t at = (size_t)(t.ly[r] + k) * pitch + c0 + b;
+                    if (at >= pitch * (size_t)t.H || c0 + b >= t.W * t.C) { ++st[kStTableOob]; continue; }
+                    const float prod = (float)src[at] * t.wy[(size_t)r * t.Ty + k];
                     v = v + prod;
                 }
                 tmp[(size_t)r * rbts + b] = v;
@@ -267,8 +279,9 @@ struct Run {
             for (int v = 0; v < t.nw * t.C; ++v) {
                 const int ox = v / t.C, c = v - ox * t.C;
                 float acc = 0.0f;
-                int idx = t.lx[ox] * t.C + c;
+                int idx = t.lx[ox] * t.C + c - c0;
                 for (int k = 0; k < t.cx[ox]; ++k, idx += t.C) {
+                    if (idx < 0 || idx >= rbts) { ++st[kStTableOob]; continue; }
                     const float prod = tmp[(size_t)r * rbts + idx] * t.wx[(size_t)ox * t.Tx + k];
                     acc = acc + prod;
                 }
@@ -279,12 +292,26 @@ struct Run {
 
 }  // namespace
 
+static int plan_summary(const ResizeTables* t, int32_t* out, int cap);
+static long long plan_table(const ResizeTables* t, int which, void* out, long long cap_bytes);
+static int plan_run(const ResizeTables* t, const uint8_t* src, long long pitch, long long src_img_stride, int nimg,
+             uint8_t* dst, long long dst_pitch, long long dst_img_stride, int fma, int family, long long* stats);
+
 extern "C" {
 
 // the summary of ik_resize_plan_info's first twelve values, then per_base, band_h,
 // max_strip_weights, LDS words of the launch, fused steps, per_w steps, lds_pad
 int ikm_resize_plan(int W, int H, int C, int nw, int nh, int filter, int n, int32_t* out, int cap) {
-    const ResizeTables* t = plan_for(W, H, C, nw, nh, filter, n);
+    return plan_summary(plan_for(W, H, C, nw, nh, filter, n), out, cap);
+}
+// the same for a window (x0, y0, nw, nh) of the source resampled to iw x ih
+int ikm_resize_plan_window(int W, int H, int C, int iw, int ih, int x0, int y0, int nw, int nh, int filter, int n,
+                           int32_t* out, int cap) {
+    return plan_summary(plan_for(W, H, C, Win{iw, ih, x0, y0, nw, nh}, filter, n), out, cap);
+}
+}  // extern "C"
+
+static int plan_summary(const ResizeTables* t, int32_t* out, int cap) {
     if (!t || !out) return -1;
     const int32_t v[19] = {t->slots, t->rows, t->flush, t->weights_in_lds ? 1 : 0, t->NS, t->NB, t->per_A, t->per_R,
                            t->NBp, t->Tx, t->Ty, t->max_strip_cols, t->per_base, t->band_h, t->max_strip_weights,
@@ -297,9 +324,18 @@ int ikm_resize_plan(int W, int H, int C, int nw, int nh, int filter, int n, int3
 // table `which` of that plan: 0 lx, 1 cx, 2 wx, 3 ly, 4 cy, 5 wy, 6 strips, 7 bands,
 // 8 step_hdr, 9 step_mask (u64), 10 step_w, 11 band_step, 12 per_w, 13 per_bands.
 // Returns its size in bytes; copies it when cap_bytes suffices.
+extern "C" {
 long long ikm_resize_table(int W, int H, int C, int nw, int nh, int filter, int n, int which, void* out,
                            long long cap_bytes) {
-    const ResizeTables* t = plan_for(W, H, C, nw, nh, filter, n);
+    return plan_table(plan_for(W, H, C, nw, nh, filter, n), which, out, cap_bytes);
+}
+long long ikm_resize_table_window(int W, int H, int C, int iw, int ih, int x0, int y0, int nw, int nh, int filter,
+                                  int n, int which, void* out, long long cap_bytes) {
+    return plan_table(plan_for(W, H, C, Win{iw, ih, x0, y0, nw, nh}, filter, n), which, out, cap_bytes);
+}
+}  // extern "C"
+
+static long long plan_table(const ResizeTables* t, int which, void* out, long long cap_bytes) {
     if (!t) return -1;
     const void* p = nullptr;
     size_t bytes = 0;
@@ -323,11 +359,26 @@ long long ikm_resize_table(int W, int H, int C, int nw, int nh, int filter, int 
 // LDS word the horizontal pass read, LDS words of the launch, reads of words the
 // workgroup never wrote, reads past the launch's LDS, table indices out of range,
 // highest word row_put wrote within a row.
+extern "C" {
 int ikm_resize_run(const uint8_t* src, long long pitch, long long src_img_stride, int W, int H, int C, int nw, int nh,
                    int filter, int n, int nimg, uint8_t* dst, long long dst_pitch, long long dst_img_stride, int fma,
                    int family, long long* stats) {
-    const ResizeTables* t = plan_for(W, H, C, nw, nh, filter, n);
-    if (!t || !src || !dst || pitch < (long long)W * C || dst_pitch < (long long)nw * C || nimg < 1) return -1;
+    return plan_run(plan_for(W, H, C, nw, nh, filter, n), src, pitch, src_img_stride, nimg, dst, dst_pitch,
+                    dst_img_stride, fma, family, stats);
+}
+// the same over a window: dst receives nw x nh pixels per image
+int ikm_resize_run_window(const uint8_t* src, long long pitch, long long src_img_stride, int W, int H, int C, int iw,
+                          int ih, int x0, int y0, int nw, int nh, int filter, int n, int nimg, uint8_t* dst,
+                          long long dst_pitch, long long dst_img_stride, int fma, int family, long long* stats) {
+    return plan_run(plan_for(W, H, C, Win{iw, ih, x0, y0, nw, nh}, filter, n), src, pitch, src_img_stride, nimg, dst,
+                    dst_pitch, dst_img_stride, fma, family, stats);
+}
+}  // extern "C"
+
+static int plan_run(const ResizeTables* t, const uint8_t* src, long long pitch, long long src_img_stride, int nimg,
+             uint8_t* dst, long long dst_pitch, long long dst_img_stride, int fma, int family, long long* stats) {
+    if (!t || !src || !dst || pitch < (long long)t->W * t->C || dst_pitch < (long long)t->nw * t->C || nimg < 1)
+        return -1;
     int fam = family;
     if (fam < 0) fam = !t->slots ? kFamilyNaive : (t->per_A ? kFamilyPeriodic : kFamilyFused);
     if (fam == kFamilyPeriodic && !t->per_A) return -1;
@@ -350,5 +401,3 @@ int ikm_resize_run(const uint8_t* src, long long pitch, long long src_img_stride
         for (int i = 0; i < kStCount; ++i) stats[i] = st[i];
     return 0;
 }
-
-}  // extern "C"

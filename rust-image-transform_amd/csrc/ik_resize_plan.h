@@ -4,6 +4,11 @@
 // plain vectors.  build_resize_plan (ik_plan.cpp) uploads them; the CPU model
 // (ik_resize_model.cpp, test infrastructure) walks them.  Host code only.
 //
+// A plan is made for a window (x0, y0, nw, nh) of the source resampled to a virtual
+// iw x ih (fit=cover's crop; a whole resize is the full window): the tables hold the
+// window's output rows and columns only, indexed from 0, with absolute source
+// positions, so the kernels compute and read nothing the crop would discard.
+//
 // Weights follow image 0.25.8 src/imageops/sample.rs (vertical_sample /
 // horizontal_sample, called from reference src/transform.rs:85-89): per output
 // index, centre (o + 0.5) * ratio, support * max(ratio, 1), window
@@ -103,10 +108,13 @@ inline float support_of(int filter) {
 
 }  // namespace rplan
 
-// sample.rs weights for one axis; returns the tap count T (row stride of w).
-inline int axis_weights(int in, int out, int filter, std::vector<int>& left, std::vector<int>& cnt,
-                        std::vector<float>& w) {
-    const float ratio = (float)in / (float)out;
+// sample.rs weights for outputs [o0, o0 + out) of an axis resampled from `in` to
+// `virt` samples (the window of a cropped output: O(out) work however large virt
+// is); left stays an absolute source position.  Returns the tap count T (row
+// stride of w) of those outputs.
+inline int axis_weights_window(int in, int virt, int o0, int out, int filter, std::vector<int>& left,
+                               std::vector<int>& cnt, std::vector<float>& w) {
+    const float ratio = (float)in / (float)virt;
     const float sratio = ratio < 1.0f ? 1.0f : ratio;
     const float src_support = rplan::support_of(filter) * sratio;
     left.assign(out, 0);
@@ -114,7 +122,7 @@ inline int axis_weights(int in, int out, int filter, std::vector<int>& left, std
     std::vector<std::vector<float>> rows(out);
     int T = 1;
     for (int o = 0; o < out; ++o) {
-        float c = ((float)o + 0.5f) * ratio;
+        float c = ((float)(o0 + o) + 0.5f) * ratio;
         long long l = (long long)floorf(c - src_support);
         l = l < 0 ? 0 : (l > in - 1 ? in - 1 : l);
         long long r = (long long)ceilf(c + src_support);
@@ -138,6 +146,12 @@ inline int axis_weights(int in, int out, int filter, std::vector<int>& left, std
     return T;
 }
 
+// sample.rs weights for one whole axis
+inline int axis_weights(int in, int out, int filter, std::vector<int>& left, std::vector<int>& cnt,
+                        std::vector<float>& w) {
+    return axis_weights_window(in, out, 0, out, filter, left, cnt, w);
+}
+
 // smallest A with left[r + A] >= left[r] + cnt[r] for every r: no more than A
 // output rows are ever open at once in a top-to-bottom sweep
 inline int required_slots(const std::vector<int>& left, const std::vector<int>& cnt) {
@@ -153,6 +167,13 @@ inline int required_slots(const std::vector<int>& left, const std::vector<int>& 
 // Everything build_resize_plan uploads, and the variant the launch picks.
 struct ResizeTables {
     int W = 0, H = 0, C = 0, nw = 0, nh = 0, filter = 0, n = 0;
+    // the output is columns [x0, x0 + nw) and rows [y0, y0 + nh) of the source resampled
+    // to iw x ih (a whole resize: iw = nw, ih = nh, x0 = y0 = 0).  Every table below is
+    // indexed by the window's own columns and rows; lx / ly are source positions.
+    int iw = 0, ih = 0, x0 = 0, y0 = 0;
+    // the source samples per row the window's columns read, [col0, col0 + col_span):
+    // what the two-pass kernels' vertical pass covers (a whole resize: 0, W * C)
+    int col0 = 0, col_span = 0;
     int slots = 0;        // accumulator slots the fused kernel needs (0 = naive path)
     int rows = 0;         // prefetch depth: max source rows consumed per output row
     bool weights_in_lds = false;
@@ -179,11 +200,21 @@ struct ResizeTables {
 
 // First half: weights, variant, strips and the band height (what a plan is cached
 // by).  n: images sharing the launch.
-inline void resize_plan_head(int W, int H, int C, int nw, int nh, int filter, int n, ResizeTables& t) {
+inline void resize_plan_head_window(int W, int H, int C, int iw, int ih, int x0, int y0, int nw, int nh, int filter,
+                                    int n, ResizeTables& t) {
     t.W = W; t.H = H; t.C = C; t.nw = nw; t.nh = nh; t.filter = filter; t.n = n;
+    t.iw = iw; t.ih = ih; t.x0 = x0; t.y0 = y0;
     std::vector<int>&lx = t.lx, &cx = t.cx, &ly = t.ly, &cy = t.cy;
-    const int Tx = t.Tx = axis_weights(W, nw, filter, lx, cx, t.wx);
-    const int Ty = t.Ty = axis_weights(H, nh, filter, ly, cy, t.wy);
+    const int Tx = t.Tx = axis_weights_window(W, iw, x0, nw, filter, lx, cx, t.wx);
+    const int Ty = t.Ty = axis_weights_window(H, ih, y0, nh, filter, ly, cy, t.wy);
+    int c_lo = W, c_hi = 0;
+    for (int ox = 0; ox < nw; ++ox) {
+        c_lo = std::min(c_lo, lx[ox]);
+        c_hi = std::max(c_hi, lx[ox] + cx[ox]);
+    }
+    if (nw == iw) { c_lo = 0; c_hi = W; }  // a whole row of outputs: the whole source row, as ever
+    t.col0 = c_lo * C;
+    t.col_span = (c_hi - c_lo) * C;
     int A = required_slots(ly, cy);
     int slots = A <= 2 ? 2 : A <= 4 ? 4 : A <= 8 ? 8 : A <= 16 ? 16 : 0;
 
@@ -259,6 +290,10 @@ inline void resize_plan_head(int W, int H, int C, int nw, int nh, int filter, in
     t.slots = slots; t.rows = rows; t.weights_in_lds = wl; t.NS = NS; t.band_h = band_h;
 }
 
+inline void resize_plan_head(int W, int H, int C, int nw, int nh, int filter, int n, ResizeTables& t) {
+    resize_plan_head_window(W, H, C, nw, nh, 0, 0, nw, nh, filter, n, t);
+}
+
 // Second half: bands, step tables, the periodic tables and the LDS sizes.
 inline void resize_plan_tables(ResizeTables& t) {
     const int nh = t.nh, H = t.H, n = t.n, slots = t.slots, rows = t.rows, band_h = t.band_h, Ty = t.Ty, NS = t.NS;
@@ -322,13 +357,14 @@ inline void resize_plan_tables(ResizeTables& t) {
     // masks, no accumulator shifts.  Taps outside an output's own window carry weight
     // 0 (+0 added to the sum, so the f32 sequence of the reference is unchanged; the
     // first tap is assigned, not added to 0, which can differ only in the sign of a
-    // zero sum and so never in an output byte).
+    // zero sum and so never in an output byte).  A window keeps the ratio of its
+    // virtual height ih; y counts the window's rows, so per_base takes in R * y0.
     int per_A = 0, per_R = 0, per_base = 0;
     std::vector<float>& per_w = t.per_w;
     std::vector<int>& per_bands = t.per_bands;
     per_w.clear(); per_bands.clear();
-    if (slots && nh > 0 && H % nh == 0) {
-        const int R = H / nh;
+    if (slots && nh > 0 && t.ih > 0 && H % t.ih == 0) {
+        const int R = H / t.ih;
         int lo = 1 << 30, hi = -(1 << 30);
         for (int y = 0; y < nh; ++y) {
             lo = std::min(lo, ly[y] - R * y);
@@ -396,6 +432,17 @@ inline void resize_plan_tables(ResizeTables& t) {
 
 inline void build_resize_tables(int W, int H, int C, int nw, int nh, int filter, int n, ResizeTables& t) {
     resize_plan_head(W, H, C, nw, nh, filter, n, t);
+    resize_plan_tables(t);
+}
+
+inline bool resize_window_ok(long long iw, long long ih, long long x0, long long y0, long long nw, long long nh) {
+    return iw >= 1 && ih >= 1 && nw >= 1 && nh >= 1 && x0 >= 0 && y0 >= 0 && x0 + nw <= iw && y0 + nh <= ih &&
+           iw <= 0x7FFFFFFFll && ih <= 0x7FFFFFFFll;
+}
+
+inline void build_resize_tables_window(int W, int H, int C, int iw, int ih, int x0, int y0, int nw, int nh, int filter,
+                                       int n, ResizeTables& t) {
+    resize_plan_head_window(W, H, C, iw, ih, x0, y0, nw, nh, filter, n, t);
     resize_plan_tables(t);
 }
 

@@ -464,7 +464,7 @@ void encode_shutdown();  // ik_shutdown: their pinned blocks, the per-device con
 // arithmetic: ik_post_plan.h) and a one-launch resize of same-geometry 8-bit images
 // (ik_encode.cpp)
 int resize_target(uint32_t W, uint32_t H, int64_t w, int64_t h, uint32_t* nw, uint32_t* nh);
-int resize_group(const std::vector<ik_image*>& src, uint32_t nw, uint32_t nh, int filter, std::vector<ik_image*>& out);
+int resize_group(const std::vector<ik_image*>& src, const FitWindow& win, int filter, std::vector<ik_image*>& out);
 
 // Per-device phase gates (ik_pool.cpp).  Concurrent batch calls on one device
 // take its GPU phases in turn: kGateUpload covers a PNG batch's staging, H2D and

@@ -127,6 +127,19 @@ SIGNATURES = [
     ("ik_memcpy_h2d", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
     ("ik_memcpy_d2h", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
     ("ik_dev_synchronize", ctypes.c_int, []),
+    ("ik_fit_target", ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)]),
+    ("ik_resize_fit", ctypes.c_int, [c_img_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_img_p)]),
+    ("ik_resize_window", ctypes.c_int, [c_img_p] + [ctypes.c_uint32] * 6 + [ctypes.c_int, ctypes.POINTER(c_img_p)]),
+    ("ik_resize_window_batch_device", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32] + [ctypes.c_uint32] * 6 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]),
+    ("ik_resize_plan_info_window", ctypes.c_int, [ctypes.c_uint32] * 9 + [ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int]),
+    ("ik_transform_fit", ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t)]),
+    ("ik_transform_batch_fit", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint32, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]),
+    ("ik_transform_batch_submit_fit", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint32, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint64)]),
+    ("ik_post_plan_fit", ctypes.c_int,
+     [ctypes.c_uint32, ctypes.POINTER(ctypes.c_int)] + [ctypes.POINTER(ctypes.c_uint32)] * 3
+     + [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint32)]
+     + [ctypes.POINTER(ctypes.c_int64)] * 2 + [ctypes.POINTER(ctypes.c_int)] * 3 + [ctypes.c_int, ctypes.c_int]
+     + [ctypes.POINTER(ctypes.c_uint32)] * 2 + [ctypes.POINTER(ctypes.c_int)] * 3 + [ctypes.POINTER(ctypes.c_uint32)] * 2),
 ]
 
 

@@ -35,6 +35,26 @@ class FilterType(enum.IntEnum):
     Lanczos3 = 4
 
 
+class FitMode(enum.IntEnum):
+    """ik_fit: how a request's (w, h) becomes pixels (the reference's query parser
+    declares fit=cover|contain, src/transform/params.rs:37-64).  contain is
+    DynamicImage::resize (resize_image as the reference calls it), cover
+    DynamicImage::resize_to_fill, exact DynamicImage::resize_exact."""
+
+    contain = 0
+    cover = 1
+    exact = 2
+
+
+def _fits(fits, n):
+    """The per-request fit array of a batch call, or None (every request contain)."""
+    if fits is None:
+        return None
+    if len(fits) != n:
+        raise InvalidArgument("fits must have one entry per request")
+    return (ctypes.c_int * n)(*[int(FitMode(f)) for f in fits])
+
+
 _COLOR = {1: "L8", 2: "La8", 3: "Rgb8", 4: "Rgba8"}
 
 
@@ -128,6 +148,15 @@ class DynamicImage:
         if st:
             _raise(st, "resize")
         return DynamicImage(out.value)
+
+    def resize_exact(self, nw: int, nh: int, filter: FilterType = FilterType.Lanczos3) -> "DynamicImage":
+        """DynamicImage::resize_exact: nw x nh, the aspect ratio not kept."""
+        return self.resize(nw, nh, filter)
+
+    def resize_to_fill(self, nw: int, nh: int, filter: FilterType = FilterType.Lanczos3) -> "DynamicImage":
+        """DynamicImage::resize_to_fill: scaled to cover nw x nh, then cropped to it about
+        the centre (only the kept window is computed)."""
+        return resize_image(self, nw, nh, filter, fit=FitMode.cover)
 
     def clone(self) -> "DynamicImage":
         return DynamicImage.from_array(self.to_array())
@@ -245,9 +274,11 @@ def _inputs(datas):
     return keep, ptrs, lens
 
 
-def transform_batch(datas, sizes, fmts, qualities, filter: "FilterType" = None, threads: int = 0) -> List[bytes]:
+def transform_batch(datas, sizes, fmts, qualities, filter: "FilterType" = None, threads: int = 0,
+                    fits=None) -> List[bytes]:
     """ik_transform_batch: decode -> resize_image -> encode_image for many requests
-    (sizes: (w, h) per request, None = unset; fmts: ImageFormat per request)."""
+    (sizes: (w, h) per request, None = unset; fmts: ImageFormat per request; fits: a
+    FitMode per request, None = contain for all)."""
     lib = _lib.load()
     bufs, ptrs, lens = _inputs(datas)
     n = len(bufs)
@@ -261,7 +292,11 @@ def transform_batch(datas, sizes, fmts, qualities, filter: "FilterType" = None, 
     outs = (ctypes.c_void_p * n)()
     olens = (ctypes.c_size_t * n)()
     status = (ctypes.c_int * n)()
-    st = lib.ik_transform_batch(ptrs, lens, n, ws, hs, fs, qs, filt, threads, outs, olens, status)
+    fa = _fits(fits, n)
+    if fa is None:
+        st = lib.ik_transform_batch(ptrs, lens, n, ws, hs, fs, qs, filt, threads, outs, olens, status)
+    else:
+        st = lib.ik_transform_batch_fit(ptrs, lens, n, ws, hs, fa, fs, qs, filt, threads, outs, olens, status)
     res = []
     for i in range(n):
         res.append(ctypes.string_at(outs[i], olens[i]) if outs[i] else None)
@@ -299,7 +334,7 @@ class PendingBatch:
 
 
 def transform_batch_submit(datas, sizes, fmts, qualities, filter: "FilterType" = None,
-                           threads: int = 0) -> PendingBatch:
+                           threads: int = 0, fits=None) -> PendingBatch:
     """ik_transform_batch_submit: the device half of transform_batch now, the host
     coders in the background; PendingBatch.wait() gives what transform_batch gives."""
     lib = _lib.load()
@@ -316,11 +351,16 @@ def transform_batch_submit(datas, sizes, fmts, qualities, filter: "FilterType" =
     olens = (ctypes.c_size_t * n)()
     status = (ctypes.c_int * n)()
     ticket = ctypes.c_uint64()
-    st = lib.ik_transform_batch_submit(ptrs, lens, n, ws, hs, fs, qs, filt, threads, outs, olens, status,
-                                       ctypes.byref(ticket))
+    fa = _fits(fits, n)
+    if fa is None:
+        st = lib.ik_transform_batch_submit(ptrs, lens, n, ws, hs, fs, qs, filt, threads, outs, olens, status,
+                                           ctypes.byref(ticket))
+    else:
+        st = lib.ik_transform_batch_submit_fit(ptrs, lens, n, ws, hs, fa, fs, qs, filt, threads, outs, olens, status,
+                                               ctypes.byref(ticket))
     if st:
         raise TransformError(_lib.last_error())
-    return PendingBatch((bufs, ptrs, lens, ws, hs, fs, qs), outs, olens, status, ticket.value, n)
+    return PendingBatch((bufs, ptrs, lens, ws, hs, fs, qs, fa), outs, olens, status, ticket.value, n)
 
 
 def transform_batch_submit_device(datas, sizes, fmts, qualities, filter: "FilterType" = None,
@@ -353,16 +393,16 @@ def transform_batch_submit_device(datas, sizes, fmts, qualities, filter: "Filter
 
 
 def resize_image(img: DynamicImage, w: Optional[int], h: Optional[int],
-                 filter: FilterType = FilterType.Lanczos3) -> DynamicImage:
-    """src/transform.rs:62-90 (Lanczos3; `filter` is an extension)."""
+                 filter: FilterType = FilterType.Lanczos3, fit: FitMode = FitMode.contain) -> DynamicImage:
+    """src/transform.rs:62-90 (Lanczos3; `filter` and `fit` are extensions: FitMode)."""
     if w is None and h is None:
         return img
     for v in (w, h):
         if v is not None and not 0 <= v <= 0xFFFFFFFF:
             raise InvalidArgument("dimension must be a u32")
     out = ctypes.c_void_p()
-    st = _lib.load().ik_resize(img._h, -1 if w is None else int(w), -1 if h is None else int(h),
-                               int(filter), ctypes.byref(out))
+    st = _lib.load().ik_resize_fit(img._h, -1 if w is None else int(w), -1 if h is None else int(h),
+                                   int(FitMode(fit)), int(filter), ctypes.byref(out))
     if st:
         _raise(st, "resize_image")
     return DynamicImage(out.value)
@@ -385,15 +425,15 @@ def encode_image(img: DynamicImage, fmt: ImageFormat, quality: int) -> bytes:
 
 
 def transform(data: bytes, w: Optional[int], h: Optional[int], fmt: ImageFormat, quality: int,
-              filter: FilterType = FilterType.Lanczos3) -> bytes:
+              filter: FilterType = FilterType.Lanczos3, fit: FitMode = FitMode.contain) -> bytes:
     """decode -> resize_image -> encode_image in one device-resident call."""
     lib = _lib.load()
     b = bytes(data)
     buf = _lib.u8p()
     n = ctypes.c_size_t()
-    st = lib.ik_transform(b, len(b), -1 if w is None else int(w), -1 if h is None else int(h),
-                          ImageFormat(fmt).value, int(quality), int(filter), ctypes.byref(buf),
-                          ctypes.byref(n))
+    st = lib.ik_transform_fit(b, len(b), -1 if w is None else int(w), -1 if h is None else int(h),
+                              int(FitMode(fit)), ImageFormat(fmt).value, int(quality), int(filter), ctypes.byref(buf),
+                              ctypes.byref(n))
     if st:
         raise TransformError(_lib.last_error())
     try:

@@ -107,6 +107,9 @@ def main():
     ap.add_argument("--size", type=int, default=2000)
     ap.add_argument("--formats", default="webp")
     ap.add_argument("--quality", type=int, default=80)
+    ap.add_argument("--fit", choices=["contain", "cover"], default="contain",
+                    help="contain: resize_image as the reference calls it; cover: every request filled and cropped "
+                         "to its w x h (ik_transform_batch*_fit)")
     ap.add_argument("--restart", action="store_true")
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--seed", type=int, default=0)
@@ -143,7 +146,7 @@ def main():
         dist.init_process_group(backend="nccl" if torch.cuda.is_available() else "gloo")
     if torch.cuda.is_available():
         torch.cuda.set_device(local)
-    from imagekit import ImageFormat, _lib, transform_batch, transform_batch_submit
+    from imagekit import FitMode, ImageFormat, _lib, transform_batch, transform_batch_submit
     lib = _lib.load()
     queue = world == 1
     assert lib.ik_init(-1 if queue else local) == 0, _lib.last_error()
@@ -152,9 +155,13 @@ def main():
         args.clients = max(1, ndev)
     mine = [(s, w, h, ImageFormat[f]) for s, w, h, f in shard(reqs, rank, world)]
 
+    def fits(chunk):  # None: the calls without a fit, as before
+        return [FitMode.cover] * len(chunk) if args.fit == "cover" else None
+
     def run_batch(chunk):
         return transform_batch([srcs[s] for s, _, _, _ in chunk], [(w, h) for _, w, h, _ in chunk],
-                               [f for _, _, _, f in chunk], [args.quality] * len(chunk), threads=args.threads)
+                               [f for _, _, _, f in chunk], [args.quality] * len(chunk), threads=args.threads,
+                               fits=fits(chunk))
 
     run_batch(mine[:min(len(mine), 8)])  # warm-up: plans, streams, pinned staging
 
@@ -192,7 +199,8 @@ def main():
                 done(tb, run_batch(chunk))
                 continue
             p = transform_batch_submit([srcs[s] for s, _, _, _ in chunk], [(w, h) for _, w, h, _ in chunk],
-                                       [f for _, _, _, f in chunk], [args.quality] * len(chunk), threads=args.threads)
+                                       [f for _, _, _, f in chunk], [args.quality] * len(chunk), threads=args.threads,
+                                       fits=fits(chunk))
             if pend is not None:
                 done(pend[0], pend[1].wait())
             pend = (tb, p)
