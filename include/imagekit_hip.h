@@ -446,6 +446,35 @@ int ik_libwebp_version(void);
 size_t ik_codec_library(int fmt, char *buf, size_t cap);
 int ik_get_webp_encoder(void);
 
+/* ---- EXIF orientation -------------------------------------------------- */
+/* image 0.25.8 offers ImageDecoder::orientation(), Orientation::from_exif and
+ * DynamicImage::apply_orientation; the reference's decode_image never calls them
+ * (src/transform.rs:27-43), and neither does any entry point above: a file's pixels are
+ * decoded as stored.  The calls below are the opt-in equivalent, pixels staying in HBM.
+ * With S the stored image, H rows by W columns, orientation o gives out[y][x]:
+ *   1 S[y][x]        2 S[y][W-1-x]    3 S[H-1-y][W-1-x]    4 S[H-1-y][x]        (W x H)
+ *   5 S[x][y]        6 S[H-1-x][y]    7 S[H-1-x][W-1-y]    8 S[x][W-1-y]        (H x W)
+ * (6 turns 90 degrees clockwise, 8 counter-clockwise; the mapping is recalled and pinned
+ * to Pillow's ImageOps.exif_transpose) */
+/* The file's EXIF Orientation, 1..8: JPEG APP1 before the first SOS, PNG eXIf, WebP
+ * (VP8X) EXIF chunk; IFD0 only, tag 0x0112 as one SHORT.  1 when there is none, for any
+ * other format, and for a malformed or truncated file: never an error, never a read past
+ * len.  Needs no device (csrc/ik_exif.h). */
+int ik_exif_orientation(const uint8_t *bytes, size_t len);
+/* the `orient` argument of the *_oriented calls: IK_ORIENT_STORED, the pixels as stored
+ * (the calls without the argument); IK_ORIENT_AUTO, ik_exif_orientation of the bytes;
+ * 1..8, that value whatever the file says (a caller's rotate= parameter).  Anything else
+ * is IK_ERR_INVALID. */
+typedef enum { IK_ORIENT_AUTO = -1, IK_ORIENT_STORED = 0 /* 1..8: apply that EXIF value */ } ik_orient;
+/* DynamicImage::apply_orientation as a new image (orientation 1: a copy); 8- and 16-bit */
+int ik_image_orient(const ik_image *img, int orientation /* 1..8 */, ik_image **out);
+/* ik_decode, then the turn.  An effective orientation of 1 adds no pass. */
+int ik_decode_oriented(const uint8_t *bytes, size_t len, int orient, ik_image **out, int *fmt_out);
+/* the edge of the transposing kernel's square tile and the row kernel's strip, in
+ * pixels (the sizes at which the kernels' edge handling changes; for tests) */
+int ik_orient_tile(void);
+int ik_orient_strip(void);
+
 /* ---- fused / batched entry points (pixels stay in HBM) ----------------- */
 /* decode -> resize_image -> encode_image in one call (handler src/lib.rs:175-191) */
 int ik_transform(const uint8_t *bytes, size_t len, int64_t w, int64_t h, int fmt, int quality,
@@ -453,6 +482,13 @@ int ik_transform(const uint8_t *bytes, size_t len, int64_t w, int64_t h, int fmt
 /* ik_transform under a fit mode (ik_fit; IK_FIT_CONTAIN is ik_transform) */
 int ik_transform_fit(const uint8_t *bytes, size_t len, int64_t w, int64_t h, int fit, int fmt, int quality,
                      int filter, uint8_t **out, size_t *out_len);
+/* ik_transform_fit with the decoded image turned first (orient: ik_orient): fit, w and h
+ * refer to the oriented image, as apply_orientation followed by resize would in Rust (the
+ * turn is never done after the resize: the resampler's f32 sums would run in another
+ * order).  IK_ORIENT_STORED, or an effective orientation of 1, is ik_transform_fit: the
+ * same calls, no extra pass.  Scheduled over several devices as ik_transform_fit is. */
+int ik_transform_oriented(const uint8_t *bytes, size_t len, int64_t w, int64_t h, int fit, int orient, int fmt,
+                          int quality, int filter, uint8_t **out, size_t *out_len);
 
 /* ik_transform over n requests at once (the /img handler under load, loadtest C4
  * mix): decode_image (one set of GPU launches for the batch's PNG streams, one set
@@ -495,6 +531,22 @@ int ik_transform_batch_fit(const uint8_t *const *bytes, const size_t *lens, uint
 int ik_transform_batch_submit_fit(const uint8_t *const *bytes, const size_t *lens, uint32_t n, const int64_t *w,
                                   const int64_t *h, const int *fit, const int *fmt, const int *quality, int filter,
                                   int threads, uint8_t **outs, size_t *out_lens, int *status, uint64_t *ticket);
+/* ... and an orientation (ik_orient) per request; orient NULL, or all IK_ORIENT_STORED, is
+ * the _fit call.  IK_ORIENT_AUTO is resolved from the bytes at submit, on the host.  The
+ * turn runs in the post stage on the device that holds the decoded image, before the
+ * post plan (ik_post_plan_fit), which sees the oriented W, H and pitch: images of one
+ * (W, H, C, depth, orientation) are turned by one launch, a lone one by its own, and a
+ * request whose effective orientation is 1 is not touched.  Wait with
+ * ik_transform_batch_wait.  (ik_transform_batch_submit_device has no oriented form: its
+ * in-place JPEG marker walk steps over APP1.) */
+int ik_transform_batch_oriented(const uint8_t *const *bytes, const size_t *lens, uint32_t n, const int64_t *w,
+                                const int64_t *h, const int *fit, const int *orient, const int *fmt,
+                                const int *quality, int filter, int threads, uint8_t **outs, size_t *out_lens,
+                                int *status);
+int ik_transform_batch_submit_oriented(const uint8_t *const *bytes, const size_t *lens, uint32_t n, const int64_t *w,
+                                       const int64_t *h, const int *fit, const int *orient, const int *fmt,
+                                       const int *quality, int filter, int threads, uint8_t **outs, size_t *out_lens,
+                                       int *status, uint64_t *ticket);
 
 /* ik_transform_batch_submit over request bodies already in device memory (HBM)
  * of one device: dev_bytes[i] are device addresses (hipMalloc / ik_dev_alloc),
@@ -568,6 +620,20 @@ int ik_resize_window_batch_device(const uint8_t *dev_src, uint32_t W, uint32_t H
                                   size_t src_image_stride, uint32_t n, uint32_t iw, uint32_t ih, uint32_t x0,
                                   uint32_t y0, uint32_t nw, uint32_t nh, int filter, uint8_t *dev_dst,
                                   size_t dst_pitch, size_t dst_image_stride, void *hip_stream);
+/* apply_orientation over n images of W x H pixels of C samples of `depth` bytes (pixel
+ * size C * depth: 1, 2, 3, 4, 6 or 8), image i at dev_src + i*src_image_stride, written at
+ * dev_dst + i*dst_image_stride as W x H (orientation 1..4) or H x W (5..8) pixels.
+ * Orientation 1 is a pitched device copy.  Nothing outside out_w*C*depth bytes of each of
+ * the out_h destination rows is written, and nothing outside W*C*depth bytes of each of
+ * the H source rows is read.  Bases, pitches and strides that are all multiples of 4 take
+ * the dword path, any others the byte path.  Enqueued on hip_stream (NULL: the calling
+ * thread's stream) without waiting.  IK_ERR_INVALID, with nothing launched: orientation
+ * outside 1..8, a null pointer, a zero size, C outside 1..4, depth outside 1..2, a pitch
+ * below the row bytes, n > 1 with an image stride below rows * pitch, n above 65535, or
+ * (5..8) H above 65535 * 64. */
+int ik_orient_batch_device(const uint8_t *dev_src, uint32_t W, uint32_t H, uint32_t C, uint32_t depth,
+                           size_t src_pitch, size_t src_image_stride, uint32_t n, int orientation,
+                           uint8_t *dev_dst, size_t dst_pitch, size_t dst_image_stride, void *hip_stream);
 /* the WebP colour conversion (to_rgb8 + libwebp RGB->YUV420) on the device;
  * dev_yuv receives the Y (w*h), U and V ((w+1)/2 * (h+1)/2) planes back to back */
 int ik_webp_yuv420_device(const uint8_t *dev_src, uint32_t w, uint32_t h, uint32_t C,

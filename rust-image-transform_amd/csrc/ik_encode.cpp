@@ -521,6 +521,53 @@ int resize_group(const std::vector<ik_image*>& src, const FitWindow& win, int fi
     return rc;
 }
 
+// apply_orientation (2..8) over n images of one geometry (same W, H, C, depth, pitch) in
+// ONE launch, as resize_group: new images, the kernel reads the bases from a table.
+// Returns IK_ERR_UNSUPPORTED (nothing allocated) when a base is not 4-byte aligned (a
+// wrapped caller buffer); the caller then turns image by image.
+int orient_group(const std::vector<ik_image*>& src, int orientation, std::vector<ik_image*>& out) {
+    const size_t n = src.size();
+    out.assign(n, nullptr);
+    if (!n) return IK_OK;
+    const ik_image* s0 = src[0];
+    if (n > kOrientMaxImages || !s0->w || !s0->h) return IK_ERR_UNSUPPORTED;
+    for (const ik_image* im : src)
+        if ((uintptr_t)im->d & 3) return IK_ERR_UNSUPPORTED;
+    DeviceGuard g(s0->device);
+    const bool t = orientation >= 5;
+    std::vector<uint64_t> tab(2 * n);
+    for (size_t i = 0; i < n; ++i) {
+        const int st = alloc_image(t ? s0->h : s0->w, t ? s0->w : s0->h, s0->c, &out[i], s0->depth);
+        if (st) {
+            for (ik_image*& o : out) { ik_image_free(o); o = nullptr; }
+            return st;
+        }
+        tab[i] = (uint64_t)(uintptr_t)src[i]->d;
+        tab[n + i] = (uint64_t)(uintptr_t)out[i]->d;
+    }
+    hipStream_t s = thread_stream();
+    uint64_t* dtab = reinterpret_cast<uint64_t*>(scratch_slot(kScratchPtrTable, sizeof(uint64_t) * 2 * n));
+    uint8_t* ht = pinned_slot(kPinnedGroupStage, 16 * n);
+    void* dht = nullptr;
+    int rc = IK_OK;
+    if (!dtab) rc = fail(IK_ERR_DEVICE, "cannot allocate device scratch");
+    else if (!ht || hipHostGetDevicePointer(&dht, ht, 0) != hipSuccess || !dht)
+        rc = fail(IK_ERR_NOMEM, "cannot map pinned orientation table");
+    if (!rc) {
+        (void)hipStreamSynchronize(s);  // the previous table is read
+        std::memcpy(ht, tab.data(), 16 * n);
+        hipError_t e = launch_copy_words(reinterpret_cast<const uint32_t*>(dht), reinterpret_cast<uint32_t*>(dtab), 4 * n, s);
+        if (e == hipSuccess)
+            e = launch_orient(nullptr, s0->pitch, 0, nullptr, out[0]->pitch, 0, s0->w, s0->h, (int)(s0->c * s0->depth),
+                              orientation, (int)n, s, dtab, dtab + n);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) rc = hip_fail(e, "orientation (batched)");
+    }
+    if (rc)
+        for (ik_image*& o : out) { ik_image_free(o); o = nullptr; }
+    return rc;
+}
+
 // ik_shutdown: the batched colour launches' pinned blocks, the per-device constant tables
 void encode_shutdown() {
     {

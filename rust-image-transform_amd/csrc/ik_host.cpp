@@ -25,6 +25,7 @@
 #include <deque>
 
 #include "../../include/imagekit_hip.h"
+#include "ik_exif.h"
 #include "ik_png.h"
 #include "ik_runtime.h"
 #include "ik_jpeg_walk.h"
@@ -911,6 +912,63 @@ int ik_resize_fit(ik_image* img, int64_t w, int64_t h, int fit, int filter, ik_i
     return ik_resize_window(img, f[0], f[1], f[2], f[3], f[4], f[5], filter, out);
 }
 
+int ik_exif_orientation(const uint8_t* bytes, size_t len) { return exif_orientation(bytes, len); }
+
+int ik_orient_tile(void) { return kOrientTile; }
+int ik_orient_strip(void) { return kOrientStrip; }
+
+int ik_orient_batch_device(const uint8_t* dev_src, uint32_t W, uint32_t H, uint32_t C, uint32_t depth, size_t src_pitch,
+                           size_t src_image_stride, uint32_t n, int orientation, uint8_t* dev_dst, size_t dst_pitch,
+                           size_t dst_image_stride, void* hip_stream) {
+    IK_API_ENTER();
+    if (orientation < 1 || orientation > 8) return fail(IK_ERR_INVALID, "orientation %d outside 1..8", orientation);
+    if (!dev_src || !dev_dst) return fail(IK_ERR_INVALID, "null device pointer");
+    if (C < 1 || C > 4 || depth < 1 || depth > 2 || !W || !H || !n) return fail(IK_ERR_INVALID, "bad geometry");
+    const bool t = orientation >= 5;
+    const uint32_t ow = t ? H : W, oh = t ? W : H;
+    const size_t px = (size_t)C * depth;
+    if (src_pitch < W * px || dst_pitch < ow * px) return fail(IK_ERR_INVALID, "pitch too small");
+    if (n > 1 && (src_image_stride < src_pitch * H || dst_image_stride < dst_pitch * oh))
+        return fail(IK_ERR_INVALID, "image stride too small");
+    if (n > kOrientMaxImages) return fail(IK_ERR_INVALID, "more than %u images", kOrientMaxImages);
+    if (t && H > 65535u * kOrientTile) return fail(IK_ERR_INVALID, "image too tall to transpose");
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : thread_stream();
+    if (orientation == 1) {  // a plain pitched copy
+        for (uint32_t i = 0; i < n; ++i)
+            IK_HIP(hipMemcpy2DAsync(dev_dst + i * dst_image_stride, dst_pitch, dev_src + i * src_image_stride, src_pitch,
+                                    W * px, H, hipMemcpyDeviceToDevice, s));
+        return IK_OK;
+    }
+    const hipError_t e = launch_orient(dev_src, src_pitch, src_image_stride, dev_dst, dst_pitch, dst_image_stride, W, H,
+                                       (int)px, orientation, (int)n, s);
+    if (e != hipSuccess) return hip_fail(e, "orientation kernel launch");
+    return IK_OK;
+}
+
+// DynamicImage::apply_orientation: a new image on the device that holds img
+int ik_image_orient(const ik_image* img, int orientation, ik_image** out) {
+    IK_API_ENTER();
+    if (!img || !out) return fail(IK_ERR_INVALID, "null pointer");
+    if (orientation < 1 || orientation > 8) return fail(IK_ERR_INVALID, "orientation %d outside 1..8", orientation);
+    DeviceGuard g(img->device);
+    const bool t = orientation >= 5;
+    ik_image* o = nullptr;
+    int rc = alloc_image(t ? img->h : img->w, t ? img->w : img->h, img->c, &o, img->depth);
+    if (rc) return rc;
+    if (img->w && img->h) {
+        hipStream_t s = thread_stream();
+        rc = ik_orient_batch_device(img->d, img->w, img->h, img->c, img->depth, img->pitch, 0, 1, orientation, o->d,
+                                    o->pitch, 0, s);
+        if (rc == IK_OK) {
+            const hipError_t e = hipStreamSynchronize(s);
+            if (e != hipSuccess) rc = hip_fail(e, "orientation");
+        }
+    }
+    if (rc) { ik_image_free(o); return rc; }
+    *out = o;
+    return IK_OK;
+}
+
 int ik_encode(const ik_image* img, int fmt, int quality, uint8_t** out, size_t* out_len) {
     IK_API_ENTER();
     if (!img || !out || !out_len) return fail(IK_ERR_INVALID, "null pointer");
@@ -1097,6 +1155,30 @@ int ik_decode(const uint8_t* bytes, size_t len, ik_image** out, int* fmt_out) {
     return st;
 }
 
+// the orientation an `orient` argument (ik_orient) means for these bytes: 0 = none
+// (stored order, or an effective 1: no pass), 2..8, or -1 for a bad argument
+static int effective_orientation(const uint8_t* bytes, size_t len, int orient) {
+    if (orient < IK_ORIENT_AUTO || orient > 8) return -1;
+    const int o = orient == IK_ORIENT_AUTO ? exif_orientation(bytes, len) : orient;
+    return o <= 1 ? 0 : o;
+}
+
+int ik_decode_oriented(const uint8_t* bytes, size_t len, int orient, ik_image** out, int* fmt_out) {
+    IK_API_ENTER();
+    const int o = effective_orientation(bytes, len, orient);
+    if (o < 0) return fail(IK_ERR_INVALID, "unknown orientation %d", orient);
+    if (!out) return fail(IK_ERR_INVALID, "null pointer");
+    ik_image* img = nullptr;
+    int st = ik_decode(bytes, len, &img, fmt_out);
+    if (st || !o) {
+        if (!st) *out = img;
+        return st;
+    }
+    st = ik_image_orient(img, o, out);
+    ik_image_free(img);
+    return st;
+}
+
 int ik_decode_batch(const uint8_t* const* bytes, const size_t* lens, uint32_t n, ik_image** outs, int* fmts,
                     int* status) {
     IK_API_ENTER();
@@ -1241,8 +1323,9 @@ static void transform_decode_phase(const uint8_t* const* bytes, const size_t* le
 // Device half, post stage: resize, the encoders' device front ends (under the
 // post gate, so a batch's resize runs beside the next batch's decode kernels);
 // request i's status / message land in st[i] / errs[i]
-static void transform_post_phase(const int64_t* w, const int64_t* h, const int* fit, const int* fmt, const int* quality,
-                                 int filter, int* st, std::string* errs, HostPhase& hp) {
+// orient: null, or each request's effective orientation (0 = as stored, 2..8)
+static void transform_post_phase(const int64_t* w, const int64_t* h, const int* fit, const int* orient, const int* fmt,
+                                 const int* quality, int filter, int* st, std::string* errs, HostPhase& hp) {
     const std::vector<uint32_t>& idx = hp.idx;
     const int threads = hp.threads;
     const uint32_t m = (uint32_t)idx.size();
@@ -1262,6 +1345,41 @@ static void transform_post_phase(const int64_t* w, const int64_t* h, const int* 
     hp.bytes_out.assign(m, std::vector<uint8_t>());
     std::vector<EncodePrep>& prep = hp.prep;
     std::vector<std::vector<uint8_t>>& bytes_out = hp.bytes_out;
+    // apply_orientation first, on the device that holds each decoded image: the post plan
+    // below sees the oriented W, H and pitch.  Images of one (W, H, C, depth, pitch,
+    // orientation) go through one launch, a lone one through its own; the stored-order
+    // image returns to the pool once it has been turned.
+    if (orient) {
+        std::map<std::array<uint64_t, 7>, std::vector<uint32_t>> turn;
+        for (uint32_t k = 0; k < m; ++k) {
+            const ik_image* im = imgs[k];
+            if (ds[k] || !im || !orient[idx[k]]) continue;
+            turn[{im->w, im->h, im->c, im->depth, im->pitch, (uint64_t)im->device, (uint64_t)orient[idx[k]]}].push_back(k);
+        }
+        for (const auto& kv : turn) {
+            const std::vector<uint32_t>& ks = kv.second;
+            const int o = (int)kv.first[6];
+            std::vector<ik_image*> out(ks.size(), nullptr);
+            bool grouped = false;
+            if (ks.size() > 1) {
+                std::vector<ik_image*> src;
+                for (uint32_t k : ks) src.push_back(imgs[k]);
+                grouped = orient_group(src, o, out) == IK_OK;
+            }
+            for (size_t j = 0; j < ks.size(); ++j) {
+                const uint32_t k = ks[j];
+                if (!grouped) {
+                    if (int r = ik_image_orient(imgs[k], o, &out[j])) {
+                        ds[k] = r;
+                        dm[k] = last_error_str();
+                        out[j] = nullptr;
+                    }
+                }
+                ik_image_free(imgs[k]);
+                imgs[k] = out[j];
+            }
+        }
+    }
     // which launch resizes each request and which coder writes its file: ik_post_plan.h
     // (the encoder setting and the mixed mode are read once for the batch)
     std::vector<PostRequest> rq(m);
@@ -1440,6 +1558,9 @@ struct Ticket {
     // back (by device address), and the skeletons' bytes
     JpegInPlaceMap jin;
     std::vector<uint8_t> jskel;
+    // ik_transform_batch_submit_oriented: each request's effective orientation, resolved
+    // at submit (0 = as stored, 2..8); empty when no request is turned
+    std::vector<int> orient;
 };
 
 // one device's share of a ticket
@@ -1450,6 +1571,7 @@ struct BatchPart {
     const int64_t* w = nullptr;
     const int64_t* h = nullptr;
     const int* fit = nullptr;  // null: every request IK_FIT_CONTAIN
+    const int* orient = nullptr;  // null: every request as stored; else Ticket::orient
     const int* fmt = nullptr;
     const int* quality = nullptr;
     int filter = 0;
@@ -1524,8 +1646,8 @@ private:
             if (stage == 2) {
                 // resize + the encoders' device front ends, beside the next batch's decode
                 Ticket& t = *p->t;
-                transform_post_phase(p->w, p->h, p->fit, p->fmt, p->quality, p->filter, t.st.data(), t.errs.data(),
-                                     p->hp);
+                transform_post_phase(p->w, p->h, p->fit, p->orient, p->fmt, p->quality, p->filter, t.st.data(),
+                                     t.errs.data(), p->hp);
                 pool_->post([p] {
                     Ticket& tk = *p->t;
                     transform_host_phase(tk.outs, tk.out_lens, tk.st.data(), tk.errs.data(), p->hp);
@@ -1688,6 +1810,7 @@ int submit_parts(const std::shared_ptr<Ticket>& t, const uint8_t* const* bytes, 
         auto p = std::make_shared<BatchPart>();
         p->t = t;
         p->bytes = bytes; p->lens = lens; p->w = w; p->h = h; p->fit = fit; p->fmt = fmt; p->quality = quality;
+        p->orient = t->orient.empty() ? nullptr : t->orient.data();
         p->sniff = sniff;
         p->filter = filter;
         p->hp.threads = threads;
@@ -1769,6 +1892,36 @@ int ik_transform_batch_submit_fit(const uint8_t* const* bytes, const size_t* len
         if (fit[i] < IK_FIT_CONTAIN || fit[i] > IK_FIT_EXACT)
             return fail(IK_ERR_INVALID, "request %u: unknown fit %d", i, fit[i]);
     auto t = new_ticket(n, outs, out_lens, status);
+    return submit_parts(t, bytes, nullptr, -1, lens, n, w, h, fit, fmt, quality, filter, threads, ticket);
+}
+
+int ik_transform_batch_submit_oriented(const uint8_t* const* bytes, const size_t* lens, uint32_t n, const int64_t* w,
+                                       const int64_t* h, const int* fit, const int* orient, const int* fmt,
+                                       const int* quality, int filter, int threads, uint8_t** outs, size_t* out_lens,
+                                       int* status, uint64_t* ticket) {
+    IK_API_ENTER();
+    if (!bytes || !lens || !w || !h || !fmt || !quality || !outs || !out_lens || !n || !ticket)
+        return fail(IK_ERR_INVALID, "bad batch");
+    // AUTO is resolved here, on the host: a header walk of a few hundred bytes per file
+    std::vector<int> eff;
+    bool any = false;
+    for (uint32_t i = 0; orient && i < n; ++i) {
+        if (orient[i] == IK_ORIENT_STORED) continue;  // (also keeps an all-STORED batch off the files)
+        const int o = effective_orientation(bytes[i], lens[i], orient[i]);
+        if (o < 0) return fail(IK_ERR_INVALID, "request %u: unknown orientation %d", i, orient[i]);
+        if (!o) continue;
+        if (!any) eff.assign(n, 0);
+        any = true;
+        eff[i] = o;
+    }
+    if (!any)  // nothing to turn: the _fit call itself
+        return ik_transform_batch_submit_fit(bytes, lens, n, w, h, fit, fmt, quality, filter, threads, outs, out_lens,
+                                             status, ticket);
+    for (uint32_t i = 0; fit && i < n; ++i)
+        if (fit[i] < IK_FIT_CONTAIN || fit[i] > IK_FIT_EXACT)
+            return fail(IK_ERR_INVALID, "request %u: unknown fit %d", i, fit[i]);
+    auto t = new_ticket(n, outs, out_lens, status);
+    t->orient.swap(eff);
     return submit_parts(t, bytes, nullptr, -1, lens, n, w, h, fit, fmt, quality, filter, threads, ticket);
 }
 
@@ -1950,11 +2103,31 @@ int ik_transform_batch_fit(const uint8_t* const* bytes, const size_t* lens, uint
     return ik_transform_batch_wait(ticket);
 }
 
-static int transform_here(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int fmt, int quality,
-                          int filter, uint8_t** out, size_t* out_len) {
+int ik_transform_batch_oriented(const uint8_t* const* bytes, const size_t* lens, uint32_t n, const int64_t* w,
+                                const int64_t* h, const int* fit, const int* orient, const int* fmt,
+                                const int* quality, int filter, int threads, uint8_t** outs, size_t* out_lens,
+                                int* status) {
+    IK_API_ENTER();
+    uint64_t ticket = 0;
+    if (int rc = ik_transform_batch_submit_oriented(bytes, lens, n, w, h, fit, orient, fmt, quality, filter, threads,
+                                                    outs, out_lens, status, &ticket))
+        return rc;
+    return ik_transform_batch_wait(ticket);
+}
+
+// orientation: 0 = the pixels as stored, 2..8 = turned first (effective_orientation)
+static int transform_here(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orientation, int fmt,
+                          int quality, int filter, uint8_t** out, size_t* out_len) {
     ik_image* img = nullptr;
     int st = decode_one(bytes, len, &img, nullptr);
     if (st) return st;
+    if (orientation) {
+        ik_image* turned = nullptr;
+        st = ik_image_orient(img, orientation, &turned);
+        ik_image_free(img);
+        if (st) return st;
+        img = turned;
+    }
     ik_image* rs = nullptr;
     st = ik_resize_fit(img, w, h, fit, filter, &rs);
     if (st) { ik_image_free(img); return st; }
@@ -1970,10 +2143,27 @@ int ik_transform(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fmt
     return ik_transform_fit(bytes, len, w, h, IK_FIT_CONTAIN, fmt, quality, filter, out, out_len);
 }
 
+static int transform_scheduled(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orientation, int fmt,
+                               int quality, int filter, uint8_t** out, size_t* out_len);
+
 int ik_transform_fit(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int fmt, int quality,
                      int filter, uint8_t** out, size_t* out_len) {
     IK_API_ENTER();
-    if (!sched_multi()) return transform_here(bytes, len, w, h, fit, fmt, quality, filter, out, out_len);
+    return transform_scheduled(bytes, len, w, h, fit, 0, fmt, quality, filter, out, out_len);
+}
+
+int ik_transform_oriented(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orient, int fmt,
+                          int quality, int filter, uint8_t** out, size_t* out_len) {
+    IK_API_ENTER();
+    const int o = effective_orientation(bytes, len, orient);
+    if (o < 0) return fail(IK_ERR_INVALID, "unknown orientation %d", orient);
+    return transform_scheduled(bytes, len, w, h, fit, o, fmt, quality, filter, out, out_len);
+}
+
+// on this device, or (several devices) on the least-loaded one's workers
+static int transform_scheduled(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orientation, int fmt,
+                               int quality, int filter, uint8_t** out, size_t* out_len) {
+    if (!sched_multi()) return transform_here(bytes, len, w, h, fit, orientation, fmt, quality, filter, out, out_len);
     // several devices: queue the request to the least-loaded device's workers
     const uint64_t cost = request_cost(bytes, len, w, h, fmt);
     const int ld = sched_acquire(cost);
@@ -1983,7 +2173,7 @@ int ik_transform_fit(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int
     int st = IK_OK;
     std::string msg;
     sched_pool(ld).post([&] {
-        const int r = transform_here(bytes, len, w, h, fit, fmt, quality, filter, out, out_len);
+        const int r = transform_here(bytes, len, w, h, fit, orientation, fmt, quality, filter, out, out_len);
         std::string m = r ? last_error_str() : std::string();
         std::lock_guard<std::mutex> lk(mu);
         st = r;

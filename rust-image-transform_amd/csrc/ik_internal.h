@@ -268,6 +268,18 @@ inline JpegEncGeom jpeg_enc_geom(uint32_t w, uint32_t h) {
     return JpegEncGeom{nmcu, nmcu * 3 * 64 * sizeof(int16_t), cap, 2 * cap};
 }
 
+// ---- EXIF orientation (ik_orient.hip) ----
+// apply_orientation over n images of W x H pixels of px = C * depth bytes (1, 2, 3, 4, 6
+// or 8): orientation 2..8 (1 is a copy: the callers use hipMemcpy2DAsync).  Transposing
+// kinds (5..8) write H x W pixels.  Images i at src + i * src_img_stride, or at
+// src_tab[i] / dst_tab[i] (device arrays of 4-byte-aligned bases) when those are given.
+constexpr int kOrientTile = 64;    // the transposing kernel's tile edge, pixels
+constexpr int kOrientStrip = 256;  // pixels of a row one wave of the row kernel takes
+constexpr uint32_t kOrientMaxImages = 65535;  // grid.z
+hipError_t launch_orient(const uint8_t* src, size_t src_pitch, size_t src_img_stride, uint8_t* dst, size_t dst_pitch,
+                         size_t dst_img_stride, uint32_t W, uint32_t H, int px, int orientation, int n, hipStream_t s,
+                         const uint64_t* src_tab = nullptr, const uint64_t* dst_tab = nullptr);
+
 // ---- plans (ik_plan.cpp) ----
 // axis_weights, required_slots and the tables themselves: ik_resize_plan.h
 ResizePlan* get_resize_plan(int device, int W, int H, int C, int nw, int nh, int filter, int n);

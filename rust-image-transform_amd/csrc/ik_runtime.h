@@ -211,8 +211,9 @@ uint8_t* pinned_slot(int slot, size_t bytes);  // per-thread grow-only pinned ho
 constexpr int kScratchDefault = 0;
 // copy_h2d_2d / copy_d2h_2d's staging; each copy synchronises the stream before it returns
 constexpr int kPinnedStaging = 0;
-// a group launch's table of image base pointers, webp_front_group's and resize_group's:
-// both run on one thread and synchronise the stream after the launch that reads the table
+// a group launch's table of image base pointers, webp_front_group's, resize_group's and
+// orient_group's (which stages it in kPinnedGroupStage as resize_group does): all run on
+// one thread and synchronise the stream after the launch that reads the table
 constexpr int kScratchPtrTable = 3;
 // jpeg_front_group's device work area: quantisation tables, source table, coefficients, Huffman work
 constexpr int kScratchJpegGroup = 4;
@@ -465,6 +466,9 @@ void encode_shutdown();  // ik_shutdown: their pinned blocks, the per-device con
 // (ik_encode.cpp)
 int resize_target(uint32_t W, uint32_t H, int64_t w, int64_t h, uint32_t* nw, uint32_t* nh);
 int resize_group(const std::vector<ik_image*>& src, const FitWindow& win, int filter, std::vector<ik_image*>& out);
+// apply_orientation (2..8) of same-geometry images in one launch (ik_encode.cpp); a return
+// other than IK_OK leaves every image to ik_image_orient
+int orient_group(const std::vector<ik_image*>& src, int orientation, std::vector<ik_image*>& out);
 
 // Per-device phase gates (ik_pool.cpp).  Concurrent batch calls on one device
 // take its GPU phases in turn: kGateUpload covers a PNG batch's staging, H2D and

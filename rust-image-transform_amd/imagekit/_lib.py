@@ -140,6 +140,15 @@ SIGNATURES = [
      + [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint32)]
      + [ctypes.POINTER(ctypes.c_int64)] * 2 + [ctypes.POINTER(ctypes.c_int)] * 3 + [ctypes.c_int, ctypes.c_int]
      + [ctypes.POINTER(ctypes.c_uint32)] * 2 + [ctypes.POINTER(ctypes.c_int)] * 3 + [ctypes.POINTER(ctypes.c_uint32)] * 2),
+    ("ik_exif_orientation", ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t]),
+    ("ik_orient_tile", ctypes.c_int, []),
+    ("ik_orient_strip", ctypes.c_int, []),
+    ("ik_image_orient", ctypes.c_int, [c_img_p, ctypes.c_int, ctypes.POINTER(c_img_p)]),
+    ("ik_decode_oriented", ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(c_img_p), ctypes.POINTER(ctypes.c_int)]),
+    ("ik_orient_batch_device", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_uint32] * 4 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]),
+    ("ik_transform_oriented", ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int] * 5 + [ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t)]),
+    ("ik_transform_batch_oriented", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint32, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)] + [ctypes.POINTER(ctypes.c_int)] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]),
+    ("ik_transform_batch_submit_oriented", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint32, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)] + [ctypes.POINTER(ctypes.c_int)] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint64)]),
 ]
 
 

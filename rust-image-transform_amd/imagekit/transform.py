@@ -55,6 +55,47 @@ def _fits(fits, n):
     return (ctypes.c_int * n)(*[int(FitMode(f)) for f in fits])
 
 
+class Orientation(enum.IntEnum):
+    """ik_orient / image::metadata::Orientation by its EXIF value: what the `orient=`
+    arguments take.  stored (the default everywhere) leaves the pixels as the file holds
+    them, as the reference's decode_image does; auto applies the file's EXIF Orientation
+    (exif_orientation); the eight values apply that one whatever the file says."""
+
+    auto = -1
+    stored = 0
+    no_transforms = 1
+    flip_horizontal = 2
+    rotate180 = 3
+    flip_vertical = 4
+    rotate90_flip_h = 5
+    rotate90 = 6
+    rotate270_flip_h = 7
+    rotate270 = 8
+
+
+def _orient(o) -> int:
+    try:
+        return int(Orientation(o))
+    except ValueError:
+        raise InvalidArgument(f"unknown orientation {o!r}") from None
+
+
+def _orients(orients, n):
+    """The per-request orientation array of a batch call, or None (every request stored)."""
+    if orients is None:
+        return None
+    if len(orients) != n:
+        raise InvalidArgument("orients must have one entry per request")
+    return (ctypes.c_int * n)(*[_orient(o) for o in orients])
+
+
+def exif_orientation(data: bytes) -> int:
+    """ImageDecoder::orientation() as its EXIF value, 1..8: JPEG APP1, PNG eXIf, WebP EXIF;
+    1 when the file carries none or it cannot be read (ik_exif_orientation; host only)."""
+    b = bytes(data)
+    return int(_lib.load().ik_exif_orientation(b, len(b)))
+
+
 _COLOR = {1: "L8", 2: "La8", 3: "Rgb8", 4: "Rgba8"}
 
 
@@ -158,6 +199,18 @@ class DynamicImage:
         the centre (only the kept window is computed)."""
         return resize_image(self, nw, nh, filter, fit=FitMode.cover)
 
+    def apply_orientation(self, o) -> "DynamicImage":
+        """DynamicImage::apply_orientation as a new image (ik_image_orient): o is an EXIF
+        value 1..8 (Orientation); 1 copies."""
+        o = _orient(o)
+        if not 1 <= o <= 8:
+            raise InvalidArgument("apply_orientation takes an EXIF value 1..8")
+        out = ctypes.c_void_p()
+        st = _lib.load().ik_image_orient(self._h, o, ctypes.byref(out))
+        if st:
+            _raise(st, "apply_orientation")
+        return DynamicImage(out.value)
+
     def clone(self) -> "DynamicImage":
         return DynamicImage.from_array(self.to_array())
 
@@ -172,13 +225,18 @@ class DynamicImage:
         return f"DynamicImage({_COLOR[c]}, {w}x{h}, device)"
 
 
-def decode_image(data: bytes) -> Tuple[DynamicImage, Optional[ImageFormat]]:
-    """src/transform.rs:27-43 -- guess_format + load_from_memory_with_format."""
+def decode_image(data: bytes, orient=Orientation.stored) -> Tuple[DynamicImage, Optional[ImageFormat]]:
+    """src/transform.rs:27-43 -- guess_format + load_from_memory_with_format.  orient (an
+    extension: Orientation) turns the decoded image; the default leaves it as stored."""
     lib = _lib.load()
     b = bytes(data)
     out = ctypes.c_void_p()
     fmt = ctypes.c_int(-1)
-    st = lib.ik_decode(b, len(b), ctypes.byref(out), ctypes.byref(fmt))
+    o = _orient(orient)
+    if o == Orientation.stored:
+        st = lib.ik_decode(b, len(b), ctypes.byref(out), ctypes.byref(fmt))
+    else:
+        st = lib.ik_decode_oriented(b, len(b), o, ctypes.byref(out), ctypes.byref(fmt))
     if st:
         raise TransformError(_lib.last_error())
     f = None if fmt.value < 0 else ImageFormat(fmt.value)
@@ -275,10 +333,11 @@ def _inputs(datas):
 
 
 def transform_batch(datas, sizes, fmts, qualities, filter: "FilterType" = None, threads: int = 0,
-                    fits=None) -> List[bytes]:
+                    fits=None, orient=None) -> List[bytes]:
     """ik_transform_batch: decode -> resize_image -> encode_image for many requests
     (sizes: (w, h) per request, None = unset; fmts: ImageFormat per request; fits: a
-    FitMode per request, None = contain for all)."""
+    FitMode per request, None = contain for all; orient: an Orientation per request,
+    None = stored for all)."""
     lib = _lib.load()
     bufs, ptrs, lens = _inputs(datas)
     n = len(bufs)
@@ -293,7 +352,10 @@ def transform_batch(datas, sizes, fmts, qualities, filter: "FilterType" = None, 
     olens = (ctypes.c_size_t * n)()
     status = (ctypes.c_int * n)()
     fa = _fits(fits, n)
-    if fa is None:
+    oa = _orients(orient, n)
+    if oa is not None:
+        st = lib.ik_transform_batch_oriented(ptrs, lens, n, ws, hs, fa, oa, fs, qs, filt, threads, outs, olens, status)
+    elif fa is None:
         st = lib.ik_transform_batch(ptrs, lens, n, ws, hs, fs, qs, filt, threads, outs, olens, status)
     else:
         st = lib.ik_transform_batch_fit(ptrs, lens, n, ws, hs, fa, fs, qs, filt, threads, outs, olens, status)
@@ -334,7 +396,7 @@ class PendingBatch:
 
 
 def transform_batch_submit(datas, sizes, fmts, qualities, filter: "FilterType" = None,
-                           threads: int = 0, fits=None) -> PendingBatch:
+                           threads: int = 0, fits=None, orient=None) -> PendingBatch:
     """ik_transform_batch_submit: the device half of transform_batch now, the host
     coders in the background; PendingBatch.wait() gives what transform_batch gives."""
     lib = _lib.load()
@@ -352,7 +414,11 @@ def transform_batch_submit(datas, sizes, fmts, qualities, filter: "FilterType" =
     status = (ctypes.c_int * n)()
     ticket = ctypes.c_uint64()
     fa = _fits(fits, n)
-    if fa is None:
+    oa = _orients(orient, n)
+    if oa is not None:
+        st = lib.ik_transform_batch_submit_oriented(ptrs, lens, n, ws, hs, fa, oa, fs, qs, filt, threads, outs, olens,
+                                                    status, ctypes.byref(ticket))
+    elif fa is None:
         st = lib.ik_transform_batch_submit(ptrs, lens, n, ws, hs, fs, qs, filt, threads, outs, olens, status,
                                            ctypes.byref(ticket))
     else:
@@ -360,7 +426,7 @@ def transform_batch_submit(datas, sizes, fmts, qualities, filter: "FilterType" =
                                                ctypes.byref(ticket))
     if st:
         raise TransformError(_lib.last_error())
-    return PendingBatch((bufs, ptrs, lens, ws, hs, fs, qs, fa), outs, olens, status, ticket.value, n)
+    return PendingBatch((bufs, ptrs, lens, ws, hs, fs, qs, fa, oa), outs, olens, status, ticket.value, n)
 
 
 def transform_batch_submit_device(datas, sizes, fmts, qualities, filter: "FilterType" = None,
@@ -425,15 +491,24 @@ def encode_image(img: DynamicImage, fmt: ImageFormat, quality: int) -> bytes:
 
 
 def transform(data: bytes, w: Optional[int], h: Optional[int], fmt: ImageFormat, quality: int,
-              filter: FilterType = FilterType.Lanczos3, fit: FitMode = FitMode.contain) -> bytes:
-    """decode -> resize_image -> encode_image in one device-resident call."""
+              filter: FilterType = FilterType.Lanczos3, fit: FitMode = FitMode.contain,
+              orient=Orientation.stored) -> bytes:
+    """decode -> resize_image -> encode_image in one device-resident call; with orient
+    (Orientation) the decoded image is turned first, and w, h and fit refer to the turned
+    image."""
     lib = _lib.load()
     b = bytes(data)
     buf = _lib.u8p()
     n = ctypes.c_size_t()
-    st = lib.ik_transform_fit(b, len(b), -1 if w is None else int(w), -1 if h is None else int(h),
-                              int(FitMode(fit)), ImageFormat(fmt).value, int(quality), int(filter), ctypes.byref(buf),
-                              ctypes.byref(n))
+    o = _orient(orient)
+    if o == Orientation.stored:
+        st = lib.ik_transform_fit(b, len(b), -1 if w is None else int(w), -1 if h is None else int(h),
+                                  int(FitMode(fit)), ImageFormat(fmt).value, int(quality), int(filter),
+                                  ctypes.byref(buf), ctypes.byref(n))
+    else:
+        st = lib.ik_transform_oriented(b, len(b), -1 if w is None else int(w), -1 if h is None else int(h),
+                                       int(FitMode(fit)), o, ImageFormat(fmt).value, int(quality), int(filter),
+                                       ctypes.byref(buf), ctypes.byref(n))
     if st:
         raise TransformError(_lib.last_error())
     try:

@@ -110,6 +110,10 @@ def main():
     ap.add_argument("--fit", choices=["contain", "cover"], default="contain",
                     help="contain: resize_image as the reference calls it; cover: every request filled and cropped "
                          "to its w x h (ik_transform_batch*_fit)")
+    ap.add_argument("--orient", choices=["stored", "auto"], default="stored",
+                    help="stored: the calls without an orientation, as before; auto: every request passes "
+                         "IK_ORIENT_AUTO (ik_transform_batch*_oriented; the sources here carry no EXIF, so no "
+                         "image is turned: it measures the header walk at submit)")
     ap.add_argument("--restart", action="store_true")
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--seed", type=int, default=0)
@@ -146,7 +150,7 @@ def main():
         dist.init_process_group(backend="nccl" if torch.cuda.is_available() else "gloo")
     if torch.cuda.is_available():
         torch.cuda.set_device(local)
-    from imagekit import FitMode, ImageFormat, _lib, transform_batch, transform_batch_submit
+    from imagekit import FitMode, ImageFormat, Orientation, _lib, transform_batch, transform_batch_submit
     lib = _lib.load()
     queue = world == 1
     assert lib.ik_init(-1 if queue else local) == 0, _lib.last_error()
@@ -158,10 +162,13 @@ def main():
     def fits(chunk):  # None: the calls without a fit, as before
         return [FitMode.cover] * len(chunk) if args.fit == "cover" else None
 
+    def orients(chunk):  # None: the calls without an orientation, as before
+        return [Orientation.auto] * len(chunk) if args.orient == "auto" else None
+
     def run_batch(chunk):
         return transform_batch([srcs[s] for s, _, _, _ in chunk], [(w, h) for _, w, h, _ in chunk],
                                [f for _, _, _, f in chunk], [args.quality] * len(chunk), threads=args.threads,
-                               fits=fits(chunk))
+                               fits=fits(chunk), orient=orients(chunk))
 
     run_batch(mine[:min(len(mine), 8)])  # warm-up: plans, streams, pinned staging
 
@@ -200,7 +207,7 @@ def main():
                 continue
             p = transform_batch_submit([srcs[s] for s, _, _, _ in chunk], [(w, h) for _, w, h, _ in chunk],
                                        [f for _, _, _, f in chunk], [args.quality] * len(chunk), threads=args.threads,
-                                       fits=fits(chunk))
+                                       fits=fits(chunk), orient=orients(chunk))
             if pend is not None:
                 done(pend[0], pend[1].wait())
             pend = (tb, p)
