@@ -475,6 +475,53 @@ int ik_decode_oriented(const uint8_t *bytes, size_t len, int orient, ik_image **
 int ik_orient_tile(void);
 int ik_orient_strip(void);
 
+/* ---- background flatten ------------------------------------------------- */
+/* encode_image goes through to_rgb8 for JPEG and WebP, which drops the alpha channel: the
+ * colours under alpha 0 become visible, and the (non-premultiplying, bit-exact) resampler
+ * has already bled them into opaque edges.  The calls below are the opt-in remedy: the
+ * decoded image composited onto a constant colour BEFORE the resize, pixels staying in HBM.
+ * The image crate has no such call; the arithmetic is this project's own definition
+ * (DESIGN section 4).  With the background b per channel given as 0xRRGGBB, a sample c with
+ * alpha a, and M = 255 (8-bit) or 65535 (16-bit, where b = b8 * 257):
+ *     out = (c*a + b*(M - a) + M/2) / M        (integers, floor division)
+ * the integer nearest to the exact quotient (M is odd: no ties); a = 0 gives b, a = M gives c.
+ *     Rgba                          -> Rgb
+ *     LumaA, colour with R == G == B -> Luma
+ *     LumaA, any other colour        -> Rgb (luma replicated, as to_rgb8 replicates it)
+ *     Luma, Rgb                      -> as they are: no pass
+ * The depth is kept.  Flatten-then-resize equals a premultiplied resample followed by the
+ * composite, apart from one rounding of the flattened pixels to integers (the resampler is
+ * linear and its weights sum to 1), so no transparent pixel's colour reaches an output. */
+#define IK_BG_NONE (-1)
+/* the image flattened onto `background` (0x000000..0xFFFFFF) as a new image on the device
+ * that holds img; an image without alpha, or IK_BG_NONE, gives a copy.  Any other
+ * background is IK_ERR_INVALID. */
+int ik_image_flatten(const ik_image *img, int32_t background, ik_image **out);
+/* the pixels of a row one workgroup of the flatten kernel takes, and the most rows of
+ * workgroups in a launch (further rows are grid-strided): the sizes at which the kernel's
+ * edge handling changes; for tests */
+int ik_flatten_span(void);
+int ik_flatten_row_cap(void);
+/* process-wide: out[0] flatten kernel launches, out[1] images flattened by them */
+int ik_flatten_counters(unsigned long long out[2]);
+
+/* ---- per-request options ------------------------------------------------ */
+/* What the *_opts entry points take for each request, in place of one suffixed entry
+ * point per option.  Defaults: IK_FIT_CONTAIN, IK_ORIENT_STORED, IK_BG_NONE; with every
+ * request at its defaults (or opts NULL) an *_opts call makes the very calls of the entry
+ * point without options.  The order is decode -> orient -> flatten -> resize -> encode: fit,
+ * w and h refer to the oriented image, and the background applies whatever the output
+ * format (an AVIF request with a background is opaque and carries no alpha plane).
+ * opt_size must be sizeof(ik_request_opts) as this header declares it; any other value is
+ * IK_ERR_INVALID ("unknown options size") before any device work, which is what lets the
+ * struct grow.  A fit outside ik_fit, an orient outside ik_orient / 1..8 and a background
+ * that is neither IK_BG_NONE nor 0x000000..0xFFFFFF are IK_ERR_INVALID. */
+typedef struct {
+    int fit;            /* ik_fit */
+    int orient;         /* ik_orient, or 1..8 */
+    int32_t background; /* IK_BG_NONE, or 0xRRGGBB */
+} ik_request_opts;
+
 /* ---- fused / batched entry points (pixels stay in HBM) ----------------- */
 /* decode -> resize_image -> encode_image in one call (handler src/lib.rs:175-191) */
 int ik_transform(const uint8_t *bytes, size_t len, int64_t w, int64_t h, int fmt, int quality,
@@ -489,6 +536,12 @@ int ik_transform_fit(const uint8_t *bytes, size_t len, int64_t w, int64_t h, int
  * same calls, no extra pass.  Scheduled over several devices as ik_transform_fit is. */
 int ik_transform_oriented(const uint8_t *bytes, size_t len, int64_t w, int64_t h, int fit, int orient, int fmt,
                           int quality, int filter, uint8_t **out, size_t *out_len);
+/* ik_transform with per-request options (ik_request_opts above: fit, orientation and
+ * background): decode, turn, flatten onto the background, resize, encode.  opts NULL, or at
+ * its defaults, is ik_transform: the same calls.  An image without alpha is not touched by
+ * a background: no pass, no copy. */
+int ik_transform_opts(const uint8_t *bytes, size_t len, int64_t w, int64_t h, int fmt, int quality, int filter,
+                      const ik_request_opts *opts, size_t opt_size, uint8_t **out, size_t *out_len);
 
 /* ik_transform over n requests at once (the /img handler under load, loadtest C4
  * mix): decode_image (one set of GPU launches for the batch's PNG streams, one set
@@ -570,6 +623,32 @@ int ik_transform_batch_submit_device(const uint8_t *const *dev_bytes, const size
                                      int filter, int threads, uint8_t **outs, size_t *out_lens, int *status,
                                      uint64_t *ticket);
 
+/* The batch calls with per-request options: opts holds n ik_request_opts (or is NULL: every
+ * request at its defaults, the call without options), opt_size is sizeof(ik_request_opts).
+ * IK_ORIENT_AUTO is resolved from the bytes at submit, on the host.  In the post stage, on
+ * the device that holds each decoded image, the turn runs first (as in the _oriented
+ * calls), then the flatten, then the unchanged post plan, which sees the flattened C and
+ * pitch: images of one (W, H, C, depth, pitch, background) are flattened by one launch, a
+ * lone one by its own, and a request whose decoded image has no alpha, or whose background
+ * is IK_BG_NONE, is not touched.  Wait with ik_transform_batch_wait. */
+int ik_transform_batch_opts(const uint8_t *const *bytes, const size_t *lens, uint32_t n, const int64_t *w,
+                            const int64_t *h, const ik_request_opts *opts, size_t opt_size, const int *fmt,
+                            const int *quality, int filter, int threads, uint8_t **outs, size_t *out_lens,
+                            int *status);
+int ik_transform_batch_submit_opts(const uint8_t *const *bytes, const size_t *lens, uint32_t n, const int64_t *w,
+                                   const int64_t *h, const ik_request_opts *opts, size_t opt_size, const int *fmt,
+                                   const int *quality, int filter, int threads, uint8_t **outs, size_t *out_lens,
+                                   int *status, uint64_t *ticket);
+/* ik_transform_batch_submit_device with options: fit, background and an explicit
+ * orientation 1..8 work as above.  IK_ORIENT_AUTO on any request is IK_ERR_INVALID before
+ * anything is queued: the in-place JPEG marker walk steps over APP1, so the file's
+ * orientation is not known on the host. */
+int ik_transform_batch_submit_device_opts(const uint8_t *const *dev_bytes, const size_t *lens, uint32_t n,
+                                          const int64_t *w, const int64_t *h, const ik_request_opts *opts,
+                                          size_t opt_size, const int *fmt, const int *quality, int filter,
+                                          int threads, uint8_t **outs, size_t *out_lens, int *status,
+                                          uint64_t *ticket);
+
 /* A batch of n same-geometry 8-bit images already resident in device memory
  * (image i at dev_src + i*src_image_stride, rows src_pitch bytes apart) ->
  * resize to nw x nh -> encode.  Encoded bytes are written into the caller's
@@ -634,6 +713,22 @@ int ik_resize_window_batch_device(const uint8_t *dev_src, uint32_t W, uint32_t H
 int ik_orient_batch_device(const uint8_t *dev_src, uint32_t W, uint32_t H, uint32_t C, uint32_t depth,
                            size_t src_pitch, size_t src_image_stride, uint32_t n, int orientation,
                            uint8_t *dev_dst, size_t dst_pitch, size_t dst_image_stride, void *hip_stream);
+/* the background flatten (above) over n images of W x H pixels of C samples of `depth`
+ * bytes, C 4 (Rgba) or 2 (LumaA), image i at dev_src + i*src_image_stride, written at
+ * dev_dst + i*dst_image_stride as W x H pixels of out_channels samples: 3 for C = 4; for
+ * C = 2, 1 (only when rgb has R == G == B) or 3.  rgb is 0xRRGGBB.  Nothing outside
+ * W*out_channels*depth bytes of each of the H destination rows is written, and nothing
+ * outside W*C*depth bytes of each of the H source rows is read.  Bases, pitches and strides
+ * that are all multiples of 4 take the wide path (16-byte loads, whole-dword stores), for
+ * source and destination independently; any others the byte path.  Enqueued on hip_stream
+ * (NULL: the calling thread's stream) without waiting.  IK_ERR_INVALID, with nothing
+ * launched: C outside {2, 4}, out_channels not allowed for that C and rgb, rgb outside
+ * 0x000000..0xFFFFFF, depth outside 1..2, a null pointer, a zero size, a pitch below the row
+ * bytes, n > 1 with an image stride below rows * pitch, or n above 65535. */
+int ik_flatten_batch_device(const uint8_t *dev_src, uint32_t W, uint32_t H, uint32_t C, uint32_t depth,
+                            size_t src_pitch, size_t src_image_stride, uint32_t n, int32_t rgb,
+                            uint32_t out_channels, uint8_t *dev_dst, size_t dst_pitch, size_t dst_image_stride,
+                            void *hip_stream);
 /* the WebP colour conversion (to_rgb8 + libwebp RGB->YUV420) on the device;
  * dev_yuv receives the Y (w*h), U and V ((w+1)/2 * (h+1)/2) planes back to back */
 int ik_webp_yuv420_device(const uint8_t *dev_src, uint32_t w, uint32_t h, uint32_t C,

@@ -568,6 +568,53 @@ int orient_group(const std::vector<ik_image*>& src, int orientation, std::vector
     return rc;
 }
 
+// the background flatten over n images of one geometry (same W, H, C, depth, pitch; C is 2
+// or 4) onto one colour in ONE launch, as orient_group: new images of
+// flatten_out_channels(C, rgb) channels, the kernel reads the bases from a table.
+int flatten_group(const std::vector<ik_image*>& src, uint32_t rgb, std::vector<ik_image*>& out) {
+    const size_t n = src.size();
+    out.assign(n, nullptr);
+    if (!n) return IK_OK;
+    const ik_image* s0 = src[0];
+    if (n > kFlattenMaxImages || !s0->w || !s0->h || (s0->c != 2 && s0->c != 4)) return IK_ERR_UNSUPPORTED;
+    for (const ik_image* im : src)
+        if ((uintptr_t)im->d & 3) return IK_ERR_UNSUPPORTED;
+    DeviceGuard g(s0->device);
+    const uint32_t oc = flatten_out_channels(s0->c, rgb);
+    std::vector<uint64_t> tab(2 * n);
+    for (size_t i = 0; i < n; ++i) {
+        const int st = alloc_image(s0->w, s0->h, oc, &out[i], s0->depth);
+        if (st) {
+            for (ik_image*& o : out) { ik_image_free(o); o = nullptr; }
+            return st;
+        }
+        tab[i] = (uint64_t)(uintptr_t)src[i]->d;
+        tab[n + i] = (uint64_t)(uintptr_t)out[i]->d;
+    }
+    hipStream_t s = thread_stream();
+    uint64_t* dtab = reinterpret_cast<uint64_t*>(scratch_slot(kScratchPtrTable, sizeof(uint64_t) * 2 * n));
+    uint8_t* ht = pinned_slot(kPinnedGroupStage, 16 * n);
+    void* dht = nullptr;
+    int rc = IK_OK;
+    if (!dtab) rc = fail(IK_ERR_DEVICE, "cannot allocate device scratch");
+    else if (!ht || hipHostGetDevicePointer(&dht, ht, 0) != hipSuccess || !dht)
+        rc = fail(IK_ERR_NOMEM, "cannot map pinned flatten table");
+    if (!rc) {
+        (void)hipStreamSynchronize(s);  // the previous table is read
+        std::memcpy(ht, tab.data(), 16 * n);
+        hipError_t e = launch_copy_words(reinterpret_cast<const uint32_t*>(dht), reinterpret_cast<uint32_t*>(dtab), 4 * n, s);
+        if (e == hipSuccess)
+            e = launch_flatten(nullptr, s0->pitch, 0, nullptr, out[0]->pitch, 0, s0->w, s0->h, (int)s0->c, (int)oc,
+                               (int)s0->depth, rgb, (int)n, s, dtab, dtab + n);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) rc = hip_fail(e, "background flatten (batched)");
+        else flatten_count(1, n);
+    }
+    if (rc)
+        for (ik_image*& o : out) { ik_image_free(o); o = nullptr; }
+    return rc;
+}
+
 // ik_shutdown: the batched colour launches' pinned blocks, the per-device constant tables
 void encode_shutdown() {
     {

@@ -506,6 +506,15 @@ int resize_mode() {
     return m;
 }
 
+namespace {
+std::atomic<unsigned long long> g_flatten_launches{0}, g_flatten_images{0};  // ik_flatten_counters
+}  // namespace
+
+void flatten_count(uint64_t launches, uint64_t images) {
+    g_flatten_launches += launches;
+    g_flatten_images += images;
+}
+
 }  // namespace ik
 
 using namespace ik;
@@ -969,6 +978,68 @@ int ik_image_orient(const ik_image* img, int orientation, ik_image** out) {
     return IK_OK;
 }
 
+int ik_flatten_span(void) { return kFlattenSpan; }
+int ik_flatten_row_cap(void) { return kFlattenRowCap; }
+
+int ik_flatten_counters(unsigned long long out[2]) {
+    if (!out) return fail(IK_ERR_INVALID, "null pointer");
+    out[0] = g_flatten_launches.load();
+    out[1] = g_flatten_images.load();
+    return IK_OK;
+}
+
+int ik_flatten_batch_device(const uint8_t* dev_src, uint32_t W, uint32_t H, uint32_t C, uint32_t depth, size_t src_pitch,
+                            size_t src_image_stride, uint32_t n, int32_t rgb, uint32_t out_channels, uint8_t* dev_dst,
+                            size_t dst_pitch, size_t dst_image_stride, void* hip_stream) {
+    IK_API_ENTER();
+    if (rgb < 0 || rgb > 0xFFFFFF) return fail(IK_ERR_INVALID, "background %d outside 0x000000..0xFFFFFF", (int)rgb);
+    if (!dev_src || !dev_dst) return fail(IK_ERR_INVALID, "null device pointer");
+    if ((C != 2 && C != 4) || depth < 1 || depth > 2 || !W || !H || !n) return fail(IK_ERR_INVALID, "bad geometry");
+    // Rgba -> Rgb; LumaA -> Luma (a gray colour only) or Rgb
+    if (out_channels != 3 && !(C == 2 && out_channels == 1 && flatten_out_channels(2, (uint32_t)rgb) == 1))
+        return fail(IK_ERR_INVALID, "%u channels cannot be flattened to %u onto %06x", C, out_channels, (unsigned)rgb);
+    if (src_pitch < (size_t)W * C * depth || dst_pitch < (size_t)W * out_channels * depth)
+        return fail(IK_ERR_INVALID, "pitch too small");
+    if (n > 1 && (src_image_stride < src_pitch * H || dst_image_stride < dst_pitch * H))
+        return fail(IK_ERR_INVALID, "image stride too small");
+    if (n > kFlattenMaxImages) return fail(IK_ERR_INVALID, "more than %u images", kFlattenMaxImages);
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : thread_stream();
+    const hipError_t e = launch_flatten(dev_src, src_pitch, src_image_stride, dev_dst, dst_pitch, dst_image_stride, W, H,
+                                        (int)C, (int)out_channels, (int)depth, (uint32_t)rgb, (int)n, s);
+    if (e != hipSuccess) return hip_fail(e, "flatten kernel launch");
+    flatten_count(1, n);
+    return IK_OK;
+}
+
+// the image composited onto a background colour: a new image on the device that holds img
+// (an image without alpha, or IK_BG_NONE: a copy)
+int ik_image_flatten(const ik_image* img, int32_t background, ik_image** out) {
+    IK_API_ENTER();
+    if (!img || !out) return fail(IK_ERR_INVALID, "null pointer");
+    if (background != IK_BG_NONE && (background < 0 || background > 0xFFFFFF))
+        return fail(IK_ERR_INVALID, "background %d is neither IK_BG_NONE nor 0x000000..0xFFFFFF", (int)background);
+    const bool pass = background != IK_BG_NONE && (img->c == 2 || img->c == 4);
+    const uint32_t oc = pass ? flatten_out_channels(img->c, (uint32_t)background) : img->c;
+    DeviceGuard g(img->device);
+    ik_image* o = nullptr;
+    int rc = alloc_image(img->w, img->h, oc, &o, img->depth);
+    if (rc) return rc;
+    if (img->w && img->h) {
+        hipStream_t s = thread_stream();
+        rc = pass ? ik_flatten_batch_device(img->d, img->w, img->h, img->c, img->depth, img->pitch, 0, 1, background, oc,
+                                            o->d, o->pitch, 0, s)
+                  : ik_orient_batch_device(img->d, img->w, img->h, img->c, img->depth, img->pitch, 0, 1, 1, o->d,
+                                           o->pitch, 0, s);
+        if (rc == IK_OK) {
+            const hipError_t e = hipStreamSynchronize(s);
+            if (e != hipSuccess) rc = hip_fail(e, "background flatten");
+        }
+    }
+    if (rc) { ik_image_free(o); return rc; }
+    *out = o;
+    return IK_OK;
+}
+
 int ik_encode(const ik_image* img, int fmt, int quality, uint8_t** out, size_t* out_len) {
     IK_API_ENTER();
     if (!img || !out || !out_len) return fail(IK_ERR_INVALID, "null pointer");
@@ -1324,8 +1395,10 @@ static void transform_decode_phase(const uint8_t* const* bytes, const size_t* le
 // post gate, so a batch's resize runs beside the next batch's decode kernels);
 // request i's status / message land in st[i] / errs[i]
 // orient: null, or each request's effective orientation (0 = as stored, 2..8)
-static void transform_post_phase(const int64_t* w, const int64_t* h, const int* fit, const int* orient, const int* fmt,
-                                 const int* quality, int filter, int* st, std::string* errs, HostPhase& hp) {
+// bg: null, or each request's background (IK_BG_NONE, or 0xRRGGBB)
+static void transform_post_phase(const int64_t* w, const int64_t* h, const int* fit, const int* orient,
+                                 const int32_t* bg, const int* fmt, const int* quality, int filter, int* st,
+                                 std::string* errs, HostPhase& hp) {
     const std::vector<uint32_t>& idx = hp.idx;
     const int threads = hp.threads;
     const uint32_t m = (uint32_t)idx.size();
@@ -1370,6 +1443,42 @@ static void transform_post_phase(const int64_t* w, const int64_t* h, const int* 
                 const uint32_t k = ks[j];
                 if (!grouped) {
                     if (int r = ik_image_orient(imgs[k], o, &out[j])) {
+                        ds[k] = r;
+                        dm[k] = last_error_str();
+                        out[j] = nullptr;
+                    }
+                }
+                ik_image_free(imgs[k]);
+                imgs[k] = out[j];
+            }
+        }
+    }
+    // then the background flatten of the images that carry alpha, so that the post plan sees
+    // the flattened C and pitch: images of one (W, H, C, depth, pitch, device, colour) go
+    // through one launch (the output channels follow from C and the colour), a lone one
+    // through its own; an image without alpha, or a request without a background, is not
+    // touched
+    if (bg) {
+        std::map<std::array<uint64_t, 7>, std::vector<uint32_t>> flat;
+        for (uint32_t k = 0; k < m; ++k) {
+            const ik_image* im = imgs[k];
+            if (ds[k] || !im || bg[idx[k]] == IK_BG_NONE || (im->c != 2 && im->c != 4)) continue;
+            flat[{im->w, im->h, im->c, im->depth, im->pitch, (uint64_t)im->device, (uint64_t)(uint32_t)bg[idx[k]]}].push_back(k);
+        }
+        for (const auto& kv : flat) {
+            const std::vector<uint32_t>& ks = kv.second;
+            const int32_t colour = (int32_t)kv.first[6];
+            std::vector<ik_image*> out(ks.size(), nullptr);
+            bool grouped = false;
+            if (ks.size() > 1) {
+                std::vector<ik_image*> src;
+                for (uint32_t k : ks) src.push_back(imgs[k]);
+                grouped = flatten_group(src, (uint32_t)colour, out) == IK_OK;
+            }
+            for (size_t j = 0; j < ks.size(); ++j) {
+                const uint32_t k = ks[j];
+                if (!grouped) {
+                    if (int r = ik_image_flatten(imgs[k], colour, &out[j])) {
                         ds[k] = r;
                         dm[k] = last_error_str();
                         out[j] = nullptr;
@@ -1561,6 +1670,10 @@ struct Ticket {
     // ik_transform_batch_submit_oriented: each request's effective orientation, resolved
     // at submit (0 = as stored, 2..8); empty when no request is turned
     std::vector<int> orient;
+    // the *_opts submits: the fit modes (the other submits read the caller's array) and the
+    // backgrounds (IK_BG_NONE or 0xRRGGBB), each empty when every request is at its default
+    std::vector<int> fitv;
+    std::vector<int32_t> bg;
 };
 
 // one device's share of a ticket
@@ -1572,6 +1685,7 @@ struct BatchPart {
     const int64_t* h = nullptr;
     const int* fit = nullptr;  // null: every request IK_FIT_CONTAIN
     const int* orient = nullptr;  // null: every request as stored; else Ticket::orient
+    const int32_t* bg = nullptr;  // null: no request has a background; else Ticket::bg
     const int* fmt = nullptr;
     const int* quality = nullptr;
     int filter = 0;
@@ -1646,7 +1760,7 @@ private:
             if (stage == 2) {
                 // resize + the encoders' device front ends, beside the next batch's decode
                 Ticket& t = *p->t;
-                transform_post_phase(p->w, p->h, p->fit, p->orient, p->fmt, p->quality, p->filter, t.st.data(),
+                transform_post_phase(p->w, p->h, p->fit, p->orient, p->bg, p->fmt, p->quality, p->filter, t.st.data(),
                                      t.errs.data(), p->hp);
                 pool_->post([p] {
                     Ticket& tk = *p->t;
@@ -1811,6 +1925,7 @@ int submit_parts(const std::shared_ptr<Ticket>& t, const uint8_t* const* bytes, 
         p->t = t;
         p->bytes = bytes; p->lens = lens; p->w = w; p->h = h; p->fit = fit; p->fmt = fmt; p->quality = quality;
         p->orient = t->orient.empty() ? nullptr : t->orient.data();
+        p->bg = t->bg.empty() ? nullptr : t->bg.data();
         p->sniff = sniff;
         p->filter = filter;
         p->hp.threads = threads;
@@ -1925,11 +2040,115 @@ int ik_transform_batch_submit_oriented(const uint8_t* const* bytes, const size_t
     return submit_parts(t, bytes, nullptr, -1, lens, n, w, h, fit, fmt, quality, filter, threads, ticket);
 }
 
+// ---- per-request options (ik_request_opts) ----
+static bool opts_size_ok(size_t opt_size) { return opt_size == sizeof(ik_request_opts); }
+static bool background_ok(int32_t b) { return b == IK_BG_NONE || (b >= 0 && b <= 0xFFFFFF); }
+
+// a batch's options as the arrays its ticket keeps, each left empty when every request is at
+// that option's default (so an all-default batch makes the calls of the plain submit)
+struct OptArrays {
+    std::vector<int> fit, orient;  // orient: effective orientations (0 = as stored, 2..8)
+    std::vector<int32_t> bg;
+    bool none() const { return fit.empty() && orient.empty() && bg.empty(); }
+};
+
+// bytes: the files in host memory, or null (device-resident inputs: IK_ORIENT_AUTO cannot be
+// resolved and is refused).  Returns IK_OK or IK_ERR_INVALID with the message set.
+static int split_opts(const ik_request_opts* opts, uint32_t n, const uint8_t* const* bytes, const size_t* lens,
+                      OptArrays& a) {
+    for (uint32_t i = 0; opts && i < n; ++i) {
+        const ik_request_opts& o = opts[i];
+        if (o.fit < IK_FIT_CONTAIN || o.fit > IK_FIT_EXACT)
+            return fail(IK_ERR_INVALID, "request %u: unknown fit %d", i, o.fit);
+        if (!background_ok(o.background))
+            return fail(IK_ERR_INVALID, "request %u: background %d is neither IK_BG_NONE nor 0x000000..0xFFFFFF", i,
+                        (int)o.background);
+        if (o.orient == IK_ORIENT_AUTO && !bytes)
+            return fail(IK_ERR_INVALID, "request %u: IK_ORIENT_AUTO cannot be resolved for device-resident inputs", i);
+        if (o.orient < IK_ORIENT_AUTO || o.orient > 8)
+            return fail(IK_ERR_INVALID, "request %u: unknown orientation %d", i, o.orient);
+        // (STORED is not looked up: an all-STORED batch stays off the files)
+        const int eff = o.orient == IK_ORIENT_STORED ? 0
+                        : bytes                      ? effective_orientation(bytes[i], lens[i], o.orient)
+                                                     : (o.orient <= 1 ? 0 : o.orient);
+        if (o.fit != IK_FIT_CONTAIN) {
+            if (a.fit.empty()) a.fit.assign(n, IK_FIT_CONTAIN);
+            a.fit[i] = o.fit;
+        }
+        if (eff) {
+            if (a.orient.empty()) a.orient.assign(n, 0);
+            a.orient[i] = eff;
+        }
+        if (o.background != IK_BG_NONE) {
+            if (a.bg.empty()) a.bg.assign(n, IK_BG_NONE);
+            a.bg[i] = o.background;
+        }
+    }
+    return IK_OK;
+}
+
+int ik_transform_batch_submit_opts(const uint8_t* const* bytes, const size_t* lens, uint32_t n, const int64_t* w,
+                                   const int64_t* h, const ik_request_opts* opts, size_t opt_size, const int* fmt,
+                                   const int* quality, int filter, int threads, uint8_t** outs, size_t* out_lens,
+                                   int* status, uint64_t* ticket) {
+    IK_API_ENTER();
+    if (!opts_size_ok(opt_size)) return fail(IK_ERR_INVALID, "unknown options size %zu", opt_size);
+    if (!bytes || !lens || !w || !h || !fmt || !quality || !outs || !out_lens || !n || !ticket)
+        return fail(IK_ERR_INVALID, "bad batch");
+    OptArrays a;
+    if (int rc = split_opts(opts, n, bytes, lens, a)) return rc;
+    if (a.none())  // every request at its defaults: the plain submit itself
+        return ik_transform_batch_submit(bytes, lens, n, w, h, fmt, quality, filter, threads, outs, out_lens, status,
+                                         ticket);
+    auto t = new_ticket(n, outs, out_lens, status);
+    t->fitv.swap(a.fit);
+    t->orient.swap(a.orient);
+    t->bg.swap(a.bg);
+    return submit_parts(t, bytes, nullptr, -1, lens, n, w, h, t->fitv.empty() ? nullptr : t->fitv.data(), fmt, quality,
+                        filter, threads, ticket);
+}
+
+int ik_transform_batch_opts(const uint8_t* const* bytes, const size_t* lens, uint32_t n, const int64_t* w,
+                            const int64_t* h, const ik_request_opts* opts, size_t opt_size, const int* fmt,
+                            const int* quality, int filter, int threads, uint8_t** outs, size_t* out_lens, int* status) {
+    IK_API_ENTER();
+    uint64_t ticket = 0;
+    if (int rc = ik_transform_batch_submit_opts(bytes, lens, n, w, h, opts, opt_size, fmt, quality, filter, threads, outs,
+                                                out_lens, status, &ticket))
+        return rc;
+    return ik_transform_batch_wait(ticket);
+}
+
+static int submit_device(const uint8_t* const* dev_bytes, const size_t* lens, uint32_t n, const int64_t* w,
+                         const int64_t* h, OptArrays& opt, const int* fmt, const int* quality, int filter, int threads,
+                         uint8_t** outs, size_t* out_lens, int* status, uint64_t* ticket);
+
 int ik_transform_batch_submit_device(const uint8_t* const* dev_bytes, const size_t* lens, uint32_t n,
                                      const int64_t* w, const int64_t* h, const int* fmt, const int* quality,
                                      int filter, int threads, uint8_t** outs, size_t* out_lens, int* status,
                                      uint64_t* ticket) {
     IK_API_ENTER();
+    OptArrays none;
+    return submit_device(dev_bytes, lens, n, w, h, none, fmt, quality, filter, threads, outs, out_lens, status, ticket);
+}
+
+int ik_transform_batch_submit_device_opts(const uint8_t* const* dev_bytes, const size_t* lens, uint32_t n,
+                                          const int64_t* w, const int64_t* h, const ik_request_opts* opts,
+                                          size_t opt_size, const int* fmt, const int* quality, int filter, int threads,
+                                          uint8_t** outs, size_t* out_lens, int* status, uint64_t* ticket) {
+    IK_API_ENTER();
+    if (!opts_size_ok(opt_size)) return fail(IK_ERR_INVALID, "unknown options size %zu", opt_size);
+    if (!dev_bytes || !lens || !w || !h || !fmt || !quality || !outs || !out_lens || !n || !ticket)
+        return fail(IK_ERR_INVALID, "bad batch");
+    OptArrays a;
+    if (int rc = split_opts(opts, n, nullptr, lens, a)) return rc;  // before anything is queued
+    return submit_device(dev_bytes, lens, n, w, h, a, fmt, quality, filter, threads, outs, out_lens, status, ticket);
+}
+
+// opt: the requests' options (all empty: the plain device submit), moved into the ticket
+static int submit_device(const uint8_t* const* dev_bytes, const size_t* lens, uint32_t n, const int64_t* w,
+                         const int64_t* h, OptArrays& opt, const int* fmt, const int* quality, int filter, int threads,
+                         uint8_t** outs, size_t* out_lens, int* status, uint64_t* ticket) {
     if (!dev_bytes || !lens || !w || !h || !fmt || !quality || !outs || !out_lens || !n || !ticket)
         return fail(IK_ERR_INVALID, "bad batch");
     // every input must be device memory of one device (the batch runs there)
@@ -2039,8 +2258,11 @@ int ik_transform_batch_submit_device(const uint8_t* const* dev_bytes, const size
     }
     // the batch runs where its inputs are: on a logical device of `phys`, or (single-
     // device mode) on the stages of `phys` whatever the calling thread's device is
-    return submit_parts(t, t->eff.data(), t->sniff.data(), phys, lens, n, w, h, nullptr, fmt, quality, filter, threads,
-                        ticket);
+    t->fitv.swap(opt.fit);
+    t->orient.swap(opt.orient);
+    t->bg.swap(opt.bg);
+    return submit_parts(t, t->eff.data(), t->sniff.data(), phys, lens, n, w, h,
+                        t->fitv.empty() ? nullptr : t->fitv.data(), fmt, quality, filter, threads, ticket);
 }
 
 int ik_memory_stats(uint64_t* out, int n) {
@@ -2115,9 +2337,10 @@ int ik_transform_batch_oriented(const uint8_t* const* bytes, const size_t* lens,
     return ik_transform_batch_wait(ticket);
 }
 
-// orientation: 0 = the pixels as stored, 2..8 = turned first (effective_orientation)
-static int transform_here(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orientation, int fmt,
-                          int quality, int filter, uint8_t** out, size_t* out_len) {
+// orientation: 0 = the pixels as stored, 2..8 = turned first (effective_orientation);
+// background: IK_BG_NONE, or the colour an image with alpha is flattened onto after the turn
+static int transform_here(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orientation,
+                          int32_t background, int fmt, int quality, int filter, uint8_t** out, size_t* out_len) {
     ik_image* img = nullptr;
     int st = decode_one(bytes, len, &img, nullptr);
     if (st) return st;
@@ -2127,6 +2350,13 @@ static int transform_here(const uint8_t* bytes, size_t len, int64_t w, int64_t h
         ik_image_free(img);
         if (st) return st;
         img = turned;
+    }
+    if (background != IK_BG_NONE && (img->c == 2 || img->c == 4)) {  // (no alpha: no pass, no copy)
+        ik_image* flat = nullptr;
+        st = ik_image_flatten(img, background, &flat);
+        ik_image_free(img);
+        if (st) return st;
+        img = flat;
     }
     ik_image* rs = nullptr;
     st = ik_resize_fit(img, w, h, fit, filter, &rs);
@@ -2143,13 +2373,27 @@ int ik_transform(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fmt
     return ik_transform_fit(bytes, len, w, h, IK_FIT_CONTAIN, fmt, quality, filter, out, out_len);
 }
 
-static int transform_scheduled(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orientation, int fmt,
-                               int quality, int filter, uint8_t** out, size_t* out_len);
+static int transform_scheduled(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orientation,
+                               int32_t background, int fmt, int quality, int filter, uint8_t** out, size_t* out_len);
 
 int ik_transform_fit(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int fmt, int quality,
                      int filter, uint8_t** out, size_t* out_len) {
     IK_API_ENTER();
-    return transform_scheduled(bytes, len, w, h, fit, 0, fmt, quality, filter, out, out_len);
+    return transform_scheduled(bytes, len, w, h, fit, 0, IK_BG_NONE, fmt, quality, filter, out, out_len);
+}
+
+// (the *_opts calls; opts_size_ok and background_ok: above, with the batch submits)
+
+int ik_transform_opts(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fmt, int quality, int filter,
+                      const ik_request_opts* opts, size_t opt_size, uint8_t** out, size_t* out_len) {
+    IK_API_ENTER();
+    if (!opts_size_ok(opt_size)) return fail(IK_ERR_INVALID, "unknown options size %zu", opt_size);
+    if (!opts) return ik_transform(bytes, len, w, h, fmt, quality, filter, out, out_len);
+    if (!background_ok(opts->background))
+        return fail(IK_ERR_INVALID, "background %d is neither IK_BG_NONE nor 0x000000..0xFFFFFF", (int)opts->background);
+    const int o = effective_orientation(bytes, len, opts->orient);
+    if (o < 0) return fail(IK_ERR_INVALID, "unknown orientation %d", opts->orient);
+    return transform_scheduled(bytes, len, w, h, opts->fit, o, opts->background, fmt, quality, filter, out, out_len);
 }
 
 int ik_transform_oriented(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orient, int fmt,
@@ -2157,13 +2401,14 @@ int ik_transform_oriented(const uint8_t* bytes, size_t len, int64_t w, int64_t h
     IK_API_ENTER();
     const int o = effective_orientation(bytes, len, orient);
     if (o < 0) return fail(IK_ERR_INVALID, "unknown orientation %d", orient);
-    return transform_scheduled(bytes, len, w, h, fit, o, fmt, quality, filter, out, out_len);
+    return transform_scheduled(bytes, len, w, h, fit, o, IK_BG_NONE, fmt, quality, filter, out, out_len);
 }
 
 // on this device, or (several devices) on the least-loaded one's workers
-static int transform_scheduled(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orientation, int fmt,
-                               int quality, int filter, uint8_t** out, size_t* out_len) {
-    if (!sched_multi()) return transform_here(bytes, len, w, h, fit, orientation, fmt, quality, filter, out, out_len);
+static int transform_scheduled(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orientation,
+                               int32_t background, int fmt, int quality, int filter, uint8_t** out, size_t* out_len) {
+    if (!sched_multi())
+        return transform_here(bytes, len, w, h, fit, orientation, background, fmt, quality, filter, out, out_len);
     // several devices: queue the request to the least-loaded device's workers
     const uint64_t cost = request_cost(bytes, len, w, h, fmt);
     const int ld = sched_acquire(cost);
@@ -2173,7 +2418,7 @@ static int transform_scheduled(const uint8_t* bytes, size_t len, int64_t w, int6
     int st = IK_OK;
     std::string msg;
     sched_pool(ld).post([&] {
-        const int r = transform_here(bytes, len, w, h, fit, orientation, fmt, quality, filter, out, out_len);
+        const int r = transform_here(bytes, len, w, h, fit, orientation, background, fmt, quality, filter, out, out_len);
         std::string m = r ? last_error_str() : std::string();
         std::lock_guard<std::mutex> lk(mu);
         st = r;

@@ -280,6 +280,24 @@ hipError_t launch_orient(const uint8_t* src, size_t src_pitch, size_t src_img_st
                          size_t dst_img_stride, uint32_t W, uint32_t H, int px, int orientation, int n, hipStream_t s,
                          const uint64_t* src_tab = nullptr, const uint64_t* dst_tab = nullptr);
 
+// ---- background flatten (ik_flatten.hip) ----
+// alpha composited onto the colour rgb (0xRRGGBB) over n images of W x H pixels of cin
+// samples of `depth` bytes: (cin, cout) = (4, 3), (2, 1) or (2, 3); images addressed as
+// launch_orient addresses them.
+constexpr int kFlattenSpan = 1024;            // pixels of a row one workgroup takes
+constexpr int kFlattenRowCap = 256;           // most rows of workgroups in a launch (the rest: grid stride)
+constexpr uint32_t kFlattenMaxImages = 65535;  // grid.z
+hipError_t launch_flatten(const uint8_t* src, size_t src_pitch, size_t src_img_stride, uint8_t* dst, size_t dst_pitch,
+                          size_t dst_img_stride, uint32_t W, uint32_t H, int cin, int cout, int depth, uint32_t rgb,
+                          int n, hipStream_t s, const uint64_t* src_tab = nullptr, const uint64_t* dst_tab = nullptr);
+// the channels a flatten of a c-channel image onto rgb leaves: Rgba -> 3, LumaA -> 1 for a
+// gray colour and 3 for any other, anything without alpha -> c (no pass)
+inline uint32_t flatten_out_channels(uint32_t c, uint32_t rgb) {
+    if (c == 4) return 3;
+    if (c == 2) return ((rgb >> 16) & 0xFF) == ((rgb >> 8) & 0xFF) && ((rgb >> 8) & 0xFF) == (rgb & 0xFF) ? 1 : 3;
+    return c;
+}
+
 // ---- plans (ik_plan.cpp) ----
 // axis_weights, required_slots and the tables themselves: ik_resize_plan.h
 ResizePlan* get_resize_plan(int device, int W, int H, int C, int nw, int nh, int filter, int n);

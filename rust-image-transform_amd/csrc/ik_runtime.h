@@ -211,9 +211,9 @@ uint8_t* pinned_slot(int slot, size_t bytes);  // per-thread grow-only pinned ho
 constexpr int kScratchDefault = 0;
 // copy_h2d_2d / copy_d2h_2d's staging; each copy synchronises the stream before it returns
 constexpr int kPinnedStaging = 0;
-// a group launch's table of image base pointers, webp_front_group's, resize_group's and
-// orient_group's (which stages it in kPinnedGroupStage as resize_group does): all run on
-// one thread and synchronise the stream after the launch that reads the table
+// a group launch's table of image base pointers, webp_front_group's, resize_group's,
+// orient_group's and flatten_group's (which stage it in kPinnedGroupStage as resize_group
+// does): all run on one thread and synchronise the stream after the launch that reads the table
 constexpr int kScratchPtrTable = 3;
 // jpeg_front_group's device work area: quantisation tables, source table, coefficients, Huffman work
 constexpr int kScratchJpegGroup = 4;
@@ -469,6 +469,11 @@ int resize_group(const std::vector<ik_image*>& src, const FitWindow& win, int fi
 // apply_orientation (2..8) of same-geometry images in one launch (ik_encode.cpp); a return
 // other than IK_OK leaves every image to ik_image_orient
 int orient_group(const std::vector<ik_image*>& src, int orientation, std::vector<ik_image*>& out);
+// the background flatten of same-geometry images with alpha onto one colour in one launch
+// (ik_encode.cpp); a return other than IK_OK leaves every image to ik_image_flatten
+int flatten_group(const std::vector<ik_image*>& src, uint32_t rgb, std::vector<ik_image*>& out);
+// process-wide flatten launches and images flattened (ik_flatten_counters)
+void flatten_count(uint64_t launches, uint64_t images);
 
 // Per-device phase gates (ik_pool.cpp).  Concurrent batch calls on one device
 // take its GPU phases in turn: kGateUpload covers a PNG batch's staging, H2D and

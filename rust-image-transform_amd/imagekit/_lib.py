@@ -26,6 +26,18 @@ class WebpExactItem(ctypes.Structure):
     _fields_ = [("dev_yuv", ctypes.c_void_p), ("w", ctypes.c_uint32), ("h", ctypes.c_uint32), ("quality", ctypes.c_int)]
 
 
+class RequestOpts(ctypes.Structure):
+    """ik_request_opts: one request's options for the *_opts entry points (the defaults are
+    IK_FIT_CONTAIN, IK_ORIENT_STORED, IK_BG_NONE)."""
+    _fields_ = [("fit", ctypes.c_int), ("orient", ctypes.c_int), ("background", ctypes.c_int32)]
+
+
+_opts_p = ctypes.POINTER(RequestOpts)
+_batch_head = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint32,
+               ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
+_batch_opts = (_batch_head + [_opts_p, ctypes.c_size_t] + [ctypes.POINTER(ctypes.c_int)] * 2 + [ctypes.c_int, ctypes.c_int]
+               + [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)])
+
 # (name, restype, argtypes) for every entry point declared in include/imagekit_hip.h
 SIGNATURES = [
     ("ik_init", ctypes.c_int, [ctypes.c_int]),
@@ -149,6 +161,15 @@ SIGNATURES = [
     ("ik_transform_oriented", ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int] * 5 + [ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t)]),
     ("ik_transform_batch_oriented", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint32, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)] + [ctypes.POINTER(ctypes.c_int)] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]),
     ("ik_transform_batch_submit_oriented", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint32, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)] + [ctypes.POINTER(ctypes.c_int)] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint64)]),
+    ("ik_flatten_span", ctypes.c_int, []),
+    ("ik_flatten_row_cap", ctypes.c_int, []),
+    ("ik_flatten_counters", ctypes.c_int, [ctypes.POINTER(ctypes.c_ulonglong)]),
+    ("ik_image_flatten", ctypes.c_int, [c_img_p, ctypes.c_int32, ctypes.POINTER(c_img_p)]),
+    ("ik_flatten_batch_device", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_uint32] * 4 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]),
+    ("ik_transform_opts", ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int] * 3 + [_opts_p, ctypes.c_size_t, ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t)]),
+    ("ik_transform_batch_opts", ctypes.c_int, _batch_opts),
+    ("ik_transform_batch_submit_opts", ctypes.c_int, _batch_opts + [ctypes.POINTER(ctypes.c_uint64)]),
+    ("ik_transform_batch_submit_device_opts", ctypes.c_int, _batch_opts + [ctypes.POINTER(ctypes.c_uint64)]),
 ]
 
 

@@ -89,6 +89,48 @@ def _orients(orients, n):
     return (ctypes.c_int * n)(*[_orient(o) for o in orients])
 
 
+BG_NONE = -1  # IK_BG_NONE
+
+
+def _background(bg) -> int:
+    """A `background=` argument as ik_request_opts.background: None (no flatten: IK_BG_NONE),
+    an int 0xRRGGBB, an (r, g, b) tuple of 0..255, or an "rrggbb" / "#rrggbb" string.
+    Anything else raises ValueError, before the library is called."""
+    if bg is None:
+        return BG_NONE
+    if isinstance(bg, bool):
+        raise ValueError(f"background {bg!r} is not a colour")
+    if isinstance(bg, (int, np.integer)):
+        if not 0 <= int(bg) <= 0xFFFFFF:
+            raise ValueError(f"background {bg!r} outside 0x000000..0xFFFFFF")
+        return int(bg)
+    if isinstance(bg, str):
+        s = bg[1:] if bg.startswith("#") else bg
+        if len(s) != 6 or any(ch not in "0123456789abcdefABCDEF" for ch in s):
+            raise ValueError(f"background {bg!r} is not rrggbb")
+        return int(s, 16)
+    if isinstance(bg, (tuple, list)):
+        if len(bg) != 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 255
+                               for v in bg):
+            raise ValueError(f"background {bg!r} is not (r, g, b) of 0..255")
+        return (int(bg[0]) << 16) | (int(bg[1]) << 8) | int(bg[2])
+    raise ValueError(f"background {bg!r} is not a colour")
+
+
+def _request_opts(n, fits=None, orients=None, backgrounds=None):
+    """The ik_request_opts array of a *_opts batch call (each argument: one entry per
+    request, or None for that option's default everywhere)."""
+    for name, v in (("fits", fits), ("orient", orients), ("backgrounds", backgrounds)):
+        if v is not None and len(v) != n:
+            raise InvalidArgument(f"{name} must have one entry per request")
+    arr = (_lib.RequestOpts * n)()
+    for i in range(n):
+        arr[i].fit = int(FitMode(fits[i])) if fits is not None else int(FitMode.contain)
+        arr[i].orient = _orient(orients[i]) if orients is not None else int(Orientation.stored)
+        arr[i].background = _background(backgrounds[i]) if backgrounds is not None else BG_NONE
+    return arr
+
+
 def exif_orientation(data: bytes) -> int:
     """ImageDecoder::orientation() as its EXIF value, 1..8: JPEG APP1, PNG eXIf, WebP EXIF;
     1 when the file carries none or it cannot be read (ik_exif_orientation; host only)."""
@@ -209,6 +251,16 @@ class DynamicImage:
         st = _lib.load().ik_image_orient(self._h, o, ctypes.byref(out))
         if st:
             _raise(st, "apply_orientation")
+        return DynamicImage(out.value)
+
+    def flatten(self, background) -> "DynamicImage":
+        """The image composited onto a background colour as a new image (ik_image_flatten;
+        the project's own arithmetic): Rgba -> Rgb, LumaA -> Luma for a gray
+        colour and Rgb for any other; an image without alpha, or None, gives a copy."""
+        out = ctypes.c_void_p()
+        st = _lib.load().ik_image_flatten(self._h, _background(background), ctypes.byref(out))
+        if st:
+            _raise(st, "flatten")
         return DynamicImage(out.value)
 
     def clone(self) -> "DynamicImage":
@@ -333,11 +385,12 @@ def _inputs(datas):
 
 
 def transform_batch(datas, sizes, fmts, qualities, filter: "FilterType" = None, threads: int = 0,
-                    fits=None, orient=None) -> List[bytes]:
+                    fits=None, orient=None, backgrounds=None) -> List[bytes]:
     """ik_transform_batch: decode -> resize_image -> encode_image for many requests
     (sizes: (w, h) per request, None = unset; fmts: ImageFormat per request; fits: a
     FitMode per request, None = contain for all; orient: an Orientation per request,
-    None = stored for all)."""
+    None = stored for all; backgrounds: a colour per request as `transform` takes it,
+    None = no flatten for any: with it the call is ik_transform_batch_opts)."""
     lib = _lib.load()
     bufs, ptrs, lens = _inputs(datas)
     n = len(bufs)
@@ -353,7 +406,11 @@ def transform_batch(datas, sizes, fmts, qualities, filter: "FilterType" = None, 
     status = (ctypes.c_int * n)()
     fa = _fits(fits, n)
     oa = _orients(orient, n)
-    if oa is not None:
+    if backgrounds is not None:
+        ra = _request_opts(n, fits, orient, backgrounds)
+        st = lib.ik_transform_batch_opts(ptrs, lens, n, ws, hs, ra, ctypes.sizeof(_lib.RequestOpts), fs, qs, filt,
+                                         threads, outs, olens, status)
+    elif oa is not None:
         st = lib.ik_transform_batch_oriented(ptrs, lens, n, ws, hs, fa, oa, fs, qs, filt, threads, outs, olens, status)
     elif fa is None:
         st = lib.ik_transform_batch(ptrs, lens, n, ws, hs, fs, qs, filt, threads, outs, olens, status)
@@ -396,9 +453,10 @@ class PendingBatch:
 
 
 def transform_batch_submit(datas, sizes, fmts, qualities, filter: "FilterType" = None,
-                           threads: int = 0, fits=None, orient=None) -> PendingBatch:
+                           threads: int = 0, fits=None, orient=None, backgrounds=None) -> PendingBatch:
     """ik_transform_batch_submit: the device half of transform_batch now, the host
-    coders in the background; PendingBatch.wait() gives what transform_batch gives."""
+    coders in the background; PendingBatch.wait() gives what transform_batch gives.
+    fits, orient and backgrounds as transform_batch takes them."""
     lib = _lib.load()
     bufs, ptrs, lens = _inputs(datas)
     n = len(bufs)
@@ -415,7 +473,12 @@ def transform_batch_submit(datas, sizes, fmts, qualities, filter: "FilterType" =
     ticket = ctypes.c_uint64()
     fa = _fits(fits, n)
     oa = _orients(orient, n)
-    if oa is not None:
+    ra = None
+    if backgrounds is not None:
+        ra = _request_opts(n, fits, orient, backgrounds)
+        st = lib.ik_transform_batch_submit_opts(ptrs, lens, n, ws, hs, ra, ctypes.sizeof(_lib.RequestOpts), fs, qs,
+                                                filt, threads, outs, olens, status, ctypes.byref(ticket))
+    elif oa is not None:
         st = lib.ik_transform_batch_submit_oriented(ptrs, lens, n, ws, hs, fa, oa, fs, qs, filt, threads, outs, olens,
                                                     status, ctypes.byref(ticket))
     elif fa is None:
@@ -426,13 +489,15 @@ def transform_batch_submit(datas, sizes, fmts, qualities, filter: "FilterType" =
                                                ctypes.byref(ticket))
     if st:
         raise TransformError(_lib.last_error())
-    return PendingBatch((bufs, ptrs, lens, ws, hs, fs, qs, fa, oa), outs, olens, status, ticket.value, n)
+    return PendingBatch((bufs, ptrs, lens, ws, hs, fs, qs, fa, oa, ra), outs, olens, status, ticket.value, n)
 
 
 def transform_batch_submit_device(datas, sizes, fmts, qualities, filter: "FilterType" = None,
-                                  threads: int = 0) -> PendingBatch:
+                                  threads: int = 0, fits=None, orient=None, backgrounds=None) -> PendingBatch:
     """ik_transform_batch_submit_device: as transform_batch_submit, over request
-    bodies already in device memory (DeviceBytes)."""
+    bodies already in device memory (DeviceBytes).  With fits, orient or backgrounds the
+    call is ik_transform_batch_submit_device_opts; Orientation.auto is refused there (the
+    files are not read on the host)."""
     lib = _lib.load()
     keep = list(datas)
     n = len(keep)
@@ -451,11 +516,17 @@ def transform_batch_submit_device(datas, sizes, fmts, qualities, filter: "Filter
     olens = (ctypes.c_size_t * n)()
     status = (ctypes.c_int * n)()
     ticket = ctypes.c_uint64()
-    st = lib.ik_transform_batch_submit_device(ptrs, lens, n, ws, hs, fs, qs, filt, threads, outs, olens, status,
-                                              ctypes.byref(ticket))
+    ra = None
+    if fits is None and orient is None and backgrounds is None:
+        st = lib.ik_transform_batch_submit_device(ptrs, lens, n, ws, hs, fs, qs, filt, threads, outs, olens, status,
+                                                  ctypes.byref(ticket))
+    else:
+        ra = _request_opts(n, fits, orient, backgrounds)
+        st = lib.ik_transform_batch_submit_device_opts(ptrs, lens, n, ws, hs, ra, ctypes.sizeof(_lib.RequestOpts), fs,
+                                                       qs, filt, threads, outs, olens, status, ctypes.byref(ticket))
     if st:
         raise TransformError(_lib.last_error())
-    return PendingBatch((keep, ptrs, lens, ws, hs, fs, qs), outs, olens, status, ticket.value, n)
+    return PendingBatch((keep, ptrs, lens, ws, hs, fs, qs, ra), outs, olens, status, ticket.value, n)
 
 
 def resize_image(img: DynamicImage, w: Optional[int], h: Optional[int],
@@ -492,16 +563,24 @@ def encode_image(img: DynamicImage, fmt: ImageFormat, quality: int) -> bytes:
 
 def transform(data: bytes, w: Optional[int], h: Optional[int], fmt: ImageFormat, quality: int,
               filter: FilterType = FilterType.Lanczos3, fit: FitMode = FitMode.contain,
-              orient=Orientation.stored) -> bytes:
+              orient=Orientation.stored, background=None) -> bytes:
     """decode -> resize_image -> encode_image in one device-resident call; with orient
     (Orientation) the decoded image is turned first, and w, h and fit refer to the turned
-    image."""
+    image; with background (0xRRGGBB, (r, g, b), "rrggbb" or "#rrggbb") an image that
+    carries alpha is then composited onto that colour, before the resize
+    (ik_transform_opts)."""
+    bg = _background(background)
     lib = _lib.load()
     b = bytes(data)
     buf = _lib.u8p()
     n = ctypes.c_size_t()
     o = _orient(orient)
-    if o == Orientation.stored:
+    if bg != BG_NONE:
+        ro = _lib.RequestOpts(int(FitMode(fit)), o, bg)
+        st = lib.ik_transform_opts(b, len(b), -1 if w is None else int(w), -1 if h is None else int(h),
+                                   ImageFormat(fmt).value, int(quality), int(filter), ctypes.byref(ro),
+                                   ctypes.sizeof(ro), ctypes.byref(buf), ctypes.byref(n))
+    elif o == Orientation.stored:
         st = lib.ik_transform_fit(b, len(b), -1 if w is None else int(w), -1 if h is None else int(h),
                                   int(FitMode(fit)), ImageFormat(fmt).value, int(quality), int(filter),
                                   ctypes.byref(buf), ctypes.byref(n))

@@ -114,6 +114,12 @@ def main():
                     help="stored: the calls without an orientation, as before; auto: every request passes "
                          "IK_ORIENT_AUTO (ik_transform_batch*_oriented; the sources here carry no EXIF, so no "
                          "image is turned: it measures the header walk at submit)")
+    ap.add_argument("--background", default=None, metavar="RRGGBB",
+                    help="every request passes this background colour (ik_transform_batch*_opts): images with alpha "
+                         "are flattened onto it before the resize.  The default JPEG sources carry no alpha, so "
+                         "none is flattened.  Without the flag: the calls without options, as before")
+    ap.add_argument("--source", choices=["jpeg", "png-rgba"], default="jpeg",
+                    help="png-rgba: translucent RGBA PNG sources of the same size (what --background acts on)")
     ap.add_argument("--restart", action="store_true")
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--seed", type=int, default=0)
@@ -134,8 +140,12 @@ def main():
     srcs = []
     for k in range(args.sources):
         buf = io.BytesIO()
-        kw = {"restart_marker_rows": 1} if args.restart else {}
-        Image.fromarray(ikutil.synth(S, S, 3, seed=100 + k, pattern="S")).save(buf, format="JPEG", quality=85, **kw)
+        if args.source == "png-rgba":
+            Image.fromarray(ikutil.synth(S, S, 4, seed=100 + k, pattern="S", alpha="random"), "RGBA").save(
+                buf, format="PNG", compress_level=1)
+        else:
+            kw = {"restart_marker_rows": 1} if args.restart else {}
+            Image.fromarray(ikutil.synth(S, S, 3, seed=100 + k, pattern="S")).save(buf, format="JPEG", quality=85, **kw)
         srcs.append(buf.getvalue())
     fmt_names = args.formats.split(",")
     reqs = make_requests(args.requests, args.sources, fmt_names, args.seed)
@@ -165,10 +175,13 @@ def main():
     def orients(chunk):  # None: the calls without an orientation, as before
         return [Orientation.auto] * len(chunk) if args.orient == "auto" else None
 
+    def backgrounds(chunk):  # None: the calls without options, as before
+        return [args.background] * len(chunk) if args.background is not None else None
+
     def run_batch(chunk):
         return transform_batch([srcs[s] for s, _, _, _ in chunk], [(w, h) for _, w, h, _ in chunk],
                                [f for _, _, _, f in chunk], [args.quality] * len(chunk), threads=args.threads,
-                               fits=fits(chunk), orient=orients(chunk))
+                               fits=fits(chunk), orient=orients(chunk), backgrounds=backgrounds(chunk))
 
     run_batch(mine[:min(len(mine), 8)])  # warm-up: plans, streams, pinned staging
 
@@ -207,7 +220,7 @@ def main():
                 continue
             p = transform_batch_submit([srcs[s] for s, _, _, _ in chunk], [(w, h) for _, w, h, _ in chunk],
                                        [f for _, _, _, f in chunk], [args.quality] * len(chunk), threads=args.threads,
-                                       fits=fits(chunk), orient=orients(chunk))
+                                       fits=fits(chunk), orient=orients(chunk), backgrounds=backgrounds(chunk))
             if pend is not None:
                 done(pend[0], pend[1].wait())
             pend = (tb, p)
@@ -226,6 +239,8 @@ def main():
     cores_busy = ((cpu1.user - cpu0.user) + (cpu1.system - cpu0.system)) / elapsed
     enc = (ctypes.c_ulonglong * 4)()
     lib.ik_webp_enc_counters(enc)
+    flat = (ctypes.c_ulonglong * 2)()
+    lib.ik_flatten_counters(flat)  # (the warm-up batch included)
     barrier()
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local}" if torch.cuda.is_available() else "cpu")
@@ -238,6 +253,8 @@ def main():
             "value": round(args.requests / elapsed, 1), "unit": "requests/s", "n_gpus": world,
             "requests": args.requests, "batch": args.batch, "formats": args.formats,
             "sources_restart_markers": bool(args.restart),
+            "source": args.source, "background": args.background,
+            "flatten_counters": {"launches": flat[0], "images": flat[1]},
             "batch_latency_ms": {"p50": round(float(np.percentile(lat, 50)), 2),
                                  "p95": round(float(np.percentile(lat, 95)), 2)},
             "decoded_mpix_per_s": round(args.requests * S * S / elapsed / 1e6, 1),
