@@ -512,15 +512,68 @@ int ik_flatten_counters(unsigned long long out[2]);
  * point without options.  The order is decode -> orient -> flatten -> resize -> encode: fit,
  * w and h refer to the oriented image, and the background applies whatever the output
  * format (an AVIF request with a background is opaque and carries no alpha plane).
- * opt_size must be sizeof(ik_request_opts) as this header declares it; any other value is
- * IK_ERR_INVALID ("unknown options size") before any device work, which is what lets the
- * struct grow.  A fit outside ik_fit, an orient outside ik_orient / 1..8 and a background
+ * opt_size must be the size of a layout this header declares (ik_request_opts, or
+ * ik_request_opts2 below); any other value is IK_ERR_INVALID ("unknown options size")
+ * before any device work, which is what lets the struct grow.  A fit outside ik_fit, an orient outside ik_orient / 1..8 and a background
  * that is neither IK_BG_NONE nor 0x000000..0xFFFFFF are IK_ERR_INVALID. */
 typedef struct {
     int fit;            /* ik_fit */
     int orient;         /* ik_orient, or 1..8 */
     int32_t background; /* IK_BG_NONE, or 0xRRGGBB */
 } ik_request_opts;
+/* The second declared layout, 24 bytes: the first one's fields, then blur and unsharpen
+ * (below).  The *_opts entry points take `const void *opts` and accept either declared
+ * size in opt_size; in a batch the n structs lie opt_size bytes apart.  The new fields at
+ * zero (their defaults) make exactly the calls the 12-byte layout makes.  A sigma is 0.0
+ * (off) or within [0.0625, IK_BLUR_MAX_SIGMA]; negative, NaN, infinite or out of range is
+ * IK_ERR_INVALID, as is a threshold outside 0..65535 and a request with both sigmas set
+ * ("blur and sharpen together": one request makes at most one extra pass), all before any
+ * device work; in a batch the message names the request.  The order is decode -> orient ->
+ * flatten -> resize -> blur or sharpen -> encode: the filter sees the pixels the encoder
+ * codes (with w and h both None, the decoded image after orient and flatten). */
+typedef struct {
+    int fit;                   /* ik_fit */
+    int orient;                /* ik_orient, or 1..8 */
+    int32_t background;        /* IK_BG_NONE, or 0xRRGGBB */
+    float blur_sigma;          /* 0: no blur */
+    float sharpen_sigma;       /* 0: no unsharp mask */
+    int32_t sharpen_threshold; /* 0..65535, in the sample's own units (8- or 16-bit) */
+} ik_request_opts2;
+
+/* ---- blur and unsharpen ---------------------------------------------------- */
+/* A Gaussian blur of the caller's sigma and the unsharp mask built on it, pixels staying in
+ * HBM.  The project's own definition, modelled on image 0.25.8's
+ * imageops::blur and imageops::unsharpen as recalled; parity with the crate is not pinned.
+ * It is the resampler's arithmetic at ratio 1.  For an axis of L samples, all in f32:
+ *     gaussian(x) = (1 / (sqrtf(2 pi) * sigma)) * expf(-(x * x) / (2 * (sigma * sigma)))
+ *     support = 2 * sigma;  for output o:  c = o + 0.5
+ *     left = clamp(floorf(c - support), 0, L - 1);  right = clamp(ceilf(c + support), left + 1, L)
+ *     w[k] = gaussian((left + k) - (c - 0.5)), summed in order, each divided by the sum
+ * Blur: a vertical pass over every sample column (channels independently, alpha included),
+ * t = 0 then t = t + (float)S * w[k] for ascending k, product and sum rounded separately,
+ * into an f32 image that is neither clamped nor rounded; the same pass horizontally over
+ * it; then clamp(t, 0, M) rounded to nearest, halves away from zero (M = 255 or 65535).
+ * Unsharpen: with B the blur, d = S - B per sample and out = |d| > threshold ?
+ * clamp(S + d, 0, M) : S.  Channels and depth are kept.  The sequence is always this one:
+ * IK_RESIZE_FMA does not apply.  sigma <= 0.25 gives one tap of weight 1, the identity. */
+#define IK_BLUR_MAX_SIGMA 32.0f
+/* the weight table of one axis; needs no device.  *taps receives T, the taps of the widest
+ * output.  With left, count and weights all NULL that is all; otherwise left[o] and
+ * count[o] for each of the L outputs and weights[o * cap_taps + k], zero from count[o] on,
+ * and cap_taps < T is IK_ERR_INVALID (*taps is set).  sigma must lie in
+ * [0.0625, IK_BLUR_MAX_SIGMA], L in 1..2^24. */
+int ik_blur_axis_plan(uint32_t L, float sigma, int32_t *left, int32_t *count, float *weights, uint32_t cap_taps,
+                      uint32_t *taps);
+/* the image blurred, or sharpened by the unsharp mask, as a new image on the device that
+ * holds img (8- and 16-bit; img is not changed).  sigma as above (0 is IK_ERR_INVALID here),
+ * threshold 0..65535: one at or above M never triggers. */
+int ik_image_blur(const ik_image *img, float sigma, ik_image **out);
+int ik_image_unsharpen(const ik_image *img, float sigma, int32_t threshold, ik_image **out);
+/* out[0], out[1]: the columns and rows of the output tile one workgroup of the kernel owns,
+ * the sizes at which its edge handling changes; for tests */
+int ik_blur_tile(int out[2]);
+/* process-wide: out[0] blur kernel launches, out[1] images filtered by them */
+int ik_blur_counters(unsigned long long out[2]);
 
 /* ---- fused / batched entry points (pixels stay in HBM) ----------------- */
 /* decode -> resize_image -> encode_image in one call (handler src/lib.rs:175-191) */
@@ -541,7 +594,7 @@ int ik_transform_oriented(const uint8_t *bytes, size_t len, int64_t w, int64_t h
  * its defaults, is ik_transform: the same calls.  An image without alpha is not touched by
  * a background: no pass, no copy. */
 int ik_transform_opts(const uint8_t *bytes, size_t len, int64_t w, int64_t h, int fmt, int quality, int filter,
-                      const ik_request_opts *opts, size_t opt_size, uint8_t **out, size_t *out_len);
+                      const void *opts, size_t opt_size, uint8_t **out, size_t *out_len);
 
 /* ik_transform over n requests at once (the /img handler under load, loadtest C4
  * mix): decode_image (one set of GPU launches for the batch's PNG streams, one set
@@ -623,8 +676,12 @@ int ik_transform_batch_submit_device(const uint8_t *const *dev_bytes, const size
                                      int filter, int threads, uint8_t **outs, size_t *out_lens, int *status,
                                      uint64_t *ticket);
 
-/* The batch calls with per-request options: opts holds n ik_request_opts (or is NULL: every
- * request at its defaults, the call without options), opt_size is sizeof(ik_request_opts).
+/* The batch calls with per-request options: opts holds n ik_request_opts or n
+ * ik_request_opts2 (or is NULL: every request at its defaults, the call without options),
+ * opt_size is the size of that layout.  After a resize group's launch and before its
+ * coders, its members that share (blur or unsharpen, sigma, threshold) are filtered by one
+ * launch, a lone one by its own; requests that differ only in these settings still share
+ * the resize and coder groups.
  * IK_ORIENT_AUTO is resolved from the bytes at submit, on the host.  In the post stage, on
  * the device that holds each decoded image, the turn runs first (as in the _oriented
  * calls), then the flatten, then the unchanged post plan, which sees the flattened C and
@@ -632,11 +689,11 @@ int ik_transform_batch_submit_device(const uint8_t *const *dev_bytes, const size
  * lone one by its own, and a request whose decoded image has no alpha, or whose background
  * is IK_BG_NONE, is not touched.  Wait with ik_transform_batch_wait. */
 int ik_transform_batch_opts(const uint8_t *const *bytes, const size_t *lens, uint32_t n, const int64_t *w,
-                            const int64_t *h, const ik_request_opts *opts, size_t opt_size, const int *fmt,
+                            const int64_t *h, const void *opts, size_t opt_size, const int *fmt,
                             const int *quality, int filter, int threads, uint8_t **outs, size_t *out_lens,
                             int *status);
 int ik_transform_batch_submit_opts(const uint8_t *const *bytes, const size_t *lens, uint32_t n, const int64_t *w,
-                                   const int64_t *h, const ik_request_opts *opts, size_t opt_size, const int *fmt,
+                                   const int64_t *h, const void *opts, size_t opt_size, const int *fmt,
                                    const int *quality, int filter, int threads, uint8_t **outs, size_t *out_lens,
                                    int *status, uint64_t *ticket);
 /* ik_transform_batch_submit_device with options: fit, background and an explicit
@@ -644,7 +701,7 @@ int ik_transform_batch_submit_opts(const uint8_t *const *bytes, const size_t *le
  * anything is queued: the in-place JPEG marker walk steps over APP1, so the file's
  * orientation is not known on the host. */
 int ik_transform_batch_submit_device_opts(const uint8_t *const *dev_bytes, const size_t *lens, uint32_t n,
-                                          const int64_t *w, const int64_t *h, const ik_request_opts *opts,
+                                          const int64_t *w, const int64_t *h, const void *opts,
                                           size_t opt_size, const int *fmt, const int *quality, int filter,
                                           int threads, uint8_t **outs, size_t *out_lens, int *status,
                                           uint64_t *ticket);
@@ -729,6 +786,23 @@ int ik_flatten_batch_device(const uint8_t *dev_src, uint32_t W, uint32_t H, uint
                             size_t src_pitch, size_t src_image_stride, uint32_t n, int32_t rgb,
                             uint32_t out_channels, uint8_t *dev_dst, size_t dst_pitch, size_t dst_image_stride,
                             void *hip_stream);
+/* blur (sharpen 0) or unsharpen (sharpen 1) over n images of W x H pixels of C = 1..4
+ * samples of `depth` bytes, image i at dev_src + i*src_image_stride, written with the same
+ * geometry at dev_dst + i*dst_image_stride, in one launch.  Nothing outside W*C*depth bytes
+ * of each of the H destination rows is written, and nothing outside W*C*depth bytes of each
+ * of the H source rows is read.  Bases, pitches and strides that are all multiples of 4
+ * take the wide path (dword loads and stores), for source and destination independently;
+ * any others the byte path.  Enqueued on hip_stream (NULL: the calling thread's stream)
+ * without waiting; the weight tables of (W, sigma) and (H, sigma) are uploaded once per
+ * device and kept.  IK_ERR_INVALID, with nothing launched and nothing written: sigma
+ * outside [0.0625, IK_BLUR_MAX_SIGMA] (0 included), sharpen outside 0..1, threshold outside
+ * 0..65535, C outside 1..4, depth outside 1..2, a null pointer, a zero size, a pitch below
+ * the row bytes, n > 1 with an image stride below rows * pitch, n above 65535, W above 2^24
+ * or H above 1048560, or source and destination bytes that overlap. */
+int ik_blur_batch_device(const uint8_t *dev_src, uint32_t W, uint32_t H, uint32_t C, uint32_t depth,
+                         size_t src_pitch, size_t src_image_stride, uint32_t n, float sigma, int sharpen,
+                         int32_t threshold, uint8_t *dev_dst, size_t dst_pitch, size_t dst_image_stride,
+                         void *hip_stream);
 /* the WebP colour conversion (to_rgb8 + libwebp RGB->YUV420) on the device;
  * dev_yuv receives the Y (w*h), U and V ((w+1)/2 * (h+1)/2) planes back to back */
 int ik_webp_yuv420_device(const uint8_t *dev_src, uint32_t w, uint32_t h, uint32_t C,

@@ -1396,9 +1396,10 @@ static void transform_decode_phase(const uint8_t* const* bytes, const size_t* le
 // request i's status / message land in st[i] / errs[i]
 // orient: null, or each request's effective orientation (0 = as stored, 2..8)
 // bg: null, or each request's background (IK_BG_NONE, or 0xRRGGBB)
+// flt: null, or each request's blur or unsharpen (mode 0: none), run on the resized image
 static void transform_post_phase(const int64_t* w, const int64_t* h, const int* fit, const int* orient,
-                                 const int32_t* bg, const int* fmt, const int* quality, int filter, int* st,
-                                 std::string* errs, HostPhase& hp) {
+                                 const int32_t* bg, const FilterReq* flt, const int* fmt, const int* quality,
+                                 int filter, int* st, std::string* errs, HostPhase& hp) {
     const std::vector<uint32_t>& idx = hp.idx;
     const int threads = hp.threads;
     const uint32_t m = (uint32_t)idx.size();
@@ -1513,6 +1514,45 @@ static void transform_post_phase(const int64_t* w, const int64_t* h, const int* 
         for (uint32_t k : G.members) src.push_back(imgs[k]);
         if (resize_group(src, G.win, filter, out) != IK_OK) continue;  // its members: image by image below
         for (size_t j = 0; j < out.size(); ++j) rsz[G.members[j]] = out[j];
+        // blur or unsharpen before the group's coders run: the members that share (mode,
+        // sigma, threshold) go through one launch, a lone one through its own, and the
+        // unfiltered image returns to the pool.  A member whose filter fails keeps its
+        // resized image for the coder groups below (its status is set: its file is dropped).
+        if (flt) {
+            std::map<std::array<uint32_t, 3>, std::vector<uint32_t>> sets;
+            for (uint32_t k : G.members) {
+                const FilterReq& f = flt[idx[k]];
+                if (!f.mode) continue;
+                uint32_t sb;
+                std::memcpy(&sb, &f.sigma, 4);
+                sets[{(uint32_t)f.mode, sb, (uint32_t)f.threshold}].push_back(k);
+            }
+            for (const auto& kv : sets) {
+                const std::vector<uint32_t>& ks = kv.second;
+                const FilterReq& f = flt[idx[ks[0]]];
+                std::vector<ik_image*> fo(ks.size(), nullptr);
+                bool grouped = false;
+                if (ks.size() > 1) {
+                    std::vector<ik_image*> fs;
+                    for (uint32_t k : ks) fs.push_back(rsz[k]);
+                    grouped = blur_group(fs, f.sigma, f.mode == 2, f.threshold, fo) == IK_OK;
+                }
+                for (size_t j = 0; j < ks.size(); ++j) {
+                    const uint32_t k = ks[j];
+                    if (!grouped) {
+                        const int r = f.mode == 2 ? ik_image_unsharpen(rsz[k], f.sigma, f.threshold, &fo[j])
+                                                  : ik_image_blur(rsz[k], f.sigma, &fo[j]);
+                        if (r) {
+                            ds[k] = r;
+                            dm[k] = last_error_str();
+                            continue;
+                        }
+                    }
+                    ik_image_free(rsz[k]);
+                    rsz[k] = fo[j];
+                }
+            }
+        }
         for (uint32_t c = G.cg_lo; c < G.cg_hi; ++c) {
             const PostPlan::CoderGroup& cg = plan.cgroups[c];
             std::vector<ik_image*> im;
@@ -1535,10 +1575,29 @@ static void transform_post_phase(const int64_t* w, const int64_t* h, const int* 
     t_resize += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tg0).count();
     parallel_for((int)m, threads, [&](int k) {
         const uint32_t i = idx[k];
-        if (ds[k]) { st[i] = ds[k]; errs[i] = dm[k]; return; }
+        if (ds[k]) {
+            st[i] = ds[k];
+            errs[i] = dm[k];
+            if (rsz[k]) {  // its group's filter failed after the resize
+                ik_image_free(rsz[k]);
+                ik_image_free(imgs[k]);
+                imgs[k] = nullptr;
+                prep[k].done = true;
+            }
+            return;
+        }
         ik_image* rs = rsz[k];
         const auto t0 = std::chrono::steady_clock::now();
         int r = rs ? IK_OK : ik_resize_fit(imgs[k], w[i], h[i], fit ? fit[i] : IK_FIT_CONTAIN, filter, &rs);
+        if (!r && !rsz[k] && flt && flt[i].mode) {  // resized here (or w and h both None): filtered here
+            ik_image* fo = nullptr;
+            r = flt[i].mode == 2 ? ik_image_unsharpen(rs, flt[i].sigma, flt[i].threshold, &fo)
+                                 : ik_image_blur(rs, flt[i].sigma, &fo);
+            if (!r) {
+                if (rs != imgs[k]) ik_image_free(rs);
+                rs = fo;
+            }
+        }
         const auto t1 = std::chrono::steady_clock::now();
         if (!r && !fronted[k] && plan.req[k].solo == PostRoute::WebpMixed) {
             (void)hipStreamSynchronize(thread_stream());  // this thread's resize is done: another's stream reads it
@@ -1674,6 +1733,8 @@ struct Ticket {
     // backgrounds (IK_BG_NONE or 0xRRGGBB), each empty when every request is at its default
     std::vector<int> fitv;
     std::vector<int32_t> bg;
+    // ik_request_opts2's blur and unsharpen; empty when no request asks for either
+    std::vector<FilterReq> flt;
 };
 
 // one device's share of a ticket
@@ -1686,6 +1747,7 @@ struct BatchPart {
     const int* fit = nullptr;  // null: every request IK_FIT_CONTAIN
     const int* orient = nullptr;  // null: every request as stored; else Ticket::orient
     const int32_t* bg = nullptr;  // null: no request has a background; else Ticket::bg
+    const FilterReq* flt = nullptr;  // null: no request blurs or sharpens; else Ticket::flt
     const int* fmt = nullptr;
     const int* quality = nullptr;
     int filter = 0;
@@ -1760,7 +1822,7 @@ private:
             if (stage == 2) {
                 // resize + the encoders' device front ends, beside the next batch's decode
                 Ticket& t = *p->t;
-                transform_post_phase(p->w, p->h, p->fit, p->orient, p->bg, p->fmt, p->quality, p->filter, t.st.data(),
+                transform_post_phase(p->w, p->h, p->fit, p->orient, p->bg, p->flt, p->fmt, p->quality, p->filter, t.st.data(),
                                      t.errs.data(), p->hp);
                 pool_->post([p] {
                     Ticket& tk = *p->t;
@@ -1886,6 +1948,7 @@ int shutdown_all(bool close) {
     png_shutdown();
     jpeg_shutdown();
     plans_shutdown();
+    blur_shutdown();
     memory_shutdown();
     release_thread_resources();
     if (dev >= 0) (void)hipSetDevice(dev);
@@ -1926,6 +1989,7 @@ int submit_parts(const std::shared_ptr<Ticket>& t, const uint8_t* const* bytes, 
         p->bytes = bytes; p->lens = lens; p->w = w; p->h = h; p->fit = fit; p->fmt = fmt; p->quality = quality;
         p->orient = t->orient.empty() ? nullptr : t->orient.data();
         p->bg = t->bg.empty() ? nullptr : t->bg.data();
+        p->flt = t->flt.empty() ? nullptr : t->flt.data();
         p->sniff = sniff;
         p->filter = filter;
         p->hp.threads = threads;
@@ -2040,8 +2104,37 @@ int ik_transform_batch_submit_oriented(const uint8_t* const* bytes, const size_t
     return submit_parts(t, bytes, nullptr, -1, lens, n, w, h, fit, fmt, quality, filter, threads, ticket);
 }
 
-// ---- per-request options (ik_request_opts) ----
-static bool opts_size_ok(size_t opt_size) { return opt_size == sizeof(ik_request_opts); }
+// ---- per-request options (ik_request_opts, ik_request_opts2) ----
+static bool opts_size_ok(size_t opt_size) {
+    return opt_size == sizeof(ik_request_opts) || opt_size == sizeof(ik_request_opts2);
+}
+// request i of an options array whose structs lie opt_size bytes apart, as the larger
+// layout (the smaller one's new fields: zero, "off")
+static ik_request_opts2 opts_at(const void* opts, size_t opt_size, uint32_t i) {
+    ik_request_opts2 o{};
+    std::memcpy(&o, static_cast<const uint8_t*>(opts) + (size_t)i * opt_size, opt_size);
+    return o;
+}
+// the blur or unsharpen an options struct asks for.  Returns IK_OK, or IK_ERR_INVALID with
+// the message set (prefix: "" or "request i: ")
+static int filter_of(const ik_request_opts2& o, const char* prefix, FilterReq& f) {
+    f = FilterReq();
+    // (written so that a NaN fails)
+    const bool bs = o.blur_sigma == 0.0f || (o.blur_sigma >= 0.0625f && o.blur_sigma <= IK_BLUR_MAX_SIGMA);
+    const bool ss = o.sharpen_sigma == 0.0f || (o.sharpen_sigma >= 0.0625f && o.sharpen_sigma <= IK_BLUR_MAX_SIGMA);
+    if (!bs)
+        return fail(IK_ERR_INVALID, "%sblur sigma %g is neither 0 nor in 0.0625..%g", prefix, (double)o.blur_sigma,
+                    (double)IK_BLUR_MAX_SIGMA);
+    if (!ss)
+        return fail(IK_ERR_INVALID, "%ssharpen sigma %g is neither 0 nor in 0.0625..%g", prefix, (double)o.sharpen_sigma,
+                    (double)IK_BLUR_MAX_SIGMA);
+    if (!blur_threshold_ok(o.sharpen_threshold))
+        return fail(IK_ERR_INVALID, "%ssharpen threshold %d outside 0..65535", prefix, (int)o.sharpen_threshold);
+    if (o.blur_sigma != 0.0f && o.sharpen_sigma != 0.0f) return fail(IK_ERR_INVALID, "%sblur and sharpen together", prefix);
+    if (o.blur_sigma != 0.0f) { f.mode = 1; f.sigma = o.blur_sigma; }
+    else if (o.sharpen_sigma != 0.0f) { f.mode = 2; f.sigma = o.sharpen_sigma; f.threshold = o.sharpen_threshold; }
+    return IK_OK;
+}
 static bool background_ok(int32_t b) { return b == IK_BG_NONE || (b >= 0 && b <= 0xFFFFFF); }
 
 // a batch's options as the arrays its ticket keeps, each left empty when every request is at
@@ -2049,15 +2142,16 @@ static bool background_ok(int32_t b) { return b == IK_BG_NONE || (b >= 0 && b <=
 struct OptArrays {
     std::vector<int> fit, orient;  // orient: effective orientations (0 = as stored, 2..8)
     std::vector<int32_t> bg;
-    bool none() const { return fit.empty() && orient.empty() && bg.empty(); }
+    std::vector<FilterReq> flt;
+    bool none() const { return fit.empty() && orient.empty() && bg.empty() && flt.empty(); }
 };
 
 // bytes: the files in host memory, or null (device-resident inputs: IK_ORIENT_AUTO cannot be
 // resolved and is refused).  Returns IK_OK or IK_ERR_INVALID with the message set.
-static int split_opts(const ik_request_opts* opts, uint32_t n, const uint8_t* const* bytes, const size_t* lens,
+static int split_opts(const void* opts, size_t opt_size, uint32_t n, const uint8_t* const* bytes, const size_t* lens,
                       OptArrays& a) {
     for (uint32_t i = 0; opts && i < n; ++i) {
-        const ik_request_opts& o = opts[i];
+        const ik_request_opts2 o = opts_at(opts, opt_size, i);
         if (o.fit < IK_FIT_CONTAIN || o.fit > IK_FIT_EXACT)
             return fail(IK_ERR_INVALID, "request %u: unknown fit %d", i, o.fit);
         if (!background_ok(o.background))
@@ -2083,12 +2177,20 @@ static int split_opts(const ik_request_opts* opts, uint32_t n, const uint8_t* co
             if (a.bg.empty()) a.bg.assign(n, IK_BG_NONE);
             a.bg[i] = o.background;
         }
+        char prefix[32];
+        snprintf(prefix, sizeof prefix, "request %u: ", i);
+        FilterReq f;
+        if (int rc = filter_of(o, prefix, f)) return rc;
+        if (f.mode) {
+            if (a.flt.empty()) a.flt.assign(n, FilterReq());
+            a.flt[i] = f;
+        }
     }
     return IK_OK;
 }
 
 int ik_transform_batch_submit_opts(const uint8_t* const* bytes, const size_t* lens, uint32_t n, const int64_t* w,
-                                   const int64_t* h, const ik_request_opts* opts, size_t opt_size, const int* fmt,
+                                   const int64_t* h, const void* opts, size_t opt_size, const int* fmt,
                                    const int* quality, int filter, int threads, uint8_t** outs, size_t* out_lens,
                                    int* status, uint64_t* ticket) {
     IK_API_ENTER();
@@ -2096,7 +2198,7 @@ int ik_transform_batch_submit_opts(const uint8_t* const* bytes, const size_t* le
     if (!bytes || !lens || !w || !h || !fmt || !quality || !outs || !out_lens || !n || !ticket)
         return fail(IK_ERR_INVALID, "bad batch");
     OptArrays a;
-    if (int rc = split_opts(opts, n, bytes, lens, a)) return rc;
+    if (int rc = split_opts(opts, opt_size, n, bytes, lens, a)) return rc;
     if (a.none())  // every request at its defaults: the plain submit itself
         return ik_transform_batch_submit(bytes, lens, n, w, h, fmt, quality, filter, threads, outs, out_lens, status,
                                          ticket);
@@ -2104,12 +2206,13 @@ int ik_transform_batch_submit_opts(const uint8_t* const* bytes, const size_t* le
     t->fitv.swap(a.fit);
     t->orient.swap(a.orient);
     t->bg.swap(a.bg);
+    t->flt.swap(a.flt);
     return submit_parts(t, bytes, nullptr, -1, lens, n, w, h, t->fitv.empty() ? nullptr : t->fitv.data(), fmt, quality,
                         filter, threads, ticket);
 }
 
 int ik_transform_batch_opts(const uint8_t* const* bytes, const size_t* lens, uint32_t n, const int64_t* w,
-                            const int64_t* h, const ik_request_opts* opts, size_t opt_size, const int* fmt,
+                            const int64_t* h, const void* opts, size_t opt_size, const int* fmt,
                             const int* quality, int filter, int threads, uint8_t** outs, size_t* out_lens, int* status) {
     IK_API_ENTER();
     uint64_t ticket = 0;
@@ -2133,7 +2236,7 @@ int ik_transform_batch_submit_device(const uint8_t* const* dev_bytes, const size
 }
 
 int ik_transform_batch_submit_device_opts(const uint8_t* const* dev_bytes, const size_t* lens, uint32_t n,
-                                          const int64_t* w, const int64_t* h, const ik_request_opts* opts,
+                                          const int64_t* w, const int64_t* h, const void* opts,
                                           size_t opt_size, const int* fmt, const int* quality, int filter, int threads,
                                           uint8_t** outs, size_t* out_lens, int* status, uint64_t* ticket) {
     IK_API_ENTER();
@@ -2141,7 +2244,7 @@ int ik_transform_batch_submit_device_opts(const uint8_t* const* dev_bytes, const
     if (!dev_bytes || !lens || !w || !h || !fmt || !quality || !outs || !out_lens || !n || !ticket)
         return fail(IK_ERR_INVALID, "bad batch");
     OptArrays a;
-    if (int rc = split_opts(opts, n, nullptr, lens, a)) return rc;  // before anything is queued
+    if (int rc = split_opts(opts, opt_size, n, nullptr, lens, a)) return rc;  // before anything is queued
     return submit_device(dev_bytes, lens, n, w, h, a, fmt, quality, filter, threads, outs, out_lens, status, ticket);
 }
 
@@ -2261,6 +2364,7 @@ static int submit_device(const uint8_t* const* dev_bytes, const size_t* lens, ui
     t->fitv.swap(opt.fit);
     t->orient.swap(opt.orient);
     t->bg.swap(opt.bg);
+    t->flt.swap(opt.flt);
     return submit_parts(t, t->eff.data(), t->sniff.data(), phys, lens, n, w, h,
                         t->fitv.empty() ? nullptr : t->fitv.data(), fmt, quality, filter, threads, ticket);
 }
@@ -2339,8 +2443,10 @@ int ik_transform_batch_oriented(const uint8_t* const* bytes, const size_t* lens,
 
 // orientation: 0 = the pixels as stored, 2..8 = turned first (effective_orientation);
 // background: IK_BG_NONE, or the colour an image with alpha is flattened onto after the turn
+// flt: the blur or unsharpen of the resized image (mode 0: none)
 static int transform_here(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orientation,
-                          int32_t background, int fmt, int quality, int filter, uint8_t** out, size_t* out_len) {
+                          int32_t background, FilterReq flt, int fmt, int quality, int filter, uint8_t** out,
+                          size_t* out_len) {
     ik_image* img = nullptr;
     int st = decode_one(bytes, len, &img, nullptr);
     if (st) return st;
@@ -2361,6 +2467,13 @@ static int transform_here(const uint8_t* bytes, size_t len, int64_t w, int64_t h
     ik_image* rs = nullptr;
     st = ik_resize_fit(img, w, h, fit, filter, &rs);
     if (st) { ik_image_free(img); return st; }
+    if (flt.mode) {  // the filter sees the pixels the encoder will code
+        ik_image* fo = nullptr;
+        st = flt.mode == 2 ? ik_image_unsharpen(rs, flt.sigma, flt.threshold, &fo) : ik_image_blur(rs, flt.sigma, &fo);
+        if (rs != img) ik_image_free(rs);
+        if (st) { ik_image_free(img); return st; }
+        rs = fo;
+    }
     st = ik_encode(rs, fmt, quality, out, out_len);
     if (rs != img) ik_image_free(rs);
     ik_image_free(img);
@@ -2374,26 +2487,30 @@ int ik_transform(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fmt
 }
 
 static int transform_scheduled(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orientation,
-                               int32_t background, int fmt, int quality, int filter, uint8_t** out, size_t* out_len);
+                               int32_t background, FilterReq flt, int fmt, int quality, int filter, uint8_t** out,
+                               size_t* out_len);
 
 int ik_transform_fit(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int fmt, int quality,
                      int filter, uint8_t** out, size_t* out_len) {
     IK_API_ENTER();
-    return transform_scheduled(bytes, len, w, h, fit, 0, IK_BG_NONE, fmt, quality, filter, out, out_len);
+    return transform_scheduled(bytes, len, w, h, fit, 0, IK_BG_NONE, FilterReq(), fmt, quality, filter, out, out_len);
 }
 
 // (the *_opts calls; opts_size_ok and background_ok: above, with the batch submits)
 
 int ik_transform_opts(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fmt, int quality, int filter,
-                      const ik_request_opts* opts, size_t opt_size, uint8_t** out, size_t* out_len) {
+                      const void* opts, size_t opt_size, uint8_t** out, size_t* out_len) {
     IK_API_ENTER();
     if (!opts_size_ok(opt_size)) return fail(IK_ERR_INVALID, "unknown options size %zu", opt_size);
     if (!opts) return ik_transform(bytes, len, w, h, fmt, quality, filter, out, out_len);
-    if (!background_ok(opts->background))
-        return fail(IK_ERR_INVALID, "background %d is neither IK_BG_NONE nor 0x000000..0xFFFFFF", (int)opts->background);
-    const int o = effective_orientation(bytes, len, opts->orient);
-    if (o < 0) return fail(IK_ERR_INVALID, "unknown orientation %d", opts->orient);
-    return transform_scheduled(bytes, len, w, h, opts->fit, o, opts->background, fmt, quality, filter, out, out_len);
+    const ik_request_opts2 ro = opts_at(opts, opt_size, 0);
+    if (!background_ok(ro.background))
+        return fail(IK_ERR_INVALID, "background %d is neither IK_BG_NONE nor 0x000000..0xFFFFFF", (int)ro.background);
+    FilterReq flt;
+    if (int rc = filter_of(ro, "", flt)) return rc;
+    const int o = effective_orientation(bytes, len, ro.orient);
+    if (o < 0) return fail(IK_ERR_INVALID, "unknown orientation %d", ro.orient);
+    return transform_scheduled(bytes, len, w, h, ro.fit, o, ro.background, flt, fmt, quality, filter, out, out_len);
 }
 
 int ik_transform_oriented(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orient, int fmt,
@@ -2401,14 +2518,15 @@ int ik_transform_oriented(const uint8_t* bytes, size_t len, int64_t w, int64_t h
     IK_API_ENTER();
     const int o = effective_orientation(bytes, len, orient);
     if (o < 0) return fail(IK_ERR_INVALID, "unknown orientation %d", orient);
-    return transform_scheduled(bytes, len, w, h, fit, o, IK_BG_NONE, fmt, quality, filter, out, out_len);
+    return transform_scheduled(bytes, len, w, h, fit, o, IK_BG_NONE, FilterReq(), fmt, quality, filter, out, out_len);
 }
 
 // on this device, or (several devices) on the least-loaded one's workers
 static int transform_scheduled(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orientation,
-                               int32_t background, int fmt, int quality, int filter, uint8_t** out, size_t* out_len) {
+                               int32_t background, FilterReq flt, int fmt, int quality, int filter, uint8_t** out,
+                               size_t* out_len) {
     if (!sched_multi())
-        return transform_here(bytes, len, w, h, fit, orientation, background, fmt, quality, filter, out, out_len);
+        return transform_here(bytes, len, w, h, fit, orientation, background, flt, fmt, quality, filter, out, out_len);
     // several devices: queue the request to the least-loaded device's workers
     const uint64_t cost = request_cost(bytes, len, w, h, fmt);
     const int ld = sched_acquire(cost);
@@ -2418,7 +2536,7 @@ static int transform_scheduled(const uint8_t* bytes, size_t len, int64_t w, int6
     int st = IK_OK;
     std::string msg;
     sched_pool(ld).post([&] {
-        const int r = transform_here(bytes, len, w, h, fit, orientation, background, fmt, quality, filter, out, out_len);
+        const int r = transform_here(bytes, len, w, h, fit, orientation, background, flt, fmt, quality, filter, out, out_len);
         std::string m = r ? last_error_str() : std::string();
         std::lock_guard<std::mutex> lk(mu);
         st = r;

@@ -298,6 +298,37 @@ inline uint32_t flatten_out_channels(uint32_t c, uint32_t rgb) {
     return c;
 }
 
+// ---- blur and unsharpen (ik_blur.hip) ----
+// a Gaussian blur, or the unsharp mask built on it, over n images of W x H pixels of C
+// samples of `depth` bytes, images addressed as launch_orient addresses them.  One axis's
+// device tables are those of ik_blur_plan.h: per output left and count, T zero-padded
+// weights, and the interior run that shares one weight vector.
+constexpr int kBlurTileW = 64;   // output columns of a workgroup's tile
+constexpr int kBlurTileH = 16;   // its rows
+constexpr int kBlurMaxR = 65;    // most halo columns on a side (sigma 32: 64, one spare for f32 rounding)
+constexpr uint32_t kBlurMaxImages = 65535;  // grid.z
+struct BlurAxisTab {
+    const int* left;
+    const int* cnt;
+    const float* w;
+    int T;
+    int u_lo, u_hi, u_dl, u_cnt;  // outputs [u_lo, u_hi): left = o - u_dl, u_cnt taps, the weights of row u_lo
+};
+struct BlurArgs {
+    const uint8_t* src;
+    size_t src_pitch, src_img_stride;
+    uint8_t* dst;
+    size_t dst_pitch, dst_img_stride;
+    const uint64_t* src_tab;  // per-image bases (device), or null: src + img * src_img_stride
+    const uint64_t* dst_tab;
+    uint32_t W, H, C;
+    BlurAxisTab x, y;
+    int halo;                      // most source columns left plus right of an output's own (<= 2 * kBlurMaxR)
+    int threshold;                 // unsharpen: |S - B| above it sharpens
+    int src_aligned, dst_aligned;  // bases, pitches and strides are multiples of 4
+};
+hipError_t launch_blur(const BlurArgs& a, int depth, bool sharpen, int n, hipStream_t s);
+
 // ---- plans (ik_plan.cpp) ----
 // axis_weights, required_slots and the tables themselves: ik_resize_plan.h
 ResizePlan* get_resize_plan(int device, int W, int H, int C, int nw, int nh, int filter, int n);

@@ -474,6 +474,18 @@ int orient_group(const std::vector<ik_image*>& src, int orientation, std::vector
 int flatten_group(const std::vector<ik_image*>& src, uint32_t rgb, std::vector<ik_image*>& out);
 // process-wide flatten launches and images flattened (ik_flatten_counters)
 void flatten_count(uint64_t launches, uint64_t images);
+// one request's blur or unsharpen, after its resize (ik_request_opts2)
+struct FilterReq {
+    int mode = 0;  // 0: none, 1: blur, 2: unsharpen
+    float sigma = 0.0f;
+    int32_t threshold = 0;
+};
+// blur or unsharpen of same-geometry images in one launch (ik_blur_host.cpp); a return other
+// than IK_OK leaves every image to ik_image_blur / ik_image_unsharpen
+int blur_group(const std::vector<ik_image*>& src, float sigma, bool sharpen, int32_t threshold,
+               std::vector<ik_image*>& out);
+bool blur_threshold_ok(int32_t t);  // 0..65535
+void blur_shutdown();               // ik_shutdown: the cached axis tables (ik_blur_host.cpp)
 
 // Per-device phase gates (ik_pool.cpp).  Concurrent batch calls on one device
 // take its GPU phases in turn: kGateUpload covers a PNG batch's staging, H2D and

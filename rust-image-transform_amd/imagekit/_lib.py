@@ -32,7 +32,13 @@ class RequestOpts(ctypes.Structure):
     _fields_ = [("fit", ctypes.c_int), ("orient", ctypes.c_int), ("background", ctypes.c_int32)]
 
 
-_opts_p = ctypes.POINTER(RequestOpts)
+class RequestOpts2(ctypes.Structure):
+    """ik_request_opts2: RequestOpts' fields, then blur and unsharpen (a sigma of 0 is off)."""
+    _fields_ = [("fit", ctypes.c_int), ("orient", ctypes.c_int), ("background", ctypes.c_int32),
+                ("blur_sigma", ctypes.c_float), ("sharpen_sigma", ctypes.c_float), ("sharpen_threshold", ctypes.c_int32)]
+
+
+_opts_p = ctypes.c_void_p  # either layout (const void *opts, with its size)
 _batch_head = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint32,
                ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
 _batch_opts = (_batch_head + [_opts_p, ctypes.c_size_t] + [ctypes.POINTER(ctypes.c_int)] * 2 + [ctypes.c_int, ctypes.c_int]
@@ -166,6 +172,12 @@ SIGNATURES = [
     ("ik_flatten_counters", ctypes.c_int, [ctypes.POINTER(ctypes.c_ulonglong)]),
     ("ik_image_flatten", ctypes.c_int, [c_img_p, ctypes.c_int32, ctypes.POINTER(c_img_p)]),
     ("ik_flatten_batch_device", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_uint32] * 4 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]),
+    ("ik_blur_axis_plan", ctypes.c_int, [ctypes.c_uint32, ctypes.c_float, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    ("ik_image_blur", ctypes.c_int, [c_img_p, ctypes.c_float, ctypes.POINTER(c_img_p)]),
+    ("ik_image_unsharpen", ctypes.c_int, [c_img_p, ctypes.c_float, ctypes.c_int32, ctypes.POINTER(c_img_p)]),
+    ("ik_blur_tile", ctypes.c_int, [ctypes.POINTER(ctypes.c_int)]),
+    ("ik_blur_counters", ctypes.c_int, [ctypes.POINTER(ctypes.c_ulonglong)]),
+    ("ik_blur_batch_device", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_uint32] * 4 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_float, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]),
     ("ik_transform_opts", ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int] * 3 + [_opts_p, ctypes.c_size_t, ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t)]),
     ("ik_transform_batch_opts", ctypes.c_int, _batch_opts),
     ("ik_transform_batch_submit_opts", ctypes.c_int, _batch_opts + [ctypes.POINTER(ctypes.c_uint64)]),

@@ -117,13 +117,62 @@ def _background(bg) -> int:
     raise ValueError(f"background {bg!r} is not a colour")
 
 
-def _request_opts(n, fits=None, orients=None, backgrounds=None):
-    """The ik_request_opts array of a *_opts batch call (each argument: one entry per
-    request, or None for that option's default everywhere)."""
-    for name, v in (("fits", fits), ("orient", orients), ("backgrounds", backgrounds)):
+BLUR_MIN_SIGMA, BLUR_MAX_SIGMA = 0.0625, 32.0  # IK_BLUR_MAX_SIGMA
+
+
+def _sigma(v, what="sigma") -> float:
+    """A sigma argument: None or 0 (off: 0.0), or a number within [0.0625, 32].  Anything
+    else raises ValueError, before the library is called."""
+    if v is None:
+        return 0.0
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{what} {v!r} is not a number")
+    f = float(v)
+    if f == 0.0:
+        return 0.0
+    if not BLUR_MIN_SIGMA <= f <= BLUR_MAX_SIGMA:  # (a NaN fails both comparisons)
+        raise ValueError(f"{what} {v!r} outside {BLUR_MIN_SIGMA}..{BLUR_MAX_SIGMA}")
+    return f
+
+
+def _sharpen(v) -> Tuple[float, int]:
+    """A `sharpen=` argument as (sigma, threshold): None (off), a sigma, or (sigma,
+    threshold) with the threshold an int in 0..65535, in the sample's own units."""
+    if v is None:
+        return 0.0, 0
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2:
+            raise ValueError(f"sharpen {v!r} is not (sigma, threshold)")
+        t = v[1]
+        if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= int(t) <= 65535:
+            raise ValueError(f"sharpen threshold {t!r} is not an int in 0..65535")
+        return _sigma(v[0], "sharpen sigma"), int(t)
+    return _sigma(v, "sharpen sigma"), 0
+
+
+def _filter_args(blur, sharpen) -> Tuple[float, float, int]:
+    """(blur sigma, sharpen sigma, sharpen threshold) of one request; both at once is a
+    ValueError, as the library refuses it."""
+    b = _sigma(blur, "blur sigma")
+    s, t = _sharpen(sharpen)
+    if b and s:
+        raise ValueError("blur and sharpen together")
+    return b, s, t
+
+
+def _request_opts(n, fits=None, orients=None, backgrounds=None, blurs=None, sharpens=None):
+    """The options array of a *_opts batch call (each argument: one entry per request, or
+    None for that option's default everywhere): ik_request_opts, or ik_request_opts2 when
+    blurs or sharpens is given.  Its element size is ctypes.sizeof(arr._type_)."""
+    for name, v in (("fits", fits), ("orient", orients), ("backgrounds", backgrounds), ("blurs", blurs),
+                    ("sharpens", sharpens)):
         if v is not None and len(v) != n:
             raise InvalidArgument(f"{name} must have one entry per request")
-    arr = (_lib.RequestOpts * n)()
+    wide = blurs is not None or sharpens is not None
+    arr = ((_lib.RequestOpts2 if wide else _lib.RequestOpts) * n)()
+    for i in range(n if wide else 0):
+        arr[i].blur_sigma, arr[i].sharpen_sigma, arr[i].sharpen_threshold = _filter_args(
+            blurs[i] if blurs is not None else None, sharpens[i] if sharpens is not None else None)
     for i in range(n):
         arr[i].fit = int(FitMode(fits[i])) if fits is not None else int(FitMode.contain)
         arr[i].orient = _orient(orients[i]) if orients is not None else int(Orientation.stored)
@@ -263,6 +312,30 @@ class DynamicImage:
             _raise(st, "flatten")
         return DynamicImage(out.value)
 
+    def blur(self, sigma: float) -> "DynamicImage":
+        """A Gaussian blur of the image as a new image (ik_image_blur; the project's own
+        definition): sigma within [0.0625, 32], channels and depth kept."""
+        f = _sigma(sigma)
+        if not f:
+            raise ValueError(f"sigma {sigma!r} outside {BLUR_MIN_SIGMA}..{BLUR_MAX_SIGMA}")
+        out = ctypes.c_void_p()
+        st = _lib.load().ik_image_blur(self._h, f, ctypes.byref(out))
+        if st:
+            _raise(st, "blur")
+        return DynamicImage(out.value)
+
+    def unsharpen(self, sigma: float, threshold: int = 0) -> "DynamicImage":
+        """The unsharp mask as a new image (ik_image_unsharpen): with B the blur of sigma,
+        a sample S whose |S - B| exceeds threshold becomes clamp(2 S - B)."""
+        f, t = _sharpen((sigma, threshold))
+        if not f:
+            raise ValueError(f"sigma {sigma!r} outside {BLUR_MIN_SIGMA}..{BLUR_MAX_SIGMA}")
+        out = ctypes.c_void_p()
+        st = _lib.load().ik_image_unsharpen(self._h, f, t, ctypes.byref(out))
+        if st:
+            _raise(st, "unsharpen")
+        return DynamicImage(out.value)
+
     def clone(self) -> "DynamicImage":
         return DynamicImage.from_array(self.to_array())
 
@@ -385,12 +458,14 @@ def _inputs(datas):
 
 
 def transform_batch(datas, sizes, fmts, qualities, filter: "FilterType" = None, threads: int = 0,
-                    fits=None, orient=None, backgrounds=None) -> List[bytes]:
+                    fits=None, orient=None, backgrounds=None, blurs=None, sharpens=None) -> List[bytes]:
     """ik_transform_batch: decode -> resize_image -> encode_image for many requests
     (sizes: (w, h) per request, None = unset; fmts: ImageFormat per request; fits: a
     FitMode per request, None = contain for all; orient: an Orientation per request,
     None = stored for all; backgrounds: a colour per request as `transform` takes it,
-    None = no flatten for any: with it the call is ik_transform_batch_opts)."""
+    None = no flatten for any; blurs: a sigma per request, sharpens: a sigma or (sigma,
+    threshold) per request, None = off.  With backgrounds, blurs or sharpens the call is
+    ik_transform_batch_opts)."""
     lib = _lib.load()
     bufs, ptrs, lens = _inputs(datas)
     n = len(bufs)
@@ -406,9 +481,9 @@ def transform_batch(datas, sizes, fmts, qualities, filter: "FilterType" = None, 
     status = (ctypes.c_int * n)()
     fa = _fits(fits, n)
     oa = _orients(orient, n)
-    if backgrounds is not None:
-        ra = _request_opts(n, fits, orient, backgrounds)
-        st = lib.ik_transform_batch_opts(ptrs, lens, n, ws, hs, ra, ctypes.sizeof(_lib.RequestOpts), fs, qs, filt,
+    if backgrounds is not None or blurs is not None or sharpens is not None:
+        ra = _request_opts(n, fits, orient, backgrounds, blurs, sharpens)
+        st = lib.ik_transform_batch_opts(ptrs, lens, n, ws, hs, ra, ctypes.sizeof(ra._type_), fs, qs, filt,
                                          threads, outs, olens, status)
     elif oa is not None:
         st = lib.ik_transform_batch_oriented(ptrs, lens, n, ws, hs, fa, oa, fs, qs, filt, threads, outs, olens, status)
@@ -453,10 +528,11 @@ class PendingBatch:
 
 
 def transform_batch_submit(datas, sizes, fmts, qualities, filter: "FilterType" = None,
-                           threads: int = 0, fits=None, orient=None, backgrounds=None) -> PendingBatch:
+                           threads: int = 0, fits=None, orient=None, backgrounds=None, blurs=None,
+                           sharpens=None) -> PendingBatch:
     """ik_transform_batch_submit: the device half of transform_batch now, the host
     coders in the background; PendingBatch.wait() gives what transform_batch gives.
-    fits, orient and backgrounds as transform_batch takes them."""
+    fits, orient, backgrounds, blurs and sharpens as transform_batch takes them."""
     lib = _lib.load()
     bufs, ptrs, lens = _inputs(datas)
     n = len(bufs)
@@ -474,9 +550,9 @@ def transform_batch_submit(datas, sizes, fmts, qualities, filter: "FilterType" =
     fa = _fits(fits, n)
     oa = _orients(orient, n)
     ra = None
-    if backgrounds is not None:
-        ra = _request_opts(n, fits, orient, backgrounds)
-        st = lib.ik_transform_batch_submit_opts(ptrs, lens, n, ws, hs, ra, ctypes.sizeof(_lib.RequestOpts), fs, qs,
+    if backgrounds is not None or blurs is not None or sharpens is not None:
+        ra = _request_opts(n, fits, orient, backgrounds, blurs, sharpens)
+        st = lib.ik_transform_batch_submit_opts(ptrs, lens, n, ws, hs, ra, ctypes.sizeof(ra._type_), fs, qs,
                                                 filt, threads, outs, olens, status, ctypes.byref(ticket))
     elif oa is not None:
         st = lib.ik_transform_batch_submit_oriented(ptrs, lens, n, ws, hs, fa, oa, fs, qs, filt, threads, outs, olens,
@@ -493,9 +569,10 @@ def transform_batch_submit(datas, sizes, fmts, qualities, filter: "FilterType" =
 
 
 def transform_batch_submit_device(datas, sizes, fmts, qualities, filter: "FilterType" = None,
-                                  threads: int = 0, fits=None, orient=None, backgrounds=None) -> PendingBatch:
+                                  threads: int = 0, fits=None, orient=None, backgrounds=None, blurs=None,
+                                  sharpens=None) -> PendingBatch:
     """ik_transform_batch_submit_device: as transform_batch_submit, over request
-    bodies already in device memory (DeviceBytes).  With fits, orient or backgrounds the
+    bodies already in device memory (DeviceBytes).  With fits, orient, backgrounds, blurs or sharpens the
     call is ik_transform_batch_submit_device_opts; Orientation.auto is refused there (the
     files are not read on the host)."""
     lib = _lib.load()
@@ -517,12 +594,12 @@ def transform_batch_submit_device(datas, sizes, fmts, qualities, filter: "Filter
     status = (ctypes.c_int * n)()
     ticket = ctypes.c_uint64()
     ra = None
-    if fits is None and orient is None and backgrounds is None:
+    if fits is None and orient is None and backgrounds is None and blurs is None and sharpens is None:
         st = lib.ik_transform_batch_submit_device(ptrs, lens, n, ws, hs, fs, qs, filt, threads, outs, olens, status,
                                                   ctypes.byref(ticket))
     else:
-        ra = _request_opts(n, fits, orient, backgrounds)
-        st = lib.ik_transform_batch_submit_device_opts(ptrs, lens, n, ws, hs, ra, ctypes.sizeof(_lib.RequestOpts), fs,
+        ra = _request_opts(n, fits, orient, backgrounds, blurs, sharpens)
+        st = lib.ik_transform_batch_submit_device_opts(ptrs, lens, n, ws, hs, ra, ctypes.sizeof(ra._type_), fs,
                                                        qs, filt, threads, outs, olens, status, ctypes.byref(ticket))
     if st:
         raise TransformError(_lib.last_error())
@@ -563,19 +640,26 @@ def encode_image(img: DynamicImage, fmt: ImageFormat, quality: int) -> bytes:
 
 def transform(data: bytes, w: Optional[int], h: Optional[int], fmt: ImageFormat, quality: int,
               filter: FilterType = FilterType.Lanczos3, fit: FitMode = FitMode.contain,
-              orient=Orientation.stored, background=None) -> bytes:
+              orient=Orientation.stored, background=None, blur=None, sharpen=None) -> bytes:
     """decode -> resize_image -> encode_image in one device-resident call; with orient
     (Orientation) the decoded image is turned first, and w, h and fit refer to the turned
     image; with background (0xRRGGBB, (r, g, b), "rrggbb" or "#rrggbb") an image that
-    carries alpha is then composited onto that colour, before the resize
-    (ik_transform_opts)."""
+    carries alpha is then composited onto that colour, before the resize; with blur (a
+    sigma) or sharpen (a sigma, or (sigma, threshold)) the resized image is blurred or
+    sharpened by the unsharp mask before it is encoded (ik_transform_opts)."""
     bg = _background(background)
+    fa = _filter_args(blur, sharpen)
     lib = _lib.load()
     b = bytes(data)
     buf = _lib.u8p()
     n = ctypes.c_size_t()
     o = _orient(orient)
-    if bg != BG_NONE:
+    if fa[0] or fa[1]:
+        ro = _lib.RequestOpts2(int(FitMode(fit)), o, bg, *fa)
+        st = lib.ik_transform_opts(b, len(b), -1 if w is None else int(w), -1 if h is None else int(h),
+                                   ImageFormat(fmt).value, int(quality), int(filter), ctypes.byref(ro),
+                                   ctypes.sizeof(ro), ctypes.byref(buf), ctypes.byref(n))
+    elif bg != BG_NONE:
         ro = _lib.RequestOpts(int(FitMode(fit)), o, bg)
         st = lib.ik_transform_opts(b, len(b), -1 if w is None else int(w), -1 if h is None else int(h),
                                    ImageFormat(fmt).value, int(quality), int(filter), ctypes.byref(ro),

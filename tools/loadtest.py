@@ -118,6 +118,11 @@ def main():
                     help="every request passes this background colour (ik_transform_batch*_opts): images with alpha "
                          "are flattened onto it before the resize.  The default JPEG sources carry no alpha, so "
                          "none is flattened.  Without the flag: the calls without options, as before")
+    ap.add_argument("--sharpen", default=None, metavar="SIGMA[,THRESHOLD]",
+                    help="every request sharpens its resized image with the unsharp mask (ik_transform_batch*_opts, "
+                         "the 24-byte options).  Without --sharpen and --blur: the calls made before")
+    ap.add_argument("--blur", default=None, type=float, metavar="SIGMA",
+                    help="every request blurs its resized image (not together with --sharpen)")
     ap.add_argument("--source", choices=["jpeg", "png-rgba"], default="jpeg",
                     help="png-rgba: translucent RGBA PNG sources of the same size (what --background acts on)")
     ap.add_argument("--restart", action="store_true")
@@ -178,10 +183,22 @@ def main():
     def backgrounds(chunk):  # None: the calls without options, as before
         return [args.background] * len(chunk) if args.background is not None else None
 
+    sharpen = None
+    if args.sharpen is not None:
+        parts = args.sharpen.split(",")
+        sharpen = float(parts[0]) if len(parts) == 1 else (float(parts[0]), int(parts[1]))
+
+    def blurs(chunk):  # None (with sharpens None too): the calls made before
+        return [args.blur] * len(chunk) if args.blur is not None else None
+
+    def sharpens(chunk):
+        return [sharpen] * len(chunk) if sharpen is not None else None
+
     def run_batch(chunk):
         return transform_batch([srcs[s] for s, _, _, _ in chunk], [(w, h) for _, w, h, _ in chunk],
                                [f for _, _, _, f in chunk], [args.quality] * len(chunk), threads=args.threads,
-                               fits=fits(chunk), orient=orients(chunk), backgrounds=backgrounds(chunk))
+                               fits=fits(chunk), orient=orients(chunk), backgrounds=backgrounds(chunk),
+                               blurs=blurs(chunk), sharpens=sharpens(chunk))
 
     run_batch(mine[:min(len(mine), 8)])  # warm-up: plans, streams, pinned staging
 
@@ -220,7 +237,8 @@ def main():
                 continue
             p = transform_batch_submit([srcs[s] for s, _, _, _ in chunk], [(w, h) for _, w, h, _ in chunk],
                                        [f for _, _, _, f in chunk], [args.quality] * len(chunk), threads=args.threads,
-                                       fits=fits(chunk), orient=orients(chunk), backgrounds=backgrounds(chunk))
+                                       fits=fits(chunk), orient=orients(chunk), backgrounds=backgrounds(chunk),
+                                       blurs=blurs(chunk), sharpens=sharpens(chunk))
             if pend is not None:
                 done(pend[0], pend[1].wait())
             pend = (tb, p)
@@ -241,6 +259,8 @@ def main():
     lib.ik_webp_enc_counters(enc)
     flat = (ctypes.c_ulonglong * 2)()
     lib.ik_flatten_counters(flat)  # (the warm-up batch included)
+    blur = (ctypes.c_ulonglong * 2)()
+    lib.ik_blur_counters(blur)  # (likewise)
     barrier()
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local}" if torch.cuda.is_available() else "cpu")
@@ -255,6 +275,8 @@ def main():
             "sources_restart_markers": bool(args.restart),
             "source": args.source, "background": args.background,
             "flatten_counters": {"launches": flat[0], "images": flat[1]},
+            "sharpen": args.sharpen, "blur": args.blur,
+            "blur_counters": {"launches": blur[0], "images": blur[1]},
             "batch_latency_ms": {"p50": round(float(np.percentile(lat, 50)), 2),
                                  "p95": round(float(np.percentile(lat, 95)), 2)},
             "decoded_mpix_per_s": round(args.requests * S * S / elapsed / 1e6, 1),
