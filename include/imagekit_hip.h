@@ -513,7 +513,7 @@ int ik_flatten_counters(unsigned long long out[2]);
  * w and h refer to the oriented image, and the background applies whatever the output
  * format (an AVIF request with a background is opaque and carries no alpha plane).
  * opt_size must be the size of a layout this header declares (ik_request_opts, or
- * ik_request_opts2 below); any other value is IK_ERR_INVALID ("unknown options size")
+ * ik_request_opts2 and ik_request_opts3 below); any other value is IK_ERR_INVALID ("unknown options size")
  * before any device work, which is what lets the struct grow.  A fit outside ik_fit, an orient outside ik_orient / 1..8 and a background
  * that is neither IK_BG_NONE nor 0x000000..0xFFFFFF are IK_ERR_INVALID. */
 typedef struct {
@@ -574,6 +574,87 @@ int ik_image_unsharpen(const ik_image *img, float sigma, int32_t threshold, ik_i
 int ik_blur_tile(int out[2]);
 /* process-wide: out[0] blur kernel launches, out[1] images filtered by them */
 int ik_blur_counters(unsigned long long out[2]);
+
+/* ---- watermark overlay ---------------------------------------------------- */
+/* One image (a logo, a line of text) composited over another before it is encoded, pixels
+ * staying in HBM.  The project's own definition, all integers.  B is
+ * the base, W x H, C channels, M = 255 or 65535; O the overlay, wo x ho, any of the
+ * channel counts and depths; neither the base's channels nor its depth change, and the
+ * overlay is never resized or turned (prepare it once with the calls above).
+ *   depth     overlay samples, alpha included, go to the base's depth first: 8 -> 16
+ *             v * 257, 16 -> 8 (v + 128) / 257
+ *   channels  no alpha: fa = M; a gray overlay is replicated onto a colour base; a colour
+ *             overlay on a gray base gives L = (2126 R + 7152 G + 722 B) / 10000 (floor)
+ *   opacity   op in 1..255, opM = op or op * 257; a = (fa * opM + M / 2) / M
+ *   C 1 or 3  out = (f * a + c * (M - a) + M / 2) / M per colour sample
+ *   C 2 or 4  Porter-Duff "over" on straight alpha, ca the base's alpha:
+ *             t = ca * (M - a), D = a * M + t, out_a = (D + M / 2) / M; D == 0 leaves the
+ *             pixel; else out_c = (f * a * M + c * t + D / 2) / D  (ca = M: the line above)
+ *   place     x0 is 0, floor((W - wo) / 2) or W - wo by the gravity (floor towards minus
+ *             infinity), then x0 += dx; y0 likewise; |dx|, |dy| <= 2^24.  The window is
+ *             the overlay's rectangle clipped to the base; empty: nothing changes and
+ *             nothing is launched
+ *   tile      the window is the whole base and pixel (x, y) takes
+ *             O[(x - x0) mod wo, (y - y0) mod ho], the Euclidean mod */
+enum ik_gravity {
+    IK_GRAVITY_CENTER = 0,
+    IK_GRAVITY_N = 1,
+    IK_GRAVITY_S = 2,
+    IK_GRAVITY_E = 3,
+    IK_GRAVITY_W = 4,
+    IK_GRAVITY_NE = 5,
+    IK_GRAVITY_NW = 6,
+    IK_GRAVITY_SE = 7,
+    IK_GRAVITY_SW = 8
+};
+/* the placement; needs no device.  out[0..3]: the window x, y, w, h in the base (all four 0
+ * when it is empty), out[4], out[5]: the overlay's origin x0, y0.  W, H <= 2^24 (0 allowed:
+ * an empty window), wo, ho in 1..2^24.  Every other call computes its window through this. */
+int ik_overlay_place(uint32_t W, uint32_t H, uint32_t wo, uint32_t ho, int gravity, int32_t dx, int32_t dy, int tile,
+                     int32_t out[6]);
+/* img under the overlay as a new image on the device that holds img (a device copy, then
+ * the kernel in place on it; img is not changed).  opacity 1..255.  An overlay held by
+ * another device is copied over for the call. */
+int ik_image_overlay(const ik_image *img, const ik_image *overlay, int gravity, int32_t dx, int32_t dy, int opacity,
+                     int tile, ik_image **out);
+/* the window columns one workgroup of the kernel takes, the size at which its edge handling
+ * changes; for tests */
+int ik_overlay_span(void);
+/* process-wide: out[0] overlay kernel launches, out[1] images composited by them */
+int ik_overlay_counters(unsigned long long out[2]);
+
+/* The third declared layout, 56 bytes: ik_request_opts2's 24, then a watermark composited
+ * on the pixels the encoder codes: decode -> orient -> flatten -> resize -> blur or sharpen
+ * -> overlay -> encode (the mark is not blurred).  overlay NULL means none; the other
+ * overlay fields must then be zero, and the call makes exactly the calls of the 24-byte
+ * layout.  An unknown gravity, an opacity outside 0..255, a tile outside 0/1, a non-zero
+ * reserved and offsets beyond +-2^24 are IK_ERR_INVALID before any device work; in a batch
+ * the message names the request.  LIFETIME: the overlay handle is the caller's; it must
+ * stay alive (not freed, its pixels not written) until the call returns, and for a
+ * submitted ticket until ik_transform_batch_wait has returned for it.  One handle may
+ * serve any number of requests and calls at once.  In a batch, members of a resize group
+ * that share (handle, gravity, dx, dy, opacity, tile) are composited by one launch. */
+typedef struct {
+    int fit;                   /* ik_fit */
+    int orient;                /* ik_orient, or 1..8 */
+    int32_t background;        /* IK_BG_NONE, or 0xRRGGBB */
+    float blur_sigma;          /* 0: no blur */
+    float sharpen_sigma;       /* 0: no unsharp mask */
+    int32_t sharpen_threshold; /* 0..65535 */
+    const ik_image *overlay;   /* NULL: no watermark */
+    int32_t overlay_gravity;   /* ik_gravity */
+    int32_t overlay_dx;        /* added to the gravity's origin, pixels */
+    int32_t overlay_dy;
+    int32_t overlay_opacity;   /* 0 means 255 (a zeroed struct with only `overlay` set is an
+                                  opaque centred mark), else 1..255 */
+    int32_t overlay_tile;      /* 0 or 1 */
+    int32_t reserved;          /* must be 0 */
+} ik_request_opts3;
+#ifdef __cplusplus
+static_assert(sizeof(ik_request_opts3) == 56, "ik_request_opts3 is 56 bytes");
+#else
+_Static_assert(sizeof(ik_request_opts3) == 56, "ik_request_opts3 is 56 bytes");
+#endif
 
 /* ---- fused / batched entry points (pixels stay in HBM) ----------------- */
 /* decode -> resize_image -> encode_image in one call (handler src/lib.rs:175-191) */
@@ -676,8 +757,8 @@ int ik_transform_batch_submit_device(const uint8_t *const *dev_bytes, const size
                                      int filter, int threads, uint8_t **outs, size_t *out_lens, int *status,
                                      uint64_t *ticket);
 
-/* The batch calls with per-request options: opts holds n ik_request_opts or n
- * ik_request_opts2 (or is NULL: every request at its defaults, the call without options),
+/* The batch calls with per-request options: opts holds n ik_request_opts, n
+ * ik_request_opts2 or n ik_request_opts3 (or is NULL: every request at its defaults, the call without options),
  * opt_size is the size of that layout.  After a resize group's launch and before its
  * coders, its members that share (blur or unsharpen, sigma, threshold) are filtered by one
  * launch, a lone one by its own; requests that differ only in these settings still share
@@ -803,6 +884,24 @@ int ik_blur_batch_device(const uint8_t *dev_src, uint32_t W, uint32_t H, uint32_
                          size_t src_pitch, size_t src_image_stride, uint32_t n, float sigma, int sharpen,
                          int32_t threshold, uint8_t *dev_dst, size_t dst_pitch, size_t dst_image_stride,
                          void *hip_stream);
+/* the watermark overlay (above) composited IN PLACE over n base images of W x H pixels of C
+ * samples of `depth` bytes, image i at dev_base + i*image_stride, in one launch: one
+ * overlay of wo x ho pixels of overlay_channels samples of overlay_depth bytes, one
+ * placement and one opacity (1..255) for all of them.  The work is proportional to the
+ * window, not to the image.  Nothing outside the window is written, nothing outside
+ * W*C*depth bytes of a base row is read, and the overlay is only read.  A base, pitch and
+ * stride that are all multiples of 4 take the wide path (whole dwords for the shares of a
+ * row that lie inside the window, bytes for its ragged ends); any others the byte path.
+ * Enqueued on hip_stream (NULL: the calling thread's stream) without waiting.  An empty
+ * window is IK_OK: nothing is launched and the counters do not move.  IK_ERR_INVALID, with
+ * nothing launched and nothing written: an unknown gravity, an opacity outside 1..255, a
+ * tile outside 0..1, offsets beyond +-2^24, channels outside 1..4, a depth outside 1..2, a
+ * null pointer, a zero size, a size above 2^24, a pitch below the row bytes, n > 1 with an
+ * image stride below rows * pitch, n above 65535, or base and overlay bytes that overlap. */
+int ik_overlay_batch_device(uint8_t *dev_base, uint32_t W, uint32_t H, uint32_t C, uint32_t depth, size_t pitch,
+                            size_t image_stride, uint32_t n, const uint8_t *dev_overlay, uint32_t wo, uint32_t ho,
+                            uint32_t overlay_channels, uint32_t overlay_depth, size_t overlay_pitch, int gravity,
+                            int32_t dx, int32_t dy, int opacity, int tile, void *hip_stream);
 /* the WebP colour conversion (to_rgb8 + libwebp RGB->YUV420) on the device;
  * dev_yuv receives the Y (w*h), U and V ((w+1)/2 * (h+1)/2) planes back to back */
 int ik_webp_yuv420_device(const uint8_t *dev_src, uint32_t w, uint32_t h, uint32_t C,

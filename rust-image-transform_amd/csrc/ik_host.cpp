@@ -1397,8 +1397,10 @@ static void transform_decode_phase(const uint8_t* const* bytes, const size_t* le
 // orient: null, or each request's effective orientation (0 = as stored, 2..8)
 // bg: null, or each request's background (IK_BG_NONE, or 0xRRGGBB)
 // flt: null, or each request's blur or unsharpen (mode 0: none), run on the resized image
+// ovl: null, or each request's watermark (mark null: none), composited in place after that
 static void transform_post_phase(const int64_t* w, const int64_t* h, const int* fit, const int* orient,
-                                 const int32_t* bg, const FilterReq* flt, const int* fmt, const int* quality,
+                                 const int32_t* bg, const FilterReq* flt, const OverlayReq* ovl, const int* fmt,
+                                 const int* quality,
                                  int filter, int* st, std::string* errs, HostPhase& hp) {
     const std::vector<uint32_t>& idx = hp.idx;
     const int threads = hp.threads;
@@ -1553,6 +1555,36 @@ static void transform_post_phase(const int64_t* w, const int64_t* h, const int* 
                 }
             }
         }
+        // then the watermark, in place on the resized (and filtered) images: the members
+        // that share (overlay handle, gravity, dx, dy, opacity, tile) go through one launch,
+        // a lone one or a failed group through launches of their own.  A member whose
+        // overlay fails gets its status and message: its file is dropped as above.
+        if (ovl) {
+            std::vector<std::vector<uint32_t>> sets;
+            for (uint32_t k : G.members) {
+                if (ds[k] || !ovl[idx[k]].mark) continue;
+                size_t q = 0;
+                while (q < sets.size() && !ovl[idx[sets[q][0]]].same(ovl[idx[k]])) ++q;
+                if (q == sets.size()) sets.emplace_back();
+                sets[q].push_back(k);
+            }
+            for (const std::vector<uint32_t>& ks : sets) {
+                const OverlayReq& o = ovl[idx[ks[0]]];
+                bool grouped = false;
+                if (ks.size() > 1) {
+                    std::vector<ik_image*> bs;
+                    for (uint32_t k : ks) bs.push_back(rsz[k]);
+                    grouped = overlay_group(bs, o) == IK_OK;
+                }
+                for (size_t j = 0; !grouped && j < ks.size(); ++j) {
+                    const uint32_t k = ks[j];
+                    if (int r = overlay_image(rsz[k], o)) {
+                        ds[k] = r;
+                        dm[k] = last_error_str();
+                    }
+                }
+            }
+        }
         for (uint32_t c = G.cg_lo; c < G.cg_hi; ++c) {
             const PostPlan::CoderGroup& cg = plan.cgroups[c];
             std::vector<ik_image*> im;
@@ -1598,6 +1630,9 @@ static void transform_post_phase(const int64_t* w, const int64_t* h, const int* 
                 rs = fo;
             }
         }
+        // (with w and h both None rs is the decoded image itself: this call owns it, so in
+        // place is still right)
+        if (!r && !rsz[k] && ovl && ovl[i].mark) r = overlay_image(rs, ovl[i]);
         const auto t1 = std::chrono::steady_clock::now();
         if (!r && !fronted[k] && plan.req[k].solo == PostRoute::WebpMixed) {
             (void)hipStreamSynchronize(thread_stream());  // this thread's resize is done: another's stream reads it
@@ -1735,6 +1770,9 @@ struct Ticket {
     std::vector<int32_t> bg;
     // ik_request_opts2's blur and unsharpen; empty when no request asks for either
     std::vector<FilterReq> flt;
+    // ik_request_opts3's watermarks (the handles are the caller's, alive until the wait
+    // returns); empty when no request has one
+    std::vector<OverlayReq> ovl;
 };
 
 // one device's share of a ticket
@@ -1748,6 +1786,7 @@ struct BatchPart {
     const int* orient = nullptr;  // null: every request as stored; else Ticket::orient
     const int32_t* bg = nullptr;  // null: no request has a background; else Ticket::bg
     const FilterReq* flt = nullptr;  // null: no request blurs or sharpens; else Ticket::flt
+    const OverlayReq* ovl = nullptr;  // null: no request has a watermark; else Ticket::ovl
     const int* fmt = nullptr;
     const int* quality = nullptr;
     int filter = 0;
@@ -1822,7 +1861,7 @@ private:
             if (stage == 2) {
                 // resize + the encoders' device front ends, beside the next batch's decode
                 Ticket& t = *p->t;
-                transform_post_phase(p->w, p->h, p->fit, p->orient, p->bg, p->flt, p->fmt, p->quality, p->filter, t.st.data(),
+                transform_post_phase(p->w, p->h, p->fit, p->orient, p->bg, p->flt, p->ovl, p->fmt, p->quality, p->filter, t.st.data(),
                                      t.errs.data(), p->hp);
                 pool_->post([p] {
                     Ticket& tk = *p->t;
@@ -1990,6 +2029,7 @@ int submit_parts(const std::shared_ptr<Ticket>& t, const uint8_t* const* bytes, 
         p->orient = t->orient.empty() ? nullptr : t->orient.data();
         p->bg = t->bg.empty() ? nullptr : t->bg.data();
         p->flt = t->flt.empty() ? nullptr : t->flt.data();
+        p->ovl = t->ovl.empty() ? nullptr : t->ovl.data();
         p->sniff = sniff;
         p->filter = filter;
         p->hp.threads = threads;
@@ -2104,20 +2144,21 @@ int ik_transform_batch_submit_oriented(const uint8_t* const* bytes, const size_t
     return submit_parts(t, bytes, nullptr, -1, lens, n, w, h, fit, fmt, quality, filter, threads, ticket);
 }
 
-// ---- per-request options (ik_request_opts, ik_request_opts2) ----
+// ---- per-request options (ik_request_opts, ik_request_opts2, ik_request_opts3) ----
 static bool opts_size_ok(size_t opt_size) {
-    return opt_size == sizeof(ik_request_opts) || opt_size == sizeof(ik_request_opts2);
+    return opt_size == sizeof(ik_request_opts) || opt_size == sizeof(ik_request_opts2) ||
+           opt_size == sizeof(ik_request_opts3);
 }
-// request i of an options array whose structs lie opt_size bytes apart, as the larger
-// layout (the smaller one's new fields: zero, "off")
-static ik_request_opts2 opts_at(const void* opts, size_t opt_size, uint32_t i) {
-    ik_request_opts2 o{};
+// request i of an options array whose structs lie opt_size bytes apart, as the largest
+// layout (a smaller one's new fields: zero, "off")
+static ik_request_opts3 opts_at(const void* opts, size_t opt_size, uint32_t i) {
+    ik_request_opts3 o{};
     std::memcpy(&o, static_cast<const uint8_t*>(opts) + (size_t)i * opt_size, opt_size);
     return o;
 }
 // the blur or unsharpen an options struct asks for.  Returns IK_OK, or IK_ERR_INVALID with
 // the message set (prefix: "" or "request i: ")
-static int filter_of(const ik_request_opts2& o, const char* prefix, FilterReq& f) {
+static int filter_of(const ik_request_opts3& o, const char* prefix, FilterReq& f) {
     f = FilterReq();
     // (written so that a NaN fails)
     const bool bs = o.blur_sigma == 0.0f || (o.blur_sigma >= 0.0625f && o.blur_sigma <= IK_BLUR_MAX_SIGMA);
@@ -2135,6 +2176,23 @@ static int filter_of(const ik_request_opts2& o, const char* prefix, FilterReq& f
     else if (o.sharpen_sigma != 0.0f) { f.mode = 2; f.sigma = o.sharpen_sigma; f.threshold = o.sharpen_threshold; }
     return IK_OK;
 }
+// the watermark an options struct asks for (r.mark null: none), checked as filter_of checks
+static int overlay_of(const ik_request_opts3& o, const char* prefix, OverlayReq& r) {
+    r = OverlayReq();
+    if (o.reserved != 0) return fail(IK_ERR_INVALID, "%sreserved options field is %d, not 0", prefix, (int)o.reserved);
+    if (int rc = overlay_check(o.overlay_gravity, o.overlay_dx, o.overlay_dy, o.overlay_opacity, 0, o.overlay_tile, prefix))
+        return rc;
+    if (!o.overlay) {
+        if (o.overlay_gravity || o.overlay_dx || o.overlay_dy || o.overlay_opacity || o.overlay_tile)
+            return fail(IK_ERR_INVALID, "%soverlay fields set without an overlay", prefix);
+        return IK_OK;
+    }
+    r.mark = o.overlay;
+    r.gravity = o.overlay_gravity; r.dx = o.overlay_dx; r.dy = o.overlay_dy;
+    r.opacity = o.overlay_opacity ? o.overlay_opacity : 255;
+    r.tile = o.overlay_tile;
+    return IK_OK;
+}
 static bool background_ok(int32_t b) { return b == IK_BG_NONE || (b >= 0 && b <= 0xFFFFFF); }
 
 // a batch's options as the arrays its ticket keeps, each left empty when every request is at
@@ -2143,7 +2201,8 @@ struct OptArrays {
     std::vector<int> fit, orient;  // orient: effective orientations (0 = as stored, 2..8)
     std::vector<int32_t> bg;
     std::vector<FilterReq> flt;
-    bool none() const { return fit.empty() && orient.empty() && bg.empty() && flt.empty(); }
+    std::vector<OverlayReq> ovl;
+    bool none() const { return fit.empty() && orient.empty() && bg.empty() && flt.empty() && ovl.empty(); }
 };
 
 // bytes: the files in host memory, or null (device-resident inputs: IK_ORIENT_AUTO cannot be
@@ -2151,7 +2210,7 @@ struct OptArrays {
 static int split_opts(const void* opts, size_t opt_size, uint32_t n, const uint8_t* const* bytes, const size_t* lens,
                       OptArrays& a) {
     for (uint32_t i = 0; opts && i < n; ++i) {
-        const ik_request_opts2 o = opts_at(opts, opt_size, i);
+        const ik_request_opts3 o = opts_at(opts, opt_size, i);
         if (o.fit < IK_FIT_CONTAIN || o.fit > IK_FIT_EXACT)
             return fail(IK_ERR_INVALID, "request %u: unknown fit %d", i, o.fit);
         if (!background_ok(o.background))
@@ -2185,6 +2244,12 @@ static int split_opts(const void* opts, size_t opt_size, uint32_t n, const uint8
             if (a.flt.empty()) a.flt.assign(n, FilterReq());
             a.flt[i] = f;
         }
+        OverlayReq ov;
+        if (int rc = overlay_of(o, prefix, ov)) return rc;
+        if (ov.mark) {
+            if (a.ovl.empty()) a.ovl.assign(n, OverlayReq());
+            a.ovl[i] = ov;
+        }
     }
     return IK_OK;
 }
@@ -2207,6 +2272,7 @@ int ik_transform_batch_submit_opts(const uint8_t* const* bytes, const size_t* le
     t->orient.swap(a.orient);
     t->bg.swap(a.bg);
     t->flt.swap(a.flt);
+    t->ovl.swap(a.ovl);
     return submit_parts(t, bytes, nullptr, -1, lens, n, w, h, t->fitv.empty() ? nullptr : t->fitv.data(), fmt, quality,
                         filter, threads, ticket);
 }
@@ -2365,6 +2431,7 @@ static int submit_device(const uint8_t* const* dev_bytes, const size_t* lens, ui
     t->orient.swap(opt.orient);
     t->bg.swap(opt.bg);
     t->flt.swap(opt.flt);
+    t->ovl.swap(opt.ovl);
     return submit_parts(t, t->eff.data(), t->sniff.data(), phys, lens, n, w, h,
                         t->fitv.empty() ? nullptr : t->fitv.data(), fmt, quality, filter, threads, ticket);
 }
@@ -2444,9 +2511,10 @@ int ik_transform_batch_oriented(const uint8_t* const* bytes, const size_t* lens,
 // orientation: 0 = the pixels as stored, 2..8 = turned first (effective_orientation);
 // background: IK_BG_NONE, or the colour an image with alpha is flattened onto after the turn
 // flt: the blur or unsharpen of the resized image (mode 0: none)
+// ovl: the watermark composited after it (mark null: none)
 static int transform_here(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orientation,
-                          int32_t background, FilterReq flt, int fmt, int quality, int filter, uint8_t** out,
-                          size_t* out_len) {
+                          int32_t background, FilterReq flt, OverlayReq ovl, int fmt, int quality, int filter,
+                          uint8_t** out, size_t* out_len) {
     ik_image* img = nullptr;
     int st = decode_one(bytes, len, &img, nullptr);
     if (st) return st;
@@ -2474,6 +2542,14 @@ static int transform_here(const uint8_t* bytes, size_t len, int64_t w, int64_t h
         if (st) { ik_image_free(img); return st; }
         rs = fo;
     }
+    if (ovl.mark) {  // in place: rs is this call's own (with w and h both None, img itself)
+        st = overlay_image(rs, ovl);
+        if (st) {
+            if (rs != img) ik_image_free(rs);
+            ik_image_free(img);
+            return st;
+        }
+    }
     st = ik_encode(rs, fmt, quality, out, out_len);
     if (rs != img) ik_image_free(rs);
     ik_image_free(img);
@@ -2487,13 +2563,13 @@ int ik_transform(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fmt
 }
 
 static int transform_scheduled(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orientation,
-                               int32_t background, FilterReq flt, int fmt, int quality, int filter, uint8_t** out,
-                               size_t* out_len);
+                               int32_t background, FilterReq flt, OverlayReq ovl, int fmt, int quality, int filter,
+                               uint8_t** out, size_t* out_len);
 
 int ik_transform_fit(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int fmt, int quality,
                      int filter, uint8_t** out, size_t* out_len) {
     IK_API_ENTER();
-    return transform_scheduled(bytes, len, w, h, fit, 0, IK_BG_NONE, FilterReq(), fmt, quality, filter, out, out_len);
+    return transform_scheduled(bytes, len, w, h, fit, 0, IK_BG_NONE, FilterReq(), OverlayReq(), fmt, quality, filter, out, out_len);
 }
 
 // (the *_opts calls; opts_size_ok and background_ok: above, with the batch submits)
@@ -2503,14 +2579,16 @@ int ik_transform_opts(const uint8_t* bytes, size_t len, int64_t w, int64_t h, in
     IK_API_ENTER();
     if (!opts_size_ok(opt_size)) return fail(IK_ERR_INVALID, "unknown options size %zu", opt_size);
     if (!opts) return ik_transform(bytes, len, w, h, fmt, quality, filter, out, out_len);
-    const ik_request_opts2 ro = opts_at(opts, opt_size, 0);
+    const ik_request_opts3 ro = opts_at(opts, opt_size, 0);
     if (!background_ok(ro.background))
         return fail(IK_ERR_INVALID, "background %d is neither IK_BG_NONE nor 0x000000..0xFFFFFF", (int)ro.background);
     FilterReq flt;
     if (int rc = filter_of(ro, "", flt)) return rc;
+    OverlayReq ovl;
+    if (int rc = overlay_of(ro, "", ovl)) return rc;
     const int o = effective_orientation(bytes, len, ro.orient);
     if (o < 0) return fail(IK_ERR_INVALID, "unknown orientation %d", ro.orient);
-    return transform_scheduled(bytes, len, w, h, ro.fit, o, ro.background, flt, fmt, quality, filter, out, out_len);
+    return transform_scheduled(bytes, len, w, h, ro.fit, o, ro.background, flt, ovl, fmt, quality, filter, out, out_len);
 }
 
 int ik_transform_oriented(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orient, int fmt,
@@ -2518,15 +2596,15 @@ int ik_transform_oriented(const uint8_t* bytes, size_t len, int64_t w, int64_t h
     IK_API_ENTER();
     const int o = effective_orientation(bytes, len, orient);
     if (o < 0) return fail(IK_ERR_INVALID, "unknown orientation %d", orient);
-    return transform_scheduled(bytes, len, w, h, fit, o, IK_BG_NONE, FilterReq(), fmt, quality, filter, out, out_len);
+    return transform_scheduled(bytes, len, w, h, fit, o, IK_BG_NONE, FilterReq(), OverlayReq(), fmt, quality, filter, out, out_len);
 }
 
 // on this device, or (several devices) on the least-loaded one's workers
 static int transform_scheduled(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orientation,
-                               int32_t background, FilterReq flt, int fmt, int quality, int filter, uint8_t** out,
-                               size_t* out_len) {
+                               int32_t background, FilterReq flt, OverlayReq ovl, int fmt, int quality, int filter,
+                               uint8_t** out, size_t* out_len) {
     if (!sched_multi())
-        return transform_here(bytes, len, w, h, fit, orientation, background, flt, fmt, quality, filter, out, out_len);
+        return transform_here(bytes, len, w, h, fit, orientation, background, flt, ovl, fmt, quality, filter, out, out_len);
     // several devices: queue the request to the least-loaded device's workers
     const uint64_t cost = request_cost(bytes, len, w, h, fmt);
     const int ld = sched_acquire(cost);
@@ -2536,7 +2614,7 @@ static int transform_scheduled(const uint8_t* bytes, size_t len, int64_t w, int6
     int st = IK_OK;
     std::string msg;
     sched_pool(ld).post([&] {
-        const int r = transform_here(bytes, len, w, h, fit, orientation, background, flt, fmt, quality, filter, out, out_len);
+        const int r = transform_here(bytes, len, w, h, fit, orientation, background, flt, ovl, fmt, quality, filter, out, out_len);
         std::string m = r ? last_error_str() : std::string();
         std::lock_guard<std::mutex> lk(mu);
         st = r;

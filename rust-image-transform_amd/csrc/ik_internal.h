@@ -329,6 +329,32 @@ struct BlurArgs {
 };
 hipError_t launch_blur(const BlurArgs& a, int depth, bool sharpen, int n, hipStream_t s);
 
+// ---- watermark overlay (ik_overlay.hip) ----
+// one overlay image composited in place over the window of n same-geometry base images
+// (DESIGN section 4): the base of C samples of `depth` bytes, images at base + i *
+// img_stride or at tab[i] (a device array of bases).  The overlay's own format (co
+// channels of od bytes) is a run-time switch.  The window and the origin are those of
+// ik_overlay_place; the launcher's caller has checked them against W x H.
+constexpr int kOverlaySpan = 1024;             // window columns one workgroup takes
+constexpr int kOverlayRowCap = 256;            // most rows of workgroups in a launch (the rest: grid stride)
+constexpr uint32_t kOverlayMaxImages = 65535;  // grid.z
+constexpr int32_t kOverlayMaxDim = 1 << 24;    // most pixels on an axis, and the largest |dx|, |dy|
+struct OverlayArgs {
+    uint8_t* base;
+    size_t pitch, img_stride;
+    const uint64_t* tab;           // per-image bases (device), or null: base + img * img_stride
+    const uint8_t* ov;             // the overlay's pixels
+    size_t ov_pitch;
+    int32_t wo, ho, co, od;        // its size, channels and bytes per sample
+    int32_t wx, wy, ww, wh;        // the window in the base, not empty
+    int32_t x0, y0;                // the overlay's origin in the base (may be negative)
+    int32_t tile;
+    uint32_t opM;                  // the opacity at the base's depth (op, or op * 257)
+    int aligned;                   // the bases, the pitch and the stride are multiples of 4
+    int ov_dword;                  // the overlay is 4 x 8 bits and its base and pitch are multiples of 4
+};
+hipError_t launch_overlay(const OverlayArgs& a, int C, int depth, int n, hipStream_t s);
+
 // ---- plans (ik_plan.cpp) ----
 // axis_weights, required_slots and the tables themselves: ik_resize_plan.h
 ResizePlan* get_resize_plan(int device, int W, int H, int C, int nw, int nh, int filter, int n);

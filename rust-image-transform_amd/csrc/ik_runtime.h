@@ -486,6 +486,26 @@ int blur_group(const std::vector<ik_image*>& src, float sigma, bool sharpen, int
                std::vector<ik_image*>& out);
 bool blur_threshold_ok(int32_t t);  // 0..65535
 void blur_shutdown();               // ik_shutdown: the cached axis tables (ik_blur_host.cpp)
+// one request's watermark, after its blur or unsharpen (ik_request_opts3); the handle is the
+// caller's and outlives the call
+struct OverlayReq {
+    const ik_image* mark = nullptr;  // null: none
+    int32_t gravity = 0, dx = 0, dy = 0;
+    int32_t opacity = 255;  // 1..255
+    int32_t tile = 0;
+    bool same(const OverlayReq& o) const {
+        return mark == o.mark && gravity == o.gravity && dx == o.dx && dy == o.dy && opacity == o.opacity && tile == o.tile;
+    }
+};
+// IK_OK, or IK_ERR_INVALID with the message set (prefix: "" or "request i: "): the gravity,
+// the offsets, the tile flag and an opacity within opacity_lo..255 (ik_overlay_host.cpp)
+int overlay_check(int32_t gravity, int32_t dx, int32_t dy, int32_t opacity, int32_t opacity_lo, int32_t tile,
+                  const char* prefix);
+// the watermark composited in place: onto one image in a launch of its own, or onto
+// same-geometry images in one launch; a return other than IK_OK from overlay_group leaves
+// every image to overlay_image.  An overlay on another device is copied over for the call.
+int overlay_image(ik_image* base, const OverlayReq& r);
+int overlay_group(const std::vector<ik_image*>& bases, const OverlayReq& r);
 
 // Per-device phase gates (ik_pool.cpp).  Concurrent batch calls on one device
 // take its GPU phases in turn: kGateUpload covers a PNG batch's staging, H2D and

@@ -38,7 +38,15 @@ class RequestOpts2(ctypes.Structure):
                 ("blur_sigma", ctypes.c_float), ("sharpen_sigma", ctypes.c_float), ("sharpen_threshold", ctypes.c_int32)]
 
 
-_opts_p = ctypes.c_void_p  # either layout (const void *opts, with its size)
+class RequestOpts3(ctypes.Structure):
+    """ik_request_opts3: RequestOpts2's fields, then the watermark (overlay NULL is none)."""
+    _fields_ = RequestOpts2._fields_ + [
+        ("overlay", ctypes.c_void_p), ("overlay_gravity", ctypes.c_int32), ("overlay_dx", ctypes.c_int32),
+        ("overlay_dy", ctypes.c_int32), ("overlay_opacity", ctypes.c_int32), ("overlay_tile", ctypes.c_int32),
+        ("reserved", ctypes.c_int32)]
+
+
+_opts_p = ctypes.c_void_p  # any declared layout (const void *opts, with its size)
 _batch_head = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint32,
                ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
 _batch_opts = (_batch_head + [_opts_p, ctypes.c_size_t] + [ctypes.POINTER(ctypes.c_int)] * 2 + [ctypes.c_int, ctypes.c_int]
@@ -178,6 +186,11 @@ SIGNATURES = [
     ("ik_blur_tile", ctypes.c_int, [ctypes.POINTER(ctypes.c_int)]),
     ("ik_blur_counters", ctypes.c_int, [ctypes.POINTER(ctypes.c_ulonglong)]),
     ("ik_blur_batch_device", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_uint32] * 4 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_float, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]),
+    ("ik_overlay_place", ctypes.c_int, [ctypes.c_uint32] * 4 + [ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int, ctypes.POINTER(ctypes.c_int32)]),
+    ("ik_image_overlay", ctypes.c_int, [c_img_p, c_img_p, ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_img_p)]),
+    ("ik_overlay_span", ctypes.c_int, []),
+    ("ik_overlay_counters", ctypes.c_int, [ctypes.POINTER(ctypes.c_ulonglong)]),
+    ("ik_overlay_batch_device", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_uint32] * 4 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p] + [ctypes.c_uint32] * 4 + [ctypes.c_size_t, ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     ("ik_transform_opts", ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int] * 3 + [_opts_p, ctypes.c_size_t, ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t)]),
     ("ik_transform_batch_opts", ctypes.c_int, _batch_opts),
     ("ik_transform_batch_submit_opts", ctypes.c_int, _batch_opts + [ctypes.POINTER(ctypes.c_uint64)]),

@@ -160,19 +160,97 @@ def _filter_args(blur, sharpen) -> Tuple[float, float, int]:
     return b, s, t
 
 
-def _request_opts(n, fits=None, orients=None, backgrounds=None, blurs=None, sharpens=None):
+class Gravity(enum.IntEnum):
+    """ik_gravity: the edge or corner of the base a watermark is placed against."""
+
+    center = 0
+    n = 1
+    s = 2
+    e = 3
+    w = 4
+    ne = 5
+    nw = 6
+    se = 7
+    sw = 8
+
+
+OVERLAY_MAX_OFFSET = 1 << 24
+
+
+class Overlay:
+    """A watermark: an image composited over the output before it is encoded (DESIGN section
+    4).  image: the mark, a DynamicImage prepared once (it is never resized or turned here)
+    and shared by any number of requests; gravity: a Gravity or its name; dx, dy: signed
+    pixel offsets added to the gravity's origin; opacity 1..255; tile: repeat the mark over
+    the whole image.  Anything else raises ValueError, before the library is called."""
+
+    __slots__ = ("image", "gravity", "dx", "dy", "opacity", "tile")
+
+    def __init__(self, image: "DynamicImage", gravity=Gravity.center, dx: int = 0, dy: int = 0, opacity: int = 255,
+                 tile: bool = False):
+        if not isinstance(image, DynamicImage):
+            raise ValueError(f"overlay image {image!r} is not a DynamicImage")
+        try:
+            self.gravity = Gravity[gravity.lower()] if isinstance(gravity, str) else Gravity(gravity)
+        except (KeyError, ValueError):
+            raise ValueError(f"unknown gravity {gravity!r}") from None
+        for name, v in (("dx", dx), ("dy", dy)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or abs(int(v)) > OVERLAY_MAX_OFFSET:
+                raise ValueError(f"overlay {name} {v!r} is not an int within +-{OVERLAY_MAX_OFFSET}")
+        if isinstance(opacity, bool) or not isinstance(opacity, (int, np.integer)) or not 1 <= int(opacity) <= 255:
+            raise ValueError(f"overlay opacity {opacity!r} is not an int in 1..255")
+        if not isinstance(tile, (bool, np.bool_)):
+            raise ValueError(f"overlay tile {tile!r} is not a bool")
+        self.image, self.dx, self.dy, self.opacity, self.tile = image, int(dx), int(dy), int(opacity), bool(tile)
+
+    def _fill(self, ro) -> None:
+        """this watermark into an ik_request_opts3"""
+        ro.overlay = self.image._h.value
+        ro.overlay_gravity, ro.overlay_dx, ro.overlay_dy = int(self.gravity), self.dx, self.dy
+        ro.overlay_opacity, ro.overlay_tile, ro.reserved = self.opacity, int(self.tile), 0
+
+
+def _overlay(v) -> Optional[Overlay]:
+    """An `overlay=` argument: None, an Overlay, or a DynamicImage (an opaque centred mark)."""
+    if v is None or isinstance(v, Overlay):
+        return v
+    return Overlay(v)
+
+
+def _overlays(overlays, n) -> Optional[list]:
+    """The per-request watermarks of a batch call, or None (no request has one): one entry per
+    request, or a single Overlay / DynamicImage (or a list of one) that applies to all."""
+    if overlays is None:
+        return None
+    if isinstance(overlays, (Overlay, DynamicImage)):
+        overlays = [overlays]
+    if len(overlays) == 1 and n != 1:
+        overlays = list(overlays) * n
+    if len(overlays) != n:
+        raise InvalidArgument("overlays must have one entry per request, or one for all")
+    marks = [_overlay(v) for v in overlays]
+    return marks if any(m is not None for m in marks) else None
+
+
+def _request_opts(n, fits=None, orients=None, backgrounds=None, blurs=None, sharpens=None, overlays=None):
     """The options array of a *_opts batch call (each argument: one entry per request, or
-    None for that option's default everywhere): ik_request_opts, or ik_request_opts2 when
-    blurs or sharpens is given.  Its element size is ctypes.sizeof(arr._type_)."""
+    None for that option's default everywhere): ik_request_opts, ik_request_opts2 when
+    blurs or sharpens is given, or ik_request_opts3 when some request has an overlay.  Its
+    element size is ctypes.sizeof(arr._type_).  The overlays' images must outlive the call
+    (a submitted batch: its wait)."""
     for name, v in (("fits", fits), ("orient", orients), ("backgrounds", backgrounds), ("blurs", blurs),
                     ("sharpens", sharpens)):
         if v is not None and len(v) != n:
             raise InvalidArgument(f"{name} must have one entry per request")
-    wide = blurs is not None or sharpens is not None
-    arr = ((_lib.RequestOpts2 if wide else _lib.RequestOpts) * n)()
+    marks = _overlays(overlays, n)
+    wide = blurs is not None or sharpens is not None or marks is not None
+    arr = ((_lib.RequestOpts3 if marks is not None else _lib.RequestOpts2 if wide else _lib.RequestOpts) * n)()
     for i in range(n if wide else 0):
         arr[i].blur_sigma, arr[i].sharpen_sigma, arr[i].sharpen_threshold = _filter_args(
             blurs[i] if blurs is not None else None, sharpens[i] if sharpens is not None else None)
+    for i in range(n if marks is not None else 0):
+        if marks[i] is not None:
+            marks[i]._fill(arr[i])
     for i in range(n):
         arr[i].fit = int(FitMode(fits[i])) if fits is not None else int(FitMode.contain)
         arr[i].orient = _orient(orients[i]) if orients is not None else int(Orientation.stored)
@@ -336,6 +414,19 @@ class DynamicImage:
             _raise(st, "unsharpen")
         return DynamicImage(out.value)
 
+    def overlay(self, mark, gravity=Gravity.center, dx: int = 0, dy: int = 0, opacity: int = 255,
+                tile: bool = False) -> "DynamicImage":
+        """This image under a watermark as a new image (ik_image_overlay; the project's own
+        definition): mark is a DynamicImage (or an Overlay, which carries the
+        other arguments itself); channels and depth are this image's."""
+        o = mark if isinstance(mark, Overlay) else Overlay(mark, gravity, dx, dy, opacity, tile)
+        out = ctypes.c_void_p()
+        st = _lib.load().ik_image_overlay(self._h, o.image._h, int(o.gravity), o.dx, o.dy, o.opacity, int(o.tile),
+                                          ctypes.byref(out))
+        if st:
+            _raise(st, "overlay")
+        return DynamicImage(out.value)
+
     def clone(self) -> "DynamicImage":
         return DynamicImage.from_array(self.to_array())
 
@@ -458,14 +549,16 @@ def _inputs(datas):
 
 
 def transform_batch(datas, sizes, fmts, qualities, filter: "FilterType" = None, threads: int = 0,
-                    fits=None, orient=None, backgrounds=None, blurs=None, sharpens=None) -> List[bytes]:
+                    fits=None, orient=None, backgrounds=None, blurs=None, sharpens=None,
+                    overlays=None) -> List[bytes]:
     """ik_transform_batch: decode -> resize_image -> encode_image for many requests
     (sizes: (w, h) per request, None = unset; fmts: ImageFormat per request; fits: a
     FitMode per request, None = contain for all; orient: an Orientation per request,
     None = stored for all; backgrounds: a colour per request as `transform` takes it,
     None = no flatten for any; blurs: a sigma per request, sharpens: a sigma or (sigma,
-    threshold) per request, None = off.  With backgrounds, blurs or sharpens the call is
-    ik_transform_batch_opts)."""
+    threshold) per request, None = off; overlays: an Overlay (or a DynamicImage: an opaque
+    centred mark, or None) per request, or one for all of them.  With backgrounds, blurs,
+    sharpens or overlays the call is ik_transform_batch_opts)."""
     lib = _lib.load()
     bufs, ptrs, lens = _inputs(datas)
     n = len(bufs)
@@ -481,8 +574,8 @@ def transform_batch(datas, sizes, fmts, qualities, filter: "FilterType" = None, 
     status = (ctypes.c_int * n)()
     fa = _fits(fits, n)
     oa = _orients(orient, n)
-    if backgrounds is not None or blurs is not None or sharpens is not None:
-        ra = _request_opts(n, fits, orient, backgrounds, blurs, sharpens)
+    if backgrounds is not None or blurs is not None or sharpens is not None or overlays is not None:
+        ra = _request_opts(n, fits, orient, backgrounds, blurs, sharpens, overlays)
         st = lib.ik_transform_batch_opts(ptrs, lens, n, ws, hs, ra, ctypes.sizeof(ra._type_), fs, qs, filt,
                                          threads, outs, olens, status)
     elif oa is not None:
@@ -529,10 +622,11 @@ class PendingBatch:
 
 def transform_batch_submit(datas, sizes, fmts, qualities, filter: "FilterType" = None,
                            threads: int = 0, fits=None, orient=None, backgrounds=None, blurs=None,
-                           sharpens=None) -> PendingBatch:
+                           sharpens=None, overlays=None) -> PendingBatch:
     """ik_transform_batch_submit: the device half of transform_batch now, the host
     coders in the background; PendingBatch.wait() gives what transform_batch gives.
-    fits, orient, backgrounds, blurs and sharpens as transform_batch takes them."""
+    fits, orient, backgrounds, blurs, sharpens and overlays as transform_batch takes them
+    (the PendingBatch keeps the overlays' images alive until its wait)."""
     lib = _lib.load()
     bufs, ptrs, lens = _inputs(datas)
     n = len(bufs)
@@ -550,8 +644,8 @@ def transform_batch_submit(datas, sizes, fmts, qualities, filter: "FilterType" =
     fa = _fits(fits, n)
     oa = _orients(orient, n)
     ra = None
-    if backgrounds is not None or blurs is not None or sharpens is not None:
-        ra = _request_opts(n, fits, orient, backgrounds, blurs, sharpens)
+    if backgrounds is not None or blurs is not None or sharpens is not None or overlays is not None:
+        ra = _request_opts(n, fits, orient, backgrounds, blurs, sharpens, overlays)
         st = lib.ik_transform_batch_submit_opts(ptrs, lens, n, ws, hs, ra, ctypes.sizeof(ra._type_), fs, qs,
                                                 filt, threads, outs, olens, status, ctypes.byref(ticket))
     elif oa is not None:
@@ -565,15 +659,15 @@ def transform_batch_submit(datas, sizes, fmts, qualities, filter: "FilterType" =
                                                ctypes.byref(ticket))
     if st:
         raise TransformError(_lib.last_error())
-    return PendingBatch((bufs, ptrs, lens, ws, hs, fs, qs, fa, oa, ra), outs, olens, status, ticket.value, n)
+    return PendingBatch((bufs, ptrs, lens, ws, hs, fs, qs, fa, oa, ra, overlays), outs, olens, status, ticket.value, n)
 
 
 def transform_batch_submit_device(datas, sizes, fmts, qualities, filter: "FilterType" = None,
                                   threads: int = 0, fits=None, orient=None, backgrounds=None, blurs=None,
-                                  sharpens=None) -> PendingBatch:
+                                  sharpens=None, overlays=None) -> PendingBatch:
     """ik_transform_batch_submit_device: as transform_batch_submit, over request
-    bodies already in device memory (DeviceBytes).  With fits, orient, backgrounds, blurs or sharpens the
-    call is ik_transform_batch_submit_device_opts; Orientation.auto is refused there (the
+    bodies already in device memory (DeviceBytes).  With fits, orient, backgrounds, blurs, sharpens or
+    overlays the call is ik_transform_batch_submit_device_opts; Orientation.auto is refused there (the
     files are not read on the host)."""
     lib = _lib.load()
     keep = list(datas)
@@ -594,16 +688,17 @@ def transform_batch_submit_device(datas, sizes, fmts, qualities, filter: "Filter
     status = (ctypes.c_int * n)()
     ticket = ctypes.c_uint64()
     ra = None
-    if fits is None and orient is None and backgrounds is None and blurs is None and sharpens is None:
+    if (fits is None and orient is None and backgrounds is None and blurs is None and sharpens is None
+            and overlays is None):
         st = lib.ik_transform_batch_submit_device(ptrs, lens, n, ws, hs, fs, qs, filt, threads, outs, olens, status,
                                                   ctypes.byref(ticket))
     else:
-        ra = _request_opts(n, fits, orient, backgrounds, blurs, sharpens)
+        ra = _request_opts(n, fits, orient, backgrounds, blurs, sharpens, overlays)
         st = lib.ik_transform_batch_submit_device_opts(ptrs, lens, n, ws, hs, ra, ctypes.sizeof(ra._type_), fs,
                                                        qs, filt, threads, outs, olens, status, ctypes.byref(ticket))
     if st:
         raise TransformError(_lib.last_error())
-    return PendingBatch((keep, ptrs, lens, ws, hs, fs, qs, ra), outs, olens, status, ticket.value, n)
+    return PendingBatch((keep, ptrs, lens, ws, hs, fs, qs, ra, overlays), outs, olens, status, ticket.value, n)
 
 
 def resize_image(img: DynamicImage, w: Optional[int], h: Optional[int],
@@ -640,21 +735,30 @@ def encode_image(img: DynamicImage, fmt: ImageFormat, quality: int) -> bytes:
 
 def transform(data: bytes, w: Optional[int], h: Optional[int], fmt: ImageFormat, quality: int,
               filter: FilterType = FilterType.Lanczos3, fit: FitMode = FitMode.contain,
-              orient=Orientation.stored, background=None, blur=None, sharpen=None) -> bytes:
+              orient=Orientation.stored, background=None, blur=None, sharpen=None, overlay=None) -> bytes:
     """decode -> resize_image -> encode_image in one device-resident call; with orient
     (Orientation) the decoded image is turned first, and w, h and fit refer to the turned
     image; with background (0xRRGGBB, (r, g, b), "rrggbb" or "#rrggbb") an image that
     carries alpha is then composited onto that colour, before the resize; with blur (a
     sigma) or sharpen (a sigma, or (sigma, threshold)) the resized image is blurred or
-    sharpened by the unsharp mask before it is encoded (ik_transform_opts)."""
+    sharpened by the unsharp mask before it is encoded; with overlay (an Overlay, or a
+    DynamicImage for an opaque centred mark) that watermark is composited last, on the
+    pixels the encoder codes (ik_transform_opts)."""
     bg = _background(background)
     fa = _filter_args(blur, sharpen)
+    mark = _overlay(overlay)
     lib = _lib.load()
     b = bytes(data)
     buf = _lib.u8p()
     n = ctypes.c_size_t()
     o = _orient(orient)
-    if fa[0] or fa[1]:
+    if mark is not None:
+        ro = _lib.RequestOpts3(int(FitMode(fit)), o, bg, *fa)
+        mark._fill(ro)
+        st = lib.ik_transform_opts(b, len(b), -1 if w is None else int(w), -1 if h is None else int(h),
+                                   ImageFormat(fmt).value, int(quality), int(filter), ctypes.byref(ro),
+                                   ctypes.sizeof(ro), ctypes.byref(buf), ctypes.byref(n))
+    elif fa[0] or fa[1]:
         ro = _lib.RequestOpts2(int(FitMode(fit)), o, bg, *fa)
         st = lib.ik_transform_opts(b, len(b), -1 if w is None else int(w), -1 if h is None else int(h),
                                    ImageFormat(fmt).value, int(quality), int(filter), ctypes.byref(ro),

@@ -123,6 +123,10 @@ def main():
                          "the 24-byte options).  Without --sharpen and --blur: the calls made before")
     ap.add_argument("--blur", default=None, type=float, metavar="SIGMA",
                     help="every request blurs its resized image (not together with --sharpen)")
+    ap.add_argument("--watermark", default=None, metavar="WxH[,GRAVITY[,OPACITY]]",
+                    help="every request composites one shared synthetic RGBA mark of that size over its output "
+                         "(ik_transform_batch*_opts, the 56-byte options), e.g. 128x32,se,200.  Without the flag: "
+                         "the calls made before")
     ap.add_argument("--source", choices=["jpeg", "png-rgba"], default="jpeg",
                     help="png-rgba: translucent RGBA PNG sources of the same size (what --background acts on)")
     ap.add_argument("--restart", action="store_true")
@@ -165,7 +169,8 @@ def main():
         dist.init_process_group(backend="nccl" if torch.cuda.is_available() else "gloo")
     if torch.cuda.is_available():
         torch.cuda.set_device(local)
-    from imagekit import FitMode, ImageFormat, Orientation, _lib, transform_batch, transform_batch_submit
+    from imagekit import (DynamicImage, FitMode, ImageFormat, Orientation, Overlay, _lib, transform_batch,
+                          transform_batch_submit)
     lib = _lib.load()
     queue = world == 1
     assert lib.ik_init(-1 if queue else local) == 0, _lib.last_error()
@@ -194,11 +199,19 @@ def main():
     def sharpens(chunk):
         return [sharpen] * len(chunk) if sharpen is not None else None
 
+    watermark = None  # one mark, made once, shared by every request
+    if args.watermark is not None:
+        parts = args.watermark.split(",")
+        mw, mh = (int(v) for v in parts[0].lower().split("x"))
+        mark = DynamicImage.from_array(ikutil.synth(mw, mh, 4, seed=7, pattern="S", alpha="random"))
+        watermark = Overlay(mark, parts[1] if len(parts) > 1 else "center",
+                            opacity=int(parts[2]) if len(parts) > 2 else 255)
+
     def run_batch(chunk):
         return transform_batch([srcs[s] for s, _, _, _ in chunk], [(w, h) for _, w, h, _ in chunk],
                                [f for _, _, _, f in chunk], [args.quality] * len(chunk), threads=args.threads,
                                fits=fits(chunk), orient=orients(chunk), backgrounds=backgrounds(chunk),
-                               blurs=blurs(chunk), sharpens=sharpens(chunk))
+                               blurs=blurs(chunk), sharpens=sharpens(chunk), overlays=watermark)
 
     run_batch(mine[:min(len(mine), 8)])  # warm-up: plans, streams, pinned staging
 
@@ -238,7 +251,7 @@ def main():
             p = transform_batch_submit([srcs[s] for s, _, _, _ in chunk], [(w, h) for _, w, h, _ in chunk],
                                        [f for _, _, _, f in chunk], [args.quality] * len(chunk), threads=args.threads,
                                        fits=fits(chunk), orient=orients(chunk), backgrounds=backgrounds(chunk),
-                                       blurs=blurs(chunk), sharpens=sharpens(chunk))
+                                       blurs=blurs(chunk), sharpens=sharpens(chunk), overlays=watermark)
             if pend is not None:
                 done(pend[0], pend[1].wait())
             pend = (tb, p)
@@ -261,6 +274,8 @@ def main():
     lib.ik_flatten_counters(flat)  # (the warm-up batch included)
     blur = (ctypes.c_ulonglong * 2)()
     lib.ik_blur_counters(blur)  # (likewise)
+    ovl = (ctypes.c_ulonglong * 2)()
+    lib.ik_overlay_counters(ovl)  # (likewise)
     barrier()
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local}" if torch.cuda.is_available() else "cpu")
@@ -277,6 +292,8 @@ def main():
             "flatten_counters": {"launches": flat[0], "images": flat[1]},
             "sharpen": args.sharpen, "blur": args.blur,
             "blur_counters": {"launches": blur[0], "images": blur[1]},
+            "watermark": args.watermark,
+            "overlay_counters": {"launches": ovl[0], "images": ovl[1]},
             "batch_latency_ms": {"p50": round(float(np.percentile(lat, 50)), 2),
                                  "p95": round(float(np.percentile(lat, 95)), 2)},
             "decoded_mpix_per_s": round(args.requests * S * S / elapsed / 1e6, 1),
