@@ -1061,7 +1061,7 @@ namespace ik {
 
 // decode_image: image::guess_format + load_from_memory_with_format; formats the
 // reference build compiles in (Cargo.toml:20: jpeg, png, webp; avif = encoder only)
-static int decode_one(const uint8_t* bytes, size_t len, ik_image** out, int* fmt_out) {
+int decode_one(const uint8_t* bytes, size_t len, ik_image** out, int* fmt_out) {
     if (!out) return fail(IK_ERR_INVALID, "null pointer");
     if (!bytes && len) return fail(IK_ERR_INVALID, "null bytes");
     const Sniffed f = guess_format(bytes, len);
@@ -1111,7 +1111,7 @@ static int decode_one(const uint8_t* bytes, size_t len, ik_image** out, int* fmt
     return IK_OK;
 }
 
-static std::string last_error_str() { return t_err; }
+std::string last_error_str() { return t_err; }
 
 // decode_image over a batch on the calling thread's device; per-item status and
 // message (the decoder's own, as TransformError(e.to_string()) carries it).  up:
@@ -1226,14 +1226,6 @@ int ik_decode(const uint8_t* bytes, size_t len, ik_image** out, int* fmt_out) {
     return st;
 }
 
-// the orientation an `orient` argument (ik_orient) means for these bytes: 0 = none
-// (stored order, or an effective 1: no pass), 2..8, or -1 for a bad argument
-static int effective_orientation(const uint8_t* bytes, size_t len, int orient) {
-    if (orient < IK_ORIENT_AUTO || orient > 8) return -1;
-    const int o = orient == IK_ORIENT_AUTO ? exif_orientation(bytes, len) : orient;
-    return o <= 1 ? 0 : o;
-}
-
 int ik_decode_oriented(const uint8_t* bytes, size_t len, int orient, ik_image** out, int* fmt_out) {
     IK_API_ENTER();
     const int o = effective_orientation(bytes, len, orient);
@@ -1315,18 +1307,8 @@ namespace ik {
 // its own stages; a batch goes whole to the least-loaded device, or is split into
 // parts of at least IK_MIN_DEVICE_BATCH (64) requests over several devices -- the
 // inflate kernels' time hardly depends on how many frames a launch holds, so
-// small parts would only add launches.
-struct HostPhase {
-    std::vector<uint32_t> idx;
-    std::vector<EncodePrep> prep;
-    std::vector<std::vector<uint8_t>> bytes_out;
-    int threads = 0;
-    double t_resize = 0, t_front = 0;
-    // the decode stage's results, for the post stage: decoded images, status, message
-    std::vector<ik_image*> imgs;
-    std::vector<int> ds;
-    std::vector<std::string> dm;
-};
+// small parts would only add launches.  (HostPhase, what a batch part carries from stage to
+// stage: ik_runtime.h; the post stage: ik_post_stage.cpp.)
 
 // the PNG requests among idx (decode_batch_dev takes the same ones, in the same order)
 static void png_items(const uint8_t* const* bytes, const size_t* lens, const uint8_t* const* sniff,
@@ -1389,299 +1371,6 @@ static void transform_decode_phase(const uint8_t* const* bytes, const size_t* le
         fprintf(stderr, "[device_phase] gate wait %.2f ms, decode %.2f ms\n",
                 std::chrono::duration<double, std::milli>(tg1 - tg0).count(),
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tg1).count());
-}
-
-// Device half, post stage: resize, the encoders' device front ends (under the
-// post gate, so a batch's resize runs beside the next batch's decode kernels);
-// request i's status / message land in st[i] / errs[i]
-// orient: null, or each request's effective orientation (0 = as stored, 2..8)
-// bg: null, or each request's background (IK_BG_NONE, or 0xRRGGBB)
-// flt: null, or each request's blur or unsharpen (mode 0: none), run on the resized image
-// ovl: null, or each request's watermark (mark null: none), composited in place after that
-static void transform_post_phase(const int64_t* w, const int64_t* h, const int* fit, const int* orient,
-                                 const int32_t* bg, const FilterReq* flt, const OverlayReq* ovl, const int* fmt,
-                                 const int* quality,
-                                 int filter, int* st, std::string* errs, HostPhase& hp) {
-    const std::vector<uint32_t>& idx = hp.idx;
-    const int threads = hp.threads;
-    const uint32_t m = (uint32_t)idx.size();
-    if (!m) return;
-    std::vector<ik_image*>& imgs = hp.imgs;
-    std::vector<int>& ds = hp.ds;
-    std::vector<std::string>& dm = hp.dm;
-    static const bool timing = getenv("IK_TIMING") != nullptr;
-    gate_pin(kGatePost, true);
-    gate_enter(kGatePost);
-    batch_timing_reset(current_device(), true);
-    BatchTimingScope bts;
-    std::mutex tmu;
-    double& t_resize = hp.t_resize;
-    double& t_front = hp.t_front;
-    hp.prep.assign(m, EncodePrep());
-    hp.bytes_out.assign(m, std::vector<uint8_t>());
-    std::vector<EncodePrep>& prep = hp.prep;
-    std::vector<std::vector<uint8_t>>& bytes_out = hp.bytes_out;
-    // apply_orientation first, on the device that holds each decoded image: the post plan
-    // below sees the oriented W, H and pitch.  Images of one (W, H, C, depth, pitch,
-    // orientation) go through one launch, a lone one through its own; the stored-order
-    // image returns to the pool once it has been turned.
-    if (orient) {
-        std::map<std::array<uint64_t, 7>, std::vector<uint32_t>> turn;
-        for (uint32_t k = 0; k < m; ++k) {
-            const ik_image* im = imgs[k];
-            if (ds[k] || !im || !orient[idx[k]]) continue;
-            turn[{im->w, im->h, im->c, im->depth, im->pitch, (uint64_t)im->device, (uint64_t)orient[idx[k]]}].push_back(k);
-        }
-        for (const auto& kv : turn) {
-            const std::vector<uint32_t>& ks = kv.second;
-            const int o = (int)kv.first[6];
-            std::vector<ik_image*> out(ks.size(), nullptr);
-            bool grouped = false;
-            if (ks.size() > 1) {
-                std::vector<ik_image*> src;
-                for (uint32_t k : ks) src.push_back(imgs[k]);
-                grouped = orient_group(src, o, out) == IK_OK;
-            }
-            for (size_t j = 0; j < ks.size(); ++j) {
-                const uint32_t k = ks[j];
-                if (!grouped) {
-                    if (int r = ik_image_orient(imgs[k], o, &out[j])) {
-                        ds[k] = r;
-                        dm[k] = last_error_str();
-                        out[j] = nullptr;
-                    }
-                }
-                ik_image_free(imgs[k]);
-                imgs[k] = out[j];
-            }
-        }
-    }
-    // then the background flatten of the images that carry alpha, so that the post plan sees
-    // the flattened C and pitch: images of one (W, H, C, depth, pitch, device, colour) go
-    // through one launch (the output channels follow from C and the colour), a lone one
-    // through its own; an image without alpha, or a request without a background, is not
-    // touched
-    if (bg) {
-        std::map<std::array<uint64_t, 7>, std::vector<uint32_t>> flat;
-        for (uint32_t k = 0; k < m; ++k) {
-            const ik_image* im = imgs[k];
-            if (ds[k] || !im || bg[idx[k]] == IK_BG_NONE || (im->c != 2 && im->c != 4)) continue;
-            flat[{im->w, im->h, im->c, im->depth, im->pitch, (uint64_t)im->device, (uint64_t)(uint32_t)bg[idx[k]]}].push_back(k);
-        }
-        for (const auto& kv : flat) {
-            const std::vector<uint32_t>& ks = kv.second;
-            const int32_t colour = (int32_t)kv.first[6];
-            std::vector<ik_image*> out(ks.size(), nullptr);
-            bool grouped = false;
-            if (ks.size() > 1) {
-                std::vector<ik_image*> src;
-                for (uint32_t k : ks) src.push_back(imgs[k]);
-                grouped = flatten_group(src, (uint32_t)colour, out) == IK_OK;
-            }
-            for (size_t j = 0; j < ks.size(); ++j) {
-                const uint32_t k = ks[j];
-                if (!grouped) {
-                    if (int r = ik_image_flatten(imgs[k], colour, &out[j])) {
-                        ds[k] = r;
-                        dm[k] = last_error_str();
-                        out[j] = nullptr;
-                    }
-                }
-                ik_image_free(imgs[k]);
-                imgs[k] = out[j];
-            }
-        }
-    }
-    // which launch resizes each request and which coder writes its file: ik_post_plan.h
-    // (the encoder setting and the mixed mode are read once for the batch)
-    std::vector<PostRequest> rq(m);
-    for (uint32_t k = 0; k < m; ++k) {
-        const uint32_t i = idx[k];
-        const ik_image* im = imgs[k];
-        rq[k].ok = !ds[k] && im;
-        if (rq[k].ok) {
-            rq[k].W = im->w; rq[k].H = im->h; rq[k].C = im->c;
-            rq[k].pitch = im->pitch; rq[k].device = im->device; rq[k].depth = im->depth;
-        }
-        rq[k].w = w[i]; rq[k].h = h[i]; rq[k].fmt = fmt[i]; rq[k].quality = quality[i];
-        if (fit) rq[k].fit = fit[i];  // (null: every request IK_FIT_CONTAIN)
-    }
-    const PostPlan plan = post_plan(rq.data(), m, default_webp_encoder(), webp_mixed_mode());
-    std::vector<ik_image*> rsz(m, nullptr);   // resized by its group's launch
-    std::vector<char> fronted(m, 0);          // encode front end already run by its group's call
-    std::vector<ik_image*> kept(m, nullptr);  // resized image kept for the mixed exact call
-    const auto tg0 = std::chrono::steady_clock::now();
-    for (const PostPlan::ResizeGroup& G : plan.rgroups) {
-        std::vector<ik_image*> src, out;
-        for (uint32_t k : G.members) src.push_back(imgs[k]);
-        if (resize_group(src, G.win, filter, out) != IK_OK) continue;  // its members: image by image below
-        for (size_t j = 0; j < out.size(); ++j) rsz[G.members[j]] = out[j];
-        // blur or unsharpen before the group's coders run: the members that share (mode,
-        // sigma, threshold) go through one launch, a lone one through its own, and the
-        // unfiltered image returns to the pool.  A member whose filter fails keeps its
-        // resized image for the coder groups below (its status is set: its file is dropped).
-        if (flt) {
-            std::map<std::array<uint32_t, 3>, std::vector<uint32_t>> sets;
-            for (uint32_t k : G.members) {
-                const FilterReq& f = flt[idx[k]];
-                if (!f.mode) continue;
-                uint32_t sb;
-                std::memcpy(&sb, &f.sigma, 4);
-                sets[{(uint32_t)f.mode, sb, (uint32_t)f.threshold}].push_back(k);
-            }
-            for (const auto& kv : sets) {
-                const std::vector<uint32_t>& ks = kv.second;
-                const FilterReq& f = flt[idx[ks[0]]];
-                std::vector<ik_image*> fo(ks.size(), nullptr);
-                bool grouped = false;
-                if (ks.size() > 1) {
-                    std::vector<ik_image*> fs;
-                    for (uint32_t k : ks) fs.push_back(rsz[k]);
-                    grouped = blur_group(fs, f.sigma, f.mode == 2, f.threshold, fo) == IK_OK;
-                }
-                for (size_t j = 0; j < ks.size(); ++j) {
-                    const uint32_t k = ks[j];
-                    if (!grouped) {
-                        const int r = f.mode == 2 ? ik_image_unsharpen(rsz[k], f.sigma, f.threshold, &fo[j])
-                                                  : ik_image_blur(rsz[k], f.sigma, &fo[j]);
-                        if (r) {
-                            ds[k] = r;
-                            dm[k] = last_error_str();
-                            continue;
-                        }
-                    }
-                    ik_image_free(rsz[k]);
-                    rsz[k] = fo[j];
-                }
-            }
-        }
-        // then the watermark, in place on the resized (and filtered) images: the members
-        // that share (overlay handle, gravity, dx, dy, opacity, tile) go through one launch,
-        // a lone one or a failed group through launches of their own.  A member whose
-        // overlay fails gets its status and message: its file is dropped as above.
-        if (ovl) {
-            std::vector<std::vector<uint32_t>> sets;
-            for (uint32_t k : G.members) {
-                if (ds[k] || !ovl[idx[k]].mark) continue;
-                size_t q = 0;
-                while (q < sets.size() && !ovl[idx[sets[q][0]]].same(ovl[idx[k]])) ++q;
-                if (q == sets.size()) sets.emplace_back();
-                sets[q].push_back(k);
-            }
-            for (const std::vector<uint32_t>& ks : sets) {
-                const OverlayReq& o = ovl[idx[ks[0]]];
-                bool grouped = false;
-                if (ks.size() > 1) {
-                    std::vector<ik_image*> bs;
-                    for (uint32_t k : ks) bs.push_back(rsz[k]);
-                    grouped = overlay_group(bs, o) == IK_OK;
-                }
-                for (size_t j = 0; !grouped && j < ks.size(); ++j) {
-                    const uint32_t k = ks[j];
-                    if (int r = overlay_image(rsz[k], o)) {
-                        ds[k] = r;
-                        dm[k] = last_error_str();
-                    }
-                }
-            }
-        }
-        for (uint32_t c = G.cg_lo; c < G.cg_hi; ++c) {
-            const PostPlan::CoderGroup& cg = plan.cgroups[c];
-            std::vector<ik_image*> im;
-            std::vector<EncodePrep*> pp;
-            std::vector<std::vector<uint8_t>*> oo;
-            for (uint32_t k : cg.members) { im.push_back(rsz[k]); pp.push_back(&prep[k]); oo.push_back(&bytes_out[k]); }
-            const bool planes = cg.route == PostRoute::WebpFrontGroup;  // libwebp codes them in the host stage
-            const int rc = planes                                      ? webp_front_group(im, cg.quality, pp)
-                           : cg.route == PostRoute::WebpExactGroup ? webp_exact_group(im, cg.quality, oo)
-                                                                       : jpeg_front_group(im, cg.quality, oo);
-            if (rc != IK_OK) continue;  // its members: image by image below (Req::solo)
-            for (uint32_t k : cg.members) {
-                fronted[k] = 1;
-                if (planes) continue;
-                prep[k].fmt = rq[k].fmt;
-                prep[k].done = true;  // the files are final: no host coder
-            }
-        }
-    }
-    t_resize += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tg0).count();
-    parallel_for((int)m, threads, [&](int k) {
-        const uint32_t i = idx[k];
-        if (ds[k]) {
-            st[i] = ds[k];
-            errs[i] = dm[k];
-            if (rsz[k]) {  // its group's filter failed after the resize
-                ik_image_free(rsz[k]);
-                ik_image_free(imgs[k]);
-                imgs[k] = nullptr;
-                prep[k].done = true;
-            }
-            return;
-        }
-        ik_image* rs = rsz[k];
-        const auto t0 = std::chrono::steady_clock::now();
-        int r = rs ? IK_OK : ik_resize_fit(imgs[k], w[i], h[i], fit ? fit[i] : IK_FIT_CONTAIN, filter, &rs);
-        if (!r && !rsz[k] && flt && flt[i].mode) {  // resized here (or w and h both None): filtered here
-            ik_image* fo = nullptr;
-            r = flt[i].mode == 2 ? ik_image_unsharpen(rs, flt[i].sigma, flt[i].threshold, &fo)
-                                 : ik_image_blur(rs, flt[i].sigma, &fo);
-            if (!r) {
-                if (rs != imgs[k]) ik_image_free(rs);
-                rs = fo;
-            }
-        }
-        // (with w and h both None rs is the decoded image itself: this call owns it, so in
-        // place is still right)
-        if (!r && !rsz[k] && ovl && ovl[i].mark) r = overlay_image(rs, ovl[i]);
-        const auto t1 = std::chrono::steady_clock::now();
-        if (!r && !fronted[k] && plan.req[k].solo == PostRoute::WebpMixed) {
-            (void)hipStreamSynchronize(thread_stream());  // this thread's resize is done: another's stream reads it
-            kept[k] = rs;
-        } else if (!r && !fronted[k]) r = encode_image_front(rs, fmt[i], quality[i], prep[k], bytes_out[k]);
-        if (timing) {
-            const auto t2 = std::chrono::steady_clock::now();
-            std::lock_guard<std::mutex> lk(tmu);
-            t_resize += std::chrono::duration<double, std::milli>(t1 - t0).count();
-            t_front += std::chrono::duration<double, std::milli>(t2 - t1).count();
-        }
-        if (r) { errs[i] = last_error_str(); st[i] = r; prep[k].done = true; }
-        if (rs && rs != imgs[k] && rs != kept[k]) ik_image_free(rs);
-        if (imgs[k] != kept[k]) ik_image_free(imgs[k]);
-        imgs[k] = nullptr;
-    });
-    // one colour launch and one mixed exact call for the kept requests; fewer than the
-    // minimum of them (the uniform groups took the rest), or a failed call: the existing
-    // front end, image by image
-    std::vector<uint32_t> ks;
-    for (uint32_t k = 0; k < m; ++k)
-        if (kept[k]) ks.push_back(k);
-    bool coded = false;
-    if (ks.size() >= plan.mixed_min) {
-        std::vector<ik_image*> im;
-        std::vector<int> qs;
-        std::vector<std::vector<uint8_t>*> oo;
-        for (uint32_t k : ks) { im.push_back(kept[k]); qs.push_back(quality[idx[k]]); oo.push_back(&bytes_out[k]); }
-        const auto t0 = std::chrono::steady_clock::now();
-        coded = webp_exact_mixed_group(im, qs, oo) == IK_OK;
-        t_front += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    parallel_for((int)ks.size(), threads, [&](int j) {
-        const uint32_t k = ks[(size_t)j], i = idx[k];
-        if (coded) {
-            prep[k].fmt = IK_FORMAT_WEBP;
-            prep[k].done = true;  // the files are final: no host coder
-        } else if (int r = encode_image_front(kept[k], fmt[i], quality[i], prep[k], bytes_out[k])) {
-            errs[i] = last_error_str();
-            st[i] = r;
-            prep[k].done = true;
-        }
-        ik_image_free(kept[k]);
-    });
-    batch_timing_commit(current_device(), true);
-    gate_pin(kGatePost, false);
-    std::vector<ik_image*>().swap(hp.imgs);
-    std::vector<int>().swap(hp.ds);
-    std::vector<std::string>().swap(hp.dm);
 }
 
 static void transform_host_phase(uint8_t** outs, size_t* out_lens, int* st, std::string* errs, HostPhase& hp) {
@@ -1761,18 +1450,9 @@ struct Ticket {
     // back (by device address), and the skeletons' bytes
     JpegInPlaceMap jin;
     std::vector<uint8_t> jskel;
-    // ik_transform_batch_submit_oriented: each request's effective orientation, resolved
-    // at submit (0 = as stored, 2..8); empty when no request is turned
-    std::vector<int> orient;
-    // the *_opts submits: the fit modes (the other submits read the caller's array) and the
-    // backgrounds (IK_BG_NONE or 0xRRGGBB), each empty when every request is at its default
-    std::vector<int> fitv;
-    std::vector<int32_t> bg;
-    // ik_request_opts2's blur and unsharpen; empty when no request asks for either
-    std::vector<FilterReq> flt;
-    // ik_request_opts3's watermarks (the handles are the caller's, alive until the wait
-    // returns); empty when no request has one
-    std::vector<OverlayReq> ovl;
+    // each request's options, resolved at submit (request_ops; the watermarks' handles are the
+    // caller's, alive until the wait returns); empty when every request is at its defaults
+    std::vector<RequestOps> ops;
 };
 
 // one device's share of a ticket
@@ -1782,11 +1462,7 @@ struct BatchPart {
     const size_t* lens = nullptr;
     const int64_t* w = nullptr;
     const int64_t* h = nullptr;
-    const int* fit = nullptr;  // null: every request IK_FIT_CONTAIN
-    const int* orient = nullptr;  // null: every request as stored; else Ticket::orient
-    const int32_t* bg = nullptr;  // null: no request has a background; else Ticket::bg
-    const FilterReq* flt = nullptr;  // null: no request blurs or sharpens; else Ticket::flt
-    const OverlayReq* ovl = nullptr;  // null: no request has a watermark; else Ticket::ovl
+    const RequestOps* ops = nullptr;  // null: every request at its defaults; else Ticket::ops
     const int* fmt = nullptr;
     const int* quality = nullptr;
     int filter = 0;
@@ -1861,8 +1537,7 @@ private:
             if (stage == 2) {
                 // resize + the encoders' device front ends, beside the next batch's decode
                 Ticket& t = *p->t;
-                transform_post_phase(p->w, p->h, p->fit, p->orient, p->bg, p->flt, p->ovl, p->fmt, p->quality, p->filter, t.st.data(),
-                                     t.errs.data(), p->hp);
+                transform_post_phase(p->w, p->h, p->ops, p->fmt, p->quality, p->filter, t.st.data(), t.errs.data(), p->hp);
                 pool_->post([p] {
                     Ticket& tk = *p->t;
                     transform_host_phase(tk.outs, tk.out_lens, tk.st.data(), tk.errs.data(), p->hp);
@@ -2006,30 +1681,17 @@ int min_device_batch() {
     return v;
 }
 
-}  // namespace
-}  // namespace ik
-
-extern "C" {
-
-}  // extern "C"
-
-namespace ik {
-namespace {
-
 // the parts of a ticket to the stage executors.  bytes / sniff: the request array
 // the stages read (Ticket::eff / sniff for device-resident inputs); phys >= 0:
 // the inputs live on that physical device, so the batch goes whole to it
 int submit_parts(const std::shared_ptr<Ticket>& t, const uint8_t* const* bytes, const uint8_t* const* sniff,
-                 int phys, const size_t* lens, uint32_t n, const int64_t* w, const int64_t* h, const int* fit,
-                 const int* fmt, const int* quality, int filter, int threads, uint64_t* ticket) {
+                 int phys, const size_t* lens, uint32_t n, const int64_t* w, const int64_t* h, const int* fmt,
+                 const int* quality, int filter, int threads, uint64_t* ticket) {
     auto make_part = [&](uint32_t lo, uint32_t hi) {
         auto p = std::make_shared<BatchPart>();
         p->t = t;
-        p->bytes = bytes; p->lens = lens; p->w = w; p->h = h; p->fit = fit; p->fmt = fmt; p->quality = quality;
-        p->orient = t->orient.empty() ? nullptr : t->orient.data();
-        p->bg = t->bg.empty() ? nullptr : t->bg.data();
-        p->flt = t->flt.empty() ? nullptr : t->flt.data();
-        p->ovl = t->ovl.empty() ? nullptr : t->ovl.data();
+        p->bytes = bytes; p->lens = lens; p->w = w; p->h = h; p->fmt = fmt; p->quality = quality;
+        p->ops = t->ops.empty() ? nullptr : t->ops.data();
         p->sniff = sniff;
         p->filter = filter;
         p->hp.threads = threads;
@@ -2088,6 +1750,153 @@ std::shared_ptr<Ticket> new_ticket(uint32_t n, uint8_t** outs, size_t* out_lens,
     return t;
 }
 
+// device-resident inputs: every one must be device memory of one device (the batch runs there)
+int inputs_device(const uint8_t* const* dev_bytes, const size_t* lens, uint32_t n, int* phys_out) {
+    int phys = -1;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!lens[i]) continue;
+        if (!dev_bytes[i]) return fail(IK_ERR_INVALID, "input %u: null bytes", i);
+        hipPointerAttribute_t at{};
+        if (hipPointerGetAttributes(&at, dev_bytes[i]) != hipSuccess || at.type != hipMemoryTypeDevice) {
+            (void)hipGetLastError();
+            return fail(IK_ERR_INVALID, "input %u is not device memory", i);
+        }
+        if (phys < 0) phys = at.device;
+        else if (phys != at.device) return fail(IK_ERR_INVALID, "inputs on devices %d and %d", phys, at.device);
+    }
+    *phys_out = phys < 0 ? current_device() : phys;
+    return IK_OK;
+}
+
+// device-resident inputs on device phys: what the stages read of them into the ticket
+// (Ticket::eff, sniff, hcopy, heads, jin, jskel)
+int stage_device_inputs(Ticket* t, const uint8_t* const* dev_bytes, const size_t* lens, uint32_t n, int phys) {
+    t->eff.assign(dev_bytes, dev_bytes + n);
+    t->sniff.assign(n, nullptr);
+    t->hcopy.resize(n);
+    t->heads.assign(64 * (size_t)n, 0);
+    DeviceGuard g(phys);
+    // the first 64 bytes of every file, through pinned memory (the block also
+    // holds the JPEG marker walk's table, records and skeleton slots, below)
+    const size_t o_files = (64 * (size_t)n + 255) & ~size_t(255);
+    const size_t o_jrecs = o_files + 2 * sizeof(uint64_t) * n;
+    const size_t o_jskel = (o_jrecs + sizeof(jwalk::Rec) * n + 255) & ~size_t(255);
+    uint8_t* pin = pinned_slot(kPinnedDeviceHeads, o_jskel + (size_t)jwalk::kSlot * n);
+    void* dp = nullptr;
+    if (!pin || hipHostGetDevicePointer(&dp, pin, 0) != hipSuccess || !dp)
+        return fail(IK_ERR_NOMEM, "cannot allocate pinned memory for the input headers");
+    uint64_t* files = reinterpret_cast<uint64_t*>(pin + o_files);
+    for (uint32_t i = 0; i < n; ++i) {
+        files[i] = (uint64_t)(uintptr_t)dev_bytes[i];
+        files[n + i] = dev_bytes[i] ? lens[i] : 0;
+    }
+    hipStream_t s = thread_stream();
+    const uint64_t* df = reinterpret_cast<const uint64_t*>(reinterpret_cast<uint8_t*>(dp) + o_files);
+    IK_HIP(launch_copy_heads(df, df + n, (int)n, reinterpret_cast<uint8_t*>(dp), s));
+    IK_HIP(hipStreamSynchronize(s));
+    std::memcpy(t->heads.data(), pin, 64 * (size_t)n);
+    // The JPEG files: a marker walk on the GPU brings back each one's skeleton
+    // (table and frame segments), two offsets and a verdict; those it passes stay
+    // where they are, the decoder reads their scans from the caller's memory.
+    std::vector<uint32_t> ji;
+    for (uint32_t i = 0; i < n; ++i)
+        if (dev_bytes[i] && guess_format(t->heads.data() + 64 * (size_t)i, std::min<size_t>(lens[i], 64)) == Sniffed::Jpeg)
+            ji.push_back(i);
+    const size_t nj = ji.size();
+    std::vector<char> in_place(n, 0);
+    if (nj && jpeg_device_inplace()) {
+        for (size_t k = 0; k < nj; ++k) {  // (the kernel above has finished with the table)
+            files[k] = (uint64_t)(uintptr_t)dev_bytes[ji[k]];
+            files[nj + k] = lens[ji[k]];
+        }
+        uint8_t* dpin = reinterpret_cast<uint8_t*>(dp);
+        EvPair& ev = thread_events(kEvJpegWalk);
+        ev_record(ev.a, s);
+        IK_HIP(launch_jpeg_walk(df, df + nj, (int)nj, dpin + o_jskel, dpin + o_jrecs, s));
+        ev_record(ev.b, s);
+        IK_HIP(hipStreamSynchronize(s));
+        jpeg_device_walk_ms(ev_pair_ms(ev));
+        const jwalk::Rec* recs = reinterpret_cast<const jwalk::Rec*>(pin + o_jrecs);
+        size_t total = 0;
+        for (size_t k = 0; k < nj; ++k)
+            if (recs[k].verdict == jwalk::kInPlace) total += recs[k].skel_len;
+        t->jskel.resize(total);
+        size_t o = 0;
+        for (size_t k = 0; k < nj; ++k) {
+            const jwalk::Rec& r = recs[k];
+            const uint32_t i = ji[k];
+            if (r.verdict != jwalk::kInPlace) continue;
+            auto it = t->jin.find(dev_bytes[i]);
+            if (it != t->jin.end()) {  // the same address twice: one record serves both (another length: copied back)
+                in_place[i] = it->second.len == lens[i];
+                continue;
+            }
+            JpegInPlace& J = t->jin[dev_bytes[i]];
+            std::memcpy(t->jskel.data() + o, pin + o_jskel + (size_t)jwalk::kSlot * k, r.skel_len);
+            J.skel = t->jskel.data() + o;
+            J.skel_len = r.skel_len;
+            J.len = lens[i];
+            J.ent_off = r.ent_off;
+            J.eoi_off = r.eoi_off;
+            o += r.skel_len;
+            in_place[i] = 1;
+        }
+    }
+    size_t n_in = 0;
+    for (uint32_t i : ji) n_in += in_place[i] ? 1 : 0;
+    jpeg_device_count(0, n_in);
+    jpeg_device_count(1, nj - n_in);
+    // PNG files stay where they are (the upload stage walks and gathers them on
+    // the GPU), and so do the JPEG files taken in place; any other item comes
+    // back to host memory for its host-side parse
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint8_t* hd = t->heads.data() + 64 * (size_t)i;
+        if (!dev_bytes[i] || in_place[i] || guess_format(hd, std::min<size_t>(lens[i], 64)) == Sniffed::Png) {
+            t->sniff[i] = dev_bytes[i] ? hd : nullptr;
+            continue;
+        }
+        t->hcopy[i].resize(lens[i]);
+        IK_HIP(hipMemcpy(t->hcopy[i].data(), dev_bytes[i], lens[i], hipMemcpyDeviceToHost));
+        t->eff[i] = t->sniff[i] = t->hcopy[i].data();
+    }
+    return IK_OK;
+}
+
+// Every batch submit ends here with its requests' options as records (empty: all at their
+// defaults).  device: bytes are device addresses; the batch runs where they are, on a logical
+// device of that physical device or (single-device mode) on its stages whatever the calling
+// thread's device is.
+int submit_records(const uint8_t* const* bytes, const size_t* lens, uint32_t n, const int64_t* w, const int64_t* h,
+                   std::vector<RequestOps>&& ops, const int* fmt, const int* quality, int filter, int threads,
+                   uint8_t** outs, size_t* out_lens, int* status, uint64_t* ticket, bool device) {
+    int phys = -1;
+    if (device)
+        if (int rc = inputs_device(bytes, lens, n, &phys)) return rc;
+    auto t = new_ticket(n, outs, out_lens, status);
+    t->ops = std::move(ops);
+    if (!device) return submit_parts(t, bytes, nullptr, -1, lens, n, w, h, fmt, quality, filter, threads, ticket);
+    if (int rc = stage_device_inputs(t.get(), bytes, lens, n, phys)) return rc;
+    return submit_parts(t, t->eff.data(), t->sniff.data(), phys, lens, n, w, h, fmt, quality, filter, threads, ticket);
+}
+
+// ... and begins here: an entry point's arguments checked in the order the entry points have
+// always checked them (the options' size, the arrays, then request by request: request_ops),
+// all before a ticket exists or anything is queued.  fit / orient: the *_fit and *_oriented
+// calls' arrays; opts, opt_size: the *_opts calls' (the others pass null and any declared size)
+int submit_batch(const uint8_t* const* bytes, const size_t* lens, uint32_t n, const int64_t* w, const int64_t* h,
+                 const int* fit, const int* orient, const void* opts, size_t opt_size, const int* fmt,
+                 const int* quality, int filter, int threads, uint8_t** outs, size_t* out_lens, int* status,
+                 uint64_t* ticket, bool device) {
+    if (!opts_size_ok(opt_size)) return fail(IK_ERR_INVALID, "unknown options size %zu", opt_size);
+    if (!bytes || !lens || !w || !h || !fmt || !quality || !outs || !out_lens || !n || !ticket)
+        return fail(IK_ERR_INVALID, "bad batch");
+    std::vector<RequestOps> ops;
+    // (IK_ORIENT_AUTO is resolved here, on the host: a header walk of a few hundred bytes per file)
+    if (int rc = request_ops(fit, orient, opts, opt_size, n, device ? nullptr : bytes, lens, ops)) return rc;
+    return submit_records(bytes, lens, n, w, h, std::move(ops), fmt, quality, filter, threads, outs, out_lens, status,
+                          ticket, device);
+}
+
 }  // namespace
 }  // namespace ik
 
@@ -2097,21 +1906,16 @@ int ik_transform_batch_submit(const uint8_t* const* bytes, const size_t* lens, u
                               const int64_t* h, const int* fmt, const int* quality, int filter, int threads,
                               uint8_t** outs, size_t* out_lens, int* status, uint64_t* ticket) {
     IK_API_ENTER();
-    return ik_transform_batch_submit_fit(bytes, lens, n, w, h, nullptr, fmt, quality, filter, threads, outs, out_lens,
-                                         status, ticket);
+    return submit_batch(bytes, lens, n, w, h, nullptr, nullptr, nullptr, sizeof(ik_request_opts), fmt, quality, filter,
+                        threads, outs, out_lens, status, ticket, false);
 }
 
 int ik_transform_batch_submit_fit(const uint8_t* const* bytes, const size_t* lens, uint32_t n, const int64_t* w,
                                   const int64_t* h, const int* fit, const int* fmt, const int* quality, int filter,
                                   int threads, uint8_t** outs, size_t* out_lens, int* status, uint64_t* ticket) {
     IK_API_ENTER();
-    if (!bytes || !lens || !w || !h || !fmt || !quality || !outs || !out_lens || !n || !ticket)
-        return fail(IK_ERR_INVALID, "bad batch");
-    for (uint32_t i = 0; fit && i < n; ++i)
-        if (fit[i] < IK_FIT_CONTAIN || fit[i] > IK_FIT_EXACT)
-            return fail(IK_ERR_INVALID, "request %u: unknown fit %d", i, fit[i]);
-    auto t = new_ticket(n, outs, out_lens, status);
-    return submit_parts(t, bytes, nullptr, -1, lens, n, w, h, fit, fmt, quality, filter, threads, ticket);
+    return submit_batch(bytes, lens, n, w, h, fit, nullptr, nullptr, sizeof(ik_request_opts), fmt, quality, filter,
+                        threads, outs, out_lens, status, ticket, false);
 }
 
 int ik_transform_batch_submit_oriented(const uint8_t* const* bytes, const size_t* lens, uint32_t n, const int64_t* w,
@@ -2119,139 +1923,8 @@ int ik_transform_batch_submit_oriented(const uint8_t* const* bytes, const size_t
                                        const int* quality, int filter, int threads, uint8_t** outs, size_t* out_lens,
                                        int* status, uint64_t* ticket) {
     IK_API_ENTER();
-    if (!bytes || !lens || !w || !h || !fmt || !quality || !outs || !out_lens || !n || !ticket)
-        return fail(IK_ERR_INVALID, "bad batch");
-    // AUTO is resolved here, on the host: a header walk of a few hundred bytes per file
-    std::vector<int> eff;
-    bool any = false;
-    for (uint32_t i = 0; orient && i < n; ++i) {
-        if (orient[i] == IK_ORIENT_STORED) continue;  // (also keeps an all-STORED batch off the files)
-        const int o = effective_orientation(bytes[i], lens[i], orient[i]);
-        if (o < 0) return fail(IK_ERR_INVALID, "request %u: unknown orientation %d", i, orient[i]);
-        if (!o) continue;
-        if (!any) eff.assign(n, 0);
-        any = true;
-        eff[i] = o;
-    }
-    if (!any)  // nothing to turn: the _fit call itself
-        return ik_transform_batch_submit_fit(bytes, lens, n, w, h, fit, fmt, quality, filter, threads, outs, out_lens,
-                                             status, ticket);
-    for (uint32_t i = 0; fit && i < n; ++i)
-        if (fit[i] < IK_FIT_CONTAIN || fit[i] > IK_FIT_EXACT)
-            return fail(IK_ERR_INVALID, "request %u: unknown fit %d", i, fit[i]);
-    auto t = new_ticket(n, outs, out_lens, status);
-    t->orient.swap(eff);
-    return submit_parts(t, bytes, nullptr, -1, lens, n, w, h, fit, fmt, quality, filter, threads, ticket);
-}
-
-// ---- per-request options (ik_request_opts, ik_request_opts2, ik_request_opts3) ----
-static bool opts_size_ok(size_t opt_size) {
-    return opt_size == sizeof(ik_request_opts) || opt_size == sizeof(ik_request_opts2) ||
-           opt_size == sizeof(ik_request_opts3);
-}
-// request i of an options array whose structs lie opt_size bytes apart, as the largest
-// layout (a smaller one's new fields: zero, "off")
-static ik_request_opts3 opts_at(const void* opts, size_t opt_size, uint32_t i) {
-    ik_request_opts3 o{};
-    std::memcpy(&o, static_cast<const uint8_t*>(opts) + (size_t)i * opt_size, opt_size);
-    return o;
-}
-// the blur or unsharpen an options struct asks for.  Returns IK_OK, or IK_ERR_INVALID with
-// the message set (prefix: "" or "request i: ")
-static int filter_of(const ik_request_opts3& o, const char* prefix, FilterReq& f) {
-    f = FilterReq();
-    // (written so that a NaN fails)
-    const bool bs = o.blur_sigma == 0.0f || (o.blur_sigma >= 0.0625f && o.blur_sigma <= IK_BLUR_MAX_SIGMA);
-    const bool ss = o.sharpen_sigma == 0.0f || (o.sharpen_sigma >= 0.0625f && o.sharpen_sigma <= IK_BLUR_MAX_SIGMA);
-    if (!bs)
-        return fail(IK_ERR_INVALID, "%sblur sigma %g is neither 0 nor in 0.0625..%g", prefix, (double)o.blur_sigma,
-                    (double)IK_BLUR_MAX_SIGMA);
-    if (!ss)
-        return fail(IK_ERR_INVALID, "%ssharpen sigma %g is neither 0 nor in 0.0625..%g", prefix, (double)o.sharpen_sigma,
-                    (double)IK_BLUR_MAX_SIGMA);
-    if (!blur_threshold_ok(o.sharpen_threshold))
-        return fail(IK_ERR_INVALID, "%ssharpen threshold %d outside 0..65535", prefix, (int)o.sharpen_threshold);
-    if (o.blur_sigma != 0.0f && o.sharpen_sigma != 0.0f) return fail(IK_ERR_INVALID, "%sblur and sharpen together", prefix);
-    if (o.blur_sigma != 0.0f) { f.mode = 1; f.sigma = o.blur_sigma; }
-    else if (o.sharpen_sigma != 0.0f) { f.mode = 2; f.sigma = o.sharpen_sigma; f.threshold = o.sharpen_threshold; }
-    return IK_OK;
-}
-// the watermark an options struct asks for (r.mark null: none), checked as filter_of checks
-static int overlay_of(const ik_request_opts3& o, const char* prefix, OverlayReq& r) {
-    r = OverlayReq();
-    if (o.reserved != 0) return fail(IK_ERR_INVALID, "%sreserved options field is %d, not 0", prefix, (int)o.reserved);
-    if (int rc = overlay_check(o.overlay_gravity, o.overlay_dx, o.overlay_dy, o.overlay_opacity, 0, o.overlay_tile, prefix))
-        return rc;
-    if (!o.overlay) {
-        if (o.overlay_gravity || o.overlay_dx || o.overlay_dy || o.overlay_opacity || o.overlay_tile)
-            return fail(IK_ERR_INVALID, "%soverlay fields set without an overlay", prefix);
-        return IK_OK;
-    }
-    r.mark = o.overlay;
-    r.gravity = o.overlay_gravity; r.dx = o.overlay_dx; r.dy = o.overlay_dy;
-    r.opacity = o.overlay_opacity ? o.overlay_opacity : 255;
-    r.tile = o.overlay_tile;
-    return IK_OK;
-}
-static bool background_ok(int32_t b) { return b == IK_BG_NONE || (b >= 0 && b <= 0xFFFFFF); }
-
-// a batch's options as the arrays its ticket keeps, each left empty when every request is at
-// that option's default (so an all-default batch makes the calls of the plain submit)
-struct OptArrays {
-    std::vector<int> fit, orient;  // orient: effective orientations (0 = as stored, 2..8)
-    std::vector<int32_t> bg;
-    std::vector<FilterReq> flt;
-    std::vector<OverlayReq> ovl;
-    bool none() const { return fit.empty() && orient.empty() && bg.empty() && flt.empty() && ovl.empty(); }
-};
-
-// bytes: the files in host memory, or null (device-resident inputs: IK_ORIENT_AUTO cannot be
-// resolved and is refused).  Returns IK_OK or IK_ERR_INVALID with the message set.
-static int split_opts(const void* opts, size_t opt_size, uint32_t n, const uint8_t* const* bytes, const size_t* lens,
-                      OptArrays& a) {
-    for (uint32_t i = 0; opts && i < n; ++i) {
-        const ik_request_opts3 o = opts_at(opts, opt_size, i);
-        if (o.fit < IK_FIT_CONTAIN || o.fit > IK_FIT_EXACT)
-            return fail(IK_ERR_INVALID, "request %u: unknown fit %d", i, o.fit);
-        if (!background_ok(o.background))
-            return fail(IK_ERR_INVALID, "request %u: background %d is neither IK_BG_NONE nor 0x000000..0xFFFFFF", i,
-                        (int)o.background);
-        if (o.orient == IK_ORIENT_AUTO && !bytes)
-            return fail(IK_ERR_INVALID, "request %u: IK_ORIENT_AUTO cannot be resolved for device-resident inputs", i);
-        if (o.orient < IK_ORIENT_AUTO || o.orient > 8)
-            return fail(IK_ERR_INVALID, "request %u: unknown orientation %d", i, o.orient);
-        // (STORED is not looked up: an all-STORED batch stays off the files)
-        const int eff = o.orient == IK_ORIENT_STORED ? 0
-                        : bytes                      ? effective_orientation(bytes[i], lens[i], o.orient)
-                                                     : (o.orient <= 1 ? 0 : o.orient);
-        if (o.fit != IK_FIT_CONTAIN) {
-            if (a.fit.empty()) a.fit.assign(n, IK_FIT_CONTAIN);
-            a.fit[i] = o.fit;
-        }
-        if (eff) {
-            if (a.orient.empty()) a.orient.assign(n, 0);
-            a.orient[i] = eff;
-        }
-        if (o.background != IK_BG_NONE) {
-            if (a.bg.empty()) a.bg.assign(n, IK_BG_NONE);
-            a.bg[i] = o.background;
-        }
-        char prefix[32];
-        snprintf(prefix, sizeof prefix, "request %u: ", i);
-        FilterReq f;
-        if (int rc = filter_of(o, prefix, f)) return rc;
-        if (f.mode) {
-            if (a.flt.empty()) a.flt.assign(n, FilterReq());
-            a.flt[i] = f;
-        }
-        OverlayReq ov;
-        if (int rc = overlay_of(o, prefix, ov)) return rc;
-        if (ov.mark) {
-            if (a.ovl.empty()) a.ovl.assign(n, OverlayReq());
-            a.ovl[i] = ov;
-        }
-    }
-    return IK_OK;
+    return submit_batch(bytes, lens, n, w, h, fit, orient, nullptr, sizeof(ik_request_opts), fmt, quality, filter,
+                        threads, outs, out_lens, status, ticket, false);
 }
 
 int ik_transform_batch_submit_opts(const uint8_t* const* bytes, const size_t* lens, uint32_t n, const int64_t* w,
@@ -2259,22 +1932,8 @@ int ik_transform_batch_submit_opts(const uint8_t* const* bytes, const size_t* le
                                    const int* quality, int filter, int threads, uint8_t** outs, size_t* out_lens,
                                    int* status, uint64_t* ticket) {
     IK_API_ENTER();
-    if (!opts_size_ok(opt_size)) return fail(IK_ERR_INVALID, "unknown options size %zu", opt_size);
-    if (!bytes || !lens || !w || !h || !fmt || !quality || !outs || !out_lens || !n || !ticket)
-        return fail(IK_ERR_INVALID, "bad batch");
-    OptArrays a;
-    if (int rc = split_opts(opts, opt_size, n, bytes, lens, a)) return rc;
-    if (a.none())  // every request at its defaults: the plain submit itself
-        return ik_transform_batch_submit(bytes, lens, n, w, h, fmt, quality, filter, threads, outs, out_lens, status,
-                                         ticket);
-    auto t = new_ticket(n, outs, out_lens, status);
-    t->fitv.swap(a.fit);
-    t->orient.swap(a.orient);
-    t->bg.swap(a.bg);
-    t->flt.swap(a.flt);
-    t->ovl.swap(a.ovl);
-    return submit_parts(t, bytes, nullptr, -1, lens, n, w, h, t->fitv.empty() ? nullptr : t->fitv.data(), fmt, quality,
-                        filter, threads, ticket);
+    return submit_batch(bytes, lens, n, w, h, nullptr, nullptr, opts, opt_size, fmt, quality, filter, threads, outs,
+                        out_lens, status, ticket, false);
 }
 
 int ik_transform_batch_opts(const uint8_t* const* bytes, const size_t* lens, uint32_t n, const int64_t* w,
@@ -2288,17 +1947,13 @@ int ik_transform_batch_opts(const uint8_t* const* bytes, const size_t* lens, uin
     return ik_transform_batch_wait(ticket);
 }
 
-static int submit_device(const uint8_t* const* dev_bytes, const size_t* lens, uint32_t n, const int64_t* w,
-                         const int64_t* h, OptArrays& opt, const int* fmt, const int* quality, int filter, int threads,
-                         uint8_t** outs, size_t* out_lens, int* status, uint64_t* ticket);
-
 int ik_transform_batch_submit_device(const uint8_t* const* dev_bytes, const size_t* lens, uint32_t n,
                                      const int64_t* w, const int64_t* h, const int* fmt, const int* quality,
                                      int filter, int threads, uint8_t** outs, size_t* out_lens, int* status,
                                      uint64_t* ticket) {
     IK_API_ENTER();
-    OptArrays none;
-    return submit_device(dev_bytes, lens, n, w, h, none, fmt, quality, filter, threads, outs, out_lens, status, ticket);
+    return submit_batch(dev_bytes, lens, n, w, h, nullptr, nullptr, nullptr, sizeof(ik_request_opts), fmt, quality,
+                        filter, threads, outs, out_lens, status, ticket, true);
 }
 
 int ik_transform_batch_submit_device_opts(const uint8_t* const* dev_bytes, const size_t* lens, uint32_t n,
@@ -2306,134 +1961,8 @@ int ik_transform_batch_submit_device_opts(const uint8_t* const* dev_bytes, const
                                           size_t opt_size, const int* fmt, const int* quality, int filter, int threads,
                                           uint8_t** outs, size_t* out_lens, int* status, uint64_t* ticket) {
     IK_API_ENTER();
-    if (!opts_size_ok(opt_size)) return fail(IK_ERR_INVALID, "unknown options size %zu", opt_size);
-    if (!dev_bytes || !lens || !w || !h || !fmt || !quality || !outs || !out_lens || !n || !ticket)
-        return fail(IK_ERR_INVALID, "bad batch");
-    OptArrays a;
-    if (int rc = split_opts(opts, opt_size, n, nullptr, lens, a)) return rc;  // before anything is queued
-    return submit_device(dev_bytes, lens, n, w, h, a, fmt, quality, filter, threads, outs, out_lens, status, ticket);
-}
-
-// opt: the requests' options (all empty: the plain device submit), moved into the ticket
-static int submit_device(const uint8_t* const* dev_bytes, const size_t* lens, uint32_t n, const int64_t* w,
-                         const int64_t* h, OptArrays& opt, const int* fmt, const int* quality, int filter, int threads,
-                         uint8_t** outs, size_t* out_lens, int* status, uint64_t* ticket) {
-    if (!dev_bytes || !lens || !w || !h || !fmt || !quality || !outs || !out_lens || !n || !ticket)
-        return fail(IK_ERR_INVALID, "bad batch");
-    // every input must be device memory of one device (the batch runs there)
-    int phys = -1;
-    for (uint32_t i = 0; i < n; ++i) {
-        if (!lens[i]) continue;
-        if (!dev_bytes[i]) return fail(IK_ERR_INVALID, "input %u: null bytes", i);
-        hipPointerAttribute_t at{};
-        if (hipPointerGetAttributes(&at, dev_bytes[i]) != hipSuccess || at.type != hipMemoryTypeDevice) {
-            (void)hipGetLastError();
-            return fail(IK_ERR_INVALID, "input %u is not device memory", i);
-        }
-        if (phys < 0) phys = at.device;
-        else if (phys != at.device) return fail(IK_ERR_INVALID, "inputs on devices %d and %d", phys, at.device);
-    }
-    if (phys < 0) phys = current_device();
-    auto t = new_ticket(n, outs, out_lens, status);
-    t->eff.assign(dev_bytes, dev_bytes + n);
-    t->sniff.assign(n, nullptr);
-    t->hcopy.resize(n);
-    t->heads.assign(64 * (size_t)n, 0);
-    {
-        DeviceGuard g(phys);
-        // the first 64 bytes of every file, through pinned memory (the block also
-        // holds the JPEG marker walk's table, records and skeleton slots, below)
-        const size_t o_files = (64 * (size_t)n + 255) & ~size_t(255);
-        const size_t o_jrecs = o_files + 2 * sizeof(uint64_t) * n;
-        const size_t o_jskel = (o_jrecs + sizeof(jwalk::Rec) * n + 255) & ~size_t(255);
-        uint8_t* pin = pinned_slot(kPinnedDeviceHeads, o_jskel + (size_t)jwalk::kSlot * n);
-        void* dp = nullptr;
-        if (!pin || hipHostGetDevicePointer(&dp, pin, 0) != hipSuccess || !dp)
-            return fail(IK_ERR_NOMEM, "cannot allocate pinned memory for the input headers");
-        uint64_t* files = reinterpret_cast<uint64_t*>(pin + o_files);
-        for (uint32_t i = 0; i < n; ++i) {
-            files[i] = (uint64_t)(uintptr_t)dev_bytes[i];
-            files[n + i] = dev_bytes[i] ? lens[i] : 0;
-        }
-        hipStream_t s = thread_stream();
-        const uint64_t* df = reinterpret_cast<const uint64_t*>(reinterpret_cast<uint8_t*>(dp) + o_files);
-        IK_HIP(launch_copy_heads(df, df + n, (int)n, reinterpret_cast<uint8_t*>(dp), s));
-        IK_HIP(hipStreamSynchronize(s));
-        std::memcpy(t->heads.data(), pin, 64 * (size_t)n);
-        // The JPEG files: a marker walk on the GPU brings back each one's skeleton
-        // (table and frame segments), two offsets and a verdict; those it passes stay
-        // where they are, the decoder reads their scans from the caller's memory.
-        std::vector<uint32_t> ji;
-        for (uint32_t i = 0; i < n; ++i)
-            if (dev_bytes[i] && guess_format(t->heads.data() + 64 * (size_t)i, std::min<size_t>(lens[i], 64)) == Sniffed::Jpeg)
-                ji.push_back(i);
-        const size_t nj = ji.size();
-        std::vector<char> in_place(n, 0);
-        if (nj && jpeg_device_inplace()) {
-            for (size_t k = 0; k < nj; ++k) {  // (the kernel above has finished with the table)
-                files[k] = (uint64_t)(uintptr_t)dev_bytes[ji[k]];
-                files[nj + k] = lens[ji[k]];
-            }
-            uint8_t* dpin = reinterpret_cast<uint8_t*>(dp);
-            EvPair& ev = thread_events(kEvJpegWalk);
-            ev_record(ev.a, s);
-            IK_HIP(launch_jpeg_walk(df, df + nj, (int)nj, dpin + o_jskel, dpin + o_jrecs, s));
-            ev_record(ev.b, s);
-            IK_HIP(hipStreamSynchronize(s));
-            jpeg_device_walk_ms(ev_pair_ms(ev));
-            const jwalk::Rec* recs = reinterpret_cast<const jwalk::Rec*>(pin + o_jrecs);
-            size_t total = 0;
-            for (size_t k = 0; k < nj; ++k)
-                if (recs[k].verdict == jwalk::kInPlace) total += recs[k].skel_len;
-            t->jskel.resize(total);
-            size_t o = 0;
-            for (size_t k = 0; k < nj; ++k) {
-                const jwalk::Rec& r = recs[k];
-                const uint32_t i = ji[k];
-                if (r.verdict != jwalk::kInPlace) continue;
-                auto it = t->jin.find(dev_bytes[i]);
-                if (it != t->jin.end()) {  // the same address twice: one record serves both (another length: copied back)
-                    in_place[i] = it->second.len == lens[i];
-                    continue;
-                }
-                JpegInPlace& J = t->jin[dev_bytes[i]];
-                std::memcpy(t->jskel.data() + o, pin + o_jskel + (size_t)jwalk::kSlot * k, r.skel_len);
-                J.skel = t->jskel.data() + o;
-                J.skel_len = r.skel_len;
-                J.len = lens[i];
-                J.ent_off = r.ent_off;
-                J.eoi_off = r.eoi_off;
-                o += r.skel_len;
-                in_place[i] = 1;
-            }
-        }
-        size_t n_in = 0;
-        for (uint32_t i : ji) n_in += in_place[i] ? 1 : 0;
-        jpeg_device_count(0, n_in);
-        jpeg_device_count(1, nj - n_in);
-        // PNG files stay where they are (the upload stage walks and gathers them on
-        // the GPU), and so do the JPEG files taken in place; any other item comes
-        // back to host memory for its host-side parse
-        for (uint32_t i = 0; i < n; ++i) {
-            const uint8_t* hd = t->heads.data() + 64 * (size_t)i;
-            if (!dev_bytes[i] || in_place[i] || guess_format(hd, std::min<size_t>(lens[i], 64)) == Sniffed::Png) {
-                t->sniff[i] = dev_bytes[i] ? hd : nullptr;
-                continue;
-            }
-            t->hcopy[i].resize(lens[i]);
-            IK_HIP(hipMemcpy(t->hcopy[i].data(), dev_bytes[i], lens[i], hipMemcpyDeviceToHost));
-            t->eff[i] = t->sniff[i] = t->hcopy[i].data();
-        }
-    }
-    // the batch runs where its inputs are: on a logical device of `phys`, or (single-
-    // device mode) on the stages of `phys` whatever the calling thread's device is
-    t->fitv.swap(opt.fit);
-    t->orient.swap(opt.orient);
-    t->bg.swap(opt.bg);
-    t->flt.swap(opt.flt);
-    t->ovl.swap(opt.ovl);
-    return submit_parts(t, t->eff.data(), t->sniff.data(), phys, lens, n, w, h,
-                        t->fitv.empty() ? nullptr : t->fitv.data(), fmt, quality, filter, threads, ticket);
+    return submit_batch(dev_bytes, lens, n, w, h, nullptr, nullptr, opts, opt_size, fmt, quality, filter, threads, outs,
+                        out_lens, status, ticket, true);
 }
 
 int ik_memory_stats(uint64_t* out, int n) {
@@ -2508,103 +2037,10 @@ int ik_transform_batch_oriented(const uint8_t* const* bytes, const size_t* lens,
     return ik_transform_batch_wait(ticket);
 }
 
-// orientation: 0 = the pixels as stored, 2..8 = turned first (effective_orientation);
-// background: IK_BG_NONE, or the colour an image with alpha is flattened onto after the turn
-// flt: the blur or unsharpen of the resized image (mode 0: none)
-// ovl: the watermark composited after it (mark null: none)
-static int transform_here(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orientation,
-                          int32_t background, FilterReq flt, OverlayReq ovl, int fmt, int quality, int filter,
-                          uint8_t** out, size_t* out_len) {
-    ik_image* img = nullptr;
-    int st = decode_one(bytes, len, &img, nullptr);
-    if (st) return st;
-    if (orientation) {
-        ik_image* turned = nullptr;
-        st = ik_image_orient(img, orientation, &turned);
-        ik_image_free(img);
-        if (st) return st;
-        img = turned;
-    }
-    if (background != IK_BG_NONE && (img->c == 2 || img->c == 4)) {  // (no alpha: no pass, no copy)
-        ik_image* flat = nullptr;
-        st = ik_image_flatten(img, background, &flat);
-        ik_image_free(img);
-        if (st) return st;
-        img = flat;
-    }
-    ik_image* rs = nullptr;
-    st = ik_resize_fit(img, w, h, fit, filter, &rs);
-    if (st) { ik_image_free(img); return st; }
-    if (flt.mode) {  // the filter sees the pixels the encoder will code
-        ik_image* fo = nullptr;
-        st = flt.mode == 2 ? ik_image_unsharpen(rs, flt.sigma, flt.threshold, &fo) : ik_image_blur(rs, flt.sigma, &fo);
-        if (rs != img) ik_image_free(rs);
-        if (st) { ik_image_free(img); return st; }
-        rs = fo;
-    }
-    if (ovl.mark) {  // in place: rs is this call's own (with w and h both None, img itself)
-        st = overlay_image(rs, ovl);
-        if (st) {
-            if (rs != img) ik_image_free(rs);
-            ik_image_free(img);
-            return st;
-        }
-    }
-    st = ik_encode(rs, fmt, quality, out, out_len);
-    if (rs != img) ik_image_free(rs);
-    ik_image_free(img);
-    return st;
-}
-
-int ik_transform(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fmt, int quality,
-                 int filter, uint8_t** out, size_t* out_len) {
-    IK_API_ENTER();
-    return ik_transform_fit(bytes, len, w, h, IK_FIT_CONTAIN, fmt, quality, filter, out, out_len);
-}
-
-static int transform_scheduled(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orientation,
-                               int32_t background, FilterReq flt, OverlayReq ovl, int fmt, int quality, int filter,
-                               uint8_t** out, size_t* out_len);
-
-int ik_transform_fit(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int fmt, int quality,
-                     int filter, uint8_t** out, size_t* out_len) {
-    IK_API_ENTER();
-    return transform_scheduled(bytes, len, w, h, fit, 0, IK_BG_NONE, FilterReq(), OverlayReq(), fmt, quality, filter, out, out_len);
-}
-
-// (the *_opts calls; opts_size_ok and background_ok: above, with the batch submits)
-
-int ik_transform_opts(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fmt, int quality, int filter,
-                      const void* opts, size_t opt_size, uint8_t** out, size_t* out_len) {
-    IK_API_ENTER();
-    if (!opts_size_ok(opt_size)) return fail(IK_ERR_INVALID, "unknown options size %zu", opt_size);
-    if (!opts) return ik_transform(bytes, len, w, h, fmt, quality, filter, out, out_len);
-    const ik_request_opts3 ro = opts_at(opts, opt_size, 0);
-    if (!background_ok(ro.background))
-        return fail(IK_ERR_INVALID, "background %d is neither IK_BG_NONE nor 0x000000..0xFFFFFF", (int)ro.background);
-    FilterReq flt;
-    if (int rc = filter_of(ro, "", flt)) return rc;
-    OverlayReq ovl;
-    if (int rc = overlay_of(ro, "", ovl)) return rc;
-    const int o = effective_orientation(bytes, len, ro.orient);
-    if (o < 0) return fail(IK_ERR_INVALID, "unknown orientation %d", ro.orient);
-    return transform_scheduled(bytes, len, w, h, ro.fit, o, ro.background, flt, ovl, fmt, quality, filter, out, out_len);
-}
-
-int ik_transform_oriented(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orient, int fmt,
-                          int quality, int filter, uint8_t** out, size_t* out_len) {
-    IK_API_ENTER();
-    const int o = effective_orientation(bytes, len, orient);
-    if (o < 0) return fail(IK_ERR_INVALID, "unknown orientation %d", orient);
-    return transform_scheduled(bytes, len, w, h, fit, o, IK_BG_NONE, FilterReq(), OverlayReq(), fmt, quality, filter, out, out_len);
-}
-
-// on this device, or (several devices) on the least-loaded one's workers
-static int transform_scheduled(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orientation,
-                               int32_t background, FilterReq flt, OverlayReq ovl, int fmt, int quality, int filter,
-                               uint8_t** out, size_t* out_len) {
-    if (!sched_multi())
-        return transform_here(bytes, len, w, h, fit, orientation, background, flt, ovl, fmt, quality, filter, out, out_len);
+// one request on this device, or (several devices) on the least-loaded one's workers
+static int transform_scheduled(const uint8_t* bytes, size_t len, int64_t w, int64_t h, const RequestOps& ops, int fmt,
+                               int quality, int filter, uint8_t** out, size_t* out_len) {
+    if (!sched_multi()) return transform_here(bytes, len, w, h, ops, fmt, quality, filter, out, out_len);
     // several devices: queue the request to the least-loaded device's workers
     const uint64_t cost = request_cost(bytes, len, w, h, fmt);
     const int ld = sched_acquire(cost);
@@ -2614,7 +2050,7 @@ static int transform_scheduled(const uint8_t* bytes, size_t len, int64_t w, int6
     int st = IK_OK;
     std::string msg;
     sched_pool(ld).post([&] {
-        const int r = transform_here(bytes, len, w, h, fit, orientation, background, flt, ovl, fmt, quality, filter, out, out_len);
+        const int r = transform_here(bytes, len, w, h, ops, fmt, quality, filter, out, out_len);
         std::string m = r ? last_error_str() : std::string();
         std::lock_guard<std::mutex> lk(mu);
         st = r;
@@ -2629,6 +2065,41 @@ static int transform_scheduled(const uint8_t* bytes, size_t len, int64_t w, int6
     sched_release(ld, cost);
     if (st) return fail(st, "%s", msg.c_str());
     return IK_OK;
+}
+
+// the single-request calls: fit and orient, or opts when it is not null, as one record
+static int transform_single(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orient, const void* opts,
+                            size_t opt_size, int fmt, int quality, int filter, uint8_t** out, size_t* out_len) {
+    if (!opts_size_ok(opt_size)) return fail(IK_ERR_INVALID, "unknown options size %zu", opt_size);
+    RequestOps ops;
+    if (int rc = single_request_ops(fit, orient, opts, opt_size, bytes, len, ops)) return rc;
+    return transform_scheduled(bytes, len, w, h, ops, fmt, quality, filter, out, out_len);
+}
+
+int ik_transform(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fmt, int quality,
+                 int filter, uint8_t** out, size_t* out_len) {
+    IK_API_ENTER();
+    return ik_transform_fit(bytes, len, w, h, IK_FIT_CONTAIN, fmt, quality, filter, out, out_len);
+}
+
+int ik_transform_fit(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int fmt, int quality,
+                     int filter, uint8_t** out, size_t* out_len) {
+    IK_API_ENTER();
+    return ik_transform_oriented(bytes, len, w, h, fit, IK_ORIENT_STORED, fmt, quality, filter, out, out_len);
+}
+
+int ik_transform_oriented(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fit, int orient, int fmt,
+                          int quality, int filter, uint8_t** out, size_t* out_len) {
+    IK_API_ENTER();
+    return transform_single(bytes, len, w, h, fit, orient, nullptr, sizeof(ik_request_opts), fmt, quality, filter, out,
+                            out_len);
+}
+
+int ik_transform_opts(const uint8_t* bytes, size_t len, int64_t w, int64_t h, int fmt, int quality, int filter,
+                      const void* opts, size_t opt_size, uint8_t** out, size_t* out_len) {
+    IK_API_ENTER();
+    return transform_single(bytes, len, w, h, IK_FIT_CONTAIN, IK_ORIENT_STORED, opts, opt_size, fmt, quality, filter, out,
+                            out_len);
 }
 
 int ik_resize_batch_device(const uint8_t* dev_src, uint32_t W, uint32_t H, uint32_t C,

@@ -2,7 +2,7 @@
 // launch resizes each request and which coder writes its file.  Policy only, in sizes
 // and counts: plain C++17, no HIP, nothing read from the process (the caller passes the
 // WebP encoder setting and the mixed mode, each read once per batch).  The product's
-// executor (ik_host.cpp transform_post_phase) walks the plan; ik_post_plan exports it
+// executor (ik_post_stage.cpp transform_post_phase) walks the plan; ik_post_plan exports it
 // for tests/test_post_plan.py.
 //
 // The rules:

@@ -9,6 +9,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 #include <unordered_map>
 
@@ -493,9 +494,9 @@ struct OverlayReq {
     int32_t gravity = 0, dx = 0, dy = 0;
     int32_t opacity = 255;  // 1..255
     int32_t tile = 0;
-    bool same(const OverlayReq& o) const {
-        return mark == o.mark && gravity == o.gravity && dx == o.dx && dy == o.dy && opacity == o.opacity && tile == o.tile;
-    }
+    // requests whose keys are equal share a launch (overlay_group)
+    typedef std::tuple<uintptr_t, int32_t, int32_t, int32_t, int32_t, int32_t> Key;
+    Key key() const { return Key((uintptr_t)mark, gravity, dx, dy, opacity, tile); }
 };
 // IK_OK, or IK_ERR_INVALID with the message set (prefix: "" or "request i: "): the gravity,
 // the offsets, the tile flag and an opacity within opacity_lo..255 (ik_overlay_host.cpp)
@@ -506,6 +507,56 @@ int overlay_check(int32_t gravity, int32_t dx, int32_t dy, int32_t opacity, int3
 // every image to overlay_image.  An overlay on another device is copied over for the call.
 int overlay_image(ik_image* base, const OverlayReq& r);
 int overlay_group(const std::vector<ik_image*>& bases, const OverlayReq& r);
+
+// One request's options, resolved (ik_post_stage.cpp): what the *_fit, *_oriented and *_opts
+// entry points ask for beyond (w, h, fmt, quality), in the order the steps run
+struct RequestOps {
+    int fit = IK_FIT_CONTAIN;
+    int orient = 0;           // effective orientation: 0 = the pixels as stored, 2..8 = turned first
+    int32_t bg = IK_BG_NONE;  // or 0xRRGGBB: an image with alpha is flattened onto it after the turn
+    FilterReq flt;            // the blur or unsharpen of the resized image (mode 0: none)
+    OverlayReq ovl;           // the watermark composited after it (mark null: none)
+    bool is_default() const { return fit == IK_FIT_CONTAIN && !orient && bg == IK_BG_NONE && !flt.mode && !ovl.mark; }
+};
+bool opts_size_ok(size_t opt_size);  // one of the declared ik_request_opts* layouts
+// the orientation an `orient` argument (ik_orient) means for these bytes: 0 = none
+// (stored order, or an effective 1: no pass), 2..8, or -1 for a bad argument
+int effective_orientation(const uint8_t* bytes, size_t len, int orient);
+// A batch's options as records, checked request by request: from the *_fit and *_oriented
+// calls' arrays (fit, orient; each null: the default) or from an *_opts call's array (opts,
+// opt_size apart; null: the defaults).  ops is left empty when every request is at its
+// defaults, so such a batch makes the calls of the plain submit.  bytes: the files in host
+// memory, or null (device-resident inputs: IK_ORIENT_AUTO cannot be resolved and is refused).
+// Returns IK_OK or IK_ERR_INVALID with the message set ("request i: ...").
+int request_ops(const int* fit, const int* orient, const void* opts, size_t opt_size, uint32_t n,
+                const uint8_t* const* bytes, const size_t* lens, std::vector<RequestOps>& ops);
+// the same for a single-request call (fit and orient, or opts when it is not null), in the
+// order ik_transform_opts checks; the messages carry no prefix
+int single_request_ops(int fit, int orient, const void* opts, size_t opt_size, const uint8_t* bytes, size_t len,
+                       RequestOps& r);
+
+// decode_image on the calling thread's device (ik_host.cpp), and the thread's last message
+int decode_one(const uint8_t* bytes, size_t len, ik_image** out, int* fmt_out);
+std::string last_error_str();
+// decode -> orient -> flatten -> resize -> filter -> watermark -> encode of one request, here
+int transform_here(const uint8_t* bytes, size_t len, int64_t w, int64_t h, const RequestOps& ops, int fmt, int quality,
+                   int filter, uint8_t** out, size_t* out_len);
+// a batch part between its stages (ik_host.cpp StageExec): the requests it holds and what
+// each stage leaves for the next
+struct HostPhase {
+    std::vector<uint32_t> idx;
+    std::vector<EncodePrep> prep;
+    std::vector<std::vector<uint8_t>> bytes_out;
+    int threads = 0;
+    double t_resize = 0, t_front = 0;
+    // the decode stage's results, for the post stage: decoded images, status, message
+    std::vector<ik_image*> imgs;
+    std::vector<int> ds;
+    std::vector<std::string> dm;
+};
+// the post stage of a batch part (ik_post_stage.cpp); ops: null, or every request's options
+void transform_post_phase(const int64_t* w, const int64_t* h, const RequestOps* ops, const int* fmt, const int* quality,
+                          int filter, int* st, std::string* errs, HostPhase& hp);
 
 // Per-device phase gates (ik_pool.cpp).  Concurrent batch calls on one device
 // take its GPU phases in turn: kGateUpload covers a PNG batch's staging, H2D and

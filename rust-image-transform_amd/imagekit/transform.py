@@ -548,6 +548,17 @@ def _inputs(datas):
     return keep, ptrs, lens
 
 
+def _batch_arrays(n, sizes, fmts, qualities, filter):
+    """What every batch call passes beside its inputs and options: the (w, h), format and
+    quality arrays, the filter, and the output, length and status arrays the library fills."""
+    filt = int(FilterType.Lanczos3 if filter is None else filter)
+    ws = (ctypes.c_int64 * n)(*[-1 if s[0] is None else int(s[0]) for s in sizes])
+    hs = (ctypes.c_int64 * n)(*[-1 if s[1] is None else int(s[1]) for s in sizes])
+    fs = (ctypes.c_int * n)(*[int(f.value if isinstance(f, ImageFormat) else f) for f in fmts])
+    qs = (ctypes.c_int * n)(*[int(q) for q in qualities])
+    return ws, hs, fs, qs, filt, (ctypes.c_void_p * n)(), (ctypes.c_size_t * n)(), (ctypes.c_int * n)()
+
+
 def transform_batch(datas, sizes, fmts, qualities, filter: "FilterType" = None, threads: int = 0,
                     fits=None, orient=None, backgrounds=None, blurs=None, sharpens=None,
                     overlays=None) -> List[bytes]:
@@ -564,14 +575,7 @@ def transform_batch(datas, sizes, fmts, qualities, filter: "FilterType" = None, 
     n = len(bufs)
     if n == 0:
         return []
-    filt = int(FilterType.Lanczos3 if filter is None else filter)
-    ws = (ctypes.c_int64 * n)(*[-1 if s[0] is None else int(s[0]) for s in sizes])
-    hs = (ctypes.c_int64 * n)(*[-1 if s[1] is None else int(s[1]) for s in sizes])
-    fs = (ctypes.c_int * n)(*[int(f.value if isinstance(f, ImageFormat) else f) for f in fmts])
-    qs = (ctypes.c_int * n)(*[int(q) for q in qualities])
-    outs = (ctypes.c_void_p * n)()
-    olens = (ctypes.c_size_t * n)()
-    status = (ctypes.c_int * n)()
+    ws, hs, fs, qs, filt, outs, olens, status = _batch_arrays(n, sizes, fmts, qualities, filter)
     fa = _fits(fits, n)
     oa = _orients(orient, n)
     if backgrounds is not None or blurs is not None or sharpens is not None or overlays is not None:
@@ -632,14 +636,7 @@ def transform_batch_submit(datas, sizes, fmts, qualities, filter: "FilterType" =
     n = len(bufs)
     if n == 0:
         raise InvalidArgument("empty batch")
-    filt = int(FilterType.Lanczos3 if filter is None else filter)
-    ws = (ctypes.c_int64 * n)(*[-1 if s[0] is None else int(s[0]) for s in sizes])
-    hs = (ctypes.c_int64 * n)(*[-1 if s[1] is None else int(s[1]) for s in sizes])
-    fs = (ctypes.c_int * n)(*[int(f.value if isinstance(f, ImageFormat) else f) for f in fmts])
-    qs = (ctypes.c_int * n)(*[int(q) for q in qualities])
-    outs = (ctypes.c_void_p * n)()
-    olens = (ctypes.c_size_t * n)()
-    status = (ctypes.c_int * n)()
+    ws, hs, fs, qs, filt, outs, olens, status = _batch_arrays(n, sizes, fmts, qualities, filter)
     ticket = ctypes.c_uint64()
     fa = _fits(fits, n)
     oa = _orients(orient, n)
@@ -678,14 +675,7 @@ def transform_batch_submit_device(datas, sizes, fmts, qualities, filter: "Filter
         raise InvalidArgument("transform_batch_submit_device takes DeviceBytes")
     ptrs = (ctypes.c_void_p * n)(*[d.ptr for d in keep])
     lens = (ctypes.c_size_t * n)(*[len(d) for d in keep])
-    filt = int(FilterType.Lanczos3 if filter is None else filter)
-    ws = (ctypes.c_int64 * n)(*[-1 if s[0] is None else int(s[0]) for s in sizes])
-    hs = (ctypes.c_int64 * n)(*[-1 if s[1] is None else int(s[1]) for s in sizes])
-    fs = (ctypes.c_int * n)(*[int(f.value if isinstance(f, ImageFormat) else f) for f in fmts])
-    qs = (ctypes.c_int * n)(*[int(q) for q in qualities])
-    outs = (ctypes.c_void_p * n)()
-    olens = (ctypes.c_size_t * n)()
-    status = (ctypes.c_int * n)()
+    ws, hs, fs, qs, filt, outs, olens, status = _batch_arrays(n, sizes, fmts, qualities, filter)
     ticket = ctypes.c_uint64()
     ra = None
     if (fits is None and orient is None and backgrounds is None and blurs is None and sharpens is None
@@ -752,19 +742,15 @@ def transform(data: bytes, w: Optional[int], h: Optional[int], fmt: ImageFormat,
     buf = _lib.u8p()
     n = ctypes.c_size_t()
     o = _orient(orient)
-    if mark is not None:
-        ro = _lib.RequestOpts3(int(FitMode(fit)), o, bg, *fa)
-        mark._fill(ro)
-        st = lib.ik_transform_opts(b, len(b), -1 if w is None else int(w), -1 if h is None else int(h),
-                                   ImageFormat(fmt).value, int(quality), int(filter), ctypes.byref(ro),
-                                   ctypes.sizeof(ro), ctypes.byref(buf), ctypes.byref(n))
-    elif fa[0] or fa[1]:
-        ro = _lib.RequestOpts2(int(FitMode(fit)), o, bg, *fa)
-        st = lib.ik_transform_opts(b, len(b), -1 if w is None else int(w), -1 if h is None else int(h),
-                                   ImageFormat(fmt).value, int(quality), int(filter), ctypes.byref(ro),
-                                   ctypes.sizeof(ro), ctypes.byref(buf), ctypes.byref(n))
-    elif bg != BG_NONE:
-        ro = _lib.RequestOpts(int(FitMode(fit)), o, bg)
+    if mark is not None or fa[0] or fa[1] or bg != BG_NONE:
+        # the smallest declared layout that holds what is set
+        if mark is not None:
+            ro = _lib.RequestOpts3(int(FitMode(fit)), o, bg, *fa)
+            mark._fill(ro)
+        elif fa[0] or fa[1]:
+            ro = _lib.RequestOpts2(int(FitMode(fit)), o, bg, *fa)
+        else:
+            ro = _lib.RequestOpts(int(FitMode(fit)), o, bg)
         st = lib.ik_transform_opts(b, len(b), -1 if w is None else int(w), -1 if h is None else int(h),
                                    ImageFormat(fmt).value, int(quality), int(filter), ctypes.byref(ro),
                                    ctypes.sizeof(ro), ctypes.byref(buf), ctypes.byref(n))
