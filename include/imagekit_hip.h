@@ -513,7 +513,7 @@ int ik_flatten_counters(unsigned long long out[2]);
  * w and h refer to the oriented image, and the background applies whatever the output
  * format (an AVIF request with a background is opaque and carries no alpha plane).
  * opt_size must be the size of a layout this header declares (ik_request_opts, or
- * ik_request_opts2 and ik_request_opts3 below); any other value is IK_ERR_INVALID ("unknown options size")
+ * ik_request_opts2, ik_request_opts3 and ik_request_opts4 below); any other value is IK_ERR_INVALID ("unknown options size")
  * before any device work, which is what lets the struct grow.  A fit outside ik_fit, an orient outside ik_orient / 1..8 and a background
  * that is neither IK_BG_NONE nor 0x000000..0xFFFFFF are IK_ERR_INVALID. */
 typedef struct {
@@ -656,6 +656,81 @@ static_assert(sizeof(ik_request_opts3) == 56, "ik_request_opts3 is 56 bytes");
 _Static_assert(sizeof(ik_request_opts3) == 56, "ik_request_opts3 is 56 bytes");
 #endif
 
+/* ---- colour adjustments ---------------------------------------------------- */
+/* Grayscale, brightness, contrast, saturation, hue, gamma and invert on the pixels' values,
+ * pixels staying in HBM.  The project's own definition.  The host turns
+ * the six numbers into a PLAN, a colour matrix and a tone table, in f64; the device applies
+ * the plan with integers only.  M = 255 or 65535.
+ *   matrix  l = (0.2126, 0.7152, 0.0722), L the matrix whose every row is l, I the identity;
+ *           s = 1 + saturation / 100;  Sat = L + s (I - L);  t = hue * pi / 180;
+ *           Hue = L + cos t (I - L) + sin t S  (SVG hueRotate),
+ *           S = [[-l0, -l1, 1 - l2], [0.143, 0.140, -0.283], [-(1 - l0), l1, l2]];
+ *           m = Hue Sat;  Q16: off the diagonal q = floor(m * 65536 + 0.5), on it 65536 minus
+ *           the row's other two, so every row sums to 65536 and R = G = B stays itself
+ *   pixel   C >= 3:  o_i = clamp((q[i][0] R + q[i][1] G + q[i][2] B + 32768) >> 16, 0, M), the
+ *           shift arithmetic.  C 1 or 2: the matrix is not applied (it would be the identity)
+ *   table   then every colour sample v becomes T[v]:  x = v / M + brightness / 100;
+ *           k = ((100 + contrast) / 100)^2;  x = clamp((x - 0.5) k + 0.5, 0, 1);
+ *           gamma != 0: x = pow(x, 1 / gamma);  invert: x = 1 - x;  T[v] = floor(x M + 0.5)
+ * Alpha is never touched; channels and depth never change.  All six at zero is "no
+ * adjustment": nothing is launched.  saturation -100 is grayscale. */
+typedef struct {
+    int32_t brightness; /* -100..100, 0: none */
+    int32_t contrast;   /* -100..100, 0: none */
+    int32_t saturation; /* -100..100, 0: none, -100: grayscale */
+    int32_t hue;        /* degrees, -360..360, 0: none */
+    float gamma;        /* 0.0: none, else 0.1..10.0 */
+    int32_t invert;     /* 0 or 1 */
+} ik_adjust;
+#ifdef __cplusplus
+static_assert(sizeof(ik_adjust) == 24, "ik_adjust is 24 bytes");
+#else
+_Static_assert(sizeof(ik_adjust) == 24, "ik_adjust is 24 bytes");
+#endif
+/* the plan; needs no device.  depth 1 or 2.  table (or NULL) receives the M + 1 entries of
+ * T, matrix (or NULL) the nine Q16 coefficients row by row, *flags (or NULL) bit 0: the
+ * matrix is not the identity, bit 1: the table is not the identity.  A field out of range
+ * (gamma: NaN, infinite, or neither 0 nor within 0.1..10) is IK_ERR_INVALID.  Every other
+ * call builds its plan through this. */
+int ik_adjust_plan(const ik_adjust *adj, int depth, uint16_t *table, int32_t matrix[9], int *flags);
+/* img adjusted as a new image on the device that holds img (a device copy, then the kernel
+ * in place on it; img is not changed).  A plan with flags 0 (all six at zero, a gray image
+ * under a matrix alone) gives the copy and launches nothing. */
+int ik_image_adjust(const ik_image *img, const ik_adjust *adj, ik_image **out);
+/* the pixels of a row one workgroup of the kernel takes, the size at which its edge handling
+ * changes; for tests */
+int ik_adjust_span(void);
+/* process-wide: out[0] adjust kernel launches, out[1] images adjusted by them */
+int ik_adjust_counters(unsigned long long out[2]);
+
+/* The fourth declared layout, 80 bytes: ik_request_opts3's 56, then an adjustment of the
+ * resized pixels: decode -> orient -> flatten -> resize -> adjust -> blur or sharpen ->
+ * overlay -> encode (the mark keeps its colours).  With `adjust` all zero the call makes
+ * exactly the calls of the 56-byte layout.  A field out of range is IK_ERR_INVALID before
+ * any device work; in a batch the message names the request, and members of a resize group
+ * whose 24 adjustment bytes are equal are adjusted by one launch. */
+typedef struct {
+    int fit;                   /* ik_fit */
+    int orient;                /* ik_orient, or 1..8 */
+    int32_t background;        /* IK_BG_NONE, or 0xRRGGBB */
+    float blur_sigma;          /* 0: no blur */
+    float sharpen_sigma;       /* 0: no unsharp mask */
+    int32_t sharpen_threshold; /* 0..65535 */
+    const ik_image *overlay;   /* NULL: no watermark */
+    int32_t overlay_gravity;   /* ik_gravity */
+    int32_t overlay_dx;
+    int32_t overlay_dy;
+    int32_t overlay_opacity;   /* 0 means 255, else 1..255 */
+    int32_t overlay_tile;      /* 0 or 1 */
+    int32_t reserved;          /* must be 0 */
+    ik_adjust adjust;          /* all zero: none */
+} ik_request_opts4;
+#ifdef __cplusplus
+static_assert(sizeof(ik_request_opts4) == 80, "ik_request_opts4 is 80 bytes");
+#else
+_Static_assert(sizeof(ik_request_opts4) == 80, "ik_request_opts4 is 80 bytes");
+#endif
+
 /* ---- fused / batched entry points (pixels stay in HBM) ----------------- */
 /* decode -> resize_image -> encode_image in one call (handler src/lib.rs:175-191) */
 int ik_transform(const uint8_t *bytes, size_t len, int64_t w, int64_t h, int fmt, int quality,
@@ -758,7 +833,7 @@ int ik_transform_batch_submit_device(const uint8_t *const *dev_bytes, const size
                                      uint64_t *ticket);
 
 /* The batch calls with per-request options: opts holds n ik_request_opts, n
- * ik_request_opts2 or n ik_request_opts3 (or is NULL: every request at its defaults, the call without options),
+ * ik_request_opts2, n ik_request_opts3 or n ik_request_opts4 (or is NULL: every request at its defaults, the call without options),
  * opt_size is the size of that layout.  After a resize group's launch and before its
  * coders, its members that share (blur or unsharpen, sigma, threshold) are filtered by one
  * launch, a lone one by its own; requests that differ only in these settings still share
@@ -902,6 +977,19 @@ int ik_overlay_batch_device(uint8_t *dev_base, uint32_t W, uint32_t H, uint32_t 
                             size_t image_stride, uint32_t n, const uint8_t *dev_overlay, uint32_t wo, uint32_t ho,
                             uint32_t overlay_channels, uint32_t overlay_depth, size_t overlay_pitch, int gravity,
                             int32_t dx, int32_t dy, int opacity, int tile, void *hip_stream);
+/* the colour adjustment (above) applied IN PLACE over n images of W x H pixels of C samples
+ * of `depth` bytes, image i at dev + i*image_stride, in one launch.  Nothing outside
+ * W*C*depth bytes of each of the H rows is read or written, and alpha bytes keep their
+ * values.  A base, pitch and stride that are all multiples of 4 take the wide path (whole
+ * dwords; a row's ragged last share moves bytes); any others the byte path.  Enqueued on
+ * hip_stream (NULL: the calling thread's stream) without waiting; the tone table of (the 24
+ * bytes, depth) is uploaded once per device and kept.  A plan with flags 0 is IK_OK: nothing
+ * is launched and the counters do not move.  IK_ERR_INVALID, with nothing launched and
+ * nothing written: a field of adj out of range, C outside 1..4, depth outside 1..2, a null
+ * pointer, a zero size, a size above 2^24, a pitch below the row bytes, n > 1 with an image
+ * stride below rows * pitch, or n above 65535. */
+int ik_adjust_batch_device(uint8_t *dev, uint32_t W, uint32_t H, uint32_t C, uint32_t depth, size_t pitch,
+                           size_t image_stride, uint32_t n, const ik_adjust *adj, void *hip_stream);
 /* the WebP colour conversion (to_rgb8 + libwebp RGB->YUV420) on the device;
  * dev_yuv receives the Y (w*h), U and V ((w+1)/2 * (h+1)/2) planes back to back */
 int ik_webp_yuv420_device(const uint8_t *dev_src, uint32_t w, uint32_t h, uint32_t C,

@@ -1663,6 +1663,7 @@ int shutdown_all(bool close) {
     jpeg_shutdown();
     plans_shutdown();
     blur_shutdown();
+    adjust_shutdown();
     memory_shutdown();
     release_thread_resources();
     if (dev >= 0) (void)hipSetDevice(dev);

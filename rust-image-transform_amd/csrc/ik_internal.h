@@ -355,6 +355,26 @@ struct OverlayArgs {
 };
 hipError_t launch_overlay(const OverlayArgs& a, int C, int depth, int n, hipStream_t s);
 
+// ---- colour adjustment (ik_adjust.hip) ----
+// a plan (ik_adjust_plan.h) applied in place over n same-geometry images of C samples of
+// `depth` bytes, images at base + i * img_stride or at tab[i].  matrix:
+// q is applied (C >= 3 only); tone: the device table, 256 bytes at depth 1 and 65536
+// uint16 at depth 2, or null: no table.  One of the two at least.
+constexpr int kAdjustSpan = 1024;             // pixels of a row one workgroup takes
+constexpr int kAdjustRowCap = 256;            // most rows of workgroups in a launch (the rest: grid stride)
+constexpr uint32_t kAdjustMaxImages = 65535;  // grid.z
+constexpr uint32_t kAdjustMaxDim = 1u << 24;  // most pixels on an axis
+struct AdjustArgs {
+    uint8_t* base;
+    size_t pitch, img_stride;
+    const uint64_t* tab;  // per-image bases (device), or null: base + img * img_stride
+    const void* tone;     // the tone table (device), 4-byte aligned
+    int32_t q[9];         // the Q16 matrix, row by row
+    uint32_t W, H;
+    int aligned;          // the bases, the pitch and the stride are multiples of 4
+};
+hipError_t launch_adjust(const AdjustArgs& a, int C, int depth, bool matrix, int n, hipStream_t s);
+
 // ---- plans (ik_plan.cpp) ----
 // axis_weights, required_slots and the tables themselves: ik_resize_plan.h
 ResizePlan* get_resize_plan(int device, int W, int H, int C, int nw, int nh, int filter, int n);

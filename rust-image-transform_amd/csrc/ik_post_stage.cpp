@@ -1,6 +1,6 @@
 // ik_post_stage.cpp -- what a request's options mean and where they run: the entry points'
 // option arguments as one record per request (RequestOps), the batch paths' post stage
-// (orient -> flatten -> resize -> filter -> watermark -> the encoders' device front ends) and
+// (orient -> flatten -> resize -> adjust -> filter -> watermark -> the encoders' device front ends) and
 // the single-request path through the same steps (transform_here).
 #include <hip/hip_runtime.h>
 
@@ -20,21 +20,21 @@
 
 namespace ik {
 
-// ---- per-request options (ik_request_opts, ik_request_opts2, ik_request_opts3) ----
+// ---- per-request options (ik_request_opts, ik_request_opts2, ik_request_opts3, ik_request_opts4) ----
 bool opts_size_ok(size_t opt_size) {
     return opt_size == sizeof(ik_request_opts) || opt_size == sizeof(ik_request_opts2) ||
-           opt_size == sizeof(ik_request_opts3);
+           opt_size == sizeof(ik_request_opts3) || opt_size == sizeof(ik_request_opts4);
 }
 // request i of an options array whose structs lie opt_size bytes apart, as the largest
 // layout (a smaller one's new fields: zero, "off")
-static ik_request_opts3 opts_at(const void* opts, size_t opt_size, uint32_t i) {
-    ik_request_opts3 o{};
+static ik_request_opts4 opts_at(const void* opts, size_t opt_size, uint32_t i) {
+    ik_request_opts4 o{};
     std::memcpy(&o, static_cast<const uint8_t*>(opts) + (size_t)i * opt_size, opt_size);
     return o;
 }
 // the blur or unsharpen an options struct asks for.  Returns IK_OK, or IK_ERR_INVALID with
 // the message set (prefix: "" or "request i: ")
-static int filter_of(const ik_request_opts3& o, const char* prefix, FilterReq& f) {
+static int filter_of(const ik_request_opts4& o, const char* prefix, FilterReq& f) {
     f = FilterReq();
     // (written so that a NaN fails)
     const bool bs = o.blur_sigma == 0.0f || (o.blur_sigma >= 0.0625f && o.blur_sigma <= IK_BLUR_MAX_SIGMA);
@@ -53,7 +53,7 @@ static int filter_of(const ik_request_opts3& o, const char* prefix, FilterReq& f
     return IK_OK;
 }
 // the watermark an options struct asks for (r.mark null: none), checked as filter_of checks
-static int overlay_of(const ik_request_opts3& o, const char* prefix, OverlayReq& r) {
+static int overlay_of(const ik_request_opts4& o, const char* prefix, OverlayReq& r) {
     r = OverlayReq();
     if (o.reserved != 0) return fail(IK_ERR_INVALID, "%sreserved options field is %d, not 0", prefix, (int)o.reserved);
     if (int rc = overlay_check(o.overlay_gravity, o.overlay_dx, o.overlay_dy, o.overlay_opacity, 0, o.overlay_tile, prefix))
@@ -69,7 +69,14 @@ static int overlay_of(const ik_request_opts3& o, const char* prefix, OverlayReq&
     r.tile = o.overlay_tile;
     return IK_OK;
 }
-static int background_of(const ik_request_opts3& o, const char* prefix, int32_t& bg) {
+// the colour adjustment an options struct asks for (all zero: none), checked as filter_of checks
+static int adjust_of(const ik_request_opts4& o, const char* prefix, AdjustReq& r) {
+    r = AdjustReq();
+    if (int rc = adjust_check(o.adjust, prefix)) return rc;
+    r.a = o.adjust;
+    return IK_OK;
+}
+static int background_of(const ik_request_opts4& o, const char* prefix, int32_t& bg) {
     bg = o.background;
     if (bg == IK_BG_NONE || (bg >= 0 && bg <= 0xFFFFFF)) return IK_OK;
     return fail(IK_ERR_INVALID, "%sbackground %d is neither IK_BG_NONE nor 0x000000..0xFFFFFF", prefix, (int)bg);
@@ -95,7 +102,7 @@ int request_ops(const int* fit, const int* orient, const void* opts, size_t opt_
     ops.assign(n, RequestOps());
     bool any = false;
     for (uint32_t i = 0; i < n; ++i) {
-        ik_request_opts3 o{};
+        ik_request_opts4 o{};
         o.background = IK_BG_NONE;
         if (opts) o = opts_at(opts, opt_size, i);
         if (fit) o.fit = fit[i];
@@ -111,6 +118,7 @@ int request_ops(const int* fit, const int* orient, const void* opts, size_t opt_
         if (int rc = orientation_of(o.orient, bytes ? bytes[i] : nullptr, lens[i], prefix, r.orient)) return rc;
         if (int rc = filter_of(o, prefix, r.flt)) return rc;
         if (int rc = overlay_of(o, prefix, r.ovl)) return rc;
+        if (int rc = adjust_of(o, prefix, r.adj)) return rc;
         any = any || !r.is_default();
     }
     if (!any) ops.clear();
@@ -120,13 +128,14 @@ int request_ops(const int* fit, const int* orient, const void* opts, size_t opt_
 int single_request_ops(int fit, int orient, const void* opts, size_t opt_size, const uint8_t* bytes, size_t len,
                        RequestOps& r) {
     r = RequestOps();
-    ik_request_opts3 o{};
+    ik_request_opts4 o{};
     o.fit = fit; o.orient = orient; o.background = IK_BG_NONE;
     if (opts) o = opts_at(opts, opt_size, 0);
     r.fit = o.fit;  // (not checked here: ik_resize_fit refuses an unknown one, after the decode)
     if (int rc = background_of(o, "", r.bg)) return rc;
     if (int rc = filter_of(o, "", r.flt)) return rc;
     if (int rc = overlay_of(o, "", r.ovl)) return rc;
+    if (int rc = adjust_of(o, "", r.adj)) return rc;
     return orientation_of(o.orient, bytes, len, "", r.orient);
 }
 
@@ -135,7 +144,7 @@ static int filter_image(ik_image* img, const FilterReq& f, ik_image** out) {
     return f.mode == 2 ? ik_image_unsharpen(img, f.sigma, f.threshold, out) : ik_image_blur(img, f.sigma, out);
 }
 
-// resize_image, then the request's blur or unsharpen (the filter sees the pixels the encoder
+// resize_image, then the request's colour adjustment (in place), then its blur or unsharpen (the filter sees the pixels the encoder
 // will code), then its watermark, on one image: what follows the flatten for a single request
 // and for a batch's member that no resize group took.  *rs is the image to encode: a new one,
 // or, with w and h both None and no filter, img itself -- the caller owns img, so the
@@ -145,6 +154,10 @@ static int image_tail(ik_image* img, int64_t w, int64_t h, const RequestOps& ops
     ik_image* cur = nullptr;
     int st = ik_resize_fit(img, w, h, ops.fit, filter, &cur);
     if (st) return st;
+    if (ops.adj.on() && (st = adjust_image(cur, ops.adj)) != IK_OK) {
+        if (cur != img) ik_image_free(cur);
+        return st;
+    }
     if (ops.flt.mode) {
         ik_image* fo = nullptr;
         st = filter_image(cur, ops.flt, &fo);
@@ -306,6 +319,22 @@ void transform_post_phase(const int64_t* w, const int64_t* h, const RequestOps* 
         if (resize_group(src, G.win, filter, out) != IK_OK) continue;  // its members: image by image below
         for (size_t j = 0; j < out.size(); ++j) rsz[G.members[j]] = out[j];
         if (ops) {
+            // the colour adjustment first, in place on the resized images: the members that
+            // share the 24 adjustment bytes go through one launch, a lone one or a failed group
+            // through launches of their own.  A member whose adjustment fails gets its status
+            // and message: its file is dropped, and the later steps pass it by.
+            std::map<AdjustReq::Key, std::vector<uint32_t>> adjs;
+            for (uint32_t k : G.members)
+                if (op(k).adj.on()) adjs[op(k).adj.key()].push_back(k);
+            run_sets(adjs, rsz, false, ds, dm,
+                     [&](uint32_t k0, const std::vector<ik_image*>& bs, std::vector<ik_image*>& done) {
+                         done = bs;
+                         return adjust_group(bs, op(k0).adj);
+                     },
+                     [&](uint32_t k, ik_image* im, ik_image** done) {
+                         *done = im;
+                         return adjust_image(im, op(k).adj);
+                     });
             // blur or unsharpen before the group's coders run: the members that share (mode,
             // sigma, threshold) go through one launch, a lone one through its own, and the
             // unfiltered image returns to the pool.  A member whose filter fails keeps its
@@ -313,7 +342,7 @@ void transform_post_phase(const int64_t* w, const int64_t* h, const RequestOps* 
             std::map<std::tuple<int, uint32_t, int32_t>, std::vector<uint32_t>> filters;
             for (uint32_t k : G.members) {
                 const FilterReq& f = op(k).flt;
-                if (!f.mode) continue;
+                if (!f.mode || ds[k]) continue;
                 uint32_t sb;
                 std::memcpy(&sb, &f.sigma, 4);
                 filters[{f.mode, sb, f.threshold}].push_back(k);

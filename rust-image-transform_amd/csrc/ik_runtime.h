@@ -1,7 +1,9 @@
 // ik_runtime.h -- host runtime internals of libimagekit_hip.so (not part of the ABI).
 #pragma once
+#include <array>
 #include <condition_variable>
 #include <cstdarg>
+#include <cstring>
 #include <cstdint>
 #include <deque>
 #include <functional>
@@ -507,6 +509,29 @@ int overlay_check(int32_t gravity, int32_t dx, int32_t dy, int32_t opacity, int3
 // every image to overlay_image.  An overlay on another device is copied over for the call.
 int overlay_image(ik_image* base, const OverlayReq& r);
 int overlay_group(const std::vector<ik_image*>& bases, const OverlayReq& r);
+// one request's colour adjustment, after its resize (ik_request_opts4); all zero: none
+struct AdjustReq {
+    ik_adjust a{};
+    bool on() const {
+        return a.brightness || a.contrast || a.saturation || a.hue || a.gamma != 0.0f || a.invert;
+    }
+    // requests whose keys (the 24 bytes) are equal share a launch (adjust_group)
+    typedef std::array<uint8_t, sizeof(ik_adjust)> Key;
+    Key key() const {
+        Key k;
+        std::memcpy(k.data(), &a, sizeof a);
+        return k;
+    }
+};
+// IK_OK, or IK_ERR_INVALID with the message set (prefix: "" or "request i: "): every field of
+// the adjustment within its range (ik_adjust_host.cpp)
+int adjust_check(const ik_adjust& a, const char* prefix);
+// the adjustment applied in place: to one image in a launch of its own, or to same-geometry
+// images in one launch; a return other than IK_OK from adjust_group leaves every image to
+// adjust_image.  Both synchronise the stream.
+int adjust_image(ik_image* img, const AdjustReq& r);
+int adjust_group(const std::vector<ik_image*>& imgs, const AdjustReq& r);
+void adjust_shutdown();  // ik_shutdown: the cached plans and their device tables
 
 // One request's options, resolved (ik_post_stage.cpp): what the *_fit, *_oriented and *_opts
 // entry points ask for beyond (w, h, fmt, quality), in the order the steps run
@@ -514,9 +539,12 @@ struct RequestOps {
     int fit = IK_FIT_CONTAIN;
     int orient = 0;           // effective orientation: 0 = the pixels as stored, 2..8 = turned first
     int32_t bg = IK_BG_NONE;  // or 0xRRGGBB: an image with alpha is flattened onto it after the turn
-    FilterReq flt;            // the blur or unsharpen of the resized image (mode 0: none)
+    AdjustReq adj;            // the colour adjustment of the resized image (all zero: none)
+    FilterReq flt;            // the blur or unsharpen after it (mode 0: none)
     OverlayReq ovl;           // the watermark composited after it (mark null: none)
-    bool is_default() const { return fit == IK_FIT_CONTAIN && !orient && bg == IK_BG_NONE && !flt.mode && !ovl.mark; }
+    bool is_default() const {
+        return fit == IK_FIT_CONTAIN && !orient && bg == IK_BG_NONE && !adj.on() && !flt.mode && !ovl.mark;
+    }
 };
 bool opts_size_ok(size_t opt_size);  // one of the declared ik_request_opts* layouts
 // the orientation an `orient` argument (ik_orient) means for these bytes: 0 = none

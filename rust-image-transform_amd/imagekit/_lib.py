@@ -46,6 +46,17 @@ class RequestOpts3(ctypes.Structure):
         ("reserved", ctypes.c_int32)]
 
 
+class Adjust(ctypes.Structure):
+    """ik_adjust: a colour adjustment (all zero is none)."""
+    _fields_ = [("brightness", ctypes.c_int32), ("contrast", ctypes.c_int32), ("saturation", ctypes.c_int32),
+                ("hue", ctypes.c_int32), ("gamma", ctypes.c_float), ("invert", ctypes.c_int32)]
+
+
+class RequestOpts4(ctypes.Structure):
+    """ik_request_opts4: RequestOpts3's fields, then the colour adjustment (all zero is none)."""
+    _fields_ = RequestOpts3._fields_ + [("adjust", Adjust)]
+
+
 _opts_p = ctypes.c_void_p  # any declared layout (const void *opts, with its size)
 _batch_head = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint32,
                ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
@@ -191,6 +202,11 @@ SIGNATURES = [
     ("ik_overlay_span", ctypes.c_int, []),
     ("ik_overlay_counters", ctypes.c_int, [ctypes.POINTER(ctypes.c_ulonglong)]),
     ("ik_overlay_batch_device", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_uint32] * 4 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p] + [ctypes.c_uint32] * 4 + [ctypes.c_size_t, ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    ("ik_adjust_plan", ctypes.c_int, [ctypes.POINTER(Adjust), ctypes.c_int, ctypes.POINTER(ctypes.c_uint16), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int)]),
+    ("ik_image_adjust", ctypes.c_int, [c_img_p, ctypes.POINTER(Adjust), ctypes.POINTER(c_img_p)]),
+    ("ik_adjust_span", ctypes.c_int, []),
+    ("ik_adjust_counters", ctypes.c_int, [ctypes.POINTER(ctypes.c_ulonglong)]),
+    ("ik_adjust_batch_device", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_uint32] * 4 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, ctypes.POINTER(Adjust), ctypes.c_void_p]),
     ("ik_transform_opts", ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int] * 3 + [_opts_p, ctypes.c_size_t, ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t)]),
     ("ik_transform_batch_opts", ctypes.c_int, _batch_opts),
     ("ik_transform_batch_submit_opts", ctypes.c_int, _batch_opts + [ctypes.POINTER(ctypes.c_uint64)]),

@@ -232,19 +232,93 @@ def _overlays(overlays, n) -> Optional[list]:
     return marks if any(m is not None for m in marks) else None
 
 
-def _request_opts(n, fits=None, orients=None, backgrounds=None, blurs=None, sharpens=None, overlays=None):
+class Adjust:
+    """A colour adjustment of the output's pixels (ik_adjust): brightness,
+    contrast and saturation are ints in -100..100 (0: none; saturation -100 is grayscale),
+    hue degrees in -360..360, gamma None or 0 (none) or a number within 0.1..10, invert a
+    bool; grayscale=True is sugar for saturation -100.  Alpha is never touched.  Anything
+    else raises ValueError, before the library is called."""
+
+    __slots__ = ("brightness", "contrast", "saturation", "hue", "gamma", "invert")
+
+    def __init__(self, brightness: int = 0, contrast: int = 0, saturation: int = 0, hue: int = 0, gamma=None,
+                 invert: bool = False, grayscale: bool = False):
+        if not isinstance(grayscale, (bool, np.bool_)):
+            raise ValueError(f"adjust grayscale {grayscale!r} is not a bool")
+        if grayscale:
+            if saturation not in (0, -100):
+                raise ValueError("grayscale and a saturation together")
+            saturation = -100
+        for name, v, lim in (("brightness", brightness, 100), ("contrast", contrast, 100),
+                             ("saturation", saturation, 100), ("hue", hue, 360)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or abs(int(v)) > lim:
+                raise ValueError(f"adjust {name} {v!r} is not an int within +-{lim}")
+        if gamma is None:
+            gamma = 0.0
+        if isinstance(gamma, bool) or not isinstance(gamma, (int, float, np.integer, np.floating)):
+            raise ValueError(f"adjust gamma {gamma!r} is not a number")
+        g = float(np.float32(gamma))
+        if g != 0.0 and not float(np.float32(0.1)) <= g <= 10.0:  # (a NaN fails both comparisons)
+            raise ValueError(f"adjust gamma {gamma!r} is neither 0 nor within 0.1..10")
+        if not isinstance(invert, (bool, np.bool_)):
+            raise ValueError(f"adjust invert {invert!r} is not a bool")
+        self.brightness, self.contrast, self.saturation, self.hue = int(brightness), int(contrast), int(saturation), int(hue)
+        self.gamma, self.invert = g, bool(invert)
+
+    def is_none(self) -> bool:
+        return not (self.brightness or self.contrast or self.saturation or self.hue or self.gamma or self.invert)
+
+    def _struct(self) -> "_lib.Adjust":
+        return _lib.Adjust(self.brightness, self.contrast, self.saturation, self.hue, self.gamma, int(self.invert))
+
+
+def _adjust(v) -> Optional[Adjust]:
+    """An `adjust=` argument: None, an Adjust, or a dict of Adjust's keyword arguments.  One
+    that changes nothing is None."""
+    if v is None:
+        return None
+    if isinstance(v, dict):
+        v = Adjust(**v)
+    if not isinstance(v, Adjust):
+        raise ValueError(f"adjust {v!r} is not an Adjust")
+    return None if v.is_none() else v
+
+
+def _adjusts(adjusts, n) -> Optional[list]:
+    """The per-request adjustments of a batch call, or None (no request has one): one entry
+    per request, or a single Adjust (or a list of one) that applies to all."""
+    if adjusts is None:
+        return None
+    if isinstance(adjusts, (Adjust, dict)):
+        adjusts = [adjusts]
+    if len(adjusts) == 1 and n != 1:
+        adjusts = list(adjusts) * n
+    if len(adjusts) != n:
+        raise InvalidArgument("adjusts must have one entry per request, or one for all")
+    adj = [_adjust(v) for v in adjusts]
+    return adj if any(a is not None for a in adj) else None
+
+
+def _request_opts(n, fits=None, orients=None, backgrounds=None, blurs=None, sharpens=None, overlays=None,
+                  adjusts=None):
     """The options array of a *_opts batch call (each argument: one entry per request, or
     None for that option's default everywhere): ik_request_opts, ik_request_opts2 when
-    blurs or sharpens is given, or ik_request_opts3 when some request has an overlay.  Its
-    element size is ctypes.sizeof(arr._type_).  The overlays' images must outlive the call
-    (a submitted batch: its wait)."""
+    blurs or sharpens is given, ik_request_opts3 when some request has an overlay, or
+    ik_request_opts4 when some request has an adjustment.  Its element size is
+    ctypes.sizeof(arr._type_).  The overlays' images must outlive the call (a submitted
+    batch: its wait)."""
     for name, v in (("fits", fits), ("orient", orients), ("backgrounds", backgrounds), ("blurs", blurs),
                     ("sharpens", sharpens)):
         if v is not None and len(v) != n:
             raise InvalidArgument(f"{name} must have one entry per request")
     marks = _overlays(overlays, n)
-    wide = blurs is not None or sharpens is not None or marks is not None
-    arr = ((_lib.RequestOpts3 if marks is not None else _lib.RequestOpts2 if wide else _lib.RequestOpts) * n)()
+    adj = _adjusts(adjusts, n)
+    wide = blurs is not None or sharpens is not None or marks is not None or adj is not None
+    arr = ((_lib.RequestOpts4 if adj is not None else _lib.RequestOpts3 if marks is not None
+            else _lib.RequestOpts2 if wide else _lib.RequestOpts) * n)()
+    for i in range(n if adj is not None else 0):
+        if adj[i] is not None:
+            arr[i].adjust = adj[i]._struct()
     for i in range(n if wide else 0):
         arr[i].blur_sigma, arr[i].sharpen_sigma, arr[i].sharpen_threshold = _filter_args(
             blurs[i] if blurs is not None else None, sharpens[i] if sharpens is not None else None)
@@ -427,6 +501,24 @@ class DynamicImage:
             _raise(st, "overlay")
         return DynamicImage(out.value)
 
+    def adjust(self, adjust=None, **kwargs) -> "DynamicImage":
+        """This image under a colour adjustment as a new image (ik_image_adjust; the project's
+        own definition): an Adjust, or Adjust's keyword arguments
+        (img.adjust(grayscale=True)); channels and depth are kept, alpha is not touched."""
+        if adjust is not None and kwargs:
+            raise ValueError("an Adjust and keyword arguments together")
+        a = adjust if adjust is not None else Adjust(**kwargs)
+        if isinstance(a, dict):
+            a = Adjust(**a)
+        if not isinstance(a, Adjust):
+            raise ValueError(f"adjust {a!r} is not an Adjust")
+        st_a = a._struct()
+        out = ctypes.c_void_p()
+        st = _lib.load().ik_image_adjust(self._h, ctypes.byref(st_a), ctypes.byref(out))
+        if st:
+            _raise(st, "adjust")
+        return DynamicImage(out.value)
+
     def clone(self) -> "DynamicImage":
         return DynamicImage.from_array(self.to_array())
 
@@ -561,7 +653,7 @@ def _batch_arrays(n, sizes, fmts, qualities, filter):
 
 def transform_batch(datas, sizes, fmts, qualities, filter: "FilterType" = None, threads: int = 0,
                     fits=None, orient=None, backgrounds=None, blurs=None, sharpens=None,
-                    overlays=None) -> List[bytes]:
+                    overlays=None, adjusts=None) -> List[bytes]:
     """ik_transform_batch: decode -> resize_image -> encode_image for many requests
     (sizes: (w, h) per request, None = unset; fmts: ImageFormat per request; fits: a
     FitMode per request, None = contain for all; orient: an Orientation per request,
@@ -569,7 +661,8 @@ def transform_batch(datas, sizes, fmts, qualities, filter: "FilterType" = None, 
     None = no flatten for any; blurs: a sigma per request, sharpens: a sigma or (sigma,
     threshold) per request, None = off; overlays: an Overlay (or a DynamicImage: an opaque
     centred mark, or None) per request, or one for all of them.  With backgrounds, blurs,
-    sharpens or overlays the call is ik_transform_batch_opts)."""
+    sharpens, overlays or adjusts the call is ik_transform_batch_opts; adjusts: an Adjust (or
+    None) per request, or one for all of them, applied after the resize)."""
     lib = _lib.load()
     bufs, ptrs, lens = _inputs(datas)
     n = len(bufs)
@@ -578,8 +671,9 @@ def transform_batch(datas, sizes, fmts, qualities, filter: "FilterType" = None, 
     ws, hs, fs, qs, filt, outs, olens, status = _batch_arrays(n, sizes, fmts, qualities, filter)
     fa = _fits(fits, n)
     oa = _orients(orient, n)
-    if backgrounds is not None or blurs is not None or sharpens is not None or overlays is not None:
-        ra = _request_opts(n, fits, orient, backgrounds, blurs, sharpens, overlays)
+    if (backgrounds is not None or blurs is not None or sharpens is not None or overlays is not None
+            or adjusts is not None):
+        ra = _request_opts(n, fits, orient, backgrounds, blurs, sharpens, overlays, adjusts=adjusts)
         st = lib.ik_transform_batch_opts(ptrs, lens, n, ws, hs, ra, ctypes.sizeof(ra._type_), fs, qs, filt,
                                          threads, outs, olens, status)
     elif oa is not None:
@@ -626,7 +720,7 @@ class PendingBatch:
 
 def transform_batch_submit(datas, sizes, fmts, qualities, filter: "FilterType" = None,
                            threads: int = 0, fits=None, orient=None, backgrounds=None, blurs=None,
-                           sharpens=None, overlays=None) -> PendingBatch:
+                           sharpens=None, overlays=None, adjusts=None) -> PendingBatch:
     """ik_transform_batch_submit: the device half of transform_batch now, the host
     coders in the background; PendingBatch.wait() gives what transform_batch gives.
     fits, orient, backgrounds, blurs, sharpens and overlays as transform_batch takes them
@@ -641,8 +735,9 @@ def transform_batch_submit(datas, sizes, fmts, qualities, filter: "FilterType" =
     fa = _fits(fits, n)
     oa = _orients(orient, n)
     ra = None
-    if backgrounds is not None or blurs is not None or sharpens is not None or overlays is not None:
-        ra = _request_opts(n, fits, orient, backgrounds, blurs, sharpens, overlays)
+    if (backgrounds is not None or blurs is not None or sharpens is not None or overlays is not None
+            or adjusts is not None):
+        ra = _request_opts(n, fits, orient, backgrounds, blurs, sharpens, overlays, adjusts=adjusts)
         st = lib.ik_transform_batch_submit_opts(ptrs, lens, n, ws, hs, ra, ctypes.sizeof(ra._type_), fs, qs,
                                                 filt, threads, outs, olens, status, ctypes.byref(ticket))
     elif oa is not None:
@@ -661,7 +756,7 @@ def transform_batch_submit(datas, sizes, fmts, qualities, filter: "FilterType" =
 
 def transform_batch_submit_device(datas, sizes, fmts, qualities, filter: "FilterType" = None,
                                   threads: int = 0, fits=None, orient=None, backgrounds=None, blurs=None,
-                                  sharpens=None, overlays=None) -> PendingBatch:
+                                  sharpens=None, overlays=None, adjusts=None) -> PendingBatch:
     """ik_transform_batch_submit_device: as transform_batch_submit, over request
     bodies already in device memory (DeviceBytes).  With fits, orient, backgrounds, blurs, sharpens or
     overlays the call is ik_transform_batch_submit_device_opts; Orientation.auto is refused there (the
@@ -679,11 +774,11 @@ def transform_batch_submit_device(datas, sizes, fmts, qualities, filter: "Filter
     ticket = ctypes.c_uint64()
     ra = None
     if (fits is None and orient is None and backgrounds is None and blurs is None and sharpens is None
-            and overlays is None):
+            and overlays is None and adjusts is None):
         st = lib.ik_transform_batch_submit_device(ptrs, lens, n, ws, hs, fs, qs, filt, threads, outs, olens, status,
                                                   ctypes.byref(ticket))
     else:
-        ra = _request_opts(n, fits, orient, backgrounds, blurs, sharpens, overlays)
+        ra = _request_opts(n, fits, orient, backgrounds, blurs, sharpens, overlays, adjusts=adjusts)
         st = lib.ik_transform_batch_submit_device_opts(ptrs, lens, n, ws, hs, ra, ctypes.sizeof(ra._type_), fs,
                                                        qs, filt, threads, outs, olens, status, ctypes.byref(ticket))
     if st:
@@ -725,7 +820,7 @@ def encode_image(img: DynamicImage, fmt: ImageFormat, quality: int) -> bytes:
 
 def transform(data: bytes, w: Optional[int], h: Optional[int], fmt: ImageFormat, quality: int,
               filter: FilterType = FilterType.Lanczos3, fit: FitMode = FitMode.contain,
-              orient=Orientation.stored, background=None, blur=None, sharpen=None, overlay=None) -> bytes:
+              orient=Orientation.stored, background=None, blur=None, sharpen=None, overlay=None, adjust=None) -> bytes:
     """decode -> resize_image -> encode_image in one device-resident call; with orient
     (Orientation) the decoded image is turned first, and w, h and fit refer to the turned
     image; with background (0xRRGGBB, (r, g, b), "rrggbb" or "#rrggbb") an image that
@@ -733,18 +828,25 @@ def transform(data: bytes, w: Optional[int], h: Optional[int], fmt: ImageFormat,
     sigma) or sharpen (a sigma, or (sigma, threshold)) the resized image is blurred or
     sharpened by the unsharp mask before it is encoded; with overlay (an Overlay, or a
     DynamicImage for an opaque centred mark) that watermark is composited last, on the
-    pixels the encoder codes (ik_transform_opts)."""
+    pixels the encoder codes; with adjust (an Adjust) the resized image's colours are
+    adjusted before the blur or sharpen and the watermark (ik_transform_opts)."""
     bg = _background(background)
     fa = _filter_args(blur, sharpen)
     mark = _overlay(overlay)
+    adj = _adjust(adjust)
     lib = _lib.load()
     b = bytes(data)
     buf = _lib.u8p()
     n = ctypes.c_size_t()
     o = _orient(orient)
-    if mark is not None or fa[0] or fa[1] or bg != BG_NONE:
+    if adj is not None or mark is not None or fa[0] or fa[1] or bg != BG_NONE:
         # the smallest declared layout that holds what is set
-        if mark is not None:
+        if adj is not None:
+            ro = _lib.RequestOpts4(int(FitMode(fit)), o, bg, *fa)
+            if mark is not None:
+                mark._fill(ro)
+            ro.adjust = adj._struct()
+        elif mark is not None:
             ro = _lib.RequestOpts3(int(FitMode(fit)), o, bg, *fa)
             mark._fill(ro)
         elif fa[0] or fa[1]:

@@ -127,6 +127,10 @@ def main():
                     help="every request composites one shared synthetic RGBA mark of that size over its output "
                          "(ik_transform_batch*_opts, the 56-byte options), e.g. 128x32,se,200.  Without the flag: "
                          "the calls made before")
+    ap.add_argument("--adjust", default=None, metavar="grayscale | B,C,S,H,G,I",
+                    help="every request adjusts its resized image's colours (ik_transform_batch*_opts, the 80-byte "
+                         "options): grayscale, or brightness,contrast,saturation,hue,gamma,invert, e.g. "
+                         "10,20,-30,15,2.2,0.  Without the flag: the calls made before")
     ap.add_argument("--source", choices=["jpeg", "png-rgba"], default="jpeg",
                     help="png-rgba: translucent RGBA PNG sources of the same size (what --background acts on)")
     ap.add_argument("--restart", action="store_true")
@@ -169,7 +173,7 @@ def main():
         dist.init_process_group(backend="nccl" if torch.cuda.is_available() else "gloo")
     if torch.cuda.is_available():
         torch.cuda.set_device(local)
-    from imagekit import (DynamicImage, FitMode, ImageFormat, Orientation, Overlay, _lib, transform_batch,
+    from imagekit import (Adjust, DynamicImage, FitMode, ImageFormat, Orientation, Overlay, _lib, transform_batch,
                           transform_batch_submit)
     lib = _lib.load()
     queue = world == 1
@@ -207,11 +211,19 @@ def main():
         watermark = Overlay(mark, parts[1] if len(parts) > 1 else "center",
                             opacity=int(parts[2]) if len(parts) > 2 else 255)
 
+    adjust = None  # one adjustment for every request
+    if args.adjust is not None:
+        if args.adjust == "grayscale":
+            adjust = Adjust(grayscale=True)
+        else:
+            b, c, sa, hu, g, inv = args.adjust.split(",")
+            adjust = Adjust(int(b), int(c), int(sa), int(hu), float(g), bool(int(inv)))
+
     def run_batch(chunk):
         return transform_batch([srcs[s] for s, _, _, _ in chunk], [(w, h) for _, w, h, _ in chunk],
                                [f for _, _, _, f in chunk], [args.quality] * len(chunk), threads=args.threads,
                                fits=fits(chunk), orient=orients(chunk), backgrounds=backgrounds(chunk),
-                               blurs=blurs(chunk), sharpens=sharpens(chunk), overlays=watermark)
+                               blurs=blurs(chunk), sharpens=sharpens(chunk), overlays=watermark, adjusts=adjust)
 
     run_batch(mine[:min(len(mine), 8)])  # warm-up: plans, streams, pinned staging
 
@@ -251,7 +263,7 @@ def main():
             p = transform_batch_submit([srcs[s] for s, _, _, _ in chunk], [(w, h) for _, w, h, _ in chunk],
                                        [f for _, _, _, f in chunk], [args.quality] * len(chunk), threads=args.threads,
                                        fits=fits(chunk), orient=orients(chunk), backgrounds=backgrounds(chunk),
-                                       blurs=blurs(chunk), sharpens=sharpens(chunk), overlays=watermark)
+                                       blurs=blurs(chunk), sharpens=sharpens(chunk), overlays=watermark, adjusts=adjust)
             if pend is not None:
                 done(pend[0], pend[1].wait())
             pend = (tb, p)
@@ -276,6 +288,8 @@ def main():
     lib.ik_blur_counters(blur)  # (likewise)
     ovl = (ctypes.c_ulonglong * 2)()
     lib.ik_overlay_counters(ovl)  # (likewise)
+    adj = (ctypes.c_ulonglong * 2)()
+    lib.ik_adjust_counters(adj)  # (likewise)
     barrier()
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local}" if torch.cuda.is_available() else "cpu")
@@ -294,6 +308,8 @@ def main():
             "blur_counters": {"launches": blur[0], "images": blur[1]},
             "watermark": args.watermark,
             "overlay_counters": {"launches": ovl[0], "images": ovl[1]},
+            "adjust": args.adjust,
+            "adjust_counters": {"launches": adj[0], "images": adj[1]},
             "batch_latency_ms": {"p50": round(float(np.percentile(lat, 50)), 2),
                                  "p95": round(float(np.percentile(lat, 95)), 2)},
             "decoded_mpix_per_s": round(args.requests * S * S / elapsed / 1e6, 1),
