@@ -513,7 +513,7 @@ int ik_flatten_counters(unsigned long long out[2]);
  * w and h refer to the oriented image, and the background applies whatever the output
  * format (an AVIF request with a background is opaque and carries no alpha plane).
  * opt_size must be the size of a layout this header declares (ik_request_opts, or
- * ik_request_opts2, ik_request_opts3 and ik_request_opts4 below); any other value is IK_ERR_INVALID ("unknown options size")
+ * ik_request_opts2, ik_request_opts3, ik_request_opts4 and ik_request_opts5 below); any other value is IK_ERR_INVALID ("unknown options size")
  * before any device work, which is what lets the struct grow.  A fit outside ik_fit, an orient outside ik_orient / 1..8 and a background
  * that is neither IK_BG_NONE nor 0x000000..0xFFFFFF are IK_ERR_INVALID. */
 typedef struct {
@@ -731,6 +731,90 @@ static_assert(sizeof(ik_request_opts4) == 80, "ik_request_opts4 is 80 bytes");
 _Static_assert(sizeof(ik_request_opts4) == 80, "ik_request_opts4 is 80 bytes");
 #endif
 
+/* ---- pad: the output extended onto a canvas --------------------------------- */
+/* The image placed on a larger canvas with a frame around it ("fit=pad", extend,
+ * letterbox), pixels staying in HBM.  The project's own definition.
+ * Channels and depth never change; nothing is blended; alpha is copied like any other
+ * channel.  The image I is W x H, M = 255 or 65535.
+ *   canvas  cw = max(W, width), ch = max(H, height): an axis the image already fills is
+ *           not padded.  cw == W and ch == H: no pass, no launch.
+ *   place   x0 = 0, (cw - W) / 2 (floor) or cw - W by the ik_gravity, y0 likewise; no offsets
+ *   sample  canvas pixel (x, y) = I[fy(y - y0), fx(x - x0)], n the axis length, i signed:
+ *           IK_PAD_EDGE    clamp(i, 0, n - 1)
+ *           IK_PAD_WRAP    i mod n, Euclidean
+ *           IK_PAD_MIRROR  j = i mod 2n;  j < n ? j : 2n - 1 - j  (the edge sample repeats;
+ *                          the index folds as often as the margin needs)
+ *           IK_PAD_COLOR   inside the image its pixel, outside the frame pixel
+ *   frame   pixel (colour mode): the colour 0xRRGGBB, each channel b * 257 at 16 bits; C 3 or
+ *           4: as it is; C 1 or 2: L = (2126 R + 7152 G + 722 B) / 10000, floor, on the
+ *           channels at the image's depth (the overlay's gray rule); the alpha sample, where
+ *           the image has one: alpha, * 257 at 16 bits */
+enum ik_pad_mode { IK_PAD_NONE = 0, IK_PAD_COLOR = 1, IK_PAD_EDGE = 2, IK_PAD_MIRROR = 3, IK_PAD_WRAP = 4 };
+typedef struct {
+    int32_t mode;    /* ik_pad_mode; IK_PAD_NONE: no pad, and the other five must be 0 */
+    int32_t gravity; /* ik_gravity: where the image lies in the canvas */
+    int32_t width;   /* the canvas, 0..2^24.  0: ik_image_pad: the image's side; the _opts */
+    int32_t height;  /*   calls: the side of the request's target (w, h), "pad to the box" */
+    int32_t color;   /* 0xRRGGBB (colour mode) */
+    int32_t alpha;   /* 0..255: the frame's alpha where the image has one (colour mode) */
+} ik_pad;
+#ifdef __cplusplus
+static_assert(sizeof(ik_pad) == 24, "ik_pad is 24 bytes");
+#else
+_Static_assert(sizeof(ik_pad) == 24, "ik_pad is 24 bytes");
+#endif
+/* the placement; needs no device.  out: cw, ch, x0, y0.  W, H, width, height within
+ * 0..2^24 and a known gravity, else IK_ERR_INVALID.  Every other call places through the
+ * rule behind this one. */
+int ik_pad_place(uint32_t W, uint32_t H, uint32_t width, uint32_t height, int gravity, int32_t out[4]);
+/* img on its canvas as a new image on the device that holds img; 8- and 16-bit.  A pad whose
+ * canvas is the image gives a copy and launches nothing.  IK_ERR_INVALID: IK_PAD_NONE or an
+ * unknown mode or gravity, a size outside 0..2^24, a colour outside 0..0xFFFFFF, an alpha
+ * outside 0..255, an empty image under a larger canvas. */
+int ik_image_pad(const ik_image *img, const ik_pad *pad, ik_image **out);
+/* the canvas pixels of a row one workgroup of the kernel takes, and the most rows of
+ * workgroups of a launch (further rows are grid-strided); for tests */
+int ik_pad_span(void);
+int ik_pad_row_cap(void);
+/* process-wide: out[0] pad kernel launches, out[1] images padded by them */
+int ik_pad_counters(unsigned long long out[2]);
+
+/* The fifth declared layout, 104 bytes: ik_request_opts4's 80, then a pad of the finished
+ * pixels: decode -> orient -> flatten -> resize -> adjust -> blur or sharpen -> pad ->
+ * overlay -> encode.  The frame is neither adjusted nor blurred, and the watermark's gravity
+ * sees the canvas.  A pad width or height of 0 is the side of the request's target (tw, th)
+ * -- w and h with a missing side computed as the resize computes it -- so IK_FIT_CONTAIN
+ * with a zero-size pad returns exactly the box asked for; with w and h both None a zero
+ * side is the image's.  With pad.mode IK_PAD_NONE the other five fields must be 0 and the
+ * call makes exactly the calls of the 80-byte layout.  A field out of range, or fields set
+ * without a mode, is IK_ERR_INVALID before any device work; in a batch the message names
+ * the request.  In a batch a resize group's members share their canvas and origin as they
+ * share their window (a WebP canvas side above 16383 is judged on the canvas); members whose
+ * 24 pad bytes are equal are padded by one launch, and requests that differ only in mode,
+ * colour or alpha still share the resize and coder groups. */
+typedef struct {
+    int fit;                   /* ik_fit */
+    int orient;                /* ik_orient, or 1..8 */
+    int32_t background;        /* IK_BG_NONE, or 0xRRGGBB */
+    float blur_sigma;          /* 0: no blur */
+    float sharpen_sigma;       /* 0: no unsharp mask */
+    int32_t sharpen_threshold; /* 0..65535 */
+    const ik_image *overlay;   /* NULL: no watermark */
+    int32_t overlay_gravity;   /* ik_gravity */
+    int32_t overlay_dx;
+    int32_t overlay_dy;
+    int32_t overlay_opacity;   /* 0 means 255, else 1..255 */
+    int32_t overlay_tile;      /* 0 or 1 */
+    int32_t reserved;          /* must be 0 */
+    ik_adjust adjust;          /* all zero: none */
+    ik_pad pad;                /* all zero: none */
+} ik_request_opts5;
+#ifdef __cplusplus
+static_assert(sizeof(ik_request_opts5) == 104, "ik_request_opts5 is 104 bytes");
+#else
+_Static_assert(sizeof(ik_request_opts5) == 104, "ik_request_opts5 is 104 bytes");
+#endif
+
 /* ---- fused / batched entry points (pixels stay in HBM) ----------------- */
 /* decode -> resize_image -> encode_image in one call (handler src/lib.rs:175-191) */
 int ik_transform(const uint8_t *bytes, size_t len, int64_t w, int64_t h, int fmt, int quality,
@@ -833,7 +917,7 @@ int ik_transform_batch_submit_device(const uint8_t *const *dev_bytes, const size
                                      uint64_t *ticket);
 
 /* The batch calls with per-request options: opts holds n ik_request_opts, n
- * ik_request_opts2, n ik_request_opts3 or n ik_request_opts4 (or is NULL: every request at its defaults, the call without options),
+ * ik_request_opts2, n ik_request_opts3, n ik_request_opts4 or n ik_request_opts5 (or is NULL: every request at its defaults, the call without options),
  * opt_size is the size of that layout.  After a resize group's launch and before its
  * coders, its members that share (blur or unsharpen, sigma, threshold) are filtered by one
  * launch, a lone one by its own; requests that differ only in these settings still share
@@ -990,6 +1074,23 @@ int ik_overlay_batch_device(uint8_t *dev_base, uint32_t W, uint32_t H, uint32_t 
  * stride below rows * pitch, or n above 65535. */
 int ik_adjust_batch_device(uint8_t *dev, uint32_t W, uint32_t H, uint32_t C, uint32_t depth, size_t pitch,
                            size_t image_stride, uint32_t n, const ik_adjust *adj, void *hip_stream);
+/* the pad (above) of n images of W x H pixels of C samples of `depth` bytes, image i at
+ * dev_src + i*src_image_stride, onto canvases of canvas_w x canvas_h pixels at dev_dst +
+ * i*dst_image_stride, in one launch; the image lies where ik_pad_place(W, H, canvas_w,
+ * canvas_h, pad->gravity) puts it; pad->width and pad->height must be in range like every
+ * field of pad, but it is canvas_w and canvas_h that set the canvas.  Every byte
+ * of the canvas rows is written, nothing past canvas_w*C*depth bytes of a row is, and no
+ * source byte past W*C*depth of a row reaches an output.  The source may lie at any
+ * address; dev_dst, dst_pitch and dst_image_stride must be multiples of 4.  Enqueued on
+ * hip_stream (NULL: the calling thread's stream) without waiting.  IK_ERR_INVALID, with
+ * nothing launched and nothing written: a field of pad out of range or IK_PAD_NONE, C
+ * outside 1..4, depth outside 1..2, a null pointer, a zero size, a size above 2^24, a canvas
+ * smaller than the image, a pitch below the row bytes, n > 1 with an image stride below
+ * rows * pitch, n above 65535, or areas that overlap. */
+int ik_pad_batch_device(const uint8_t *dev_src, uint32_t W, uint32_t H, uint32_t C, uint32_t depth,
+                        size_t src_pitch, size_t src_image_stride, uint32_t n, const ik_pad *pad,
+                        uint32_t canvas_w, uint32_t canvas_h, uint8_t *dev_dst, size_t dst_pitch,
+                        size_t dst_image_stride, void *hip_stream);
 /* the WebP colour conversion (to_rgb8 + libwebp RGB->YUV420) on the device;
  * dev_yuv receives the Y (w*h), U and V ((w+1)/2 * (h+1)/2) planes back to back */
 int ik_webp_yuv420_device(const uint8_t *dev_src, uint32_t w, uint32_t h, uint32_t C,

@@ -375,6 +375,29 @@ struct AdjustArgs {
 };
 hipError_t launch_adjust(const AdjustArgs& a, int C, int depth, bool matrix, int n, hipStream_t s);
 
+// ---- pad (ik_pad.hip) ----
+// n same-geometry images of W x H pixels of px = C * depth bytes (1, 2, 3, 4, 6 or 8) placed
+// at (x0, y0) of cw x ch canvases, images addressed as launch_orient
+// addresses them.  W, H >= 1; the canvas holds the image; the canvas bases, pitch and stride
+// are multiples of 4 (the source's may be anything).
+constexpr int kPadSpan = 1024;             // canvas pixels of a row one workgroup takes
+constexpr int kPadRowCap = 256;            // most rows of workgroups in a launch (the rest: grid stride)
+constexpr uint32_t kPadMaxImages = 65535;  // grid.z
+constexpr uint32_t kPadMaxDim = 1u << 24;  // most pixels on an axis of the image and of the canvas
+struct PadArgs {
+    const uint8_t* src;
+    size_t src_pitch, src_img_stride;
+    uint8_t* dst;
+    size_t dst_pitch, dst_img_stride;
+    const uint64_t* src_tab;  // per-image bases (device), or null: src + img * src_img_stride
+    const uint64_t* dst_tab;
+    uint32_t W, H, cw, ch;
+    int32_t x0, y0;      // the image's origin in the canvas, >= 0
+    uint32_t fpx[2];     // colour mode: the frame pixel's px bytes
+    uint32_t pat[3][4];  // colour mode: the 16 bytes of a frame share at phase (16 * m) % px, m = 0..2
+};
+hipError_t launch_pad(const PadArgs& a, int px, int mode, int n, hipStream_t s);
+
 // ---- plans (ik_plan.cpp) ----
 // axis_weights, required_slots and the tables themselves: ik_resize_plan.h
 ResizePlan* get_resize_plan(int device, int W, int H, int C, int nw, int nh, int filter, int n);

@@ -10,7 +10,11 @@
 //                   whose windows (iw, ih, x0, y0, nw, nh; fit_target) agree resize in one
 //                   launch (resize_group), when there are at least 2 of them: an exact and a
 //                   cover request of one output size are different groups.  Emitted in
-//                   ascending key order, members in request order.
+//                   ascending key order, members in request order.  A request's pad
+//                   (ik_pad) gives it a canvas and an origin (pad_canvas), which are part
+//                   of the key as the window is: a group's images leave it with one final
+//                   geometry, which is what its coder groups need.  The pad's mode, colour
+//                   and alpha are not.
 //   coder groups    inside a resize group, its WebP and its JPEG requests of one quality
 //                   (at least 2) are coded by one group call.  WebP groups first, then
 //                   JPEG, each in ascending quality.
@@ -25,7 +29,7 @@
 // Kept as they are, odd as they look:
 //   - a request that needs no resize (w = h = None, or a target equal to its size)
 //     joins no group, so 32 of them never reach the uniform exact call: WebpMixed or Single
-//   - a WebP group with an output dimension above 16383 is routed Single: the per-image
+//   - a WebP group with an output dimension (of the canvas, under a pad) above 16383 is routed Single: the per-image
 //     front end reports "WebP dimensions ... exceed 16383" for each of its requests
 //   - 16-bit images are never grouped and are never mixed candidates
 //   - the candidate count behind `mixed` includes requests an exact group then takes, so
@@ -151,6 +155,48 @@ inline int fit_target(uint32_t W, uint32_t H, int64_t w, int64_t h, int fit, Fit
     return 0;
 }
 
+// Where a W x H image lies on its canvas (ik_pad): cw = max(W, width), ch
+// = max(H, height), so a width or height of 0 leaves that axis alone; x0 is 0, (cw - W) / 2
+// (floor) or cw - W by the gravity, y0 likewise.  The gravity is one of ik_gravity (checked
+// by the caller).  Everything that places a pad does it here.
+struct PadGeom {
+    uint32_t cw = 0, ch = 0, x0 = 0, y0 = 0;
+    bool operator==(const PadGeom& o) const { return cw == o.cw && ch == o.ch && x0 == o.x0 && y0 == o.y0; }
+};
+inline PadGeom pad_place(uint32_t W, uint32_t H, uint32_t width, uint32_t height, int gravity) {
+    PadGeom g;
+    g.cw = W > width ? W : width;
+    g.ch = H > height ? H : height;
+    const bool left = gravity == IK_GRAVITY_W || gravity == IK_GRAVITY_NW || gravity == IK_GRAVITY_SW;
+    const bool right = gravity == IK_GRAVITY_E || gravity == IK_GRAVITY_NE || gravity == IK_GRAVITY_SE;
+    const bool top = gravity == IK_GRAVITY_N || gravity == IK_GRAVITY_NE || gravity == IK_GRAVITY_NW;
+    const bool bottom = gravity == IK_GRAVITY_S || gravity == IK_GRAVITY_SE || gravity == IK_GRAVITY_SW;
+    g.x0 = left ? 0 : right ? g.cw - W : (g.cw - W) / 2;
+    g.y0 = top ? 0 : bottom ? g.ch - H : (g.ch - H) / 2;
+    return g;
+}
+// one request's pad as the plan sees it: its geometry only (mode, colour and alpha do not
+// route anything)
+struct PostPad {
+    bool on = false;
+    int gravity = IK_GRAVITY_CENTER;
+    uint32_t width = 0, height = 0;  // 0: the side of the request's target
+};
+// The canvas of a request whose W x H image, asked for as (w, h), came out of the resize as
+// nw x nh: a pad side of 0 is the side of the request's target (request_target), or with w
+// and h both None the image's own.  No pad: the image is the canvas.
+inline PadGeom pad_canvas(const PostPad& p, uint32_t W, uint32_t H, int64_t w, int64_t h, uint32_t nw, uint32_t nh) {
+    uint32_t width = p.width, height = p.height;
+    if (p.on && !(w < 0 && h < 0) && (!width || !height)) {
+        uint32_t tw = 0, th = 0;
+        if (request_target(W, H, w, h, &tw, &th) == 0) {  // (it failed: so did the resize)
+            if (!width) width = tw;
+            if (!height) height = th;
+        }
+    }
+    return p.on ? pad_place(nw, nh, width, height, p.gravity) : pad_place(nw, nh, 0, 0, IK_GRAVITY_NW);
+}
+
 enum class PostRoute : int {  // (ik_post_route, as ik_post_plan reports it)
     None = IK_POST_NONE,                       // the decode failed: its status is the request's
     Single = IK_POST_SINGLE,                   // the per-image ik_resize and / or encode_image_front
@@ -169,6 +215,7 @@ struct PostRequest {
     int64_t w = -1, h = -1;  // negative: None
     int fmt = 0, quality = 0;
     int fit = IK_FIT_CONTAIN;
+    PostPad pad;  // (default: none)
 };
 
 struct PostPlan {
@@ -176,6 +223,7 @@ struct PostPlan {
         bool sized = false;    // (nw, nh) is the size its encoder sees (false: the decode or fit_target failed)
         uint32_t nw = 0, nh = 0;
         FitWindow win;         // (sized) what it computes: win.nw x win.nh = nw x nh
+        PadGeom canvas;        // (sized) where those pixels lie in the image that is coded: nw x nh at (0, 0) without a pad
         int rgroup = -1, cgroup = -1;
         PostRoute route = PostRoute::None;
         // its route when no group call takes it (it is in no coder group, or its group's
@@ -185,6 +233,7 @@ struct PostPlan {
     struct ResizeGroup {
         uint32_t nw = 0, nh = 0;
         FitWindow win;
+        PadGeom canvas;                 // its members' final geometry
         std::vector<uint32_t> members;  // request order
         uint32_t cg_lo = 0, cg_hi = 0;  // its coder groups: cgroups[cg_lo, cg_hi)
     };
@@ -210,10 +259,16 @@ inline PostPlan post_plan(const PostRequest* rq, uint32_t m, int webp_encoder, i
         for (uint32_t k = 0; k < m; ++k) cand += rq[k].ok && rq[k].depth == 1 && rq[k].fmt == IK_FORMAT_WEBP;
         P.mixed = cand >= P.mixed_min;
     }
-    // (W, H, C, pitch, device), then the window: iw, ih, x0, y0 and with them (nw, nh)
+    // (W, H, C, pitch, device), then the window: iw, ih, x0, y0 and with them (nw, nh), then
+    // the canvas and the origin in it (without a pad: nw, nh, 0, 0 for every member)
     typedef std::tuple<uint32_t, uint32_t, uint32_t, size_t, int, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t,
-                       uint32_t> GroupKey;
-    std::map<GroupKey, std::pair<FitWindow, std::vector<uint32_t>>> groups;
+                       uint32_t, uint32_t, uint32_t, uint32_t, uint32_t> GroupKey;
+    struct GroupSlot {
+        FitWindow win;
+        PadGeom canvas;
+        std::vector<uint32_t> members;
+    };
+    std::map<GroupKey, GroupSlot> groups;
     for (uint32_t k = 0; k < m; ++k) {
         const PostRequest& r = rq[k];
         PostPlan::Req& q = P.req[k];
@@ -229,24 +284,27 @@ inline PostPlan post_plan(const PostRequest* rq, uint32_t m, int webp_encoder, i
         q.nw = q.sized ? q.win.nw : 0;
         q.nh = q.sized ? q.win.nh : 0;
         if (!q.sized) continue;  // Single: ik_resize reports it
-        if (P.mixed && r.fmt == IK_FORMAT_WEBP && r.depth == 1 && q.nw >= 1 && q.nh >= 1 && q.nw <= kWebpMaxDim &&
-            q.nh <= kWebpMaxDim)
+        q.canvas = pad_canvas(r.pad, r.W, r.H, r.w, r.h, q.nw, q.nh);
+        if (P.mixed && r.fmt == IK_FORMAT_WEBP && r.depth == 1 && q.nw >= 1 && q.nh >= 1 && q.canvas.cw <= kWebpMaxDim &&
+            q.canvas.ch <= kWebpMaxDim)
             q.route = q.solo = PostRoute::WebpMixed;
         // (never a request that needs no resampling: a whole copy or, under COVER, a crop of one)
         if (r.depth == 1 && !(q.win.iw == r.W && q.win.ih == r.H)) {
             // ordered by (nw, nh) first, as before the windows, then by the rest of the window
             auto& slot = groups[GroupKey(r.W, r.H, r.C, r.pitch, r.device, q.nw, q.nh, q.win.iw, q.win.ih, q.win.x0,
-                                         q.win.y0)];
-            slot.first = q.win;
-            slot.second.push_back(k);
+                                         q.win.y0, q.canvas.cw, q.canvas.ch, q.canvas.x0, q.canvas.y0)];
+            slot.win = q.win;
+            slot.canvas = q.canvas;
+            slot.members.push_back(k);
         }
     }
     for (auto& gv : groups) {
-        std::vector<uint32_t>& gm = gv.second.second;
+        std::vector<uint32_t>& gm = gv.second.members;
         if (gm.size() < 2) continue;
         const int g = (int)P.rgroups.size();
         PostPlan::ResizeGroup G;
-        G.win = gv.second.first;
+        G.win = gv.second.win;
+        G.canvas = gv.second.canvas;
         G.nw = G.win.nw;
         G.nh = G.win.nh;
         G.cg_lo = (uint32_t)P.cgroups.size();
@@ -270,7 +328,7 @@ inline PostPlan post_plan(const PostRequest* rq, uint32_t m, int webp_encoder, i
         };
         for (auto& qv : byq) {
             if (qv.second.size() < 2) continue;
-            if (G.nw > kWebpMaxDim || G.nh > kWebpMaxDim) continue;  // Single, for the per-image error
+            if (G.canvas.cw > kWebpMaxDim || G.canvas.ch > kWebpMaxDim) continue;  // Single, for the per-image error
             if (webp_takes_exact(webp_encoder, qv.second.size())) emit(PostRoute::WebpExactGroup, qv.first, qv.second);
             else if (!P.mixed) emit(PostRoute::WebpFrontGroup, qv.first, qv.second);
         }

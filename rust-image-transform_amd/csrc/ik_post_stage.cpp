@@ -1,6 +1,6 @@
 // ik_post_stage.cpp -- what a request's options mean and where they run: the entry points'
 // option arguments as one record per request (RequestOps), the batch paths' post stage
-// (orient -> flatten -> resize -> adjust -> filter -> watermark -> the encoders' device front ends) and
+// (orient -> flatten -> resize -> adjust -> filter -> pad -> watermark -> the encoders' device front ends) and
 // the single-request path through the same steps (transform_here).
 #include <hip/hip_runtime.h>
 
@@ -20,21 +20,22 @@
 
 namespace ik {
 
-// ---- per-request options (ik_request_opts, ik_request_opts2, ik_request_opts3, ik_request_opts4) ----
+// ---- per-request options (ik_request_opts, ik_request_opts2, ik_request_opts3, ik_request_opts4, ik_request_opts5) ----
 bool opts_size_ok(size_t opt_size) {
     return opt_size == sizeof(ik_request_opts) || opt_size == sizeof(ik_request_opts2) ||
-           opt_size == sizeof(ik_request_opts3) || opt_size == sizeof(ik_request_opts4);
+           opt_size == sizeof(ik_request_opts3) || opt_size == sizeof(ik_request_opts4) ||
+           opt_size == sizeof(ik_request_opts5);
 }
 // request i of an options array whose structs lie opt_size bytes apart, as the largest
 // layout (a smaller one's new fields: zero, "off")
-static ik_request_opts4 opts_at(const void* opts, size_t opt_size, uint32_t i) {
-    ik_request_opts4 o{};
+static ik_request_opts5 opts_at(const void* opts, size_t opt_size, uint32_t i) {
+    ik_request_opts5 o{};
     std::memcpy(&o, static_cast<const uint8_t*>(opts) + (size_t)i * opt_size, opt_size);
     return o;
 }
 // the blur or unsharpen an options struct asks for.  Returns IK_OK, or IK_ERR_INVALID with
 // the message set (prefix: "" or "request i: ")
-static int filter_of(const ik_request_opts4& o, const char* prefix, FilterReq& f) {
+static int filter_of(const ik_request_opts5& o, const char* prefix, FilterReq& f) {
     f = FilterReq();
     // (written so that a NaN fails)
     const bool bs = o.blur_sigma == 0.0f || (o.blur_sigma >= 0.0625f && o.blur_sigma <= IK_BLUR_MAX_SIGMA);
@@ -53,7 +54,7 @@ static int filter_of(const ik_request_opts4& o, const char* prefix, FilterReq& f
     return IK_OK;
 }
 // the watermark an options struct asks for (r.mark null: none), checked as filter_of checks
-static int overlay_of(const ik_request_opts4& o, const char* prefix, OverlayReq& r) {
+static int overlay_of(const ik_request_opts5& o, const char* prefix, OverlayReq& r) {
     r = OverlayReq();
     if (o.reserved != 0) return fail(IK_ERR_INVALID, "%sreserved options field is %d, not 0", prefix, (int)o.reserved);
     if (int rc = overlay_check(o.overlay_gravity, o.overlay_dx, o.overlay_dy, o.overlay_opacity, 0, o.overlay_tile, prefix))
@@ -70,13 +71,20 @@ static int overlay_of(const ik_request_opts4& o, const char* prefix, OverlayReq&
     return IK_OK;
 }
 // the colour adjustment an options struct asks for (all zero: none), checked as filter_of checks
-static int adjust_of(const ik_request_opts4& o, const char* prefix, AdjustReq& r) {
+static int adjust_of(const ik_request_opts5& o, const char* prefix, AdjustReq& r) {
     r = AdjustReq();
     if (int rc = adjust_check(o.adjust, prefix)) return rc;
     r.a = o.adjust;
     return IK_OK;
 }
-static int background_of(const ik_request_opts4& o, const char* prefix, int32_t& bg) {
+// the pad an options struct asks for (mode 0: none, and then every field 0), checked as filter_of checks
+static int pad_of(const ik_request_opts5& o, const char* prefix, PadReq& r) {
+    r = PadReq();
+    if (int rc = pad_check(o.pad, prefix, true)) return rc;
+    r.p = o.pad;
+    return IK_OK;
+}
+static int background_of(const ik_request_opts5& o, const char* prefix, int32_t& bg) {
     bg = o.background;
     if (bg == IK_BG_NONE || (bg >= 0 && bg <= 0xFFFFFF)) return IK_OK;
     return fail(IK_ERR_INVALID, "%sbackground %d is neither IK_BG_NONE nor 0x000000..0xFFFFFF", prefix, (int)bg);
@@ -102,7 +110,7 @@ int request_ops(const int* fit, const int* orient, const void* opts, size_t opt_
     ops.assign(n, RequestOps());
     bool any = false;
     for (uint32_t i = 0; i < n; ++i) {
-        ik_request_opts4 o{};
+        ik_request_opts5 o{};
         o.background = IK_BG_NONE;
         if (opts) o = opts_at(opts, opt_size, i);
         if (fit) o.fit = fit[i];
@@ -119,6 +127,7 @@ int request_ops(const int* fit, const int* orient, const void* opts, size_t opt_
         if (int rc = filter_of(o, prefix, r.flt)) return rc;
         if (int rc = overlay_of(o, prefix, r.ovl)) return rc;
         if (int rc = adjust_of(o, prefix, r.adj)) return rc;
+        if (int rc = pad_of(o, prefix, r.pad)) return rc;
         any = any || !r.is_default();
     }
     if (!any) ops.clear();
@@ -128,7 +137,7 @@ int request_ops(const int* fit, const int* orient, const void* opts, size_t opt_
 int single_request_ops(int fit, int orient, const void* opts, size_t opt_size, const uint8_t* bytes, size_t len,
                        RequestOps& r) {
     r = RequestOps();
-    ik_request_opts4 o{};
+    ik_request_opts5 o{};
     o.fit = fit; o.orient = orient; o.background = IK_BG_NONE;
     if (opts) o = opts_at(opts, opt_size, 0);
     r.fit = o.fit;  // (not checked here: ik_resize_fit refuses an unknown one, after the decode)
@@ -136,6 +145,7 @@ int single_request_ops(int fit, int orient, const void* opts, size_t opt_size, c
     if (int rc = filter_of(o, "", r.flt)) return rc;
     if (int rc = overlay_of(o, "", r.ovl)) return rc;
     if (int rc = adjust_of(o, "", r.adj)) return rc;
+    if (int rc = pad_of(o, "", r.pad)) return rc;
     return orientation_of(o.orient, bytes, len, "", r.orient);
 }
 
@@ -145,9 +155,9 @@ static int filter_image(ik_image* img, const FilterReq& f, ik_image** out) {
 }
 
 // resize_image, then the request's colour adjustment (in place), then its blur or unsharpen (the filter sees the pixels the encoder
-// will code), then its watermark, on one image: what follows the flatten for a single request
+// will code), then its pad (a new image: the canvas), then its watermark, on one image: what follows the flatten for a single request
 // and for a batch's member that no resize group took.  *rs is the image to encode: a new one,
-// or, with w and h both None and no filter, img itself -- the caller owns img, so the
+// or, with w and h both None and neither filter nor pad, img itself -- the caller owns img, so the
 // watermark in place is still right.  On failure *rs is null and img is all the caller holds.
 static int image_tail(ik_image* img, int64_t w, int64_t h, const RequestOps& ops, int filter, ik_image** rs) {
     *rs = nullptr;
@@ -164,6 +174,17 @@ static int image_tail(ik_image* img, int64_t w, int64_t h, const RequestOps& ops
         if (cur != img) ik_image_free(cur);
         if (st) return st;
         cur = fo;
+    }
+    if (ops.pad.on()) {
+        // (w, h and the target refer to img, the image the resize saw)
+        const PadGeom g = pad_canvas(ops.pad.geometry(), img->w, img->h, w, h, cur->w, cur->h);
+        if (g.cw != cur->w || g.ch != cur->h) {  // (a canvas that is the image: no pass)
+            ik_image* po = nullptr;
+            st = pad_image(cur, ops.pad, g, &po);
+            if (cur != img) ik_image_free(cur);
+            if (st) return st;
+            cur = po;
+        }
     }
     if (ops.ovl.mark && (st = overlay_image(cur, ops.ovl)) != IK_OK) {
         if (cur != img) ik_image_free(cur);
@@ -307,6 +328,7 @@ void transform_post_phase(const int64_t* w, const int64_t* h, const RequestOps* 
         }
         rq[k].w = w[i]; rq[k].h = h[i]; rq[k].fmt = fmt[i]; rq[k].quality = quality[i];
         rq[k].fit = op(k).fit;
+        rq[k].pad = op(k).pad.geometry();
     }
     const PostPlan plan = post_plan(rq.data(), m, default_webp_encoder(), webp_mixed_mode());
     std::vector<ik_image*> rsz(m, nullptr);   // resized by its group's launch
@@ -353,7 +375,21 @@ void transform_post_phase(const int64_t* w, const int64_t* h, const RequestOps* 
                          return blur_group(fs, f.sigma, f.mode == 2, f.threshold, fo);
                      },
                      [&](uint32_t k, ik_image* im, ik_image** fo) { return filter_image(im, op(k).flt, fo); });
-            // then the watermark, in place on the resized (and filtered) images: the members
+            // then the pad: the group's members share their canvas and origin (the plan's
+            // key), those whose 24 pad bytes are equal go through one launch onto new images,
+            // a lone one or a failed group through launches of their own, and the unpadded
+            // image returns to the pool.  A canvas that is the image: no pass.  A member whose
+            // pad fails keeps its image and its status is set (its file is dropped).
+            std::map<PadReq::Key, std::vector<uint32_t>> pads;
+            if (G.canvas.cw != G.nw || G.canvas.ch != G.nh)
+                for (uint32_t k : G.members)
+                    if (!ds[k] && op(k).pad.on()) pads[op(k).pad.key()].push_back(k);
+            run_sets(pads, rsz, false, ds, dm,
+                     [&](uint32_t k0, const std::vector<ik_image*>& ps, std::vector<ik_image*>& po) {
+                         return pad_group(ps, op(k0).pad, G.canvas, po);
+                     },
+                     [&](uint32_t k, ik_image* im, ik_image** po) { return pad_image(im, op(k).pad, G.canvas, po); });
+            // then the watermark, in place on the resized (filtered and padded) images: the members
             // that share (overlay handle, gravity, dx, dy, opacity, tile) go through one launch,
             // a lone one or a failed group through launches of their own.  A member whose
             // overlay fails gets its status and message: its file is dropped as above.
@@ -375,7 +411,14 @@ void transform_post_phase(const int64_t* w, const int64_t* h, const RequestOps* 
             std::vector<ik_image*> im;
             std::vector<EncodePrep*> pp;
             std::vector<std::vector<uint8_t>*> oo;
-            for (uint32_t k : cg.members) { im.push_back(rsz[k]); pp.push_back(&prep[k]); oo.push_back(&bytes_out[k]); }
+            bool agree = true;  // (a member whose pad failed still has its unpadded image)
+            for (uint32_t k : cg.members) {
+                im.push_back(rsz[k]);
+                pp.push_back(&prep[k]);
+                oo.push_back(&bytes_out[k]);
+                agree = agree && rsz[k]->w == G.canvas.cw && rsz[k]->h == G.canvas.ch;
+            }
+            if (!agree) continue;  // its members: image by image below
             const bool planes = cg.route == PostRoute::WebpFrontGroup;  // libwebp codes them in the host stage
             const int rc = planes                                      ? webp_front_group(im, cg.quality, pp)
                            : cg.route == PostRoute::WebpExactGroup ? webp_exact_group(im, cg.quality, oo)

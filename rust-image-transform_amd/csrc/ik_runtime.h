@@ -532,6 +532,37 @@ int adjust_check(const ik_adjust& a, const char* prefix);
 int adjust_image(ik_image* img, const AdjustReq& r);
 int adjust_group(const std::vector<ik_image*>& imgs, const AdjustReq& r);
 void adjust_shutdown();  // ik_shutdown: the cached plans and their device tables
+// one request's pad, after its blur or unsharpen (ik_request_opts5); mode IK_PAD_NONE: none
+struct PadReq {
+    ik_pad p{};
+    bool on() const { return p.mode != IK_PAD_NONE; }
+    // requests whose keys (the 24 bytes) are equal share a launch (pad_group)
+    typedef std::array<uint8_t, sizeof(ik_pad)> Key;
+    Key key() const {
+        Key k;
+        std::memcpy(k.data(), &p, sizeof p);
+        return k;
+    }
+    // what the post plan routes by
+    PostPad geometry() const {
+        PostPad g;
+        g.on = on();
+        g.gravity = p.gravity;
+        g.width = (uint32_t)p.width;
+        g.height = (uint32_t)p.height;
+        return g;
+    }
+};
+// IK_OK, or IK_ERR_INVALID with the message set (prefix: "" or "request i: "): a known mode
+// (IK_PAD_NONE only with allow_none, and then with every other field 0) and gravity, sizes
+// within 0..2^24, a colour within 0..0xFFFFFF, an alpha within 0..255 (ik_pad_host.cpp)
+int pad_check(const ik_pad& p, const char* prefix, bool allow_none);
+// an image, or same-geometry images in one launch, placed at g's origin on new canvases of
+// g's size (the caller has resolved g: pad_canvas); r gives the mode, the colour and the
+// alpha.  A return other than IK_OK from pad_group leaves every image to pad_image.  Both
+// synchronise the stream.
+int pad_image(const ik_image* img, const PadReq& r, const PadGeom& g, ik_image** out);
+int pad_group(const std::vector<ik_image*>& src, const PadReq& r, const PadGeom& g, std::vector<ik_image*>& out);
 
 // One request's options, resolved (ik_post_stage.cpp): what the *_fit, *_oriented and *_opts
 // entry points ask for beyond (w, h, fmt, quality), in the order the steps run
@@ -541,9 +572,10 @@ struct RequestOps {
     int32_t bg = IK_BG_NONE;  // or 0xRRGGBB: an image with alpha is flattened onto it after the turn
     AdjustReq adj;            // the colour adjustment of the resized image (all zero: none)
     FilterReq flt;            // the blur or unsharpen after it (mode 0: none)
+    PadReq pad;               // the canvas the result is placed on after it (mode 0: none)
     OverlayReq ovl;           // the watermark composited after it (mark null: none)
     bool is_default() const {
-        return fit == IK_FIT_CONTAIN && !orient && bg == IK_BG_NONE && !adj.on() && !flt.mode && !ovl.mark;
+        return fit == IK_FIT_CONTAIN && !orient && bg == IK_BG_NONE && !adj.on() && !flt.mode && !pad.on() && !ovl.mark;
     }
 };
 bool opts_size_ok(size_t opt_size);  // one of the declared ik_request_opts* layouts
@@ -566,7 +598,7 @@ int single_request_ops(int fit, int orient, const void* opts, size_t opt_size, c
 // decode_image on the calling thread's device (ik_host.cpp), and the thread's last message
 int decode_one(const uint8_t* bytes, size_t len, ik_image** out, int* fmt_out);
 std::string last_error_str();
-// decode -> orient -> flatten -> resize -> filter -> watermark -> encode of one request, here
+// decode -> orient -> flatten -> resize -> adjust -> filter -> pad -> watermark -> encode of one request, here
 int transform_here(const uint8_t* bytes, size_t len, int64_t w, int64_t h, const RequestOps& ops, int fmt, int quality,
                    int filter, uint8_t** out, size_t* out_len);
 // a batch part between its stages (ik_host.cpp StageExec): the requests it holds and what

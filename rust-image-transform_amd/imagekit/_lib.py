@@ -57,6 +57,17 @@ class RequestOpts4(ctypes.Structure):
     _fields_ = RequestOpts3._fields_ + [("adjust", Adjust)]
 
 
+class Pad(ctypes.Structure):
+    """ik_pad: the output extended onto a canvas (mode 0 is none, and then all zero)."""
+    _fields_ = [("mode", ctypes.c_int32), ("gravity", ctypes.c_int32), ("width", ctypes.c_int32),
+                ("height", ctypes.c_int32), ("color", ctypes.c_int32), ("alpha", ctypes.c_int32)]
+
+
+class RequestOpts5(ctypes.Structure):
+    """ik_request_opts5: RequestOpts4's fields, then the pad (all zero is none)."""
+    _fields_ = RequestOpts4._fields_ + [("pad", Pad)]
+
+
 _opts_p = ctypes.c_void_p  # any declared layout (const void *opts, with its size)
 _batch_head = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_uint32,
                ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
@@ -207,6 +218,12 @@ SIGNATURES = [
     ("ik_adjust_span", ctypes.c_int, []),
     ("ik_adjust_counters", ctypes.c_int, [ctypes.POINTER(ctypes.c_ulonglong)]),
     ("ik_adjust_batch_device", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_uint32] * 4 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, ctypes.POINTER(Adjust), ctypes.c_void_p]),
+    ("ik_pad_place", ctypes.c_int, [ctypes.c_uint32] * 4 + [ctypes.c_int, ctypes.POINTER(ctypes.c_int32)]),
+    ("ik_image_pad", ctypes.c_int, [c_img_p, ctypes.POINTER(Pad), ctypes.POINTER(c_img_p)]),
+    ("ik_pad_span", ctypes.c_int, []),
+    ("ik_pad_row_cap", ctypes.c_int, []),
+    ("ik_pad_counters", ctypes.c_int, [ctypes.POINTER(ctypes.c_ulonglong)]),
+    ("ik_pad_batch_device", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_uint32] * 4 + [ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, ctypes.POINTER(Pad), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]),
     ("ik_transform_opts", ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_int64] + [ctypes.c_int] * 3 + [_opts_p, ctypes.c_size_t, ctypes.POINTER(u8p), ctypes.POINTER(ctypes.c_size_t)]),
     ("ik_transform_batch_opts", ctypes.c_int, _batch_opts),
     ("ik_transform_batch_submit_opts", ctypes.c_int, _batch_opts + [ctypes.POINTER(ctypes.c_uint64)]),

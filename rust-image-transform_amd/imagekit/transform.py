@@ -299,12 +299,80 @@ def _adjusts(adjusts, n) -> Optional[list]:
     return adj if any(a is not None for a in adj) else None
 
 
+class PadMode(enum.IntEnum):
+    """ik_pad_mode: what the frame of a pad is made of."""
+    color = 1
+    edge = 2
+    mirror = 3
+    wrap = 4
+
+
+class Pad:
+    """The output extended onto a canvas (ik_pad): mode a PadMode or its name
+    ("color", "edge", "mirror", "wrap"), gravity a Gravity or its name (where the image lies in
+    the canvas), width and height ints in 0..2**24 (0: the side of the request's box in a
+    transform call, the image's own side in DynamicImage.pad), color as `background` takes it
+    (0xRRGGBB, (r, g, b), "rrggbb" or "#rrggbb"), alpha 0..255: the frame's alpha where the
+    image has one.  Anything else raises ValueError, before the library is called."""
+
+    __slots__ = ("mode", "gravity", "width", "height", "color", "alpha")
+
+    def __init__(self, mode="color", gravity="center", width: int = 0, height: int = 0, color=0, alpha: int = 255):
+        try:
+            self.mode = PadMode[mode.lower()] if isinstance(mode, str) else PadMode(mode)
+        except (KeyError, ValueError):
+            raise ValueError(f"unknown pad mode {mode!r}") from None
+        try:
+            self.gravity = Gravity[gravity.lower()] if isinstance(gravity, str) else Gravity(gravity)
+        except (KeyError, ValueError):
+            raise ValueError(f"unknown pad gravity {gravity!r}") from None
+        for name, v in (("width", width), ("height", height)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 1 << 24:
+                raise ValueError(f"pad {name} {v!r} is not an int within 0..2**24")
+        if isinstance(alpha, bool) or not isinstance(alpha, (int, np.integer)) or not 0 <= int(alpha) <= 255:
+            raise ValueError(f"pad alpha {alpha!r} is not an int within 0..255")
+        c = _background(color)
+        if c == BG_NONE:
+            raise ValueError("pad color None")
+        self.width, self.height, self.color, self.alpha = int(width), int(height), c, int(alpha)
+
+    def _struct(self) -> "_lib.Pad":
+        return _lib.Pad(int(self.mode), int(self.gravity), self.width, self.height, self.color, self.alpha)
+
+
+def _pad(v) -> Optional[Pad]:
+    """A `pad=` argument: None, a Pad, or a dict of Pad's keyword arguments."""
+    if v is None:
+        return None
+    if isinstance(v, dict):
+        v = Pad(**v)
+    if not isinstance(v, Pad):
+        raise ValueError(f"pad {v!r} is not a Pad")
+    return v
+
+
+def _pads(pads, n) -> Optional[list]:
+    """The per-request pads of a batch call, or None (no request has one): one entry per
+    request, or a single Pad (or a list of one) that applies to all."""
+    if pads is None:
+        return None
+    if isinstance(pads, (Pad, dict)):
+        pads = [pads]
+    if len(pads) == 1 and n != 1:
+        pads = list(pads) * n
+    if len(pads) != n:
+        raise InvalidArgument("pads must have one entry per request, or one for all")
+    pd = [_pad(v) for v in pads]
+    return pd if any(p is not None for p in pd) else None
+
+
 def _request_opts(n, fits=None, orients=None, backgrounds=None, blurs=None, sharpens=None, overlays=None,
-                  adjusts=None):
+                  adjusts=None, pads=None):
     """The options array of a *_opts batch call (each argument: one entry per request, or
     None for that option's default everywhere): ik_request_opts, ik_request_opts2 when
-    blurs or sharpens is given, ik_request_opts3 when some request has an overlay, or
-    ik_request_opts4 when some request has an adjustment.  Its element size is
+    blurs or sharpens is given, ik_request_opts3 when some request has an overlay,
+    ik_request_opts4 when some request has an adjustment, or ik_request_opts5 when some
+    request pads.  Its element size is
     ctypes.sizeof(arr._type_).  The overlays' images must outlive the call (a submitted
     batch: its wait)."""
     for name, v in (("fits", fits), ("orient", orients), ("backgrounds", backgrounds), ("blurs", blurs),
@@ -313,9 +381,13 @@ def _request_opts(n, fits=None, orients=None, backgrounds=None, blurs=None, shar
             raise InvalidArgument(f"{name} must have one entry per request")
     marks = _overlays(overlays, n)
     adj = _adjusts(adjusts, n)
-    wide = blurs is not None or sharpens is not None or marks is not None or adj is not None
-    arr = ((_lib.RequestOpts4 if adj is not None else _lib.RequestOpts3 if marks is not None
-            else _lib.RequestOpts2 if wide else _lib.RequestOpts) * n)()
+    pd = _pads(pads, n)
+    wide = blurs is not None or sharpens is not None or marks is not None or adj is not None or pd is not None
+    arr = ((_lib.RequestOpts5 if pd is not None else _lib.RequestOpts4 if adj is not None
+            else _lib.RequestOpts3 if marks is not None else _lib.RequestOpts2 if wide else _lib.RequestOpts) * n)()
+    for i in range(n if pd is not None else 0):
+        if pd[i] is not None:
+            arr[i].pad = pd[i]._struct()
     for i in range(n if adj is not None else 0):
         if adj[i] is not None:
             arr[i].adjust = adj[i]._struct()
@@ -519,6 +591,25 @@ class DynamicImage:
             _raise(st, "adjust")
         return DynamicImage(out.value)
 
+    def pad(self, pad=None, **kwargs) -> "DynamicImage":
+        """This image on a canvas as a new image (ik_image_pad; the project's own definition,
+        DESIGN section 4): a Pad, or Pad's keyword arguments (img.pad(width=512, height=512,
+        color="ffffff")); a width or height of 0, or one the image already fills, leaves that
+        axis alone.  Channels and depth are kept."""
+        if pad is not None and kwargs:
+            raise ValueError("a Pad and keyword arguments together")
+        p = pad if pad is not None else Pad(**kwargs)
+        if isinstance(p, dict):
+            p = Pad(**p)
+        if not isinstance(p, Pad):
+            raise ValueError(f"pad {p!r} is not a Pad")
+        st_p = p._struct()
+        out = ctypes.c_void_p()
+        st = _lib.load().ik_image_pad(self._h, ctypes.byref(st_p), ctypes.byref(out))
+        if st:
+            _raise(st, "pad")
+        return DynamicImage(out.value)
+
     def clone(self) -> "DynamicImage":
         return DynamicImage.from_array(self.to_array())
 
@@ -653,7 +744,7 @@ def _batch_arrays(n, sizes, fmts, qualities, filter):
 
 def transform_batch(datas, sizes, fmts, qualities, filter: "FilterType" = None, threads: int = 0,
                     fits=None, orient=None, backgrounds=None, blurs=None, sharpens=None,
-                    overlays=None, adjusts=None) -> List[bytes]:
+                    overlays=None, adjusts=None, pads=None) -> List[bytes]:
     """ik_transform_batch: decode -> resize_image -> encode_image for many requests
     (sizes: (w, h) per request, None = unset; fmts: ImageFormat per request; fits: a
     FitMode per request, None = contain for all; orient: an Orientation per request,
@@ -662,7 +753,9 @@ def transform_batch(datas, sizes, fmts, qualities, filter: "FilterType" = None, 
     threshold) per request, None = off; overlays: an Overlay (or a DynamicImage: an opaque
     centred mark, or None) per request, or one for all of them.  With backgrounds, blurs,
     sharpens, overlays or adjusts the call is ik_transform_batch_opts; adjusts: an Adjust (or
-    None) per request, or one for all of them, applied after the resize)."""
+    None) per request, or one for all of them, applied after the resize; pads: a Pad (or
+    None) per request, or one for all of them: the result placed on a canvas, a Pad size of
+    0 being the side of the request's box)."""
     lib = _lib.load()
     bufs, ptrs, lens = _inputs(datas)
     n = len(bufs)
@@ -672,8 +765,8 @@ def transform_batch(datas, sizes, fmts, qualities, filter: "FilterType" = None, 
     fa = _fits(fits, n)
     oa = _orients(orient, n)
     if (backgrounds is not None or blurs is not None or sharpens is not None or overlays is not None
-            or adjusts is not None):
-        ra = _request_opts(n, fits, orient, backgrounds, blurs, sharpens, overlays, adjusts=adjusts)
+            or adjusts is not None or pads is not None):
+        ra = _request_opts(n, fits, orient, backgrounds, blurs, sharpens, overlays, adjusts=adjusts, pads=pads)
         st = lib.ik_transform_batch_opts(ptrs, lens, n, ws, hs, ra, ctypes.sizeof(ra._type_), fs, qs, filt,
                                          threads, outs, olens, status)
     elif oa is not None:
@@ -720,7 +813,7 @@ class PendingBatch:
 
 def transform_batch_submit(datas, sizes, fmts, qualities, filter: "FilterType" = None,
                            threads: int = 0, fits=None, orient=None, backgrounds=None, blurs=None,
-                           sharpens=None, overlays=None, adjusts=None) -> PendingBatch:
+                           sharpens=None, overlays=None, adjusts=None, pads=None) -> PendingBatch:
     """ik_transform_batch_submit: the device half of transform_batch now, the host
     coders in the background; PendingBatch.wait() gives what transform_batch gives.
     fits, orient, backgrounds, blurs, sharpens and overlays as transform_batch takes them
@@ -736,8 +829,8 @@ def transform_batch_submit(datas, sizes, fmts, qualities, filter: "FilterType" =
     oa = _orients(orient, n)
     ra = None
     if (backgrounds is not None or blurs is not None or sharpens is not None or overlays is not None
-            or adjusts is not None):
-        ra = _request_opts(n, fits, orient, backgrounds, blurs, sharpens, overlays, adjusts=adjusts)
+            or adjusts is not None or pads is not None):
+        ra = _request_opts(n, fits, orient, backgrounds, blurs, sharpens, overlays, adjusts=adjusts, pads=pads)
         st = lib.ik_transform_batch_submit_opts(ptrs, lens, n, ws, hs, ra, ctypes.sizeof(ra._type_), fs, qs,
                                                 filt, threads, outs, olens, status, ctypes.byref(ticket))
     elif oa is not None:
@@ -756,7 +849,7 @@ def transform_batch_submit(datas, sizes, fmts, qualities, filter: "FilterType" =
 
 def transform_batch_submit_device(datas, sizes, fmts, qualities, filter: "FilterType" = None,
                                   threads: int = 0, fits=None, orient=None, backgrounds=None, blurs=None,
-                                  sharpens=None, overlays=None, adjusts=None) -> PendingBatch:
+                                  sharpens=None, overlays=None, adjusts=None, pads=None) -> PendingBatch:
     """ik_transform_batch_submit_device: as transform_batch_submit, over request
     bodies already in device memory (DeviceBytes).  With fits, orient, backgrounds, blurs, sharpens or
     overlays the call is ik_transform_batch_submit_device_opts; Orientation.auto is refused there (the
@@ -774,11 +867,11 @@ def transform_batch_submit_device(datas, sizes, fmts, qualities, filter: "Filter
     ticket = ctypes.c_uint64()
     ra = None
     if (fits is None and orient is None and backgrounds is None and blurs is None and sharpens is None
-            and overlays is None and adjusts is None):
+            and overlays is None and adjusts is None and pads is None):
         st = lib.ik_transform_batch_submit_device(ptrs, lens, n, ws, hs, fs, qs, filt, threads, outs, olens, status,
                                                   ctypes.byref(ticket))
     else:
-        ra = _request_opts(n, fits, orient, backgrounds, blurs, sharpens, overlays, adjusts=adjusts)
+        ra = _request_opts(n, fits, orient, backgrounds, blurs, sharpens, overlays, adjusts=adjusts, pads=pads)
         st = lib.ik_transform_batch_submit_device_opts(ptrs, lens, n, ws, hs, ra, ctypes.sizeof(ra._type_), fs,
                                                        qs, filt, threads, outs, olens, status, ctypes.byref(ticket))
     if st:
@@ -820,7 +913,8 @@ def encode_image(img: DynamicImage, fmt: ImageFormat, quality: int) -> bytes:
 
 def transform(data: bytes, w: Optional[int], h: Optional[int], fmt: ImageFormat, quality: int,
               filter: FilterType = FilterType.Lanczos3, fit: FitMode = FitMode.contain,
-              orient=Orientation.stored, background=None, blur=None, sharpen=None, overlay=None, adjust=None) -> bytes:
+              orient=Orientation.stored, background=None, blur=None, sharpen=None, overlay=None, adjust=None,
+              pad=None) -> bytes:
     """decode -> resize_image -> encode_image in one device-resident call; with orient
     (Orientation) the decoded image is turned first, and w, h and fit refer to the turned
     image; with background (0xRRGGBB, (r, g, b), "rrggbb" or "#rrggbb") an image that
@@ -829,23 +923,29 @@ def transform(data: bytes, w: Optional[int], h: Optional[int], fmt: ImageFormat,
     sharpened by the unsharp mask before it is encoded; with overlay (an Overlay, or a
     DynamicImage for an opaque centred mark) that watermark is composited last, on the
     pixels the encoder codes; with adjust (an Adjust) the resized image's colours are
-    adjusted before the blur or sharpen and the watermark (ik_transform_opts)."""
+    adjusted before the blur or sharpen and the watermark; with pad (a Pad) the result is
+    placed on a canvas before the watermark, a Pad size of 0 being the side of the box (w,
+    h): fit contain with Pad() returns exactly w x h (ik_transform_opts)."""
     bg = _background(background)
     fa = _filter_args(blur, sharpen)
     mark = _overlay(overlay)
     adj = _adjust(adjust)
+    pd = _pad(pad)
     lib = _lib.load()
     b = bytes(data)
     buf = _lib.u8p()
     n = ctypes.c_size_t()
     o = _orient(orient)
-    if adj is not None or mark is not None or fa[0] or fa[1] or bg != BG_NONE:
+    if pd is not None or adj is not None or mark is not None or fa[0] or fa[1] or bg != BG_NONE:
         # the smallest declared layout that holds what is set
-        if adj is not None:
-            ro = _lib.RequestOpts4(int(FitMode(fit)), o, bg, *fa)
+        if pd is not None or adj is not None:
+            ro = (_lib.RequestOpts5 if pd is not None else _lib.RequestOpts4)(int(FitMode(fit)), o, bg, *fa)
             if mark is not None:
                 mark._fill(ro)
-            ro.adjust = adj._struct()
+            if adj is not None:
+                ro.adjust = adj._struct()
+            if pd is not None:
+                ro.pad = pd._struct()
         elif mark is not None:
             ro = _lib.RequestOpts3(int(FitMode(fit)), o, bg, *fa)
             mark._fill(ro)

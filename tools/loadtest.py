@@ -131,6 +131,10 @@ def main():
                     help="every request adjusts its resized image's colours (ik_transform_batch*_opts, the 80-byte "
                          "options): grayscale, or brightness,contrast,saturation,hue,gamma,invert, e.g. "
                          "10,20,-30,15,2.2,0.  Without the flag: the calls made before")
+    ap.add_argument("--pad", default=None, metavar="RRGGBB[,mode]",
+                    help="every request pads its output to its box (ik_transform_batch*_opts, the 104-byte options): "
+                         "the frame colour and, optionally, color | edge | mirror | wrap (color), e.g. ffffff or "
+                         "000000,mirror.  Without the flag: the calls made before")
     ap.add_argument("--source", choices=["jpeg", "png-rgba"], default="jpeg",
                     help="png-rgba: translucent RGBA PNG sources of the same size (what --background acts on)")
     ap.add_argument("--restart", action="store_true")
@@ -173,7 +177,7 @@ def main():
         dist.init_process_group(backend="nccl" if torch.cuda.is_available() else "gloo")
     if torch.cuda.is_available():
         torch.cuda.set_device(local)
-    from imagekit import (Adjust, DynamicImage, FitMode, ImageFormat, Orientation, Overlay, _lib, transform_batch,
+    from imagekit import (Adjust, DynamicImage, FitMode, ImageFormat, Orientation, Overlay, Pad, _lib, transform_batch,
                           transform_batch_submit)
     lib = _lib.load()
     queue = world == 1
@@ -219,11 +223,16 @@ def main():
             b, c, sa, hu, g, inv = args.adjust.split(",")
             adjust = Adjust(int(b), int(c), int(sa), int(hu), float(g), bool(int(inv)))
 
+    pad = None  # one pad for every request: to the request's box (sizes 0)
+    if args.pad is not None:
+        parts = args.pad.split(",")
+        pad = Pad(parts[1] if len(parts) > 1 else "color", color=parts[0])
+
     def run_batch(chunk):
         return transform_batch([srcs[s] for s, _, _, _ in chunk], [(w, h) for _, w, h, _ in chunk],
                                [f for _, _, _, f in chunk], [args.quality] * len(chunk), threads=args.threads,
                                fits=fits(chunk), orient=orients(chunk), backgrounds=backgrounds(chunk),
-                               blurs=blurs(chunk), sharpens=sharpens(chunk), overlays=watermark, adjusts=adjust)
+                               blurs=blurs(chunk), sharpens=sharpens(chunk), overlays=watermark, adjusts=adjust, pads=pad)
 
     run_batch(mine[:min(len(mine), 8)])  # warm-up: plans, streams, pinned staging
 
@@ -263,7 +272,7 @@ def main():
             p = transform_batch_submit([srcs[s] for s, _, _, _ in chunk], [(w, h) for _, w, h, _ in chunk],
                                        [f for _, _, _, f in chunk], [args.quality] * len(chunk), threads=args.threads,
                                        fits=fits(chunk), orient=orients(chunk), backgrounds=backgrounds(chunk),
-                                       blurs=blurs(chunk), sharpens=sharpens(chunk), overlays=watermark, adjusts=adjust)
+                                       blurs=blurs(chunk), sharpens=sharpens(chunk), overlays=watermark, adjusts=adjust, pads=pad)
             if pend is not None:
                 done(pend[0], pend[1].wait())
             pend = (tb, p)
@@ -290,6 +299,8 @@ def main():
     lib.ik_overlay_counters(ovl)  # (likewise)
     adj = (ctypes.c_ulonglong * 2)()
     lib.ik_adjust_counters(adj)  # (likewise)
+    padc = (ctypes.c_ulonglong * 2)()
+    lib.ik_pad_counters(padc)  # (likewise)
     barrier()
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local}" if torch.cuda.is_available() else "cpu")
@@ -310,6 +321,8 @@ def main():
             "overlay_counters": {"launches": ovl[0], "images": ovl[1]},
             "adjust": args.adjust,
             "adjust_counters": {"launches": adj[0], "images": adj[1]},
+            "pad": args.pad,
+            "pad_counters": {"launches": padc[0], "images": padc[1]},
             "batch_latency_ms": {"p50": round(float(np.percentile(lat, 50)), 2),
                                  "p95": round(float(np.percentile(lat, 95)), 2)},
             "decoded_mpix_per_s": round(args.requests * S * S / elapsed / 1e6, 1),
